@@ -45,7 +45,18 @@ sets (3 GB: nothing is re-written while it is still cached — the fraction HBM 
 HIP events like the first; the single-image figure stays beside it as `roofline.frac_cached`.
 `--output-sets 4` makes the timed loop itself alternate (what tools/make_profiles.sh runs under rocprofv3).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-step F]
+A plain run does only what the headline needs: set-up, one counted frame, `--warmup` steps, the `--steps` timed steps,
+the outputs (`--dump-outputs`) and the line; `roofline` is then priced on the timed loop itself (`roofline.output_sets`).
+`--full` adds every pass of its own: the roofline pass into four output sets (N = 1), the secondary configurations and
+the CPU baseline (N = 1; `--no-secondary`, `--no-cpu-baseline` leave them out), and with N > 1 the every-frame cadence
+(`--no-other-cadence`) and `gather_ms`.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last step — the rgba framebuffer of the frame
+that left the loop and, N = 1, its first-hit streams — as DIR/<name>.npy (float32; pixel_index.npy float64): every
+pixel of a frame of at most DUMP_PIXELS, else the same seeded sample of DUMP_PIXELS of them in every run.  Every value
+written is finite: a miss's t = +inf is written as 0 beside hit.npy (1 = hit, 0 = miss).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-step F] [--full] [--dump-outputs DIR]
                        [--variant listed|persistent|static] [--gather fp32|rgba8|none] [--gather-every step|K]
                        [--no-cpu-baseline] [--no-secondary] [--size 4096] [--depth 5] [--output-sets M] [--batch B] [--graph]
 """
@@ -77,18 +88,27 @@ BYTES_PER_PIXEL_CAPTURE = 44 + 64   # + RenderedData AoS (BEF/shaders/host_devic
 # Ray generation, shading and the normal are NOT counted (they add < 10 % on the baseline frame).
 FLOP_PER_TRACED, FLOP_PER_SOLVED, FLOP_PER_EVAL = 20, 67, 14
 
+# --dump-outputs: pixels written per frame — 2^20 x (16 B rgba + 8 x 4 B hit mask and streams + 8 B index) = 56 MB, under the 64-MB cap
+DUMP_PIXELS = 1 << 20
+DUMP_SEED = 0
+
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes of their own beyond the headline: roofline pass into four output sets, secondary "
+                         "configurations, CPU baseline (N = 1); every-frame cadence and gather_ms (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rgba, first-hit streams)")
     ap.add_argument("--frames-per-step", type=int, default=64, help="frames in one step (one batch)")
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--variant", default=None, help="render kernel variant (default: library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations (N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary configurations (N = 1 only)")
     ap.add_argument("--hits", default="tpn", choices=["tpn", "none"], help="first-hit record streams to write")
     ap.add_argument("--gather", default="fp32", choices=["fp32", "rgba8", "none"],
                     help="N>1: what is all-gathered (default: the rgba32f framebuffer)")
@@ -119,8 +139,11 @@ def parse():
                     help="replay every step as one captured hipGraph instead of launching it eagerly (measured: no gain — the "
                          "frames are bound by the GPU, not by the host's launches; DESIGN.md §7)")
     ap.add_argument("--no-other-cadence", action="store_true",
-                    help="N>1: skip the second measurement (a gather after EVERY frame, rgba8 and fp32)")
-    return ap.parse_args()
+                    help="N>1 with --full: skip the second measurement (a gather after EVERY frame, rgba8 and fp32)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ----------------------------------------------------------------------------------------------
@@ -138,6 +161,8 @@ def _free_port():
 def launch(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
+    if a.dump_outputs:   # the ranks run in ROOT: the directory as the caller named it (the last occurrence wins)
+        cmd += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
     line = None
@@ -366,6 +391,46 @@ def secondary(tr, dev, stream):
 
 
 # ----------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, for output-for-output comparisons
+# ----------------------------------------------------------------------------------------------
+def dump_index(n_pixels):
+    """Row-major pixel indices written by --dump-outputs: all of them up to DUMP_PIXELS, else a sorted sample of
+    DUMP_PIXELS drawn with DUMP_SEED (the same for every run of the same frame size)."""
+    import numpy as np
+    if n_pixels <= DUMP_PIXELS:
+        return np.arange(n_pixels, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, DUMP_PIXELS, replace=False))
+
+
+def dump_outputs(out_dir, frame, dev):
+    """The frame that left the timed loop (`frame.finish()` has run): N = 1, the output set of the last frame rendered —
+    rgba framebuffer and first-hit streams; N > 1, rank 0's last gathered frame (`rgba8.npy` when the 8-bit image is what
+    is gathered) — at the pixels of dump_index().  A miss records t = +inf (include/trt.h): `t` is written with 0 there and
+    `hit` (1 / 0) says which pixels hit, so that every value written is finite.  Returns the names written."""
+    import numpy as np
+    import torch
+    idx = dump_index(frame.H * frame.W)
+    it = torch.from_numpy(idx).to(dev)
+    outs = {"pixel_index": idx.astype(np.float64)}
+    if frame.world == 1:
+        o = (frame._k - 1) % frame.n_sets
+        outs["rgba"] = frame.locals[o].reshape(-1, 4)[it].cpu().numpy()
+        for k, v in frame.hit_sets[o].items():
+            outs[k] = v[it].float().cpu().numpy()
+        if "t" in outs:
+            hit = np.isfinite(outs["t"])
+            outs["hit"] = hit.astype(np.float32)
+            outs["t"] = np.where(hit, outs["t"], np.float32(0))
+    else:
+        full = frame.full
+        outs["rgba8" if full.dtype == torch.uint8 else "rgba"] = full.reshape(-1, 4)[it].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in outs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(outs)
+
+
+# ----------------------------------------------------------------------------------------------
 # dry run (CPU rehearsal of launcher + gather; not a measurement)
 # ----------------------------------------------------------------------------------------------
 class _PatternTracer:
@@ -446,6 +511,8 @@ def worker(a, world, rank, local):
 
     if a.backend != "nccl":
         raise SystemExit("--backend gloo is the CPU rehearsal: add --dry-run (a measurement needs the GPUs and RCCL)")
+    if a.dump_outputs and world > 1 and a.gather == "none":
+        raise SystemExit("--dump-outputs with N > 1 writes the gathered frame: --gather none leaves no whole frame anywhere")
     # stdout carries ONE line, the result.  RCCL prints a version banner on the process's stdout when the first communicator is
     # created: from here on file descriptor 1 is stderr, and the result line goes to the descriptor that was stdout.
     sys.stdout.flush()
@@ -571,6 +638,7 @@ def worker(a, world, rank, local):
     use_graph = a.graph and (gather_every % F == 0 or not frame.gather) and F % frame.n_sets == 0
     dt, kern_ms, graphed = measure(frame, a.steps, a.warmup, use_graph)
     n_frames = a.steps * F
+    dumped = dump_outputs(a.dump_outputs, frame, dev) if a.dump_outputs and rank == 0 else None
 
     def fractions(ms, st_):
         ach = BYTES_PER_PIXEL * frame.local_pixels / (ms * 1e-3) / 1e9
@@ -584,9 +652,9 @@ def worker(a, world, rank, local):
 
     # N = 1, roofline pass: the same frames into FOUR alternating output sets — nothing a frame wrote is still in the
     # Infinity Cache when it is written again, so this is the fraction HBM served (the single-image figure above is kept
-    # as frac_cached).  Skipped when the timed loop itself alternated (--output-sets >= 4).
+    # as frac_cached).  Skipped when the timed loop itself alternated (--output-sets >= 4), and without --full.
     cached = None
-    if not multi and frame.n_sets < 4:
+    if a.full and not multi and frame.n_sets < 4:
         cached = {"kernel_ms": kern_ms, "achieved": achieved, "frac": frac_hbm}
         alt = trtd.TiledFrame(trs, W, H, world, rank, dev, want_hits=want_hits, gather="none", output_sets=4)
         _, kern_ms, _ = measure(alt, min(a.steps, 10), 1, False)
@@ -602,7 +670,7 @@ def worker(a, world, rank, local):
     # N > 1, the OTHER cadence, measured in the same job: a gather after EVERY frame (rgba8: the 8-bit image a swapchain
     # presents; fp32: the rgba32f framebuffer — round 1's N > 1 line).  A few steps each: these are link-bound.
     other = None
-    if multi and frame.gather and gather_every != 1 and not a.no_other_cadence:
+    if a.full and multi and frame.gather and gather_every != 1 and not a.no_other_cadence:
         other = {}
         for mode in ("rgba8", "fp32"):
             try:
@@ -619,7 +687,7 @@ def worker(a, world, rank, local):
     # N > 1, diagnostics only (outside the timed region): the collectives of one frame alone, so that the
     # line shows what binds the step — the rank-local render (roofline.kernel_ms) or replicating the framebuffer
     gather_ms = None
-    if multi and frame.gather:
+    if a.full and multi and frame.gather:
         try:
             g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -690,6 +758,8 @@ def worker(a, world, rank, local):
             "value_gather_every_frame": other,
             "step_launch": ("one hipGraph replay per step" if graphed else "eager launches"),
             "rehearse_collective": bool(a.rehearse_collective),
+            "full": bool(a.full),
+            "dump_outputs": dumped,
             "streams": n_streams,
             "frames_per_launch": n_batch,
             "frames_in_flight": n_streams * n_batch,
@@ -711,18 +781,22 @@ def worker(a, world, rank, local):
                          "kernel_ms_cached": cached["kernel_ms"] if cached else None,
                          "algorithmic_bytes_per_pixel": BYTES_PER_PIXEL, "pixels_per_launch": px_per_launch,
                          "note": "achieved = 44 B x pixels / (classify + render kernel time per frame, HIP events on the launch stream). "
-                                 "N = 1: frac is measured on a pass of the same frames into FOUR alternating output sets (no Infinity-Cache "
-                                 "reuse between frames: what HBM served); frac_cached is the timed loop of `value`, one output set as in the "
-                                 "reference (REFL/hello_vulkan.h:123). What binds: the HBM fraction exceeds the FP32-VALU fraction by an order "
+                                 + ("N = 1: frac is measured on a pass of the same frames into FOUR alternating output sets (no Infinity-Cache "
+                                    "reuse between frames: what HBM served); frac_cached is the timed loop of `value`, one output set as in the "
+                                    "reference (REFL/hello_vulkan.h:123). " if cached else
+                                    "frac is the timed loop of `value` itself, over `output_sets` output sets (with fewer than 4, lines still "
+                                    "in the Infinity Cache are overwritten there, so it exceeds what HBM served; --full adds the pass into four "
+                                    "output sets and keeps this figure as frac_cached). ")
+                                 + "What binds: the HBM fraction exceeds the FP32-VALU fraction by an order "
                                  "of magnitude; the frame is a mixture — ~85 % of the pixels are constant fills at the chip's store ceiling "
                                  "(~6.2 TB/s), the rest is latency-bound root finding (`solved_tests_per_s`, `flops`)"},
         }
-        if world == 1 and not a.no_secondary:
+        if a.full and world == 1 and not a.no_secondary:
             try:
                 out["secondary"] = secondary(tr, dev, stream)
             except Exception as e:  # a secondary configuration must never cost the headline line
                 out["secondary_error"] = repr(e)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cb = cpu_baseline(sc, g, pc, W, H)
             out["cpu_baseline_1thread"] = cb.pop("one_thread")
             out["cpu_baseline"] = cb

@@ -718,7 +718,7 @@ def test_render_batch_equals_single_frames(tr):
 
 
 def test_bench_line_has_what_the_driver_parses():
-    """`python bench.py` as the driver runs it (N = 1, small K, no CPU baseline / secondary passes to keep it short): ONE
+    """`python bench.py --full` (N = 1, small K, no CPU baseline / secondary passes to keep it short): ONE
     JSON line with the contract's keys, `roofline` priced on the pass into four alternating output sets with the
     single-image figure beside it, and — with the CPU baseline enabled on a small frame — a `cpu_baseline` object."""
     import json
@@ -734,7 +734,7 @@ def test_bench_line_has_what_the_driver_parses():
         assert len(lines) == 1, p.stdout[-2000:]
         return json.loads(lines[0])
 
-    j = run("--no-cpu-baseline", "--no-secondary")
+    j = run("--full", "--no-cpu-baseline", "--no-secondary")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):
         assert k in j, k
@@ -747,9 +747,48 @@ def test_bench_line_has_what_the_driver_parses():
     assert abs(r["achieved"] - 44 * 4096 * 4096 / (r["kernel_ms"] * 1e-3) / 1e9) < 1e-6 * r["achieved"]
     assert "cpu_baseline" not in j
     # CPU baseline leg on a frame small enough for a test (the oracle renders whole frames of the workload)
-    j = run("--no-secondary", "--size", "512")
+    j = run("--full", "--no-secondary", "--size", "512")
     c = j["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and c["unit"] == j["unit"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path, oracle):
+    """`python bench.py` without --full: the headline only (no pass of its own: roofline of the timed loop, no secondary
+    configurations, no CPU baseline), exactly --steps timed steps, and --dump-outputs writes the last step's frame —
+    rgba framebuffer and first-hit streams, every pixel of a 256² frame, every value finite (a miss's t = +inf as 0 beside
+    the hit mask) — which is the oracle's frame."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W = H = 256
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--frames-per-step", "2",
+                        "--size", str(W), "--dump-outputs", str(tmp_path / "out")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["full"] is False
+    assert abs(j["ms_per_frame"] * 2 - j["ms_per_step"]) < 1e-9 * j["ms_per_step"]
+    assert j["unit"] == "primary ray-torus tests/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert "secondary" not in j and "cpu_baseline" not in j and "cpu_baseline_1thread" not in j
+    r = j["roofline"]
+    assert r["output_sets"] == 1 and r["frac_cached"] is None and r["kernel_ms"] > 0
+    assert sorted(j["dump_outputs"]) == sorted(["pixel_index", "rgba", "hit", *GEOM])
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in j["dump_outputs"]}
+    for k, v in got.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+    assert got["pixel_index"].dtype == np.float64 and np.array_equal(got["pixel_index"], np.arange(W * H))
+    assert got["rgba"].dtype == np.float32 and got["rgba"].shape == (W * H, 4)
+    sc, g, pc = camera.single_torus_scene(), camera.baseline_camera(W, H), camera.baseline_push(5)
+    want_rgba, want_hits, _, _ = oracle.render(sc, g, pc, W, H, abi.TRT_CAMERA_PINHOLE, nthreads=oracle.max_threads())
+    hit = np.isfinite(want_hits["t"])
+    assert 0 < hit.sum() < W * H and np.array_equal(got["hit"], hit.astype(np.float32))
+    want_hits["t"] = np.where(hit, want_hits["t"], np.float32(0))
+    for k in GEOM:
+        assert got[k].dtype == np.float32 and np.array_equal(got[k].view(np.uint32), want_hits[k].reshape(-1).view(np.uint32)), k
+    np.testing.assert_allclose(got["rgba"], want_rgba.reshape(-1, 4), rtol=COLOR_RTOL, atol=COLOR_ATOL)
 
 
 def test_trace_dev_full_size_matches_render(tr):

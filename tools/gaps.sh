@@ -3,7 +3,7 @@
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/gaps_$TAG; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log || tail -5 $OUT/err.log
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --steps 30 --warmup 5 --full --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log || tail -5 $OUT/err.log
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, statistics
 rows = []
