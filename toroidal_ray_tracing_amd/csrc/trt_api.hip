@@ -6,6 +6,7 @@
 // HelloVulkan::raytrace + the descriptor-set / push-constant plumbing do in the reference
 // (REFL/hello_vulkan.cpp:913-935, BEF/hello_vulkan.cpp:936-958).  Nothing in here computes
 // a ray on the CPU: without a HIP device trt_create fails.
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -44,9 +45,8 @@ struct trt_ctx {
   bool          ev_toro_set = false, ev_stats_set = false;
 
   Tuning        tn;                       // launch-shape knobs: defaults, or the environment ONCE in a -DTRT_TUNING build
-  unsigned long long* d_stats = nullptr;  // [8]: trt_kernels.hip block_add_stats
-  unsigned int*       d_queue = nullptr;  // words 0..2: classification accumulators (zero between frames),
-                                          // words 32..33: the published list lengths (trt_kernels.hpp RenderArgs)
+  unsigned long long* d_stats = nullptr;  // [kStatWords]: the query counters of a counted launch (StatWord, trt_kernels.hpp)
+  unsigned int*       d_queue = nullptr;  // [kQueueWords]: the classification's accumulators and published counts (QueueWord)
   uint64_t            stats_pixels = 0;
 
   // toroidal camera tables: device copy + pinned host staging + cache key
@@ -57,7 +57,7 @@ struct trt_ctx {
 
   // staging for the host-pointer entry points (grow-only, freed in trt_destroy)
   DevBuf d_in[6], d_out[8], d_rgba, d_rendered;
-  DevBuf d_tiles;  // LIVE + CLEAR tile lists of the persistent kernel
+  DevBuf d_tiles;  // LIVE + CLEAR tile lists of the listed and the persistent kernel
   DevBuf d_cost;   // cost feedback: one word per macro tile (zero = no history)
   DevBuf d_keys;   // depth|index keys of trt_splat_dev (one-pass form)
   DevBuf d_bins;   // … binned form: per-bin count / offset / cursor words (count zero between calls)
@@ -124,21 +124,26 @@ int grow(trt_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t st = nullptr, bool g
   if(capturing(st))
     return fail(ctx, TRT_E_INVALID, "the ctx's scratch would have to grow (%zu -> %zu bytes) while the stream is being "
                 "captured into a hipGraph: make one eager call with the same sizes first", b.cap, bytes);
-  if(b.p)
+  void* const old = b.p;
+  if(old && graph_visible)
   {
-    if(graph_visible)
-    {
-      ctx->retired.push_back(b.p);
-      if(bytes < b.cap + b.cap / 2) bytes = b.cap + b.cap / 2;
-    }
-    else
-      TRT_HIP(ctx, hipFree(b.p));   // (synchronises with the device: nothing is using the block any more)
+    ctx->retired.push_back(old);
+    if(bytes < b.cap + b.cap / 2) bytes = b.cap + b.cap / 2;
   }
-  b.p = nullptr;
+  b.p = nullptr;   // before any error return: the ctx must not keep (and trt_destroy free again) a freed block
   b.cap = 0;
+  if(old && !graph_visible)
+    TRT_HIP(ctx, hipFree(old));   // (synchronises with the device: nothing is using the block any more)
   TRT_HIP(ctx, hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return TRT_OK;
+}
+
+// The eight first-hit streams of a trt_hits (t, px, py, pz, nx, ny, nz, id), in that order, as the pointer fields
+// themselves: stream k is read as *s[k] and redirected by assigning to it.
+std::array<void**, 8> hit_streams(trt_hits& h)
+{
+  return {{(void**)&h.t, (void**)&h.px, (void**)&h.py, (void**)&h.pz, (void**)&h.nx, (void**)&h.ny, (void**)&h.nz, (void**)&h.id}};
 }
 
 template <class Real>
@@ -195,8 +200,9 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, SceneK& out)
   out.n_tori = (int)s->n_tori;
   out.n_mat  = (int)s->n_materials;
   out.f64    = ctx->precision == TRT_SOLVE_F64 || ctx->precision == TRT_SOLVE_DK_F64 || ctx->precision == TRT_SOLVE_FERRARI_F64;
-  out.dk     = (ctx->precision == TRT_SOLVE_DK_F32 || ctx->precision == TRT_SOLVE_DK_F64) ? 1
-               : (ctx->precision == TRT_SOLVE_FERRARI_F32 || ctx->precision == TRT_SOLVE_FERRARI_F64) ? 2 : 0;
+  out.alt_solver = (ctx->precision == TRT_SOLVE_DK_F32 || ctx->precision == TRT_SOLVE_DK_F64) ? kSolverDurandKerner
+                   : (ctx->precision == TRT_SOLVE_FERRARI_F32 || ctx->precision == TRT_SOLVE_FERRARI_F64) ? kSolverFerrari
+                   : kSolverWalk;
   for(uint32_t i = 0; i < s->n_tori; ++i)
   {
     const trt_torus& t = s->tori[i];
@@ -391,10 +397,10 @@ extern "C" int trt_create(int device, trt_ctx** out)
   ctx->device = device;
   hipDeviceProp_t prop;
   if((e = hipSetDevice(device)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device)) != hipSuccess
-     || (e = hipMalloc((void**)&ctx->d_stats, 8 * sizeof(unsigned long long))) != hipSuccess
-     || (e = hipMalloc((void**)&ctx->d_queue, 64 * sizeof(unsigned int))) != hipSuccess
-     || (e = hipMemset(ctx->d_stats, 0, 8 * sizeof(unsigned long long))) != hipSuccess
-     || (e = hipMemset(ctx->d_queue, 0, 64 * sizeof(unsigned int))) != hipSuccess
+     || (e = hipMalloc((void**)&ctx->d_stats, kStatWords * sizeof(unsigned long long))) != hipSuccess
+     || (e = hipMalloc((void**)&ctx->d_queue, kQueueWords * sizeof(unsigned int))) != hipSuccess
+     || (e = hipMemset(ctx->d_stats, 0, kStatWords * sizeof(unsigned long long))) != hipSuccess
+     || (e = hipMemset(ctx->d_queue, 0, kQueueWords * sizeof(unsigned int))) != hipSuccess
      || (e = hipEventCreateWithFlags(&ctx->ev_toro, hipEventDisableTiming)) != hipSuccess
      || (e = hipEventCreateWithFlags(&ctx->ev_stats, hipEventDisableTiming)) != hipSuccess)
   {
@@ -495,15 +501,15 @@ extern "C" int trt_get_stats(trt_ctx* ctx, trt_stats* out)
   if(!ctx || !out) return TRT_E_INVALID;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   if(ctx->ev_stats_set) TRT_HIP(ctx, hipEventSynchronize(ctx->ev_stats));
-  unsigned long long h[8];
+  unsigned long long h[kStatWords];
   TRT_HIP(ctx, hipMemcpy(h, ctx->d_stats, sizeof h, hipMemcpyDeviceToHost));
-  out->primary_tests = h[0];
-  out->bounce_tests  = h[1];
-  out->shadow_tests  = h[2];
+  out->primary_tests = h[kStatPrimary];
+  out->bounce_tests  = h[kStatBounce];
+  out->shadow_tests  = h[kStatShadow];
   out->pixels        = ctx->stats_pixels;
-  out->traced_tests  = h[4];
-  out->solved_tests  = h[5];
-  out->evaluations   = h[6];
+  out->traced_tests  = h[kStatTraced];
+  out->solved_tests  = h[kStatSolved];
+  out->evaluations   = h[kStatEvals];
   out->reserved      = 0;
   return TRT_OK;
 }
@@ -531,7 +537,7 @@ extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
   a.stats = nullptr;
   if(ctx->stats_on)
   {
-    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 16, st));
+    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 2 * kStatWords, st));
     a.stats           = ctx->d_stats;
     ctx->stats_pixels = in->n;
   }
@@ -554,9 +560,10 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)in->n * sizeof(float);
   const float* src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
-  void*        dst[8] = {out->t, out->px, out->py, out->pz, out->nx, out->ny, out->nz, out->id};
+  const auto   dst    = hit_streams(*out);
   trt_rays din = *in;
   trt_hits dout;
+  const auto dptr_out = hit_streams(dout);
   const float** dptr_in[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
   for(int k = 0; k < 6 && in->n; ++k)
   {
@@ -564,12 +571,10 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
     TRT_HIP(ctx, hipMemcpyAsync(ctx->d_in[k].p, src[k], bytes, hipMemcpyHostToDevice, nullptr));
     *dptr_in[k] = (const float*)ctx->d_in[k].p;
   }
-  void** dptr_out[8] = {(void**)&dout.t,  (void**)&dout.px, (void**)&dout.py, (void**)&dout.pz,
-                        (void**)&dout.nx, (void**)&dout.ny, (void**)&dout.nz, (void**)&dout.id};
   for(int k = 0; k < 8; ++k)
   {
     *dptr_out[k] = nullptr;
-    if(dst[k] && in->n)
+    if(*dst[k] && in->n)
     {
       if(int rc = grow(ctx, ctx->d_out[k], bytes, nullptr, false)) return rc;
       *dptr_out[k] = ctx->d_out[k].p;
@@ -577,8 +582,8 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
   }
   if(int rc = trt_trace_dev(ctx, &din, scene, tmin, tmax, &dout, nullptr)) return rc;
   for(int k = 0; k < 8 && in->n; ++k)
-    if(dst[k])
-      TRT_HIP(ctx, hipMemcpyAsync(dst[k], ctx->d_out[k].p, bytes, hipMemcpyDeviceToHost, nullptr));
+    if(*dst[k])
+      TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->d_out[k].p, bytes, hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
   return TRT_OK;
 }
@@ -624,10 +629,9 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
       return fail(ctx, TRT_E_INVALID, "trt_render: the rgba image and the RenderedData buffer must be 16-byte aligned (they are written as float4)");
     if(fr.first_hit_dev)
     {
-      const trt_hits* h = fr.first_hit_dev;
-      const void* hp[8] = {h->t, h->px, h->py, h->pz, h->nx, h->ny, h->nz, h->id};
-      for(const void* q : hp)
-        if((uintptr_t)q & 3)
+      trt_hits h = *fr.first_hit_dev;
+      for(void** q : hit_streams(h))
+        if((uintptr_t)*q & 3)
           return fail(ctx, TRT_E_INVALID, "trt_render: first-hit streams must be 4-byte aligned");
     }
   }
@@ -635,14 +639,14 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
   if(batch && (ctx->variant != kRenderListed || ctx->precision > TRT_SOLVE_F64))
     return fail(ctx, TRT_E_INVALID, "trt_render_batch: batches run the listed variant with the default solver (TRT_SOLVE_F32 / _F64) only; "
                                     "render these frames one by one");
-  if(batch && W > 8u * 8191u)
+  if(batch && W > kTile * field_max(kBatchTileXBits))
     return fail(ctx, TRT_E_INVALID, "trt_render_batch: W <= 65528 (a batch's tile lists pack the tile column in 13 bits)");
   const SceneK* Sp = nullptr;
   if(int rc = build_scene(ctx, scene, Sp)) return rc;
   const SceneK& S = *Sp;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  if(ctx->variant == kRenderPersistent && S.dk)
+  if(ctx->variant == kRenderPersistent && S.alt_solver != kSolverWalk)
     return fail(ctx, TRT_E_INVALID, "trt_render: the persistent variant implements the default solver only; "
                                     "use the listed or static variant with TRT_SOLVE_DK_* / TRT_SOLVE_FERRARI_*");
   RenderBatch B;
@@ -650,12 +654,12 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
   B.n_frames = n_frames;
   uint32_t n_local_rows = row_end - row_begin;
   if(tiling) n_local_rows = tiling_rows(*tiling, H);
-  const size_t n_tiles = (size_t)((W + 7) / 8) * ((n_local_rows + 7) / 8);              // per frame
-  const size_t n_macro = (size_t)(((W + 7) / 8 + 3) / 4) * ((n_local_rows + 7) / 8);    // per frame
+  const size_t n_tiles = (size_t)tile_count(W) * tile_count(n_local_rows);                // per frame
+  const size_t n_macro = (size_t)macro_count(tile_count(W)) * tile_count(n_local_rows);   // per frame
   const bool   lists   = ctx->variant != kRenderStatic;
   if(lists)
   {
-    if(W > 8u * 65535u || n_local_rows > 8u * 32767u)
+    if(W > kTile * field_max(kTileXBits) || n_local_rows > kTile * field_max(kTileYBits))
       return fail(ctx, TRT_E_INVALID, "trt_render: the tile lists pack tile coordinates in 16 + 15 bits (W <= 524280, rows <= 262136)");
     if(n_tiles * n_frames > 0x7fffffffull)
       return fail(ctx, TRT_E_INVALID, "trt_render_batch: %zu tiles in the batch exceed the tile lists", n_tiles * n_frames);
@@ -691,7 +695,7 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     if(fr.first_hit_dev) a.hits = *fr.first_hit_dev;
     a.rendered = rendered;
     a.counters = ctx->d_queue;
-    a.counts   = ctx->d_queue + 32;
+    a.counts   = ctx->d_queue + kQueueCounts;
     if(camera == TRT_CAMERA_TOROIDAL)
       if(int rc = build_toro(ctx, *fr.g, *fr.pc, W, H, st, a.toro, f > 0)) return rc;
     if(ctx->stats_on) a.stats = ctx->d_stats;
@@ -739,19 +743,18 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     fine_any |= a.fine;
     a.debug_skip = ctx->tn.debug_skip;   // always 0 in the release build
     uintptr_t bits = 0;
-    const void* hp[8] = {a.hits.t, a.hits.px, a.hits.py, a.hits.pz, a.hits.nx, a.hits.ny, a.hits.nz, a.hits.id};
-    for(const void* q : hp) bits |= (uintptr_t)q;
+    for(void** q : hit_streams(a.hits)) bits |= (uintptr_t)*q;
     a.vec4_ok = (W % 4 == 0 && (bits & 15) == 0) ? 1u : 0u;
   }
   if(ctx->stats_on)
   {
-    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 16, st));
+    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 2 * kStatWords, st));
     ctx->stats_pixels = (uint64_t)n_local_rows * W * n_frames;
   }
   if(batch)
   {
     for(uint32_t f = 0; f < n_frames; ++f) B.fr[f].fine = fine_any;   // one classification kernel for the whole batch
-    const uint64_t lanes = fine_any ? (uint64_t)n_macro * 4 : (uint64_t)n_macro;
+    const uint64_t lanes = fine_any ? (uint64_t)n_macro * kMacroTiles : (uint64_t)n_macro;
     B.per_frame = (uint32_t)((lanes + 63) / 64 * 64);
     TRT_HIP(ctx, launch_render_batch(S, B, ctx->n_cus, ctx->tn, st));
   }
@@ -764,10 +767,11 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
   }
   if(lists && ctx->tn.debug_tiles)
   {
-    unsigned int q[4];
+    unsigned int q[kCountWords];
     TRT_HIP(ctx, hipStreamSynchronize(st));
     TRT_HIP(ctx, hipMemcpy(q, B.fr[0].counts, sizeof q, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[trt] tiles: live=%u (heavy %u, mean cost %u ticks) clear=%u (cull=%u)\n", q[0], q[2], q[3], q[1], B.fr[0].tile_cull);
+    fprintf(stderr, "[trt] tiles: live=%u (heavy %u, mean cost %u ticks) clear=%u (cull=%u)\n", q[kCountLive], q[kCountHeavy],
+            q[kCountMeanCost], q[kCountClear], B.fr[0].tile_cull);
   }
   return TRT_OK;
 }
@@ -826,28 +830,23 @@ extern "C" int trt_render(trt_ctx* ctx, const trt_globals* g, const trt_push* pc
     if(int rc = grow(ctx, ctx->d_rgba, npx * 16, nullptr, false)) return rc;
     d_rgba = (float*)ctx->d_rgba.p;
   }
-  trt_hits dh;
+  trt_hits dh, want;
   std::memset(&dh, 0, sizeof dh);
-  void*  dst[8]  = {nullptr};
-  void** dptr[8] = {(void**)&dh.t,  (void**)&dh.px, (void**)&dh.py, (void**)&dh.pz,
-                    (void**)&dh.nx, (void**)&dh.ny, (void**)&dh.nz, (void**)&dh.id};
-  if(first_hit_out)
-  {
-    void* h[8] = {first_hit_out->t,  first_hit_out->px, first_hit_out->py, first_hit_out->pz,
-                  first_hit_out->nx, first_hit_out->ny, first_hit_out->nz, first_hit_out->id};
-    for(int k = 0; k < 8; ++k)
-      if((dst[k] = h[k]))
-      {
-        if(int rc = grow(ctx, ctx->d_out[k], npx * 4, nullptr, false)) return rc;
-        *dptr[k] = ctx->d_out[k].p;
-      }
-  }
+  std::memset(&want, 0, sizeof want);
+  if(first_hit_out) want = *first_hit_out;
+  const auto dst = hit_streams(want), dptr = hit_streams(dh);
+  for(int k = 0; k < 8; ++k)
+    if(*dst[k])
+    {
+      if(int rc = grow(ctx, ctx->d_out[k], npx * 4, nullptr, false)) return rc;
+      *dptr[k] = ctx->d_out[k].p;
+    }
   if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, d_rgba, first_hit_out ? &dh : nullptr,
                              nullptr, nullptr))
     return rc;
   if(rgba_out) TRT_HIP(ctx, hipMemcpyAsync(rgba_out, d_rgba, npx * 16, hipMemcpyDeviceToHost, nullptr));
   for(int k = 0; k < 8; ++k)
-    if(dst[k]) TRT_HIP(ctx, hipMemcpyAsync(dst[k], ctx->d_out[k].p, npx * 4, hipMemcpyDeviceToHost, nullptr));
+    if(*dst[k]) TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->d_out[k].p, npx * 4, hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
   return TRT_OK;
 }

@@ -84,11 +84,15 @@ struct MaterialK {  // the WaveFrontMaterial fields the Phong model reads (rchit
   int   illum;
 };
 
+// SceneK::alt_solver.  The kernels take the walk as ALT = false and both alternatives as ALT = true, choosing between
+// them wave-uniformly at run time (torus_first_hit).
+enum AltSolver : int { kSolverWalk = 0, kSolverDurandKerner = 1, kSolverFerrari = 2 };
+
 struct SceneK {
   int            n_tori;
   int            n_mat;
   int            f64;   // 1: FP64 root solve (BASELINE config 4), FP32 I/O
-  int            dk;    // 0: Fourier–Newton walk; alternative root solvers: 1 Durand–Kerner, 2 Ferrari
+  int            alt_solver;   // AltSolver: the Fourier–Newton walk, or an alternative root solver (kernels with ALT = true)
   int            order[TRT_MAX_TORI];  // test order: descending bounding radius R + r, ties by index
   uint32_t       inside[TRT_MAX_TORI]; // inside[i]: the tori whose tube lies strictly inside torus i's tube, as a mask over TEST-ORDER
                                        // positions (bit k = order[k]) — what a ray that leaves i's surface outwards cannot hit first
@@ -595,19 +599,19 @@ constexpr int kRenderWalk = kWalkTable;
 constexpr int kRenderWalk = kWalkNested;
 #endif
 
-template <class Real, bool DK = false, int WALK = kRenderWalk>
+template <class Real, bool ALT = false, int WALK = kRenderWalk>
 __device__ __forceinline__ bool torus_first_hit(Real ox, Real oy, Real oz, Real dx_, Real dy_,
                                                 Real dz_, Real dd, Real inv_dd, Real tmin, Real tmax,
-                                                const TorusK<Real>& T, Real& t_out, WorkCount& wc, int alt = 1)
+                                                const TorusK<Real>& T, Real& t_out, WorkCount& wc, int alt = kSolverDurandKerner)
 {
   TorusTest<Real> q;
   ++wc.traced;
   if(!q.setup(ox, oy, oz, dx_, dy_, dz_, dd, inv_dd, tmin, tmax, T))
     return false;
   ++wc.solved;
-  if(DK)
+  if(ALT)
   {
-    if(alt == 2) q.solve_ferrari(inv_dd, T.Rb2);   // wave-uniform: the scene's solver
+    if(alt == kSolverFerrari) q.solve_ferrari(inv_dd, T.Rb2);   // wave-uniform: the scene's solver
     else q.solve_dk(inv_dd, T.Rb2);
   }
   else
@@ -671,12 +675,12 @@ __device__ __forceinline__ bool round_t(double t, float tmin, float tmax, float&
 }
 
 // One ray against torus i over the open interval (tmin, tmax); t rounded to FP32.
-template <class Real, bool DK = false, int WALK = kRenderWalk>
+template <class Real, bool ALT = false, int WALK = kRenderWalk>
 __device__ __forceinline__ bool torus_hit(const SceneK& S, int i, const RayK<Real>& r, float tmin, float tmax, float& t, WorkCount& wc)
 {
   Real tt;
-  if(!torus_first_hit<Real, DK, WALK>((Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd, (Real)r.tmin, (Real)tmax,
-                                torus_k<Real>(S, i), tt, wc, S.dk))
+  if(!torus_first_hit<Real, ALT, WALK>((Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd, (Real)r.tmin, (Real)tmax,
+                                       torus_k<Real>(S, i), tt, wc, S.alt_solver))
     return false;
   return round_t(tt, tmin, tmax, t);
 }
@@ -688,7 +692,7 @@ __device__ __forceinline__ bool torus_hit(const SceneK& S, int i, const RayK<Rea
 // `skip` (a mask over test-order positions) names the tori this ray cannot hit first: tubes that lie strictly inside a
 // tube the ray's origin is known to be OUTSIDE of (enclosure cull) — they count as tests and cost nothing.
 // Returns the torus index or -1; `tests` counts ray–torus tests.
-template <class Real, bool DK = false, int WALK = kRenderWalk>
+template <class Real, bool ALT = false, int WALK = kRenderWalk>
 __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
                                            float& t_out, uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
 {
@@ -704,9 +708,9 @@ __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tm
     if((skip >> k) & 1u)
       continue;
 #ifdef TRT_FULL_WINDOW   // timing experiment only (the tail of config 4): every torus over the FULL interval, minimum afterwards
-    if(torus_hit<Real, DK, WALK>(S, i, r, tmin, tmax, t, wc) && t < best)
+    if(torus_hit<Real, ALT, WALK>(S, i, r, tmin, tmax, t, wc) && t < best)
 #else
-    if(torus_hit<Real, DK, WALK>(S, i, r, tmin, min_(tmax, best), t, wc))
+    if(torus_hit<Real, ALT, WALK>(S, i, r, tmin, min_(tmax, best), t, wc))
 #endif
     {
       best = t;
@@ -718,7 +722,7 @@ __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tm
 }
 
 // Any hit — the shadow query with gl_RayFlagsTerminateOnFirstHitEXT (REFL/shaders/raytrace.rchit:114-131).
-template <class Real, bool DK = false>
+template <class Real, bool ALT = false>
 __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
                                         uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
 {
@@ -730,7 +734,7 @@ __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin,
     ++tests;
     if((skip >> k) & 1u)
       continue;
-    if(torus_hit<Real, DK>(S, S.order[k], r, tmin, tmax, t, wc))
+    if(torus_hit<Real, ALT>(S, S.order[k], r, tmin, tmax, t, wc))
       return true;
   }
   return false;

@@ -23,6 +23,7 @@
 #include "trt_kernels.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace trt {
 
@@ -171,8 +172,9 @@ __device__ __forceinline__ void store_first_hit(const RenderArgs& a, size_t i_, 
 // atomics, then ONE global atomic per counter per block (65,536 waves adding to three words one
 // by one made the counted pass of the listed kernel 1.2 ms long).  Every thread of the block must
 // call it (it contains barriers); `stats` is kernel-uniform.
-// Layout of the totals: trt_stats without `pixels` — [0] primary, [1] bounce, [2] shadow tests, [3] unused,
-// [4] traced, [5] solved tests, [6] evaluations.
+// Layout of the totals: StatWord (trt_kernels.hpp) — the three ray classes at k, the WorkCount fields at k + 1.
+static_assert(kStatPrimary == 0 && kStatBounce == 1 && kStatShadow == 2 && kStatTraced == 4 && kStatSolved == 5 &&
+              kStatEvals == 6 && kStatWords == 8, "block_add_stats: acc[k < 3 ? k : k + 1], 8 words");
 __device__ __forceinline__ void block_add_stats(unsigned long long* stats, uint32_t v0, uint32_t v1, uint32_t v2, const WorkCount& wc)
 {
   __shared__ unsigned int acc[8];
@@ -249,7 +251,7 @@ constexpr float kTMax = 10000.0f;  // rgen:52
 // ------------------------------------------------------------------------------------------
 // trace(rays_in → hits_out)
 // ------------------------------------------------------------------------------------------
-template <class Real, bool DK>
+template <class Real, bool ALT>
 __global__ __launch_bounds__(256) void trace_kernel(const SceneK scene, const TraceArgs a)
 {
   __shared__ SceneK S;
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const SceneK scene, const Tr
     const v3 o = {a.rays.ox[i], a.rays.oy[i], a.rays.oz[i]};
     const v3 d = {a.rays.dx[i], a.rays.dy[i], a.rays.dz[i]};
     float     t;
-    const int id = closest_hit<Real, DK, kWalkTable>(S, o, d, a.tmin, a.tmax, t, tests, wc);   // incoherent rays: trt_device.hpp
+    const int id = closest_hit<Real, ALT, kWalkTable>(S, o, d, a.tmin, a.tmax, t, tests, wc);   // incoherent rays: trt_device.hpp
     v3 P = {0.0f, 0.0f, 0.0f}, N = {0.0f, 0.0f, 0.0f};
     if(id >= 0)
     {
@@ -354,7 +356,7 @@ __device__ __forceinline__ void rd_miss_tile(const RenderArgs& a, float4* tile, 
   rd_flush(a, tile, tx, ty, lane);
 }
 
-template <class Real, bool DK>
+template <class Real, bool ALT>
 __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a, uint32_t x, uint32_t y, uint32_t ly, const RdSink rd,
                                             uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
 {
@@ -381,7 +383,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
   {
     v3    prdHit, nextO = origin, nextD = direction;
     float t;
-    const int id = closest_hit<Real, DK>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
+    const int id = closest_hit<Real, ALT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
     if(id < 0)
     {
       prdHit = {a.pc.clearColor[0] * 0.8f, a.pc.clearColor[1] * 0.8f, a.pc.clearColor[2] * 0.8f};  // rmiss:37
@@ -409,7 +411,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
       bool shadowed = false;
       const uint32_t inside = S.inside[id];
       if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
-        shadowed = any_hit<Real, DK>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
+        shadowed = any_hit<Real, ALT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
       if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
         skip |= inside;
       prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
@@ -433,7 +435,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
   if(rd) rd.put(1, c);                                                     // BEF rgen:111
 }
 
-template <class Real, int TW, bool DK>
+template <class Real, int TW, bool ALT>
 __global__ __launch_bounds__(256) void render_static_kernel(const SceneK scene, const RenderArgs a)
 {
   __shared__ SceneK S;
@@ -453,7 +455,7 @@ __global__ __launch_bounds__(256) void render_static_kernel(const SceneK scene, 
   {
     const uint32_t y = image_row(a, ly);
     const RdSink rd{nullptr, a.rendered ? reinterpret_cast<float*>(&a.rendered[(size_t)x * a.H + y]) : nullptr};   // BEF rgen:72
-    trace_pixel<Real, DK>(S, a, x, y, ly, rd, n_primary, n_bounce, n_shadow, wc);
+    trace_pixel<Real, ALT>(S, a, x, y, ly, rd, n_primary, n_bounce, n_shadow, wc);
   }
   if(a.stats)
   {
@@ -608,7 +610,7 @@ __device__ __forceinline__ bool tile_is_clear(const SceneK& S, const RenderArgs&
   return true;
 }
 
-// End of a classification block.  The list lengths are accumulated in a.counters[0..1] (zero when the
+// End of a classification block.  The list lengths are accumulated in the QueueWord accumulators (zero when the
 // kernel starts); every block takes a ticket (sharded: see below) once its two reservations have
 // returned, and the block that draws the LAST ticket — every other block's additions are then
 // performed — moves the totals to a.counts (what the render kernels read) and leaves all three
@@ -618,12 +620,13 @@ __device__ __forceinline__ bool tile_is_clear(const SceneK& S, const RenderArgs&
 // writes (classify_ticket), so that the latency of the returning atomic hides behind those stores; the
 // publication itself (classify_publish) comes last.  (The list entries are read by the NEXT kernel: the
 // kernel boundary orders them, not the ticket.)
-// The tickets are sharded over eight words (a.counters[8 + blockIdx % 8]): 256 returning atomics on ONE word
+// The tickets are sharded over eight words (kQueueTickets + blockIdx % 8): 256 returning atomics on ONE word
 // take ≈3 µs (≈12 ns each, MI355X_MICROARCH.md "fanin") at the tail of a 9-µs kernel; the last block of a shard
-// draws a second-level ticket on a.counters[2], and the last of those publishes.
+// draws a second-level ticket on kQueueShardTicket, and the last of those publishes.
+static_assert(kQueueShards == 8, "classify_ticket / classify_publish: shard = blockIdx & 7");
 __device__ __forceinline__ unsigned int classify_ticket(const RenderArgs& a)
 {
-  return threadIdx.x == 0 ? atomicAdd(&a.counters[8u + (blockIdx.x & 7u)], 1u) : 0u;   // the reservations of threads 0 and 1 have returned
+  return threadIdx.x == 0 ? atomicAdd(&a.counters[kQueueTickets + (blockIdx.x & 7u)], 1u) : 0u;   // the reservations of threads 0 and 1 have returned
 }
 
 __device__ __forceinline__ void classify_publish(const RenderArgs& a, unsigned int ticket)
@@ -636,26 +639,28 @@ __device__ __forceinline__ void classify_publish(const RenderArgs& a, unsigned i
       const unsigned int shard = blockIdx.x & 7u, in_shard = (gridDim.x - shard + 7u) >> 3, n_shards = gridDim.x < 8u ? gridDim.x : 8u;
       if(ticket == in_shard - 1)
       {
-        atomicExch(&a.counters[8u + shard], 0u);
-        last = atomicAdd(&a.counters[2], 1u) == n_shards - 1 ? 1 : 0;
+        atomicExch(&a.counters[kQueueTickets + shard], 0u);
+        last = atomicAdd(&a.counters[kQueueShardTicket], 1u) == n_shards - 1 ? 1 : 0;
       }
     }
     last = __shfl(last, 0, 64);
     if(last)
     {
       // (five exchanges in ONE instruction instead of five dependent round trips at the very end of the kernel)
-      const uint32_t word = threadIdx.x < 2u ? threadIdx.x : threadIdx.x + 1u;   // counters 0, 1, 3, 4, 5
+      static_assert(kQueueLive == 0 && kQueueClear == 1 && kQueueHeavy == 3 && kQueueCostSum == 4 && kQueueCostCount == 5,
+                    "lanes 0..4 exchange the accumulators 0, 1, 3, 4, 5");
+      const uint32_t word = threadIdx.x < 2u ? threadIdx.x : threadIdx.x + 1u;   // live, clear, heavy, cost sum, cost count
       const uint32_t v = threadIdx.x < 5u ? atomicExch(&a.counters[word], 0u) : 0u;
       const unsigned int n_norm = __shfl(v, 0, 64), n_clear = __shfl(v, 1, 64), n_heavy = __shfl(v, 2, 64);
       const unsigned int cost_sum = __shfl(v, 3, 64), cost_cnt = __shfl(v, 4, 64);
       if(threadIdx.x == 0)
       {
         const unsigned int n_live = n_norm + n_heavy < a.cap_live ? n_norm + n_heavy : a.cap_live;   // (their sum never exceeds the tiles)
-        a.counts[0] = n_live;
-        a.counts[1] = n_clear < a.cap_clear ? n_clear : a.cap_clear;
-        a.counts[2] = n_heavy < n_live ? n_heavy : n_live;
-        a.counts[3] = cost_cnt ? cost_sum / cost_cnt : 0u;   // the threshold of the NEXT frame's classification
-        atomicExch(&a.counters[2], 0u);
+        a.counts[kCountLive]     = n_live;
+        a.counts[kCountClear]    = n_clear < a.cap_clear ? n_clear : a.cap_clear;
+        a.counts[kCountHeavy]    = n_heavy < n_live ? n_heavy : n_live;
+        a.counts[kCountMeanCost] = cost_cnt ? cost_sum / cost_cnt : 0u;   // the threshold of the NEXT frame's classification
+        atomicExch(&a.counters[kQueueShardTicket], 0u);
       }
     }
   }
@@ -675,23 +680,21 @@ __device__ __forceinline__ size_t live_slot(uint32_t cap_live, uint32_t n_heavy,
 #define TRT_CLASSIFY_THREADS 1024
 #endif
 constexpr int kClassifyThreads = TRT_CLASSIFY_THREADS;
-constexpr uint32_t kMacroTiles = 4;  // a macro tile = 4 horizontally adjacent 8×8 tiles = 32×8 pixels
 
-// Tile-list entries.  One frame per launch: tx | ty << 16 [| miss flag] (tx < 2^16, ty < 2^15).  A batch of frames
-// (trt_render_batch_dev): tx | ty << 13 | frame << 28 [| miss flag] (tx < 2^13: W <= 65528).
-constexpr uint32_t kTileMissFlag = 0x80000000u;
+// Tile-list entries, packed as trt_kernels.hpp states (kTileXBits, kBatchTileXBits, ...): one frame per launch, or a
+// batch of frames (trt_render_batch_dev) whose entries carry the frame.
 template <bool BATCH> struct TileCode;
 template <> struct TileCode<false> {
-  static __device__ __forceinline__ uint32_t pack(uint32_t tx, uint32_t ty, uint32_t) { return tx | (ty << 16); }
-  static __device__ __forceinline__ uint32_t x(uint32_t p) { return p & 0xffffu; }
-  static __device__ __forceinline__ uint32_t y(uint32_t p) { return (p >> 16) & 0x7fffu; }
+  static __device__ __forceinline__ uint32_t pack(uint32_t tx, uint32_t ty, uint32_t) { return tx | (ty << kTileXBits); }
+  static __device__ __forceinline__ uint32_t x(uint32_t p) { return p & field_max(kTileXBits); }
+  static __device__ __forceinline__ uint32_t y(uint32_t p) { return (p >> kTileXBits) & field_max(kTileYBits); }
   static __device__ __forceinline__ uint32_t frame(uint32_t) { return 0u; }
 };
 template <> struct TileCode<true> {
-  static __device__ __forceinline__ uint32_t pack(uint32_t tx, uint32_t ty, uint32_t f) { return tx | (ty << 13) | (f << 28); }
-  static __device__ __forceinline__ uint32_t x(uint32_t p) { return p & 0x1fffu; }
-  static __device__ __forceinline__ uint32_t y(uint32_t p) { return (p >> 13) & 0x7fffu; }
-  static __device__ __forceinline__ uint32_t frame(uint32_t p) { return (p >> 28) & 7u; }
+  static __device__ __forceinline__ uint32_t pack(uint32_t tx, uint32_t ty, uint32_t f) { return tx | (ty << kBatchTileXBits) | (f << kBatchFrameShift); }
+  static __device__ __forceinline__ uint32_t x(uint32_t p) { return p & field_max(kBatchTileXBits); }
+  static __device__ __forceinline__ uint32_t y(uint32_t p) { return (p >> kBatchTileXBits) & field_max(kTileYBits); }
+  static __device__ __forceinline__ uint32_t frame(uint32_t p) { return (p >> kBatchFrameShift) & field_max(kBatchFrameBits); }
 };
 __device__ __forceinline__ uint32_t tile_x(uint32_t packed) { return TileCode<false>::x(packed); }
 __device__ __forceinline__ uint32_t tile_y(uint32_t packed) { return TileCode<false>::y(packed); }
@@ -707,8 +710,8 @@ template <> struct LaunchArgs<true> { typedef RenderBatch type; };
 // into each other), its CLEAR macro tile, and the macro tile's previous cost.  Three wave scans (as many shuffles as two
 // lists cost before, plus one), a ballot for the number of macro tiles with a cost.  Rows of wave_cnt: 0 packed LIVE
 // totals per wave, 1 CLEAR (turned into its prefix in place), 2 cost sums, 3 cost counts, 4 exclusive prefix of row 0.
-// Threads 0, 1, 2 reserve the block's stretch of the NORMAL / CLEAR / HEAVY list (a.counters[0], [1], [3]), threads 3 and
-// 4 add the block's cost sum and count (a.counters[4], [5]) — five RETURNING atomics whose results are in LDS before
+// Threads 0, 1, 2 reserve the block's stretch of the NORMAL / CLEAR / HEAVY list (kQueueLive, kQueueClear, kQueueHeavy),
+// threads 3 and 4 add the block's cost sum and count (kQueueCostSum, kQueueCostCount) — five RETURNING atomics whose results are in LDS before
 // the barrier, hence performed before the block's ticket.
 constexpr int kClassifyRows = 5;
 
@@ -723,7 +726,7 @@ __device__ __forceinline__ uint32_t classify_take_cost(const RenderArgs& a, bool
 
 __device__ __forceinline__ bool classify_is_heavy(const RenderArgs& a, uint32_t cost)
 {
-  const uint32_t mean = a.counts[3];   // published by the previous classification
+  const uint32_t mean = a.counts[kCountMeanCost];   // published by the previous classification
   return a.heavy_x16 != 0u && mean != 0u && (uint64_t)cost * 16u > (uint64_t)mean * a.heavy_x16;
 }
 
@@ -767,7 +770,7 @@ __device__ __forceinline__ void classify_reserve(const RenderArgs& a, uint32_t (
     }
     if(k == 0u) sum &= 0xffffu;
     else if(k == 2u) sum >>= 16;
-    const uint32_t word[kClassifyRows] = {0u, 1u, 3u, 4u, 5u};
+    const uint32_t word[kClassifyRows] = {kQueueLive, kQueueClear, kQueueHeavy, kQueueCostSum, kQueueCostCount};
     block_base[k] = sum ? atomicAdd(&a.counters[word[k]], sum) : 0u;
   }
 }
@@ -1300,10 +1303,10 @@ constexpr uint32_t kListedThreads = 256;   // block size of the listed kernel: s
 // BATCH: the launch renders up to kMaxBatch frames (RenderBatch, trt_render_batch_dev): every list entry names its frame,
 // whose arguments the wave takes from the block's LDS copy of the batch.  The single-frame instantiations are the code they
 // were before batches existed.
-template <class Real, bool STATS, bool DK, bool RD, bool FB = false, bool BATCH = false>
-__global__ __launch_bounds__(256, (DK ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAVES : TRT_LISTED_WAVES_F64) - (STATS ? 1 : 0) - (RD ? 1 : 0))) void render_listed_kernel(const SceneK scene, const typename LaunchArgs<BATCH>::type args)
+template <class Real, bool STATS, bool ALT, bool RD, bool FB = false, bool BATCH = false>
+__global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAVES : TRT_LISTED_WAVES_F64) - (STATS ? 1 : 0) - (RD ? 1 : 0))) void render_listed_kernel(const SceneK scene, const typename LaunchArgs<BATCH>::type args)
 {
-  static_assert(!(BATCH && (RD || DK)), "batches: default solver, no RenderedData");
+  static_assert(!(BATCH && (RD || ALT)), "batches: default solver, no RenderedData");
   __shared__ SceneK     S;
   __shared__ RenderArgs A_lds[BATCH ? kMaxBatch : 1];
   __shared__ float4     rd_images[RD ? 4 : 1][RD ? 256 : 1];
@@ -1417,7 +1420,7 @@ __global__ __launch_bounds__(256, (DK ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAVE
           n_primary += (uint32_t)S.n_tori;
         }
         else
-          trace_pixel<Real, DK>(S, a, x, image_row(a, ly), ly, RdSink{RD ? rd_tile + rd_unit(ln & 7, ln >> 3, 0) : nullptr, nullptr},
+          trace_pixel<Real, ALT>(S, a, x, image_row(a, ly), ly, RdSink{RD ? rd_tile + rd_unit(ln & 7, ln >> 3, 0) : nullptr, nullptr},
                                 n_primary, n_bounce, n_shadow, wc);
       }
       // cost feedback (RenderArgs::tile_cost): what this wave spent on the tile, kept per macro tile as the maximum over its tiles
@@ -1585,8 +1588,7 @@ __global__ __launch_bounds__(256) void splat_points_kernel(const trt_point* __re
 // The keys, and so the image, are those of the one-pass form bit for bit (a minimum does not depend on the
 // order of its operands).  A point wider than a bin edge would need more than 4 records: such sizes, and images
 // with more than kSplatMaxBins bins, take the one-pass form.
-constexpr uint32_t kBinW = 128, kBinH = 64, kSplatMaxBins = 8192, kSplatChunk = 8192, kSplatMaxDim = 16383;
-constexpr uint32_t kSplatTicketWord = 5 * kSplatMaxBins;   // bin_words[…]: blocks of `count` that have finished (zero between calls)
+constexpr uint32_t kBinW = 128, kBinH = 64, kSplatChunk = 8192, kSplatMaxDim = 16383;   // (kSplatMaxBins: trt_kernels.hpp)
 
 struct SplatRec { uint32_t idx, z, rect; };   // rect = rx0 | rx1 << 7 | ry0 << 15 | ry1 << 21  (bin-relative, half-open)
 
@@ -2341,6 +2343,16 @@ SplatPlan splat_plan(uint32_t W, uint32_t H, float point_size, uint64_t n_points
   return pl;
 }
 
+namespace {
+// The bins the LDS arrays of a splat_bin_kernel / splat_scatter_sorted_kernel block hold: f(integral_constant<NB>).
+template <class F>
+void with_sort_bins(uint32_t n_bins, F&& f)
+{
+  if(n_bins <= 512u) f(std::integral_constant<uint32_t, 512>{});
+  else f(std::integral_constant<uint32_t, kSortBins>{});
+}
+}  // namespace
+
 hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp, uint32_t W, uint32_t H,
                         const float* clear, float point_size, const SplatScratch& sc, float* rgba, int n_cus,
                         const Tuning& tn, hipStream_t stream)
@@ -2354,11 +2366,13 @@ hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp
     SplatBins b{};
     b.bins_x = (W + kBinW - 1) / kBinW; b.bins_y = (H + kBinH - 1) / kBinH; b.n_bins = pl.n_bins;
     // fixed layout whatever n_bins is: the count words of one call never alias another call's offsets
-    b.count = sc.bin_words; b.offset = sc.bin_words + kSplatMaxBins; b.cursor = sc.bin_words + 2 * (size_t)kSplatMaxBins;
-    b.state   = reinterpret_cast<unsigned long long*>(sc.bin_words + 3 * (size_t)kSplatMaxBins);
+    b.count   = sc.bin_words + kSplatCountWord;
+    b.offset  = sc.bin_words + kSplatOffsetWord;
+    b.cursor  = sc.bin_words + kSplatCursorWord;
+    b.state   = reinterpret_cast<unsigned long long*>(sc.bin_words + kSplatStateWord);
     b.ticket  = sc.bin_words + kSplatTicketWord;
-    b.pool    = sc.bin_words + kSplatTicketWord + 1;
-    b.rticket = sc.bin_words + kSplatTicketWord + 2;
+    b.pool    = sc.bin_words + kSplatPoolWord;
+    b.rticket = sc.bin_words + kSplatRTicketWord;
     char* base = static_cast<char*>(sc.records);
     b.records  = reinterpret_cast<SplatRec*>(base);
     b.proj     = reinterpret_cast<uint2*>(base + pl.rec_bytes);
@@ -2378,8 +2392,9 @@ hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp
         uint32_t bgrid = (uint32_t)n_cus * 2u;
         if(tn.splat_blocks_per_cu) bgrid = (uint32_t)(n_cus * tn.splat_blocks_per_cu);
         if(bgrid == 0u || bgrid > schunks) bgrid = schunks;
-        if(pl.n_bins <= 512u) hipLaunchKernelGGL(splat_bin_kernel<512>, dim3(bgrid), dim3(kSortThreads), 0, stream, pts, n_points, a, b);
-        else hipLaunchKernelGGL(splat_bin_kernel<kSortBins>, dim3(bgrid), dim3(kSortThreads), 0, stream, pts, n_points, a, b);
+        with_sort_bins(pl.n_bins, [&](auto nb) {
+          hipLaunchKernelGGL(splat_bin_kernel<decltype(nb)::value>, dim3(bgrid), dim3(kSortThreads), 0, stream, pts, n_points, a, b);
+        });
       }
       hipLaunchKernelGGL(splat_resolve_bins_kernel<true>, rgrid, rblock, 0, stream, pts, a, b, cl, reinterpret_cast<float4*>(rgba));
       return hipGetLastError();
@@ -2390,10 +2405,9 @@ hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp
       if(b.table)   // sorted scatter, two passes (-DTRT_TUNING builds: TRT_SPLAT_VARIANT=1)
       {
         hipLaunchKernelGGL((splat_count_kernel<kSortChunk, 4, true>), dim3((schunks + 3) / 4), dim3(1024), 4 * pl.n_bins * sizeof(uint32_t), stream, pts, n_points, a, b);
-        if(pl.n_bins <= 512u)
-          hipLaunchKernelGGL(splat_scatter_sorted_kernel<512>, dim3(schunks), dim3(kSortThreads), 0, stream, n_points, b);
-        else
-          hipLaunchKernelGGL(splat_scatter_sorted_kernel<kSortBins>, dim3(schunks), dim3(kSortThreads), 0, stream, n_points, b);
+        with_sort_bins(pl.n_bins, [&](auto nb) {
+          hipLaunchKernelGGL(splat_scatter_sorted_kernel<decltype(nb)::value>, dim3(schunks), dim3(kSortThreads), 0, stream, n_points, b);
+        });
       }
       else
       {
@@ -2420,6 +2434,21 @@ hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp
 // ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
+namespace {
+// The one place that maps the scene's precision and solver family to <Real, ALT>: returns f(Real{}, Alt<ALT>{}).  The
+// callers instantiate only the kernels they launch (if constexpr on the tags).
+template <bool ALT> using Alt = std::integral_constant<bool, ALT>;
+template <class F>
+hipError_t with_solver(const SceneK& scene, F&& f)
+{
+  const bool alt = scene.alt_solver != kSolverWalk;
+  if(scene.f64 && alt) return f(double{}, Alt<true>{});
+  if(scene.f64) return f(double{}, Alt<false>{});
+  if(alt) return f(float{}, Alt<true>{});
+  return f(float{}, Alt<false>{});
+}
+}  // namespace
+
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream)
 {
   if(a.rays.n == 0)
@@ -2429,11 +2458,10 @@ hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& t
   if(tn.trace_blocks) cap = tn.trace_blocks;
   if(cap == 0) cap = 1;
   const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-  if(scene.f64 && scene.dk) hipLaunchKernelGGL((trace_kernel<double, true>), dim3(grid), dim3(256), 0, stream, scene, a);
-  else if(scene.f64) hipLaunchKernelGGL((trace_kernel<double, false>), dim3(grid), dim3(256), 0, stream, scene, a);
-  else if(scene.dk) hipLaunchKernelGGL((trace_kernel<float, true>), dim3(grid), dim3(256), 0, stream, scene, a);
-  else hipLaunchKernelGGL((trace_kernel<float, false>), dim3(grid), dim3(256), 0, stream, scene, a);
-  return hipGetLastError();
+  return with_solver(scene, [&](auto real, auto alt) {
+    hipLaunchKernelGGL((trace_kernel<decltype(real), decltype(alt)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+    return hipGetLastError();
+  });
 }
 
 // Zeroes up to 64 words (the query counters of a counted launch) with a one-wave kernel: a kernel
@@ -2480,84 +2508,134 @@ Tuning tuning_from_env()
   u64("TRT_TRACE_BLOCKS", t.trace_blocks);
   u64("TRT_POST_BLOCKS_PER_CU", t.post_blocks_per_cu);
   u64("TRT_SPLAT_BLOCKS_PER_CU", t.splat_blocks_per_cu);
-  i32("TRT_TRACE_VARIANT", t.trace_variant);
   i32("TRT_SPLAT_VARIANT", t.splat_variant);
 #endif
   return t;
 }
+
+namespace {
+
+// Static mapping, lane <-> pixel for the whole bounce loop.  Wave tile shape TRT_TILE = 8x8 (default) | 16x4 | 32x2 | 64x1,
+// the FP32 walk only: the FP64 and alternative-solver kernels exist for 8x8 (and are launched with the grid of TRT_TILE).
+hipError_t launch_static(const SceneK& scene, const RenderArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  int tw = tn.static_tile;
+  if(tw != 8 && tw != 16 && tw != 32 && tw != 64) tw = 8;
+  const uint64_t stiles = (uint64_t)((a.W + tw - 1) / tw) * ((a.n_local_rows + 64 / tw - 1) / (64 / tw));
+  const dim3 grid((uint32_t)((stiles + 3) / 4)), block(256);
+  return with_solver(scene, [&](auto real, auto alt) {
+    using Real = decltype(real);
+    constexpr bool ALT = decltype(alt)::value;
+    if constexpr(std::is_same<Real, float>::value && !ALT)
+    {
+      if(tw == 16) hipLaunchKernelGGL((render_static_kernel<float, 16, false>), grid, block, 0, stream, scene, a);
+      else if(tw == 32) hipLaunchKernelGGL((render_static_kernel<float, 32, false>), grid, block, 0, stream, scene, a);
+      else if(tw == 64) hipLaunchKernelGGL((render_static_kernel<float, 64, false>), grid, block, 0, stream, scene, a);
+      else hipLaunchKernelGGL((render_static_kernel<float, 8, false>), grid, block, 0, stream, scene, a);
+    }
+    else
+      hipLaunchKernelGGL((render_static_kernel<Real, 8, ALT>), grid, block, 0, stream, scene, a);
+    return hipGetLastError();
+  });
+}
+
+// The classification in front of the listed and the persistent kernel: one lane per macro tile, or per 8×8 tile when
+// `fine`; FB: with the cost feedback of the listed kernel.
+template <bool BATCH>
+void launch_classify(bool fine, bool fb, uint64_t lanes, const SceneK& scene, const typename LaunchArgs<BATCH>::type& args,
+                     hipStream_t stream)
+{
+  const dim3 grid((uint32_t)((lanes + kClassifyThreads - 1) / kClassifyThreads)), block(kClassifyThreads);
+  if(fine && fb) hipLaunchKernelGGL((tile_classify_fine_kernel<true, BATCH>), grid, block, 0, stream, scene, args);
+  else if(fine) hipLaunchKernelGGL((tile_classify_fine_kernel<false, BATCH>), grid, block, 0, stream, scene, args);
+  else if(fb) hipLaunchKernelGGL((tile_classify_kernel<true, BATCH>), grid, block, 0, stream, scene, args);
+  else hipLaunchKernelGGL((tile_classify_kernel<false, BATCH>), grid, block, 0, stream, scene, args);
+}
+
+// Grid of the listed kernel: one wave per 16 tiles (4096²: 16,384 blocks = 64 per CU), at least 4 blocks per CU, never
+// more waves than tiles.  With ≈16 % of the tiles LIVE a wave traces at most one tile and writes ≈1 clear macro tile, so
+// the dispatcher balances single tiles and compute/store phases of different blocks interleave on every CU (measured
+// optimum at 2048², 4096² and 8192²; 8,192 blocks cost +25 % at 4096²).
+uint32_t listed_grid(uint64_t tiles, int n_cus, const Tuning& tn)
+{
+  uint64_t cap = tiles / 16 > (uint64_t)n_cus * 4 ? tiles / 16 : (uint64_t)n_cus * 4;
+  if(tn.listed_blocks) cap = tn.listed_blocks;
+  constexpr uint32_t wpb = kListedThreads / 64;   // the kernel's staging assumes 256-thread blocks (64 / 128: measured slower)
+  return (uint32_t)((tiles + wpb - 1) / wpb < cap ? (tiles + wpb - 1) / wpb : cap);
+}
+
+template <class Real, bool STATS, bool ALT, bool RD, bool FB, bool BATCH>
+void launch_listed_kernel(const SceneK& scene, const typename LaunchArgs<BATCH>::type& args, uint32_t grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL((render_listed_kernel<Real, STATS, ALT, RD, FB, BATCH>), dim3(grid), dim3(kListedThreads), 0, stream,
+                     scene, args);
+}
+
+// The one place that picks the listed instantiation.  Cost feedback (fb) runs with the walk and without counters only
+// (the callers decide); RenderedData (rd) exists for single frames only — in a batch its instantiations are the plain ones.
+template <class Real, bool ALT, bool BATCH>
+void launch_listed(const SceneK& scene, const typename LaunchArgs<BATCH>::type& args, bool fb, bool rd, bool stats,
+                   uint32_t grid, hipStream_t stream)
+{
+  static_assert(!(BATCH && ALT), "batches: default solver");
+  constexpr bool RD = !BATCH;
+  if constexpr(!ALT)
+  {
+    if(fb)
+    {
+      if(rd) launch_listed_kernel<Real, false, false, RD, true, BATCH>(scene, args, grid, stream);
+      else launch_listed_kernel<Real, false, false, false, true, BATCH>(scene, args, grid, stream);
+      return;
+    }
+  }
+  if(rd && stats) launch_listed_kernel<Real, true, ALT, RD, false, BATCH>(scene, args, grid, stream);
+  else if(rd) launch_listed_kernel<Real, false, ALT, RD, false, BATCH>(scene, args, grid, stream);
+  else if(stats) launch_listed_kernel<Real, true, ALT, false, false, BATCH>(scene, args, grid, stream);
+  else launch_listed_kernel<Real, false, ALT, false, false, BATCH>(scene, args, grid, stream);
+}
+
+// Persistent wavefronts: kPersistentBlocksPerCU blocks of 4 waves per CU, never more waves than tiles; the walk only.
+hipError_t launch_persistent(const SceneK& scene, const RenderArgs& a, uint64_t tiles, int n_cus, const Tuning& tn,
+                             hipStream_t stream)
+{
+  uint64_t cap = (uint64_t)n_cus * kPersistentBlocksPerCU;
+  if(tn.persist_blocks) cap = tn.persist_blocks;
+  const uint32_t grid = (uint32_t)((tiles + 3) / 4 < cap ? (tiles + 3) / 4 : cap);
+  return with_solver(scene, [&](auto real, auto alt) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;   // (trt_api.hip refuses this before)
+    else
+    {
+      hipLaunchKernelGGL(render_persistent_kernel<decltype(real)>, dim3(grid), dim3(256), 0, stream, scene, a);
+      return hipGetLastError();
+    }
+  });
+}
+
+}  // namespace
 
 hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, int n_cus, const Tuning& tn,
                          hipStream_t stream)
 {
   if(a.n_local_rows == 0 || a.W == 0)
     return hipSuccess;
-  const uint64_t tiles = (uint64_t)((a.W + 7) / 8) * ((a.n_local_rows + 7) / 8);
-  if(v == kRenderPersistent || v == kRenderListed)
-  {
-    // 1. classify the tiles into the LIVE and CLEAR lists (one lane per macro tile, or per 8×8 tile when a.fine)
-    const uint64_t macros = (uint64_t)(((a.W + 7) / 8 + kMacroTiles - 1) / kMacroTiles) * ((a.n_local_rows + 7) / 8);
-    const uint64_t lanes  = a.fine ? macros * kMacroTiles : macros;
-    // cost feedback: the plain listed kernels only (the counted and the alternative-solver instantiations go without)
-    const bool fb = v == kRenderListed && a.tile_cost != nullptr && a.heavy_x16 != 0u && a.stats == nullptr && !scene.dk;
-    const dim3 cgrid((uint32_t)((lanes + kClassifyThreads - 1) / kClassifyThreads));
-    if(a.fine && fb) hipLaunchKernelGGL(tile_classify_fine_kernel<true>, cgrid, dim3(kClassifyThreads), 0, stream, scene, a);
-    else if(a.fine) hipLaunchKernelGGL(tile_classify_fine_kernel<false>, cgrid, dim3(kClassifyThreads), 0, stream, scene, a);
-    else if(fb) hipLaunchKernelGGL(tile_classify_kernel<true>, cgrid, dim3(kClassifyThreads), 0, stream, scene, a);
-    else hipLaunchKernelGGL(tile_classify_kernel<false>, cgrid, dim3(kClassifyThreads), 0, stream, scene, a);
-    // 2. resident grid: kPersistentBlocksPerCU blocks of 4 waves per CU, never more waves than tiles
-    uint64_t cap = (uint64_t)n_cus * kPersistentBlocksPerCU;
-    if(tn.persist_blocks) cap = tn.persist_blocks;
-    if(v == kRenderListed)
-    {
-      // one wave per 16 tiles (4096²: 16,384 blocks = 64 per CU): with ≈16 % of the tiles LIVE a
-      // wave traces at most one tile and writes ≈1 clear macro tile, so the dispatcher balances
-      // single tiles and compute/store phases of different blocks interleave on every CU
-      // (measured optimum at 2048², 4096² and 8192²; 8,192 blocks cost +25 % at 4096²)
-      uint64_t lcap = tiles / 16 > (uint64_t)n_cus * 4 ? tiles / 16 : (uint64_t)n_cus * 4;
-      if(tn.listed_blocks) lcap = tn.listed_blocks;
-      constexpr uint32_t bthreads = kListedThreads, wpb = bthreads / 64;   // the kernel's staging assumes 256-thread blocks (64 / 128: measured slower)
-      const uint32_t lgrid = (uint32_t)((tiles + wpb - 1) / wpb < lcap ? (tiles + wpb - 1) / wpb : lcap);
-#define TRT_LAUNCH_LISTED(REAL, DK_)                                                                                   \
-  do {                                                                                                                 \
-    if(fb && a.rendered) hipLaunchKernelGGL((render_listed_kernel<REAL, false, false, true, true>), dim3(lgrid), dim3(bthreads), 0, stream, scene, a);  \
-    else if(fb) hipLaunchKernelGGL((render_listed_kernel<REAL, false, false, false, true>), dim3(lgrid), dim3(bthreads), 0, stream, scene, a);      \
-    else if(a.rendered && a.stats) hipLaunchKernelGGL((render_listed_kernel<REAL, true, DK_, true>), dim3(lgrid), dim3(bthreads), 0, stream, scene, a);  \
-    else if(a.rendered) hipLaunchKernelGGL((render_listed_kernel<REAL, false, DK_, true>), dim3(lgrid), dim3(bthreads), 0, stream, scene, a);       \
-    else if(a.stats) hipLaunchKernelGGL((render_listed_kernel<REAL, true, DK_, false>), dim3(lgrid), dim3(bthreads), 0, stream, scene, a);          \
-    else hipLaunchKernelGGL((render_listed_kernel<REAL, false, DK_, false>), dim3(lgrid), dim3(bthreads), 0, stream, scene, a);                     \
-  } while(0)
-      if(scene.f64 && scene.dk) TRT_LAUNCH_LISTED(double, true);
-      else if(scene.f64) TRT_LAUNCH_LISTED(double, false);
-      else if(scene.dk) TRT_LAUNCH_LISTED(float, true);
-      else TRT_LAUNCH_LISTED(float, false);
-#undef TRT_LAUNCH_LISTED
-      return hipGetLastError();
-    }
-    if(scene.dk)
-      return hipErrorInvalidValue;  // the persistent variant implements the default solver only (trt_api.hip checks)
-    const uint32_t grid = (uint32_t)((tiles + 3) / 4 < cap ? (tiles + 3) / 4 : cap);
-    if(scene.f64)
-      hipLaunchKernelGGL(render_persistent_kernel<double>, dim3(grid), dim3(256), 0, stream, scene, a);
-    else
-      hipLaunchKernelGGL(render_persistent_kernel<float>, dim3(grid), dim3(256), 0, stream, scene, a);
+  if(v == kRenderStatic)
+    return launch_static(scene, a, tn, stream);
+  // 1. classify the tiles into the LIVE and CLEAR lists
+  const uint64_t tiles  = (uint64_t)tile_count(a.W) * tile_count(a.n_local_rows);
+  const uint64_t macros = (uint64_t)macro_count(tile_count(a.W)) * tile_count(a.n_local_rows);
+  // cost feedback: the plain listed kernels only (the counted and the alternative-solver instantiations go without)
+  const bool fb = v == kRenderListed && a.tile_cost != nullptr && a.heavy_x16 != 0u && a.stats == nullptr &&
+                  scene.alt_solver == kSolverWalk;
+  launch_classify<false>(a.fine, fb, a.fine ? macros * kMacroTiles : macros, scene, a, stream);
+  // 2. render the lists
+  if(v == kRenderPersistent)
+    return launch_persistent(scene, a, tiles, n_cus, tn, stream);
+  const uint32_t grid = listed_grid(tiles, n_cus, tn);
+  return with_solver(scene, [&](auto real, auto alt) {
+    launch_listed<decltype(real), decltype(alt)::value, false>(scene, a, fb, a.rendered != nullptr, a.stats != nullptr, grid, stream);
     return hipGetLastError();
-  }
-  // wave tile shape of the static kernel: TRT_TILE = 8x8 (default) | 16x4 | 32x2 | 64x1
-  int tw = tn.static_tile;
-  if(tw != 8 && tw != 16 && tw != 32 && tw != 64) tw = 8;
-  const uint64_t stiles = (uint64_t)((a.W + tw - 1) / tw) * ((a.n_local_rows + 64 / tw - 1) / (64 / tw));
-  const uint32_t grid = (uint32_t)((stiles + 3) / 4);
-#define TRT_LAUNCH_STATIC(REAL, TW_, DK_) \
-  hipLaunchKernelGGL((render_static_kernel<REAL, TW_, DK_>), dim3(grid), dim3(256), 0, stream, scene, a)
-  if(scene.f64 && scene.dk) TRT_LAUNCH_STATIC(double, 8, true);
-  else if(scene.f64) TRT_LAUNCH_STATIC(double, 8, false);
-  else if(scene.dk) TRT_LAUNCH_STATIC(float, 8, true);
-  else if(tw == 16) TRT_LAUNCH_STATIC(float, 16, false);
-  else if(tw == 32) TRT_LAUNCH_STATIC(float, 32, false);
-  else if(tw == 64) TRT_LAUNCH_STATIC(float, 64, false);
-  else TRT_LAUNCH_STATIC(float, 8, false);
-#undef TRT_LAUNCH_STATIC
-  return hipGetLastError();
+  });
 }
 
 // A batch of frames with the listed kernel (trt_render_batch_dev): one classification over every frame's tiles, one
@@ -2567,29 +2645,14 @@ hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, int n_
   const RenderArgs& a = b.fr[0];
   if(b.n_frames == 0 || a.n_local_rows == 0 || a.W == 0)
     return hipSuccess;
-  if(scene.dk || a.rendered)
+  if(scene.alt_solver != kSolverWalk || a.rendered)
     return hipErrorInvalidValue;   // (trt_api.hip refuses these before)
-  const uint64_t tiles = (uint64_t)((a.W + 7) / 8) * ((a.n_local_rows + 7) / 8) * b.n_frames;
-  const uint64_t lanes = (uint64_t)b.per_frame * b.n_frames;
+  const uint64_t tiles = (uint64_t)tile_count(a.W) * tile_count(a.n_local_rows) * b.n_frames;
   const bool fb = a.tile_cost != nullptr && a.heavy_x16 != 0u && a.stats == nullptr;
-  const dim3 cgrid((uint32_t)((lanes + kClassifyThreads - 1) / kClassifyThreads));
-  if(a.fine && fb) hipLaunchKernelGGL((tile_classify_fine_kernel<true, true>), cgrid, dim3(kClassifyThreads), 0, stream, scene, b);
-  else if(a.fine) hipLaunchKernelGGL((tile_classify_fine_kernel<false, true>), cgrid, dim3(kClassifyThreads), 0, stream, scene, b);
-  else if(fb) hipLaunchKernelGGL((tile_classify_kernel<true, true>), cgrid, dim3(kClassifyThreads), 0, stream, scene, b);
-  else hipLaunchKernelGGL((tile_classify_kernel<false, true>), cgrid, dim3(kClassifyThreads), 0, stream, scene, b);
-  uint64_t lcap = tiles / 16 > (uint64_t)n_cus * 4 ? tiles / 16 : (uint64_t)n_cus * 4;   // as launch_render: one wave per 16 tiles
-  if(tn.listed_blocks) lcap = tn.listed_blocks;
-  constexpr uint32_t wpb = kListedThreads / 64;
-  const uint32_t lgrid = (uint32_t)((tiles + wpb - 1) / wpb < lcap ? (tiles + wpb - 1) / wpb : lcap);
-#define TRT_LAUNCH_BATCH(REAL)                                                                                                        \
-  do {                                                                                                                                \
-    if(fb) hipLaunchKernelGGL((render_listed_kernel<REAL, false, false, false, true, true>), dim3(lgrid), dim3(kListedThreads), 0, stream, scene, b);      \
-    else if(a.stats) hipLaunchKernelGGL((render_listed_kernel<REAL, true, false, false, false, true>), dim3(lgrid), dim3(kListedThreads), 0, stream, scene, b);  \
-    else hipLaunchKernelGGL((render_listed_kernel<REAL, false, false, false, false, true>), dim3(lgrid), dim3(kListedThreads), 0, stream, scene, b);       \
-  } while(0)
-  if(scene.f64) TRT_LAUNCH_BATCH(double);
-  else TRT_LAUNCH_BATCH(float);
-#undef TRT_LAUNCH_BATCH
+  launch_classify<true>(a.fine, fb, (uint64_t)b.per_frame * b.n_frames, scene, b, stream);
+  const uint32_t grid = listed_grid(tiles, n_cus, tn);
+  if(scene.f64) launch_listed<double, false, true>(scene, b, fb, false, a.stats != nullptr, grid, stream);
+  else launch_listed<float, false, true>(scene, b, fb, false, a.stats != nullptr, grid, stream);
   return hipGetLastError();
 }
 

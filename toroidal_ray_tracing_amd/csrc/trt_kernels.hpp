@@ -9,6 +9,70 @@
 
 namespace trt {
 
+// ---- The contract between the host (trt_api.hip) and the kernels (trt_kernels.hip) ------------------------------------
+// Every layout both sides index is stated here once; the kernels' own arithmetic on these indices is pinned by
+// static_asserts next to it.
+
+// ctx->d_queue: the words of the tile-list classification (zero when the ctx is created).  Accumulators, zero between
+// frames (the classification's last block moves them to the counts and resets them), then the counts it publishes.
+enum QueueWord : uint32_t {
+  kQueueLive        = 0,    // NORMAL LIVE tiles reserved
+  kQueueClear       = 1,    // CLEAR macro tiles reserved
+  kQueueShardTicket = 2,    // second-level ticket: shards whose blocks have all finished
+  kQueueHeavy       = 3,    // HEAVY LIVE tiles reserved
+  kQueueCostSum     = 4,    // cost sum and count of the macro tiles with a cost
+  kQueueCostCount   = 5,
+  kQueueTickets     = 8,    // kQueueShards words: blocks finished per shard
+  kQueueShards      = 8,
+  kQueueCounts      = 32,   // kCountWords words: RenderArgs::counts
+  kQueueWords       = 64,
+};
+// RenderArgs::counts: what the classification publishes for the render kernels (written, never added to).
+enum CountWord : uint32_t {
+  kCountLive     = 0,   // #LIVE tiles
+  kCountClear    = 1,   // #CLEAR macro tiles
+  kCountHeavy    = 2,   // how many of the LIVE tiles are HEAVY
+  kCountMeanCost = 3,   // mean cost of the traced macro tiles: the threshold of the NEXT frame's classification
+  kCountWords    = 4,
+};
+static_assert(kQueueTickets >= kQueueCostCount + 1 && kQueueCounts >= kQueueTickets + kQueueShards &&
+              kQueueWords >= kQueueCounts + kCountWords, "queue words overlap");
+
+// ctx->d_stats: the 64-bit query counters of a counted launch (block_add_stats; zeroed as 2·kStatWords 32-bit words).
+enum StatWord : uint32_t {
+  kStatPrimary = 0, kStatBounce = 1, kStatShadow = 2,   // tests per ray class
+  kStatTraced  = 4, kStatSolved = 5, kStatEvals  = 6,   // tests executed, quartics solved, walk evaluations
+  kStatWords   = 8,
+};
+
+// Tiles: the classification and the list kernels work on kTile×kTile pixel tiles, the classification on macro tiles of
+// kMacroTiles horizontally adjacent tiles (32×8 pixels: one 128-B line of every first-hit stream per row).
+constexpr uint32_t kTile       = 8;
+constexpr uint32_t kMacroTiles = 4;
+constexpr uint32_t tile_count(uint32_t pixels) { return (pixels + kTile - 1) / kTile; }
+constexpr uint32_t macro_count(uint32_t tiles) { return (tiles + kMacroTiles - 1) / kMacroTiles; }
+// Tile-list entries (TileCode in trt_kernels.hip).  One frame per launch: tx | ty << kTileXBits [| kTileMissFlag].
+// A batch of frames: tx | ty << kBatchTileXBits | frame << kBatchFrameShift [| kTileMissFlag].
+constexpr uint32_t kTileXBits = 16, kTileYBits = 15;
+constexpr uint32_t kBatchTileXBits = 13, kBatchFrameShift = 28, kBatchFrameBits = 3;
+constexpr uint32_t kTileMissFlag = 0x80000000u;
+constexpr uint32_t field_max(uint32_t bits) { return (1u << bits) - 1u; }
+static_assert(kTileXBits + kTileYBits <= 31 && kBatchTileXBits + kTileYBits <= kBatchFrameShift &&
+              kBatchFrameShift + kBatchFrameBits <= 31 && (1u << kBatchFrameBits) >= TRT_MAX_BATCH,
+              "tile-list fields overlap the miss flag or each other");
+
+// The re-projection's bin words (SplatScratch::bin_words), laid out for the largest bin count whatever a call uses.
+constexpr uint32_t kSplatMaxBins     = 8192;
+constexpr size_t   kSplatCountWord   = 0;                  // per bin: records (zero between calls)
+constexpr size_t   kSplatOffsetWord  = kSplatMaxBins;      // per bin: first record
+constexpr size_t   kSplatCursorWord  = 2 * kSplatMaxBins;  // per bin: scatter cursor
+constexpr size_t   kSplatStateWord   = 3 * kSplatMaxBins;  // per bin: 64-bit page state (two words)
+constexpr size_t   kSplatTicketWord  = 5 * kSplatMaxBins;  // blocks of `count` that have finished (zero between calls)
+constexpr size_t   kSplatPoolWord    = kSplatTicketWord + 1;
+constexpr size_t   kSplatRTicketWord = kSplatTicketWord + 2;
+constexpr size_t   kSplatBinWords    = kSplatTicketWord + 64;   // + the ticket, pool and rticket words and a reserved tail
+static_assert(kSplatStateWord % 2 == 0, "the page state is 64-bit");
+
 struct RenderArgs {
   trt_globals g;       // GlobalUniforms, by value in the kernel-argument segment
   trt_push    pc;      // PushConstantRay
@@ -24,14 +88,13 @@ struct RenderArgs {
   float*             rgba;      // [H][W][4]                      (rgen:87)
   trt_hits           hits;      // SoA depth-0 hit record, y*W+x  (optional streams)
   trt_rendered_data* rendered;  // AoS, x*H+y                     (BEF rgen:72-73,111-112)
-  unsigned long long* stats;    // [4]: primary, bounce, shadow tests, pixels (optional)
-  // tile lists built by tile_classify*_kernel (packed tx | ty << 16 [| miss flag])
-  unsigned int*       counters;     // accumulators of the classification: [0] LIVE, [1] CLEAR, [2] shards done, [8..15] blocks done per shard.
+  unsigned long long* stats;    // [kStatWords]: StatWord (optional)
+  // tile lists built by tile_classify*_kernel (TileCode entries)
+  unsigned int*       counters;     // ctx->d_queue: the QueueWord accumulators of the classification.
                                     // Zero between frames: the LAST classification block of a frame publishes the
                                     // totals to `counts` and resets them (no memset, no double buffering: a frame
                                     // depends on no other frame, eager or replayed from a hipGraph)
-  unsigned int*       counts;       // [0] = #LIVE tiles, [1] = #CLEAR macro tiles of this frame (written, never added to);
-                                    // [2] = how many of the LIVE tiles are HEAVY, [3] = mean cost of the previous frame's traced macro tiles
+  unsigned int*       counts;       // counters + kQueueCounts: [kCountWords], CountWord
   uint32_t*           tiles_live;   // tiles that need ray tracing
   uint32_t*           tiles_clear;  // macro tiles whose every pixel provably misses
   // Cost feedback: the listed kernel leaves the time (100-MHz ticks) its slowest wave spent on each traced macro tile; the
@@ -81,7 +144,6 @@ struct Tuning {
   uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
   uint64_t splat_blocks_per_cu = 0;   // TRT_SPLAT_BLOCKS_PER_CU
-  int      trace_variant      = -1;   // TRT_TRACE_VARIANT
   int      splat_variant      = -1;   // TRT_SPLAT_VARIANT
 };
 Tuning tuning_from_env();   // defaults in the release build
@@ -100,9 +162,7 @@ hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_
                        hipStream_t stream);
 // Scratch of the re-projection: the binned form (mode != 0: kSplatBinWords zero-initialised words + the 12-B records of
 // the mode, splat_plan) or the one-pass form (keys: W·H 64-bit words).
-constexpr size_t kSplatBinWords   = 5 * 8192 + 64;   // count / offset / cursor / 64-bit page state for the largest bin count, + the ticket, pool and error words
 constexpr size_t kSplatRecordSize = 12;
-constexpr size_t kSplatSortBins = 2048, kSplatSortChunk = 4096;   // = kSortBins, kSortChunk of trt_kernels.hip
 enum SplatMode { kSplatOnePass = 0, kSplatSorted = 1, kSplatDirect = 2, kSplatPaged = 3 };
 // What a call needs (splat_plan): the form it takes and the bytes of ctx scratch behind `records`, laid out as
 // [records | proj | table | page_bin], every part 16-byte aligned.
