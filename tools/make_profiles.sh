@@ -7,7 +7,8 @@ set -u
 ROUND=${1:-r01}; V=${2:-listed}
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/profiles_$ROUND
 mkdir -p $OUT
-# the kernel sources these passes measure: bench.py reports `roofline.traffic` only while they are unchanged
+# the render path's sources these passes measure (the same list as bench.py; the tonemap and the re-projection have
+# files of their own and are not in it): bench.py reports `roofline.traffic` only while they are unchanged
 cat $R/toroidal_ray_tracing_amd/csrc/trt_kernels.hip $R/toroidal_ray_tracing_amd/csrc/trt_device.hpp $R/toroidal_ray_tracing_amd/csrc/trt_kernels.hpp \
     $R/toroidal_ray_tracing_amd/csrc/trt_api.hip | sha256sum | cut -d" " -f1 > $OUT/kernel_sources.sha256
 cd /tmp && export TMPDIR=/tmp

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "trt_kernels.hpp"
+#include "trt_splat.hpp"
 
 using namespace trt;
 

@@ -32,6 +32,15 @@ __device__ __forceinline__ float  min_(float a, float b) { return fminf(a, b); }
 __device__ __forceinline__ double min_(double a, double b) { return fmin(a, b); }
 __device__ __forceinline__ float  abs_(float a) { return fabsf(a); }
 __device__ __forceinline__ double abs_(double a) { return fabs(a); }
+__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }   // (min(int, uint32_t) resolves to the double overload)
+
+// Timing ablations (skip the CLEAR or the LIVE part of a frame, phases of the re-projection) exist in -DTRT_TUNING builds
+// only: the release library has no switch that returns an incomplete image with TRT_OK.
+#ifdef TRT_TUNING
+#define TRT_SKIP(a, bit) ((a).debug_skip & (bit))
+#else
+#define TRT_SKIP(a, bit) false
+#endif
 
 struct v3 { float x, y, z; };
 

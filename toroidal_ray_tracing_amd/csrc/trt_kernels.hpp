@@ -1,6 +1,6 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_kernels.hip).  Host-side only types; no HIP runtime types leak past this header
-// except hipStream_t / hipError_t.
+// (trt_kernels.hip, trt_post.hip; the re-projection's half is trt_splat.hpp).  Host-side only types;
+// no HIP runtime types leak past this header except hipStream_t / hipError_t.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,7 +9,7 @@
 
 namespace trt {
 
-// ---- The contract between the host (trt_api.hip) and the kernels (trt_kernels.hip) ------------------------------------
+// ---- The contract between the host (trt_api.hip) and the render kernels (trt_kernels.hip) -----------------------------
 // Every layout both sides index is stated here once; the kernels' own arithmetic on these indices is pinned by
 // static_asserts next to it.
 
@@ -60,18 +60,6 @@ constexpr uint32_t field_max(uint32_t bits) { return (1u << bits) - 1u; }
 static_assert(kTileXBits + kTileYBits <= 31 && kBatchTileXBits + kTileYBits <= kBatchFrameShift &&
               kBatchFrameShift + kBatchFrameBits <= 31 && (1u << kBatchFrameBits) >= TRT_MAX_BATCH,
               "tile-list fields overlap the miss flag or each other");
-
-// The re-projection's bin words (SplatScratch::bin_words), laid out for the largest bin count whatever a call uses.
-constexpr uint32_t kSplatMaxBins     = 8192;
-constexpr size_t   kSplatCountWord   = 0;                  // per bin: records (zero between calls)
-constexpr size_t   kSplatOffsetWord  = kSplatMaxBins;      // per bin: first record
-constexpr size_t   kSplatCursorWord  = 2 * kSplatMaxBins;  // per bin: scatter cursor
-constexpr size_t   kSplatStateWord   = 3 * kSplatMaxBins;  // per bin: 64-bit page state (two words)
-constexpr size_t   kSplatTicketWord  = 5 * kSplatMaxBins;  // blocks of `count` that have finished (zero between calls)
-constexpr size_t   kSplatPoolWord    = kSplatTicketWord + 1;
-constexpr size_t   kSplatRTicketWord = kSplatTicketWord + 2;
-constexpr size_t   kSplatBinWords    = kSplatTicketWord + 64;   // + the ticket, pool and rticket words and a reserved tail
-static_assert(kSplatStateWord % 2 == 0, "the page state is 64-bit");
 
 struct RenderArgs {
   trt_globals g;       // GlobalUniforms, by value in the kernel-argument segment
@@ -160,30 +148,6 @@ constexpr int kPersistentBlocksPerCU = 16;  // 4× the resident 4 blocks/CU: the
 
 hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_out, int n_cus, const Tuning& tn,
                        hipStream_t stream);
-// Scratch of the re-projection: the binned form (mode != 0: kSplatBinWords zero-initialised words + the 12-B records of
-// the mode, splat_plan) or the one-pass form (keys: W·H 64-bit words).
-constexpr size_t kSplatRecordSize = 12;
-enum SplatMode { kSplatOnePass = 0, kSplatSorted = 1, kSplatDirect = 2, kSplatPaged = 3 };
-// What a call needs (splat_plan): the form it takes and the bytes of ctx scratch behind `records`, laid out as
-// [records | proj | table | page_bin], every part 16-byte aligned.
-struct SplatPlan {
-  int      mode;        // SplatMode
-  uint32_t n_bins;
-  uint32_t page_shift;  // paged: a page holds 1 << page_shift records
-  uint32_t pool_pages;  // paged: pages behind the bins' first pages
-  size_t   rec_bytes, proj_bytes, table_bytes, pagebin_bytes;
-  size_t   total() const { return rec_bytes + proj_bytes + table_bytes + pagebin_bytes; }
-};
-struct SplatScratch {
-  SplatPlan           plan;
-  uint32_t*           bin_words;
-  void*               records;   // plan.total() bytes
-  unsigned long long* keys;
-};
-SplatPlan  splat_plan(uint32_t W, uint32_t H, float point_size, uint64_t n_points, const Tuning& tn);
-hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp, uint32_t W, uint32_t H,
-                        const float* clear, float point_size, const SplatScratch& sc, float* rgba, int n_cus,
-                        const Tuning& tn, hipStream_t stream);
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, int n_cus, const Tuning& tn,
