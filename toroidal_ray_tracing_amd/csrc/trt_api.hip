@@ -147,6 +147,41 @@ std::array<void**, 8> hit_streams(trt_hits& h)
   return {{(void**)&h.t, (void**)&h.px, (void**)&h.py, (void**)&h.pz, (void**)&h.nx, (void**)&h.ny, (void**)&h.nz, (void**)&h.id}};
 }
 
+// Host staging of the hit streams for the entry points that take host pointers (trt_trace, trt_render).  stage_hits()
+// points every stream of `dev` that the caller wants (non-NULL in `want`) at ctx->d_out[k], grown to `bytes`, and leaves
+// the others NULL; fetch_hits() copies those streams back and waits for the default stream.
+int stage_hits(trt_ctx* ctx, trt_hits& want, size_t bytes, trt_hits& dev)
+{
+  std::memset(&dev, 0, sizeof dev);
+  const auto dst = hit_streams(want), dptr = hit_streams(dev);
+  for(int k = 0; k < 8; ++k)
+    if(*dst[k] && bytes)
+    {
+      if(int rc = grow(ctx, ctx->d_out[k], bytes, nullptr, false)) return rc;
+      *dptr[k] = ctx->d_out[k].p;
+    }
+  return TRT_OK;
+}
+
+int fetch_hits(trt_ctx* ctx, trt_hits& want, size_t bytes)
+{
+  const auto dst = hit_streams(want);
+  for(int k = 0; k < 8 && bytes; ++k)
+    if(*dst[k]) TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->d_out[k].p, bytes, hipMemcpyDeviceToHost, nullptr));
+  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
+  return TRT_OK;
+}
+
+// TRT_SOLVE_* → the precision of the root solve and the solver (SceneK::f64, SceneK::alt_solver).
+struct Solver { bool f64; AltSolver alt; };
+Solver solver_of(int precision)
+{
+  static_assert(TRT_SOLVE_F32 == 0 && TRT_SOLVE_F64 == 1 && TRT_SOLVE_DK_F32 == 2 && TRT_SOLVE_DK_F64 == 3 &&
+                TRT_SOLVE_FERRARI_F32 == 4 && TRT_SOLVE_FERRARI_F64 == 5 && kSolverWalk == 0 && kSolverDurandKerner == 1 &&
+                kSolverFerrari == 2, "solver_of: TRT_SOLVE_* = 2 * AltSolver + f64");
+  return {(precision & 1) != 0, (AltSolver)(precision >> 1)};
+}
+
 template <class Real>
 void torus_prepare(const trt_torus& t, TorusK<Real>& k)
 {
@@ -200,10 +235,8 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, SceneK& out)
   std::memset(&out, 0, sizeof out);
   out.n_tori = (int)s->n_tori;
   out.n_mat  = (int)s->n_materials;
-  out.f64    = ctx->precision == TRT_SOLVE_F64 || ctx->precision == TRT_SOLVE_DK_F64 || ctx->precision == TRT_SOLVE_FERRARI_F64;
-  out.alt_solver = (ctx->precision == TRT_SOLVE_DK_F32 || ctx->precision == TRT_SOLVE_DK_F64) ? kSolverDurandKerner
-                   : (ctx->precision == TRT_SOLVE_FERRARI_F32 || ctx->precision == TRT_SOLVE_FERRARI_F64) ? kSolverFerrari
-                   : kSolverWalk;
+  out.f64        = solver_of(ctx->precision).f64;
+  out.alt_solver = solver_of(ctx->precision).alt;
   for(uint32_t i = 0; i < s->n_tori; ++i)
   {
     const trt_torus& t = s->tori[i];
@@ -518,13 +551,18 @@ extern "C" int trt_get_stats(trt_ctx* ctx, trt_stats* out)
 // ------------------------------------------------------------------------------------------
 // trace
 // ------------------------------------------------------------------------------------------
-extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin,
-                             float tmax, trt_hits* out, void* stream)
+static int check_rays(trt_ctx* ctx, const trt_rays* in, const trt_hits* out)
 {
   if(!ctx) return TRT_E_INVALID;
   if(!in || !out) return fail(ctx, TRT_E_INVALID, "trt_trace: NULL rays or hits");
   if(in->n && (!in->ox || !in->oy || !in->oz || !in->dx || !in->dy || !in->dz))
     return fail(ctx, TRT_E_INVALID, "trt_trace: NULL ray stream");
+  return TRT_OK;
+}
+extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin,
+                             float tmax, trt_hits* out, void* stream)
+{
+  if(int rc = check_rays(ctx, in, out)) return rc;
   const SceneK* Sp = nullptr;
   if(int rc = build_scene(ctx, scene, Sp)) return rc;
   const SceneK& S = *Sp;
@@ -554,17 +592,12 @@ extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
 extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin,
                          float tmax, trt_hits* out)
 {
-  if(!ctx) return TRT_E_INVALID;
-  if(!in || !out) return fail(ctx, TRT_E_INVALID, "trt_trace: NULL rays or hits");
-  if(in->n && (!in->ox || !in->oy || !in->oz || !in->dx || !in->dy || !in->dz))
-    return fail(ctx, TRT_E_INVALID, "trt_trace: NULL ray stream");
+  if(int rc = check_rays(ctx, in, out)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)in->n * sizeof(float);
   const float* src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
-  const auto   dst    = hit_streams(*out);
   trt_rays din = *in;
   trt_hits dout;
-  const auto dptr_out = hit_streams(dout);
   const float** dptr_in[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
   for(int k = 0; k < 6 && in->n; ++k)
   {
@@ -572,21 +605,9 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
     TRT_HIP(ctx, hipMemcpyAsync(ctx->d_in[k].p, src[k], bytes, hipMemcpyHostToDevice, nullptr));
     *dptr_in[k] = (const float*)ctx->d_in[k].p;
   }
-  for(int k = 0; k < 8; ++k)
-  {
-    *dptr_out[k] = nullptr;
-    if(*dst[k] && in->n)
-    {
-      if(int rc = grow(ctx, ctx->d_out[k], bytes, nullptr, false)) return rc;
-      *dptr_out[k] = ctx->d_out[k].p;
-    }
-  }
+  if(int rc = stage_hits(ctx, *out, bytes, dout)) return rc;
   if(int rc = trt_trace_dev(ctx, &din, scene, tmin, tmax, &dout, nullptr)) return rc;
-  for(int k = 0; k < 8 && in->n; ++k)
-    if(*dst[k])
-      TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->d_out[k].p, bytes, hipMemcpyDeviceToHost, nullptr));
-  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
-  return TRT_OK;
+  return fetch_hits(ctx, *out, bytes);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -637,7 +658,7 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     }
   }
   const bool batch = n_frames > 1;
-  if(batch && (ctx->variant != kRenderListed || ctx->precision > TRT_SOLVE_F64))
+  if(batch && (ctx->variant != kRenderListed || solver_of(ctx->precision).alt != kSolverWalk))
     return fail(ctx, TRT_E_INVALID, "trt_render_batch: batches run the listed variant with the default solver (TRT_SOLVE_F32 / _F64) only; "
                                     "render these frames one by one");
   if(batch && W > kTile * field_max(kBatchTileXBits))
@@ -700,11 +721,9 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     if(camera == TRT_CAMERA_TOROIDAL)
       if(int rc = build_toro(ctx, *fr.g, *fr.pc, W, H, st, a.toro, f > 0)) return rc;
     if(ctx->stats_on) a.stats = ctx->d_stats;
-    {
-      float eye[3];
-      mat4_origin(fr.g->viewInverse, eye);
-      a.skip_primary = primary_skip_mask(scene, S, eye, camera == TRT_CAMERA_TOROIDAL ? fr.pc->rho : 0.0f);
-    }
+    float eye[3];   // the frame's eye: the enclosure cull here, the choice of the classification below
+    mat4_origin(fr.g->viewInverse, eye);
+    a.skip_primary = primary_skip_mask(scene, S, eye, camera == TRT_CAMERA_TOROIDAL ? fr.pc->rho : 0.0f);
     if(!lists) continue;
     a.tiles_live  = (uint32_t*)ctx->d_tiles.p;
     a.tiles_clear = a.tiles_live + n_tiles * n_frames;
@@ -729,8 +748,6 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     if(camera == TRT_CAMERA_PINHOLE)
     {
       // a pinhole camera INSIDE the scene (eye within two bounding radii of a torus) sees it the same way
-      float eye[3];
-      mat4_origin(fr.g->viewInverse, eye);
       for(uint32_t i = 0; i < scene->n_tori; ++i)
       {
         const trt_torus& t = scene->tori[i];
@@ -832,24 +849,14 @@ extern "C" int trt_render(trt_ctx* ctx, const trt_globals* g, const trt_push* pc
     d_rgba = (float*)ctx->d_rgba.p;
   }
   trt_hits dh, want;
-  std::memset(&dh, 0, sizeof dh);
   std::memset(&want, 0, sizeof want);
   if(first_hit_out) want = *first_hit_out;
-  const auto dst = hit_streams(want), dptr = hit_streams(dh);
-  for(int k = 0; k < 8; ++k)
-    if(*dst[k])
-    {
-      if(int rc = grow(ctx, ctx->d_out[k], npx * 4, nullptr, false)) return rc;
-      *dptr[k] = ctx->d_out[k].p;
-    }
+  if(int rc = stage_hits(ctx, want, npx * 4, dh)) return rc;
   if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, d_rgba, first_hit_out ? &dh : nullptr,
                              nullptr, nullptr))
     return rc;
   if(rgba_out) TRT_HIP(ctx, hipMemcpyAsync(rgba_out, d_rgba, npx * 16, hipMemcpyDeviceToHost, nullptr));
-  for(int k = 0; k < 8; ++k)
-    if(*dst[k]) TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->d_out[k].p, npx * 4, hipMemcpyDeviceToHost, nullptr));
-  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
-  return TRT_OK;
+  return fetch_hits(ctx, want, npx * 4);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -228,6 +228,19 @@ struct TorusTest {
     return true;
   }
 
+  // (f, f') at u, the one statement of the quartic: Horner with every multiply-add fused.  A caller that
+  // evaluates more than once forms 4·A4 and 2·P2 first and passes them in; the others use the short form.
+  // The value is the same: ×4 and ×2 are exact, so (4·A4)·u has one rounding wherever 4·A4 was formed.
+  __device__ __forceinline__ void eval(Real u, Real A4x4, Real P2x2, Real& f, Real& d) const
+  {
+    const Real e1 = fma_(A4 * u, u, P2);
+    const Real e2 = fma_(e1, u, Q1);
+    f = fma_(e2, u, S0);
+    const Real g1 = fma_(A4x4 * u, u, P2x2);
+    d = fma_(g1, u, Q1);
+  }
+  __device__ __forceinline__ void eval(Real u, Real& f, Real& d) const { eval(u, Real(4) * A4, Real(2) * P2, f, d); }
+
   // One evaluation of (f, f') at xe, then the transitions of the walk — written as straight-
   // line predicated code (compares + selects, one division) so that the lanes of a wave, which
   // sit in different pieces and modes, execute ONE instruction stream per trip.
@@ -242,11 +255,8 @@ struct TorusTest {
   __device__ __forceinline__ bool step()
   {
     const Real u  = xe;
-    const Real e1 = fma_(A4 * u, u, P2);
-    const Real e2 = fma_(e1, u, Q1);
-    const Real fe = fma_(e2, u, S0);
-    const Real g1 = fma_((Real(4) * A4) * u, u, Real(2) * P2);
-    const Real de = fma_(g1, u, Q1);
+    Real fe, de;
+    eval(u, fe, de);
 
     const bool mEnd = mode == M_END, mProbe = mode == M_PROBE, mFwd = mode == M_FWD, mBwd = mode == M_BWD;
     const bool pos = fe > Real(0), neg = fe < Real(0), zer = fe == Real(0);
@@ -313,11 +323,8 @@ struct TorusTest {
   __device__ __forceinline__ bool step_iter()
   {
     const Real u  = xe;
-    const Real e1 = fma_(A4 * u, u, P2);
-    const Real e2 = fma_(e1, u, Q1);
-    const Real fe = fma_(e2, u, S0);
-    const Real g1 = fma_((Real(4) * A4) * u, u, Real(2) * P2);
-    const Real de = fma_(g1, u, Q1);
+    Real fe, de;
+    eval(u, fe, de);
     const bool fwd  = mode == M_FWD;
     const bool flip = fe == Real(0) || ((fe > Real(0)) ? 1 : -1) != sref;
     const int  it2  = it + 1;
@@ -359,15 +366,8 @@ struct TorusTest {
   __device__ __forceinline__ void walk(uint32_t& evals)
   {
     const Real A4x4 = Real(4) * A4, P2x2 = Real(2) * P2;
-    auto eval = [&](Real u, Real& f, Real& d) {
-      const Real e1 = fma_(A4 * u, u, P2);
-      const Real e2 = fma_(e1, u, Q1);
-      f = fma_(e2, u, S0);
-      const Real g1 = fma_(A4x4 * u, u, P2x2);
-      d = fma_(g1, u, Q1);
-    };
     Real a = A, fa, da;          // setup() leaves the window start in A
-    eval(a, fa, da);
+    eval(a, A4x4, P2x2, fa, da);
     ++evals;
     found = false;
     root  = Real(0);
@@ -384,7 +384,7 @@ struct TorusTest {
       bool run = true, noroot = false;
       if(bwd)
       {
-        eval(b, fx, dx);
+        eval(b, A4x4, P2x2, fx, dx);
         ++evals;
         x = b;
         if(fx == Real(0)) { found = true; root = b; break; }     // (oracle: sb = sigma, first check of the run)
@@ -405,16 +405,57 @@ struct TorusTest {
           if(xn == x) break;
           x = xn;
           if(abs_(st) <= ustop) break;
-          eval(x, fx, dx);
+          eval(x, A4x4, P2x2, fx, dx);
           ++evals;
           if(fx == Real(0) || (fx > Real(0)) != pos) break;
         }
         if(!noroot) { found = true; root = x; break; }
       }
       if(!(b < hi)) break;                       // that was the last piece: a miss
-      if(!bwd) { eval(b, fx, dx); ++evals; }     // (a failed probe has evaluated B already)
+      if(!bwd) { eval(b, A4x4, P2x2, fx, dx); ++evals; }     // (a failed probe has evaluated B already)
       a = b; fa = fx; da = dx;
     }
+  }
+
+  // What the two alternative solvers share.  Prologue: the monic depressed quartic u⁴ + p·u² + q·u + s, the scale sc
+  // of its roots (the bounding-sphere radius in u), the tolerance tol = kAltTol·sc and the window start lo.
+  static constexpr Real kAltTol = sizeof(Real) == 4 ? Real(0.0009765625) : Real(2.384185791015625e-07);  // 2^-10 / 2^-22
+  struct Monic { Real p, q, s, sc, tol, lo; };
+  __device__ __forceinline__ Monic monic(Real inv_dd, Real Rb2) const
+  {
+    const Real iA4 = inv_dd * inv_dd;
+    const Real p = P2 * iA4, q = Q1 * iA4, s = S0 * iA4;
+    const Real sc = sqrt_(Rb2 * inv_dd);
+    return {p, q, s, sc, kAltTol * sc, A};   // setup() leaves the window start in A (= B = xe)
+  }
+  // Epilogue: every candidate that is real (ok(k), asked when its turn comes) gets two guarded Newton steps on the
+  // quartic (a step above tol is discarded); the smallest one inside [lo, hi] becomes `root`.
+  template <class IsReal>
+  __device__ __forceinline__ void polish_and_select(const Real (&cand)[4], IsReal ok, Real lo, Real tol)
+  {
+    bool f = false;
+    Real best = Real(0);
+    const Real A4x4 = Real(4) * A4, P2x2 = Real(2) * P2;
+#pragma unroll
+    for(int k = 0; k < 4; ++k)
+    {
+      if(!ok(k))
+        continue;
+      Real u = cand[k];
+#pragma unroll
+      for(int n = 0; n < 2; ++n)
+      {
+        Real fu, du;
+        eval(u, A4x4, P2x2, fu, du);
+        const Real st = fu / du;
+        if(abs_(st) <= tol)
+          u = u - st;
+      }
+      if(u >= lo && u <= hi && (!f || u < best)) { best = u; f = true; }
+    }
+    found = f;
+    root  = best;
+    mode  = M_DONE;
   }
 
   // T2, alternative solver (TRT_SOLVE_DK_*): Durand–Kerner iteration on the monic depressed
@@ -426,14 +467,10 @@ struct TorusTest {
   __device__ __forceinline__ void solve_dk(Real inv_dd, Real Rb2)
   {
     constexpr int  kSweeps = 24;
-    constexpr Real kTol = sizeof(Real) == 4 ? Real(0.0009765625) : Real(2.384185791015625e-07);  // 2^-10 / 2^-22
     const Real CR[4] = {Real(1.0), Real(0.4), Real(-0.65), Real(-0.908)};
     const Real CI[4] = {Real(0.0), Real(0.9), Real(0.72), Real(-0.297)};
-    const Real iA4 = inv_dd * inv_dd;
-    const Real p = P2 * iA4, q = Q1 * iA4, s = S0 * iA4;
-    const Real sc  = sqrt_(Rb2 * inv_dd);
-    const Real tol = kTol * sc;
-    const Real lo  = A;   // setup() leaves the window start in A (= B = xe)
+    const Monic mq = monic(inv_dd, Rb2);
+    const Real  p = mq.p, q = mq.q, s = mq.s, sc = mq.sc;
     Real zr[4], zi[4];
 #pragma unroll
     for(int k = 0; k < 4; ++k) { zr[k] = sc * CR[k]; zi[k] = sc * CI[k]; }
@@ -465,29 +502,7 @@ struct TorusTest {
         }
       }
     }
-    bool f = false;
-    Real best = Real(0);
-    const Real A4x4 = Real(4) * A4, P2x2 = Real(2) * P2;
-#pragma unroll
-    for(int k = 0; k < 4; ++k)
-    {
-      if(!(abs_(zi[k]) <= tol))
-        continue;
-      Real u = zr[k];
-#pragma unroll
-      for(int n = 0; n < 2; ++n)
-      {
-        const Real e1 = fma_(A4 * u, u, P2), e2 = fma_(e1, u, Q1), fu = fma_(e2, u, S0);
-        const Real g1 = fma_(A4x4 * u, u, P2x2), du = fma_(g1, u, Q1);
-        const Real st = fu / du;
-        if(abs_(st) <= tol)
-          u = u - st;
-      }
-      if(u >= lo && u <= hi && (!f || u < best)) { best = u; f = true; }
-    }
-    found = f;
-    root  = best;
-    mode  = M_DONE;
+    polish_and_select(zr, [&](int k) { return abs_(zi[k]) <= mq.tol; }, mq.lo, mq.tol);
   }
 
   // T2, second alternative solver (TRT_SOLVE_FERRARI_*): Ferrari's factorisation of the monic
@@ -500,12 +515,8 @@ struct TorusTest {
   __device__ __forceinline__ void solve_ferrari(Real inv_dd, Real Rb2)
   {
     constexpr int  kSteps = sizeof(Real) == 4 ? 40 : 72;
-    constexpr Real kTol = sizeof(Real) == 4 ? Real(0.0009765625) : Real(2.384185791015625e-07);
-    const Real iA4 = inv_dd * inv_dd;
-    const Real p = P2 * iA4, q = Q1 * iA4, s = S0 * iA4;
-    const Real sc  = sqrt_(Rb2 * inv_dd);
-    const Real tol = kTol * sc;
-    const Real lo  = A;   // setup() leaves the window start in A
+    const Monic mq = monic(inv_dd, Rb2);
+    const Real  p = mq.p, q = mq.q, s = mq.s;
     const Real c1  = fma_(p, p, Real(-4) * s) * Real(0.25);
     const Real c0  = (q * q) * Real(-0.125);
     Real mlo = Real(0), mhi = Real(1) + max_(abs_(p), max_(abs_(c1), abs_(c0)));
@@ -535,29 +546,7 @@ struct TorusTest {
     const Real w1 = sqrt_(max_(d1, Real(0))), w2 = sqrt_(max_(d2, Real(0)));
     const Real cand[4] = {Real(0.5) * (sg - w1), Real(0.5) * (sg + w1), Real(0.5) * (-sg - w2), Real(0.5) * (-sg + w2)};
     const bool ok[4]   = {d1 >= Real(0), d1 >= Real(0), d2 >= Real(0), d2 >= Real(0)};
-    bool f = false;
-    Real best = Real(0);
-    const Real A4x4 = Real(4) * A4, P2x2 = Real(2) * P2;
-#pragma unroll
-    for(int k = 0; k < 4; ++k)
-    {
-      if(!ok[k])
-        continue;
-      Real u = cand[k];
-#pragma unroll
-      for(int n = 0; n < 2; ++n)
-      {
-        const Real e1 = fma_(A4 * u, u, P2), e2 = fma_(e1, u, Q1), fu = fma_(e2, u, S0);
-        const Real g1 = fma_(A4x4 * u, u, P2x2), du = fma_(g1, u, Q1);
-        const Real st = fu / du;
-        if(abs_(st) <= tol)
-          u = u - st;
-      }
-      if(u >= lo && u <= hi && (!f || u < best)) { best = u; f = true; }
-    }
-    found = f;
-    root  = best;
-    mode  = M_DONE;
+    polish_and_select(cand, [&](int k) { return ok[k]; }, mq.lo, mq.tol);
   }
 
   // T2b: one Newton step on g(u) = (ρ-R)² + py² - r², whose rounding error scales with r²

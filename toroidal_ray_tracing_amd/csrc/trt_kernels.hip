@@ -140,6 +140,14 @@ __device__ __forceinline__ size_t out_index(const RenderArgs& a, uint32_t x, uin
   return (size_t)(a.compact ? ly : y) * a.W + x;
 }
 
+// The RenderedData record of pixel (x, image row y): AoS at x·H + y (BEF rgen:72).  It takes a.rendered and a.H, not
+// the RenderArgs: rd_flush() passes image_row() for y, and with `a` as the parameter the two LDS loads come after that
+// call instead of before it — the RD instantiations of render_listed_kernel then grow by 24 instructions.
+__device__ __forceinline__ float* rendered_record(trt_rendered_data* rendered, uint32_t H, uint32_t x, uint32_t y)
+{
+  return reinterpret_cast<float*>(&rendered[(size_t)x * H + y]);
+}
+
 // The id of a miss, materialised at the store: as a plain constant hipcc hoists (-1,-1,-1,-1) out of the
 // tile loop, keeps it live across the whole solve and — in the FP64 kernels at 128 VGPRs — spills it
 // (20 B of scratch whose every reload is a vector-memory load that drains the output stores).
@@ -166,6 +174,25 @@ __device__ __forceinline__ void store_first_hit(const RenderArgs& a, size_t i_, 
   if(a.hits.ny) st1(a.hits.ny, i, N.y);
   if(a.hits.nz) st1(a.hits.nz, i, N.z);
   if(a.hits.id) st1(a.hits.id, i, id);
+}
+
+// What a pixel that misses at depth 0 gets, stated once for its five writers (trace_pixel, the persistent kernel's miss
+// shader, the listed kernel's miss-flagged tiles, clear_macro, rd_miss_tile).  The colour of a miss is clearColor·0.8
+// (REFL rmiss:37; at depth 0 it is the pixel's colour: rgen:76 with attenuation 1 and hitValue 0 → rgen:87), alpha 1; the
+// first-hit record is t = +inf, position and normal 0, id -1 (BEF rmiss:21).  A writer that has +inf, 0 or 1 in registers
+// of its own (materialised where hoisting would spill them) passes them in.
+__device__ __forceinline__ v3 miss_colour(const trt_push& pc)
+{
+  return {pc.clearColor[0] * 0.8f, pc.clearColor[1] * 0.8f, pc.clearColor[2] * 0.8f};
+}
+__device__ __forceinline__ float4 miss_rgba(const trt_push& pc, float one = 1.0f)
+{
+  const v3 c = miss_colour(pc);
+  return make_float4(c.x, c.y, c.z, one);
+}
+__device__ __forceinline__ void store_first_miss(const RenderArgs& a, size_t i, float inf = __builtin_inff(), float zero = 0.0f)
+{
+  store_first_hit(a, i, inf, {zero, zero, zero}, {zero, zero, zero}, miss_id());
 }
 
 // Query counters of a block → the three global totals: wave sums by shuffles, block sums by LDS
@@ -331,15 +358,15 @@ __device__ __forceinline__ void rd_flush(const RenderArgs& a, const float4* tile
     if(x < a.W && ly < a.n_local_rows)
     {
       const float4 v = tile[rd_unit(xl, yl, k)];
-      st4c(reinterpret_cast<float*>(&a.rendered[(size_t)x * a.H + image_row(a, ly)]) + 4 * k, v);
+      st4c(rendered_record(a.rendered, a.H, x, image_row(a, ly)) + 4 * k, v);
     }
   }
   __builtin_amdgcn_wave_barrier();
 }
 
 // The record of a pixel that misses at depth 0, for a whole tile that the classification proved
-// empty: primary ray from raygen(), pos = (0,0,0,1) (BEF rmiss:21 → rgen:112), colour = clear·0.8
-// (rmiss:37 → rgen:76 with attenuation 1 → rgen:111) — what trace_pixel() would have produced.
+// empty: primary ray from raygen(), pos = (0,0,0,1) (BEF rmiss:21 → rgen:112), colour = miss_rgba()
+// (→ rgen:111) — what trace_pixel() would have produced.
 __device__ __forceinline__ void rd_miss_tile(const RenderArgs& a, float4* tile, uint32_t tx, uint32_t ty, uint32_t lane)
 {
   const uint32_t xl = lane & 7u, yl = lane >> 3, x = tx * 8u + xl, ly = ty * 8u + yl;
@@ -349,7 +376,7 @@ __device__ __forceinline__ void rd_miss_tile(const RenderArgs& a, float4* tile, 
     raygen(a.g, a.toro, a.W, a.H, a.camera, x, image_row(a, ly), o, d);
     float4* r = tile + rd_unit(xl, yl, 0);
     r[0] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    r[1] = make_float4(a.pc.clearColor[0] * 0.8f, a.pc.clearColor[1] * 0.8f, a.pc.clearColor[2] * 0.8f, 1.0f);
+    r[1] = miss_rgba(a.pc);
     r[2] = make_float4(o.x, o.y, o.z, 1.0f);
     r[3] = make_float4(d.x, d.y, d.z, 0.0f);
   }
@@ -386,10 +413,10 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
     const int id = closest_hit<Real, ALT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
     if(id < 0)
     {
-      prdHit = {a.pc.clearColor[0] * 0.8f, a.pc.clearColor[1] * 0.8f, a.pc.clearColor[2] * 0.8f};  // rmiss:37
+      prdHit = miss_colour(a.pc);
       if(depth == 0)
       {
-        store_first_hit(a, oi, t, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, miss_id());  // BEF rmiss:21
+        store_first_miss(a, oi, t);   // (t = +inf: what closest_hit leaves without a hit)
         if(rd)
         {
           // materialised here: hoisted out of the tile loop this constant vector gets spilled
@@ -454,7 +481,7 @@ __global__ __launch_bounds__(256) void render_static_kernel(const SceneK scene, 
   if(x < a.W && ly < a.n_local_rows)
   {
     const uint32_t y = image_row(a, ly);
-    const RdSink rd{nullptr, a.rendered ? reinterpret_cast<float*>(&a.rendered[(size_t)x * a.H + y]) : nullptr};   // BEF rgen:72
+    const RdSink rd{nullptr, a.rendered ? rendered_record(a.rendered, a.H, x, y) : nullptr};
     trace_pixel<Real, ALT>(S, a, x, y, ly, rd, n_primary, n_bounce, n_shadow, wc);
   }
   if(a.stats)
@@ -670,6 +697,17 @@ __device__ __forceinline__ void classify_publish(const RenderArgs& a, unsigned i
 __device__ __forceinline__ size_t live_slot(uint32_t cap_live, uint32_t n_heavy, uint64_t L)
 {
   return L < n_heavy ? (size_t)cap_live - 1 - (size_t)L : (size_t)(L - n_heavy);
+}
+
+// The header of a list kernel: the list lengths as published by the classification (RenderArgs::counts), wave-uniform
+// and never beyond the lists' capacity.  n_heavy (live_slot(): the heavy tiles come first) is read only by the
+// instantiations that can have any (HEAVY); the others get 0.
+template <bool HEAVY = true>
+__device__ __forceinline__ void list_counts(const RenderArgs& a, uint32_t& n_live, uint32_t& n_clear, uint32_t& n_heavy)
+{
+  n_live  = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)kCountLive)), a.cap_live);
+  n_clear = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)kCountClear)), a.cap_clear);
+  n_heavy = HEAVY ? umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)kCountHeavy)), n_live) : 0u;
 }
 
 // Block size of the classification kernels: the largest there is.  Every block reserves its stretch of each list with ONE
@@ -934,10 +972,9 @@ __device__ __forceinline__ uint32_t clear_macro(const RenderArgs& a, uint32_t tx
   // The constants of the miss record are (re)materialised HERE on purpose: hoisted out of the
   // caller's tile loop they stay live across the whole solve, get spilled to scratch, and every
   // reload is a vector-memory load whose s_waitcnt drains the stream of output stores.
-  // (clearColor·0.8, 1): rmiss:37 → rgen:76 with attenuation 1 and hitValue 0 → rgen:87
   float inf, zero, one;
   asm volatile("v_mov_b32 %0, 0x7f800000\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 1.0" : "=v"(inf), "=v"(zero), "=v"(one));
-  const float4 c = make_float4(a.pc.clearColor[0] * 0.8f, a.pc.clearColor[1] * 0.8f, a.pc.clearColor[2] * 0.8f, one);
+  const float4 c = miss_rgba(a.pc, one);
   const uint32_t x0 = tx * 8, ly = ty * 8 + (lane >> 3), q = lane & 7;
   if(ly >= a.n_local_rows)
     return 0;
@@ -978,7 +1015,7 @@ __device__ __forceinline__ uint32_t clear_macro(const RenderArgs& a, uint32_t tx
   {
     for(uint32_t k = 0; k < 4; ++k)
       if(xs + k < a.W)
-        store_first_hit(a, row + xs + k, inf, {zero, zero, zero}, {zero, zero, zero}, miss_id());
+        store_first_miss(a, row + xs + k, inf, zero);
   }
   return n;
 }
@@ -996,10 +1033,8 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
   const int      n_tori  = S.n_tori;
   const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
   const uint32_t g_wave  = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  // list lengths as published by the classification, never beyond the lists' capacity
-  const uint32_t n_live  = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)0)), a.cap_live);
-  const uint32_t n_clear = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)1)), a.cap_clear);
-  const uint32_t n_heavy = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)2)), n_live);   // live_slot(): they come first
+  uint32_t n_live, n_clear, n_heavy;
+  list_counts(a, n_live, n_clear, n_heavy);
 
   // Queue state.  Wave g owns entries g, g+G, g+2G, … of both lists.  Lane k caches the
   // wave's k-th entry of the current batch of 64 (one gather load per 64 tiles) and entries
@@ -1075,15 +1110,15 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
         v3   prdHit = {0.0f, 0.0f, 0.0f};
         if(stage && kind == K_CLOSEST)
         {
-          float* rd = a.rendered ? reinterpret_cast<float*>(&a.rendered[(size_t)px * a.H + py]) : nullptr;
+          float* rd = a.rendered ? rendered_record(a.rendered, a.H, px, py) : nullptr;
           if(best_id < 0)
           {
-            // miss shader (REFL rmiss:37; BEF rmiss:21 hitPosition = 0)
-            prdHit   = {a.pc.clearColor[0] * 0.8f, a.pc.clearColor[1] * 0.8f, a.pc.clearColor[2] * 0.8f};
+            // miss shader
+            prdHit   = miss_colour(a.pc);
             have_prd = true;
             if(depth == 0)
             {
-              store_first_hit(a, oi, __builtin_inff(), {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, miss_id());
+              store_first_miss(a, oi);
               if(rd) st4(rd, make_float4(0.0f, 0.0f, 0.0f, 1.0f));
             }
           }
@@ -1138,7 +1173,7 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
           {
             const float4 c = make_float4(hitValue.x, hitValue.y, hitValue.z, 1.0f);
             if(a.rgba) st4(a.rgba + 4 * oi, c);                              // rgen:87
-            if(a.rendered) st4(reinterpret_cast<float*>(&a.rendered[(size_t)px * a.H + py]) + 4, c);
+            if(a.rendered) st4(rendered_record(a.rendered, a.H, px, py) + 4, c);
             kind = K_NONE;
           }
           else
@@ -1176,7 +1211,7 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
             raygen(a.g, a.toro, a.W, a.H, a.camera, px, py, qo, qd);
             if(a.rendered)
             {
-              float* rd = reinterpret_cast<float*>(&a.rendered[(size_t)px * a.H + py]);
+              float* rd = rendered_record(a.rendered, a.H, px, py);
               st4(rd + 8, make_float4(qo.x, qo.y, qo.z, 1.0f));
               st4(rd + 12, make_float4(qd.x, qd.y, qd.z, 0.0f));
             }
@@ -1307,12 +1342,11 @@ __global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAV
   const RenderArgs& a_arg = frame_args(args, 0u);   // lists, counters and capacities are the same in every frame of a batch
   TRT_STAMP(0, wall_clock64());
   TRT_STAMP(3, (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32));   // HW_ID, XCC_ID
-  // list lengths as published by the classification, never beyond the lists' capacity; read through the kernel
-  // arguments BEFORE anything is staged: a block none of whose waves owns an entry leaves at once (the grid is sized
-  // for the worst case, one wave per four tiles; ≈15 % of the baseline frame's blocks own nothing)
-  const uint32_t n_live  = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a_arg.counts, (size_t)0)), a_arg.cap_live);
-  const uint32_t n_clear = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a_arg.counts, (size_t)1)), a_arg.cap_clear);
-  const uint32_t n_heavy = FB ? umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a_arg.counts, (size_t)2)), n_live) : 0u;   // they come first
+  // the list lengths, read through the kernel arguments BEFORE anything is staged: a block none of whose waves owns
+  // an entry leaves at once (the grid is sized for the worst case, one wave per four tiles; ≈15 % of the baseline
+  // frame's blocks own nothing)
+  uint32_t n_live, n_clear, n_heavy;
+  list_counts<FB>(a_arg, n_live, n_clear, n_heavy);   // (no feedback: no heavy tiles)
   if(blockIdx.x * (kListedThreads / 64u) >= (n_live > n_clear ? n_live : n_clear))
   {
     TRT_STAMP(2, wall_clock64());
@@ -1405,11 +1439,9 @@ __global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAV
         if(packed & kTileMissFlag)
         {
           // classified "every ray of this tile misses": the miss record of trace_pixel, no tracing
-          // (rmiss:37 → rgen:76 with attenuation 1 → rgen:87; BEF rmiss:21)
           const size_t oi = out_index(a, x, image_row(a, ly), ly);
-          store_first_hit(a, oi, __builtin_inff(), {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, miss_id());
-          if(a.rgba)
-            st4(a.rgba + 4 * oi, make_float4(a.pc.clearColor[0] * 0.8f, a.pc.clearColor[1] * 0.8f, a.pc.clearColor[2] * 0.8f, 1.0f));
+          store_first_miss(a, oi);
+          if(a.rgba) st4(a.rgba + 4 * oi, miss_rgba(a.pc));
           n_primary += (uint32_t)S.n_tori;
         }
         else
@@ -1421,7 +1453,7 @@ __global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAV
       {
         const uint32_t ticks = (uint32_t)(wall_clock64() - tile_t0);
         if(ln == 0u)
-          atomicMax(&a.tile_cost[TC::y(packed) * ((((a.W + 7u) >> 3) + kMacroTiles - 1u) / kMacroTiles) + TC::x(packed) / kMacroTiles], ticks ? ticks : 1u);
+          atomicMax(&a.tile_cost[TC::y(packed) * macro_count(tile_count(a.W)) + TC::x(packed) / kMacroTiles], ticks ? ticks : 1u);
       }
       if(RD && !(packed & kTileMissFlag))
         rd_flush(a, rd_tile, TC::x(packed), TC::y(packed), ln);

@@ -49,8 +49,8 @@ enum StatWord : uint32_t {
 // kMacroTiles horizontally adjacent tiles (32×8 pixels: one 128-B line of every first-hit stream per row).
 constexpr uint32_t kTile       = 8;
 constexpr uint32_t kMacroTiles = 4;
-constexpr uint32_t tile_count(uint32_t pixels) { return (pixels + kTile - 1) / kTile; }
-constexpr uint32_t macro_count(uint32_t tiles) { return (tiles + kMacroTiles - 1) / kMacroTiles; }
+__host__ __device__ constexpr uint32_t tile_count(uint32_t pixels) { return (pixels + kTile - 1) / kTile; }
+__host__ __device__ constexpr uint32_t macro_count(uint32_t tiles) { return (tiles + kMacroTiles - 1) / kMacroTiles; }
 // Tile-list entries (TileCode in trt_kernels.hip).  One frame per launch: tx | ty << kTileXBits [| kTileMissFlag].
 // A batch of frames: tx | ty << kBatchTileXBits | frame << kBatchFrameShift [| kTileMissFlag].
 constexpr uint32_t kTileXBits = 16, kTileYBits = 15;
