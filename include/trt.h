@@ -197,6 +197,13 @@ int trt_render(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt
  * The only thing a frame leaves behind in the ctx is a scheduling hint: for scenes of two or more tori the
  * time its slowest wave spent on each traced tile, which the next frame uses to start the heavy tiles
  * first.  No output bit depends on it (first frame, replay, camera cut: same images, same counts).
+ * The ctx also keeps the tile lists of the last frame it classified, keyed by everything that classification read
+ * (view, push constants, scene, frame shape, tiling, camera model, variant and classification level), and a frame
+ * with the same key renders from them without classifying again (trt_set_list_reuse; never inside a capture, and never
+ * again on a ctx that has recorded a frame into a hipGraph).  No event orders such a frame behind the one that built
+ * the lists: two calls on one ctx whose streams the caller has not ordered already race (the second call's
+ * classification overwrites lists the first call's render kernel is reading), so the contract "calls on a ctx are
+ * serialised by the caller" already includes device order, and a reusing call relies on nothing more than that.
  *
  * Rows [row_begin,row_end) only; outputs are indexed relative to the FULL image, so a
  * rank that owns a row band passes pointers to the full-frame buffers (or to buffers
@@ -299,6 +306,12 @@ const char* trt_get_render_variant(const trt_ctx* ctx);
  * pixels per test + distance-function march).  Never changes an output bit, only the time. */
 enum { TRT_CLASSIFY_AUTO = -1, TRT_CLASSIFY_MACRO = 0, TRT_CLASSIFY_TILE = 1 };
 int trt_set_classification(trt_ctx* ctx, int level);
+
+/* Reuse of the tile lists between frames with the same view, scene and frame shape (trt_render_dev above): on by
+ * default; off = every frame classifies.  Never changes an output bit, only the time.  The counters are host-side
+ * totals of the render calls that launched (classified) or skipped (reused) a classification; either may be NULL. */
+int trt_set_list_reuse(trt_ctx* ctx, int on);
+int trt_get_list_reuse(const trt_ctx* ctx, uint64_t* classified, uint64_t* reused);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -30,6 +30,36 @@ struct DevBuf {
   size_t cap = 0;
 };
 
+// Everything the classification of a call read, and where it wrote: the key of the ctx's tile lists (ListCache below).
+// The tile lists and their lengths are a function of the view, the tori, the frame shape and the camera model; a call
+// whose key equals the one of the classification that ran last finds in d_tiles and d_queue exactly what its own
+// classification would write (the render kernels read the lists and the counts and never write them; the
+// classification's last block leaves the accumulators zero), and launches the render kernel alone.
+// g and pc are keyed WHOLE, shading-only fields included (light, clear colour, maxDepth): a frame that moves only the
+// light classifies again, which costs what every frame cost before, and no field list here can fall behind the kernels.
+// The output pointers (rgba, first-hit streams, the address of RenderedData) are not part of the key: the
+// classification never sees them, and vec4_ok is read by the render kernels only.
+// Only 4- and 8-byte members, zeroed before they are filled, compared as bytes.
+struct ListKey {
+  uint64_t    scene_gen;   // trt_ctx::scene_gen: the scene constants (tori, materials, solver, enclosure masks)
+  uint64_t    toro_gen;    // trt_ctx::toro_gen: the upload the toroidal tables come from (0: pinhole camera)
+  const void* toro_tab;
+  const void* tiles;       // where the lists, their counters and the cost words live
+  const void* queue;
+  const void* cost;
+  uint32_t    cap_live, cap_clear;
+  uint32_t    n_frames, per_frame, batch, variant;
+  uint32_t    W, H, row_begin, row_end, n_local_rows, tile_group, tile_parts, tile_part, compact;
+  int32_t     camera;
+  uint32_t    fb;          // render_feedback(): NOT cost_fb — a counted frame and an alternative solver go without
+  uint32_t    heavy_x16, stats, rendered;
+  struct Frame {
+    trt_globals g;
+    trt_push    pc;
+    uint32_t    fine, tile_cull, skip_primary, debug_skip;
+  } fr[kMaxBatch];
+};
+
 }  // namespace
 
 struct trt_ctx {
@@ -76,6 +106,22 @@ struct trt_ctx {
     trt_material mat[TRT_MAX_MATERIALS];
     SceneK       K;
   } scene_cache;
+  uint64_t scene_gen = 0;   // bumped whenever scene_cache is rebuilt
+  uint64_t toro_gen  = 0;   // bumped by every upload of the toroidal tables
+
+  // The tile lists the last classification left in d_tiles / d_queue, by what it read (ListKey): the third product a
+  // frame loop recomputes for nothing, and the only one that costs GPU time (8 µs of a 116-µs frame at 4096²).
+  // Cleared by: any error between a classification and the end of its call, trt_set_list_reuse, a reload of the tuning
+  // knobs; everything else that changes a launch input (variant, classification level, solver and scene through
+  // scene_gen, growth of d_tiles / d_cost and a new upload of the toroidal tables through their addresses and toro_gen)
+  // is part of the key.  A ctx that has recorded a frame into a hipGraph stops reusing for good (`captured`): a replay
+  // rewrites the lists at a time the host cannot see.
+  struct ListCache {
+    bool     on = true, valid = false, captured = false;
+    uint32_t streak = 0;   // consecutive classifications of `key`
+    uint64_t classified = 0, reused = 0;
+    ListKey  key;
+  } lists;
 };
 
 namespace {
@@ -218,6 +264,7 @@ int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
        && !std::memcmp(c.mat, s->materials, s->n_materials * sizeof(trt_material))))
   {
     c.valid = false;
+    ++ctx->scene_gen;
     if(int rc = build_scene_uncached(ctx, s, c.K)) return rc;
     c.precision = ctx->precision;
     c.n_tori = s->n_tori;
@@ -391,6 +438,7 @@ int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t 
                                 stream));
     TRT_HIP(ctx, hipEventRecord(ctx->ev_toro, stream));
     ctx->ev_toro_set = true;
+    ++ctx->toro_gen;
     key.W = W; key.H = H; key.omega = omega; key.theta = theta; key.valid = true;
   }
   out.eye[0] = eye[0]; out.eye[1] = eye[1]; out.eye[2] = eye[2];
@@ -475,6 +523,7 @@ extern "C" int trt_debug_reload_tuning(trt_ctx* ctx)
   if(!ctx) return TRT_E_INVALID;
   ctx->tn = tuning_from_env();
   ctx->scene_cache.valid = false;   // (TRT_NO_ENCLOSURE changes the scene constants)
+  ctx->lists.valid = false;         // (the knobs change what the classification is launched with)
   return TRT_OK;
 }
 #endif
@@ -514,6 +563,22 @@ extern "C" int trt_set_classification(trt_ctx* ctx, int level)
   if(level < TRT_CLASSIFY_AUTO || level > TRT_CLASSIFY_TILE)
     return fail(ctx, TRT_E_INVALID, "trt_set_classification: %d is not one of the TRT_CLASSIFY_* constants", level);
   ctx->classify = level;
+  return TRT_OK;
+}
+
+extern "C" int trt_set_list_reuse(trt_ctx* ctx, int on)
+{
+  if(!ctx) return TRT_E_INVALID;
+  ctx->lists.on = on != 0;
+  ctx->lists.valid = false;
+  return TRT_OK;
+}
+
+extern "C" int trt_get_list_reuse(const trt_ctx* ctx, uint64_t* classified, uint64_t* reused)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(classified) *classified = ctx->lists.classified;
+  if(reused) *reused = ctx->lists.reused;
   return TRT_OK;
 }
 
@@ -623,6 +688,37 @@ uint32_t tiling_rows(const trt_tiling& t, uint32_t H)
   uint32_t extra = 0;
   if(rem > start) extra = rem - start < t.group_rows ? rem - start : t.group_rows;
   return full * t.group_rows + extra;
+}
+
+// Whether a call with the list key `key` may skip its classification (ListKey, trt_ctx::ListCache).  Leaves the cache
+// invalid: list_commit() validates it again once every launch of the call is enqueued, so that any error return in
+// between clears the key.
+// No event orders a reusing call behind the classification it relies on: calls on a ctx are serialised by the caller,
+// device order included (include/trt.h, trt_render_dev) — a classifying call needs the same.
+// Cost feedback (fb): the heavy-first order exists from the second classification of a run on (the first has no costs to
+// read), so the first TWO consecutive frames of a key classify and reuse starts with the third.  The listed kernel of a
+// reusing frame keeps its atomicMax into tile_cost; nothing reads those words until the next classification resets
+// them, and no result depends on them.
+bool list_begin(trt_ctx* ctx, const ListKey& key, hipStream_t st, bool& same)
+{
+  auto& c = ctx->lists;
+  same = c.valid && !std::memcmp(&c.key, &key, sizeof key);
+  if(capturing(st)) c.captured = true;   // the frame records its own classification, and so does every later one
+  c.valid = false;
+  return same && c.on && !c.captured && (!key.fb || c.streak >= 2u);
+}
+
+void list_commit(trt_ctx* ctx, const ListKey& key, bool same, bool reused)
+{
+  auto& c = ctx->lists;
+  if(reused) ++c.reused;
+  else
+  {
+    ++c.classified;
+    c.streak = same ? c.streak + 1u : 1u;
+    c.key = key;
+  }
+  c.valid = c.on && !c.captured;
 }
 
 // One frame (the trt_render*_dev entry points) or a batch of them (trt_render_batch_dev): validates, fills one RenderArgs
@@ -774,10 +870,47 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     for(uint32_t f = 0; f < n_frames; ++f) B.fr[f].fine = fine_any;   // one classification kernel for the whole batch
     const uint64_t lanes = fine_any ? (uint64_t)n_macro * kMacroTiles : (uint64_t)n_macro;
     B.per_frame = (uint32_t)((lanes + 63) / 64 * 64);
-    TRT_HIP(ctx, launch_render_batch(S, B, ctx->n_cus, ctx->tn, st));
   }
+  // The list key, from the RenderArgs just filled (so that it cannot drift from what is launched).  A launch without
+  // lists (static variant) or without rows touches nothing and leaves the key as it is.
+  const bool keyed = lists && n_local_rows != 0;
+  ListKey    key;
+  bool       same = false, reuse = false;
+  if(keyed)
+  {
+    const RenderArgs& a = B.fr[0];
+    std::memset(&key, 0, sizeof key);
+    key.scene_gen = ctx->scene_gen;
+    if(camera == TRT_CAMERA_TOROIDAL)
+    {
+      key.toro_gen = ctx->toro_gen;
+      key.toro_tab = ctx->d_toro.p;
+    }
+    key.tiles = a.tiles_live;
+    key.queue = a.counters;
+    key.cost  = a.tile_cost;
+    key.cap_live = a.cap_live; key.cap_clear = a.cap_clear;
+    key.n_frames = n_frames; key.per_frame = B.per_frame; key.batch = batch; key.variant = (uint32_t)ctx->variant;
+    key.W = a.W; key.H = a.H; key.row_begin = a.row_begin; key.row_end = a.row_end; key.n_local_rows = a.n_local_rows;
+    key.tile_group = a.tile_group; key.tile_parts = a.tile_parts; key.tile_part = a.tile_part; key.compact = a.compact;
+    key.camera = a.camera;
+    key.fb = render_feedback(S, a, ctx->variant);
+    key.heavy_x16 = a.heavy_x16;
+    key.stats = a.stats != nullptr;
+    key.rendered = a.rendered != nullptr;
+    for(uint32_t f = 0; f < n_frames; ++f)
+    {
+      const RenderArgs& af = B.fr[f];
+      ListKey::Frame&   k  = key.fr[f];
+      k.g = af.g; k.pc = af.pc;
+      k.fine = af.fine; k.tile_cull = af.tile_cull; k.skip_primary = af.skip_primary; k.debug_skip = af.debug_skip;
+    }
+    reuse = list_begin(ctx, key, st, same);
+  }
+  if(batch)
+    TRT_HIP(ctx, launch_render_batch(S, B, !reuse, ctx->n_cus, ctx->tn, st));
   else
-    TRT_HIP(ctx, launch_render(S, B.fr[0], ctx->variant, ctx->n_cus, ctx->tn, st));
+    TRT_HIP(ctx, launch_render(S, B.fr[0], ctx->variant, !reuse, ctx->n_cus, ctx->tn, st));
   if(ctx->stats_on && !capturing(st))
   {
     TRT_HIP(ctx, hipEventRecord(ctx->ev_stats, st));
@@ -791,6 +924,7 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     fprintf(stderr, "[trt] tiles: live=%u (heavy %u, mean cost %u ticks) clear=%u (cull=%u)\n", q[kCountLive], q[kCountHeavy],
             q[kCountMeanCost], q[kCountClear], B.fr[0].tile_cull);
   }
+  if(keyed) list_commit(ctx, key, same, reuse);
   return TRT_OK;
 }
 

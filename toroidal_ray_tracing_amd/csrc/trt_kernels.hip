@@ -1651,20 +1651,24 @@ hipError_t launch_persistent(const SceneK& scene, const RenderArgs& a, uint64_t 
 
 }  // namespace
 
-hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, int n_cus, const Tuning& tn,
-                         hipStream_t stream)
+bool render_feedback(const SceneK& scene, const RenderArgs& a, RenderVariant v)
+{
+  return v == kRenderListed && a.tile_cost != nullptr && a.heavy_x16 != 0u && a.stats == nullptr &&
+         scene.alt_solver == kSolverWalk;
+}
+
+hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, bool classify, int n_cus,
+                         const Tuning& tn, hipStream_t stream)
 {
   if(a.n_local_rows == 0 || a.W == 0)
     return hipSuccess;
   if(v == kRenderStatic)
     return launch_static(scene, a, tn, stream);
-  // 1. classify the tiles into the LIVE and CLEAR lists
+  // 1. classify the tiles into the LIVE and CLEAR lists (unless the ctx still holds them)
   const uint64_t tiles  = (uint64_t)tile_count(a.W) * tile_count(a.n_local_rows);
   const uint64_t macros = (uint64_t)macro_count(tile_count(a.W)) * tile_count(a.n_local_rows);
-  // cost feedback: the plain listed kernels only (the counted and the alternative-solver instantiations go without)
-  const bool fb = v == kRenderListed && a.tile_cost != nullptr && a.heavy_x16 != 0u && a.stats == nullptr &&
-                  scene.alt_solver == kSolverWalk;
-  launch_classify<false>(a.fine, fb, a.fine ? macros * kMacroTiles : macros, scene, a, stream);
+  const bool fb = render_feedback(scene, a, v);
+  if(classify) launch_classify<false>(a.fine, fb, a.fine ? macros * kMacroTiles : macros, scene, a, stream);
   // 2. render the lists
   if(v == kRenderPersistent)
     return launch_persistent(scene, a, tiles, n_cus, tn, stream);
@@ -1677,7 +1681,8 @@ hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant
 
 // A batch of frames with the listed kernel (trt_render_batch_dev): one classification over every frame's tiles, one
 // render kernel over the joint lists — the launch shape of one frame with as many tiles as all of them together.
-hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, int n_cus, const Tuning& tn, hipStream_t stream)
+hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, bool classify, int n_cus, const Tuning& tn,
+                               hipStream_t stream)
 {
   const RenderArgs& a = b.fr[0];
   if(b.n_frames == 0 || a.n_local_rows == 0 || a.W == 0)
@@ -1685,8 +1690,8 @@ hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, int n_
   if(scene.alt_solver != kSolverWalk || a.rendered)
     return hipErrorInvalidValue;   // (trt_api.hip refuses these before)
   const uint64_t tiles = (uint64_t)tile_count(a.W) * tile_count(a.n_local_rows) * b.n_frames;
-  const bool fb = a.tile_cost != nullptr && a.heavy_x16 != 0u && a.stats == nullptr;
-  launch_classify<true>(a.fine, fb, (uint64_t)b.per_frame * b.n_frames, scene, b, stream);
+  const bool fb = render_feedback(scene, a, kRenderListed);
+  if(classify) launch_classify<true>(a.fine, fb, (uint64_t)b.per_frame * b.n_frames, scene, b, stream);
   const uint32_t grid = listed_grid(tiles, n_cus, tn);
   if(scene.f64) launch_listed<double, false, true>(scene, b, fb, false, a.stats != nullptr, grid, stream);
   else launch_listed<float, false, true>(scene, b, fb, false, a.stats != nullptr, grid, stream);

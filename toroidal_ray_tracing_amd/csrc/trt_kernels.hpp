@@ -150,10 +150,17 @@ hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_
                        hipStream_t stream);
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
-hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, int n_cus, const Tuning& tn,
-                         hipStream_t stream);
+// Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
+// — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of
+// tiles_live.  The launchers and the host's list key (trt_api.hip) ask this one function.
+bool render_feedback(const SceneK& scene, const RenderArgs& a, RenderVariant v);
+// classify = false: the lists and counts of the ctx already hold what this launch's classification would write (the
+// host's list key, trt_api.hip) — only the render kernel is launched, with the same grid and instantiation.
+hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, bool classify, int n_cus,
+                         const Tuning& tn, hipStream_t stream);
 // listed variant, default solver, no RenderedData: b.fr[0 .. n_frames) filled like the RenderArgs of launch_render, with
 // the SAME lists / counters / capacities in every frame (capacities = tiles of all frames together)
-hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, int n_cus, const Tuning& tn, hipStream_t stream);
+hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, bool classify, int n_cus, const Tuning& tn,
+                               hipStream_t stream);
 
 }  // namespace trt

@@ -45,6 +45,8 @@ SYMBOLS = {
     "trt_set_render_variant": (C.c_int, [C.c_void_p, C.c_char_p]),
     "trt_get_render_variant": (C.c_char_p, [C.c_void_p]),
     "trt_set_classification": (C.c_int, [C.c_void_p, C.c_int]),
+    "trt_set_list_reuse": (C.c_int, [C.c_void_p, C.c_int]),
+    "trt_get_list_reuse": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

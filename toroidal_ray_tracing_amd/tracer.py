@@ -64,6 +64,16 @@ class Tracer:
         """abi.TRT_CLASSIFY_AUTO (-1) | _MACRO (0) | _TILE (1): level of the tile classification."""
         self._check(self._L.trt_set_classification(self._h, int(level)))
 
+    def set_list_reuse(self, on=True):
+        """Reuse the tile lists between frames with the same view, scene and frame shape (default: on)."""
+        self._check(self._L.trt_set_list_reuse(self._h, int(bool(on))))
+
+    def list_reuse(self):
+        """Host-side totals of the render calls that launched / skipped a classification: {"classified", "reused"}."""
+        c, r = C.c_uint64(), C.c_uint64()
+        self._check(self._L.trt_get_list_reuse(self._h, C.byref(c), C.byref(r)))
+        return {"classified": int(c.value), "reused": int(r.value)}
+
     def render_variant(self):
         return self._L.trt_get_render_variant(self._h).decode()
 
