@@ -157,6 +157,122 @@ def test_two_rank_gather_reproduces_frame():
     assert out.get(timeout=5) is True
 
 
+class _LogTracer:
+    """Stand-in tracer that renders nothing and records what TiledFrame asks of it: (which instance, entry point,
+    rgba pointer of every frame, hit-pointer dict of every frame, tiling is None, camera)."""
+
+    def __init__(self, name, log):
+        self.name, self.log = name, log
+
+    def tiling_rows(self, tiling, H):
+        return len(trtd.owned_rows(H, tiling.group_rows, tiling.n_parts, tiling.part))
+
+    def render_dev(self, scene, g, pc, W, H, rgba_ptr, camera=0, hit_ptrs=None, stream=0):
+        self.log.append((self.name, "render_dev", [rgba_ptr], [hit_ptrs], True, camera))
+
+    def render_tiled_dev(self, scene, g, pc, W, H, tiling, rgba_ptr, camera=0, hit_ptrs=None, stream=0):
+        self.log.append((self.name, "render_tiled_dev", [rgba_ptr], [hit_ptrs], tiling is None, camera))
+
+    def render_batch_dev(self, scene, frames, W, H, tiling=None, camera=0, stream=0):
+        self.log.append((self.name, "render_batch_dev", [f[2] for f in frames], [f[3] for f in frames], tiling is None, camera))
+
+
+def _logged(K, want_hits=(), world=1, rank=0, **kw):
+    """A CPU TiledFrame without a gather over K recording tracers; `frames(n)` renders n more frames, frame i with
+    camera i; `take()` hands out the launches logged since the last take() as (instance, entry point, output sets,
+    hit keys, tiling is None, camera) — the pointers checked against the frame's tensors and replaced by the set's index."""
+    log = []
+    W, H = 16, 64
+    frame = trtd.TiledFrame([_LogTracer(k, log) for k in range(K)], W, H, world, rank, torch.device("cpu"), want_hits=want_hits,
+                            gather="none", group_rows=8 if world > 1 else None, **kw)
+    set_of = {t.data_ptr(): o for o, t in enumerate(frame.locals)}
+    assert len(set_of) == frame.n_sets
+
+    def frames(n):
+        for _ in range(n):
+            i = frame._k
+            frame.render(("scene", i), ("g", i), ("pc", i), i, _Stream())
+
+    def take():
+        out = []
+        for name, entry, rgba, hit_ptrs, whole, cam in log:
+            sets = tuple(set_of[p] for p in rgba)
+            for o, hp in zip(sets, hit_ptrs):
+                assert hp == {n: v.data_ptr() for n, v in frame.hit_sets[o].items()}
+            out.append((name, entry, sets, tuple(sorted(hit_ptrs[0])), whole, cam))
+        del log[:]
+        return out
+
+    return frame, frames, take
+
+
+def test_launch_log_pins_contexts_and_output_sets():
+    """Which tracer instance (= context, and with it the stream), which entry point and which output set every frame
+    gets, through render(), join(), flush and finish(), written out launch by launch."""
+    # K = 1, B = 1: every frame on the one context, into the one output set
+    frame, frames, take = _logged(1, want_hits=("t", "id"))
+    assert frame.n_sets == 1
+    frames(3)
+    frame.finish()
+    assert take() == [(0, "render_dev", (0,), ("id", "t"), True, 0),
+                      (0, "render_dev", (0,), ("id", "t"), True, 1),
+                      (0, "render_dev", (0,), ("id", "t"), True, 2)]
+
+    # K = 3, B = 1, six output sets: frame i on context i % 3 into set i % 6; a join() does not restart the rotation
+    frame, frames, take = _logged(3, output_sets=4)
+    assert frame.n_sets == 6
+    frames(4)
+    frame.join()
+    assert take() == [(0, "render_dev", (0,), (), True, 0),
+                      (1, "render_dev", (1,), (), True, 1),
+                      (2, "render_dev", (2,), (), True, 2),
+                      (0, "render_dev", (3,), (), True, 3)]
+    frames(4)
+    assert frame.finish() is frame.locals[1]
+    assert take() == [(1, "render_dev", (4,), (), True, 4),
+                      (2, "render_dev", (5,), (), True, 5),
+                      (0, "render_dev", (0,), (), True, 6),
+                      (1, "render_dev", (1,), (), True, 7)]
+    frame.restart()
+    frames(1)
+    assert take() == [(0, "render_dev", (0,), (), True, 0)]
+
+    # K = 2, B = 2, eight output sets: frame i into set i % 8, launch j SINCE THE LAST join() on context j % 2, scene and
+    # camera those of the launch's last frame; join() and finish() flush a partial batch
+    frame, frames, take = _logged(2, want_hits=("t",), output_sets=5, batch=2)
+    assert frame.n_sets == 8
+    frames(6)
+    assert take() == [(0, "render_batch_dev", (0, 1), ("t",), True, 1),
+                      (1, "render_batch_dev", (2, 3), ("t",), True, 3),
+                      (0, "render_batch_dev", (4, 5), ("t",), True, 5)]
+    frame.join()          # after three launches: the fourth is on context 0 again
+    assert take() == []
+    frames(5)
+    assert take() == [(0, "render_batch_dev", (6, 7), ("t",), True, 7),
+                      (1, "render_batch_dev", (0, 1), ("t",), True, 9)]
+    frame.join()          # flushes frame 10 alone, and restarts the rotation behind it
+    assert take() == [(0, "render_batch_dev", (2,), ("t",), True, 10)]
+    frames(3)
+    assert take() == [(0, "render_batch_dev", (3, 4), ("t",), True, 12)]
+    assert frame.finish() is frame.locals[5]
+    assert take() == [(1, "render_batch_dev", (5,), ("t",), True, 13)]
+    assert frame._k == 14
+
+    # one part of a frame tiled over 8: the tiled entry point, and the batch is handed the tiling
+    frame, frames, take = _logged(1, want_hits=("t",), world=8, rank=3)
+    assert frame.local_rows == 8
+    frames(2)
+    frame.finish()
+    assert take() == [(0, "render_tiled_dev", (0,), ("t",), False, 0),
+                      (0, "render_tiled_dev", (0,), ("t",), False, 1)]
+    frame, frames, take = _logged(1, want_hits=("t",), world=8, rank=3, batch=8)
+    assert frame.n_sets == 8
+    frames(9)
+    assert take() == [(0, "render_batch_dev", (0, 1, 2, 3, 4, 5, 6, 7), ("t",), False, 7)]
+    frame.finish()
+    assert take() == [(0, "render_batch_dev", (0,), ("t",), False, 8)]
+
+
 def _bench(args, env=None):
     import subprocess
     e = dict(os.environ)

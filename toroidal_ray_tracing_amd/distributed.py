@@ -86,6 +86,16 @@ class TiledFrame:
     once per gather — and the all-gathers read the staging copy on the process group's stream: no render stream ever
     waits for a link-bound collective, and the collective of a batch runs behind the whole next batch.  ``finish()``
     drains everything and returns the last complete row-major frame.
+
+    What a tracer must offer (tracer.Tracer, and the stand-ins of bench.py --dry-run and tests/test_distributed.py), called
+    with exactly these keywords; addresses are ints, `stream` is a raw stream handle:
+      tiling_rows(tiling, H)                                   rows of the part (world > 1 only)
+      render_dev(scene, g, pc, W, H, rgba_ptr, camera=, hit_ptrs=, stream=)                  world == 1, single frames
+      render_tiled_dev(scene, g, pc, W, H, tiling, rgba_ptr, camera=, hit_ptrs=, stream=)    world > 1, single frames
+      render_batch_dev(scene, frames, W, H, tiling=, camera=, stream=)                       batch > 1; frames =
+          [(g, pc, rgba_ptr, hit_ptrs)], tiling None with world == 1
+      post_dev(rgba_ptr, n_pixels, 0, unorm8_out_ptr, stream=)                               gather="rgba8" only
+    hit_ptrs is a dict name -> address, empty without want_hits.
     """
 
     def __init__(self, tracer, W, H, world, rank, device, want_hits=(), group_rows=None,
@@ -127,8 +137,8 @@ class TiledFrame:
         self.batch = max(1, int(batch))
         if self.batch > abi.TRT_MAX_BATCH:
             raise ValueError(f"batch={self.batch} > TRT_MAX_BATCH")
-        self._queued = []          # batch mode: (g, pc, output set, gather?) of the frames not yet launched
-        self._flushes = 0          # batch mode: launches since the last join() — launch j goes to stream j % K
+        self._queued = []          # (scene, camera, g, pc, output set, gather?) of the frames not yet launched
+        self._flushes = 0          # batch mode: launches since the last join() (flush() has the rule)
         f32 = dict(dtype=torch.float32, device=device)
         # one output set per frame in flight (K streams x B frames per launch), or more (output_sets): frame i renders into
         # set i % n_sets on stream (i // B) % K; n_sets is a multiple of K·B, so a set is only ever written on one stream
@@ -142,6 +152,8 @@ class TiledFrame:
                 h["id"] = torch.empty(self.local_pixels, dtype=torch.int32, device=device)
             self.hit_sets.append(h)
         self.hits = self.hit_sets[0]
+        # (rgba address, hit addresses) of every output set, as the tracers take them: the tensors never move
+        self._ptrs = [(loc.data_ptr(), {n: v.data_ptr() for n, v in h.items()}) for loc, h in zip(self.locals, self.hit_sets)]
         # K > 1: the render streams are this object's own; K == 1: the caller's stream is the render stream
         cuda = self.device.type == "cuda"
         self._own = [torch.cuda.Stream(device=self.device) if cuda else _NullStream() for _ in range(K)] if K > 1 else None
@@ -151,10 +163,11 @@ class TiledFrame:
         gdt = dict(dtype=torch.uint8 if self.mode == "rgba8" else torch.float32, device=device)
         self.sends = [torch.empty(self.local_rows, W, 4, **gdt) for _ in range(2)] if self.gather else []
         self.fulls = [torch.empty(H, W, 4, **gdt) for _ in range(2)] if self.gather else self.locals
+        self._send_ptrs = [t.data_ptr() for t in self.sends]
         self._pending = [[], []]   # in-flight all-gathers reading staging buffer j
         self._stage = 0            # staging buffer of the next gather
         self._k = 0                # frames rendered
-        self._last = 0             # gathered frame (or, without a gather, output set) that finish() hands out
+        self._last = 0             # gathered frame (or, without a gather, output set of the last frame) that finish() hands out
         self._newest = None        # gathered frame of the most recent gather (in flight until finish())
 
     @property
@@ -195,70 +208,74 @@ class TiledFrame:
     def render(self, scene, g, pc, camera, stream, events=None):
         """One frame: render this rank's rows on the frame's stream (the caller's `stream`, or with K tracers the next of
         the K own streams, which branch off `stream` at the first frame after construction / join()); on a gather frame
-        copy or tonemap the rows into a staging buffer and start the all-gathers behind that.
-        `events` = (start, end) torch.cuda.Events recorded around the render launches only.
+        copy or tonemap the rows into a staging buffer and start the all-gathers behind that.  In batch mode the frame
+        is queued, and the B-th one launches them all.
+        `events` = (start, end) torch.cuda.Events recorded around the render launches only (single frames only).
         Returns nothing: a frame is handed out by finish() (with frames and collectives in flight neither gathered
         frame is stable)."""
-        K = len(self.trs)
-        k = self._k % K
-        o = self._k % self.n_sets   # output set; n_sets is a multiple of K (K·B in batch mode), so set o is only ever written on one stream
+        self._frame(scene, g, pc, camera, stream, events, self.gather)
+
+    def _frame(self, scene, g, pc, camera, stream, events, gathers):
+        """render(), and what capture_step() captures (`gathers` False: a gather is never captured)."""
+        o = self._k % self.n_sets   # output set; n_sets is a multiple of K·B, so set o is only ever written on one stream
         self._k += 1
         self._caller = stream
-        if self.batch > 1:
-            self._camera, self._scene = camera, scene
-            self._queued.append((g, pc, o, self.gather and self._k % self.gather_every == 0))
-            if len(self._queued) == self.batch:
-                self.flush(stream)
-            if not self.gather:
-                self._last = o
-            return
-        if self._own is not None:
-            if not self._forked:
-                if self.device.type == "cuda":
-                    for s in self._own:
-                        s.wait_stream(stream)
-                self._forked = True
-            s = self._own[k]
-        else:
-            s = stream
-        tr, hp = self.trs[k], {n: v.data_ptr() for n, v in self.hit_sets[o].items()}
-        do_gather = self.gather and self._k % self.gather_every == 0
-        if events:
-            events[0].record(s)
-        if self.world == 1:
-            tr.render_dev(scene, g, pc, self.W, self.H, self.locals[o].data_ptr(), camera=camera, hit_ptrs=hp, stream=s.cuda_stream)
-        else:
-            tr.render_tiled_dev(scene, g, pc, self.W, self.H, self.tiling, self.locals[o].data_ptr(), camera=camera,
-                                hit_ptrs=hp, stream=s.cuda_stream)
-        if events:
-            events[1].record(s)
-        if do_gather:
-            self._gather(o, s, tr)
-        if not self.gather:
-            self._last = o
+        self._queued.append((scene, camera, g, pc, o, gathers and self._k % self.gather_every == 0))
+        if len(self._queued) == self.batch:
+            self.flush(stream, events)
 
-    def flush(self, stream=None):
-        """Batch mode: launch the frames collected so far (a full batch launches by itself)."""
-        stream = stream or self._caller
+    def flush(self, stream=None, events=None):
+        """Launch the frames collected so far — with the scene and the camera of the last of them — and start their
+        gathers (a full batch launches by itself; single frames are batches of one)."""
         if not self._queued:
             return
         q, self._queued = self._queued, []
-        kb = self._flushes % len(self.trs)   # (full batches between two join()s: n_sets / B is a multiple of K, a set keeps its stream)
-        self._flushes += 1
-        tr = self.trs[kb]
-        if self._own is not None:
-            if not self._forked:
-                if self.device.type == "cuda":
-                    for s in self._own:
-                        s.wait_stream(stream)
-                self._forked = True
-            stream = self._own[kb]
-        frames = [(g, pc, self.locals[o].data_ptr(), {n: v.data_ptr() for n, v in self.hit_sets[o].items()}) for g, pc, o, _ in q]
-        tr.render_batch_dev(self._scene, frames, self.W, self.H, self.tiling if self.world > 1 else None, camera=self._camera,
-                            stream=stream.cuda_stream)
-        for _, _, o, do_gather in q:
-            if do_gather:
-                self._gather(o, stream, tr)
+        # THE rule for the context (and own stream) of a launch.  Single frames: frame i takes context i % K, whatever
+        # was joined in between.  Batches: launch j since the last join() takes context j % K — a join() may have flushed
+        # a partial batch, and every stream has been waited for by then, so the rotation starts anew behind it.  Either
+        # way a set keeps its context between two join()s: n_sets is a multiple of K·B.
+        if self.batch == 1:
+            k = (self._k - 1) % len(self.trs)
+        else:
+            k = self._flushes % len(self.trs)
+            self._flushes += 1
+        s = self._fork(stream or self._caller, k)
+        scene, camera = q[-1][:2]
+        self._launch(k, s, scene, camera, [f[2:5] for f in q], events)
+        for f in q:
+            if f[5]:
+                self._gather(f[4], s, self.trs[k])
+
+    def _fork(self, stream, k):
+        """The stream of context k: the caller's `stream`, or the k-th of the own streams, which branch off `stream` once
+        (until join() has `stream` wait for them)."""
+        if self._own is None:
+            return stream
+        if not self._forked:
+            if self.device.type == "cuda":
+                for s in self._own:
+                    s.wait_stream(stream)
+            self._forked = True
+        return self._own[k]
+
+    def _launch(self, k, s, scene, camera, frames, events=None):
+        """Render `frames` = [(g, pc, output set)] with context k on stream s: one frame with the whole-frame or the tiled
+        entry point, B > 1 with ONE call of the batch entry point (also for a partial batch)."""
+        tr, tiling = self.trs[k], self.tiling if self.world > 1 else None
+        if self.batch > 1:
+            tr.render_batch_dev(scene, [(g, pc, *self._ptrs[o]) for g, pc, o in frames], self.W, self.H, tiling=tiling,
+                                camera=camera, stream=s.cuda_stream)
+            return
+        (g, pc, o), = frames
+        rgba, hp = self._ptrs[o]
+        if events:
+            events[0].record(s)
+        if tiling is None:
+            tr.render_dev(scene, g, pc, self.W, self.H, rgba, camera=camera, hit_ptrs=hp, stream=s.cuda_stream)
+        else:
+            tr.render_tiled_dev(scene, g, pc, self.W, self.H, tiling, rgba, camera=camera, hit_ptrs=hp, stream=s.cuda_stream)
+        if events:
+            events[1].record(s)
 
     def _gather(self, o, s, tr):
         """Copy or tonemap output set o into a staging buffer on stream s and start the all-gathers behind that."""
@@ -267,7 +284,7 @@ class TiledFrame:
         with self._on(s):
             self._retire(j)   # the gather that read this staging buffer two gathers ago is complete before it is overwritten
             if self.mode == "rgba8":
-                tr.post_dev(self.locals[o].data_ptr(), self.local_pixels, 0, self.sends[j].data_ptr(), stream=s.cuda_stream)
+                tr.post_dev(self._ptrs[o][0], self.local_pixels, 0, self._send_ptrs[j], stream=s.cuda_stream)
             else:
                 self.sends[j].copy_(self.locals[o], non_blocking=True)
             G, span = self.group_rows if self.world > 1 else self.H, (self.group_rows * self.world if self.world > 1 else self.H)
@@ -292,38 +309,17 @@ class TiledFrame:
             raise ValueError(f"a captured step must cover whole rounds of the {self.n_sets} output sets (n_frames={n_frames}, frame counter {self._k})")
         if self.gather and self.gather_every % n_frames:
             raise ValueError("a gather may only fall on the last frame of a captured step (gather_every must be a multiple of n_frames)")
-        self.join(stream)
-        K = len(self.trs)
+        self.join(stream)   # (whole rounds of the output sets are whole batches: n_sets is a multiple of K·B)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(stream)
         graph = torch.cuda.CUDAGraph()
+        k0 = self._k
         with torch.cuda.stream(side), torch.cuda.graph(graph, stream=side):
-            if self._own is not None:
-                for s in self._own:
-                    s.wait_stream(side)
-            if self.batch > 1:
-                if n_frames % self.batch:
-                    raise ValueError("a captured step must consist of whole batches")
-                self._caller = side
-                for f in range(n_frames):
-                    self._queued.append((g, pc, f % self.n_sets, False))
-                    self._camera, self._scene = camera, scene
-                    if len(self._queued) == self.batch:
-                        self.flush(side)
-            for f in range(n_frames if self.batch == 1 else 0):
-                k, o = f % K, f % self.n_sets
-                s = self._own[k] if self._own is not None else side
-                hp = {n: v.data_ptr() for n, v in self.hit_sets[o].items()}
-                if self.world == 1:
-                    self.trs[k].render_dev(scene, g, pc, self.W, self.H, self.locals[o].data_ptr(), camera=camera, hit_ptrs=hp, stream=s.cuda_stream)
-                else:
-                    self.trs[k].render_tiled_dev(scene, g, pc, self.W, self.H, self.tiling, self.locals[o].data_ptr(), camera=camera,
-                                                 hit_ptrs=hp, stream=s.cuda_stream)
-            if self._own is not None:
-                for s in self._own:
-                    side.wait_stream(s)
+            for _ in range(n_frames):
+                self._frame(scene, g, pc, camera, side, None, False)   # the own streams branch off `side` at the first
+            self.join(side)                                          # … and `side` continues behind all of them
         stream.wait_stream(side)
-        self._forked, self._flushes = False, 0   # (the capture forked and joined the own streams itself)
+        self._k, self._caller = k0, stream
         self._graph, self._graph_frames = graph, n_frames
         return graph
 
@@ -334,17 +330,14 @@ class TiledFrame:
         self._caller = stream
         self._graph.replay()
         self._k += n
-        o = (self._k - 1) % self.n_sets
         if self.gather and self._k % self.gather_every == 0:
-            self._gather(o, stream, self.trs[((n - 1) // self.batch) % len(self.trs)])
-        if not self.gather:
-            self._last = o
+            self._gather((self._k - 1) % self.n_sets, stream, self.trs[((n - 1) // self.batch) % len(self.trs)])
 
     def join(self, stream=None):
         """K own streams: order `stream` (default: the stream of the last render call) behind every frame issued so far;
         the next render() branches off again."""
         stream = stream or self._caller
-        if self.batch > 1 and stream is not None:
+        if stream is not None:
             self.flush(stream)
         self._flushes = 0
         if self._own is not None and self._forked and stream is not None:
@@ -368,4 +361,6 @@ class TiledFrame:
                     self._retire(self._stage ^ i)   # oldest gather first
             if self._newest is not None:
                 self._last = self._newest           # every gather has been waited for: the newest frame is complete
+        elif self._k:
+            self._last = (self._k - 1) % self.n_sets
         return self.full

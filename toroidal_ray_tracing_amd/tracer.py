@@ -19,6 +19,22 @@ class TrtError(RuntimeError):
         self.code = code
 
 
+def _vp(address):
+    """Device address or stream handle (int; 0 = none) as the c_void_p the C ABI takes."""
+    return C.c_void_p(int(address) or None)
+
+
+def _hits(hit_ptrs):
+    """dict name -> device address (0 / None: stream not wanted) as a trt_hits; None for no dict or an empty one."""
+    if not hit_ptrs:
+        return None
+    return abi.hits_struct({k: (int(v) if v else None) for k, v in hit_ptrs.items()})
+
+
+def _ref(struct):
+    return C.byref(struct) if struct is not None else None
+
+
 class Tracer:
     """One context per device (not re-entrant), like one ``HelloVulkan`` instance."""
 
@@ -100,9 +116,9 @@ class Tracer:
     def trace_dev(self, scene, ray_ptrs, n, hit_ptrs, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses, hit_ptrs = dict name -> address."""
         rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
-        hs = abi.hits_struct({k: (int(v) if v else None) for k, v in hit_ptrs.items()})
+        hs = _hits(hit_ptrs) or abi.trt_hits()   # (an empty dict: every stream null, for the library to refuse)
         self._check(self._L.trt_trace_dev(self._h, C.byref(rays), C.byref(scene.c), tmin, tmax,
-                                          C.byref(hs), C.c_void_p(int(stream))))
+                                          C.byref(hs), _vp(stream)))
 
     # -- render -------------------------------------------------------------------------
     def render(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, want_hits=True):
@@ -111,60 +127,44 @@ class Tracer:
         hits = abi.alloc_hits(W * H) if want_hits else None
         hs = abi.hits_struct(hits) if hits is not None else None
         self._check(self._L.trt_render(self._h, C.byref(g), C.byref(pc), C.byref(scene.c), W, H,
-                                       camera, abi.ptr(rgba), C.byref(hs) if hs is not None else None))
+                                       camera, abi.ptr(rgba), _ref(hs)))
         return rgba, hits
 
     def render_dev(self, scene, g, pc, W, H, rgba_ptr, rows=None, camera=abi.TRT_CAMERA_PINHOLE,
                    hit_ptrs=None, rendered_ptr=0, stream=0):
         """Device buffers, asynchronous on ``stream``; rows = (begin, end) of the band to render."""
         r0, r1 = (0, H) if rows is None else rows
-        hs = None
-        if hit_ptrs:
-            hs = abi.hits_struct({k: (int(v) if v else None) for k, v in hit_ptrs.items()})
         self._check(self._L.trt_render_dev(self._h, C.byref(g), C.byref(pc), C.byref(scene.c), W, H,
-                                           r0, r1, camera, C.c_void_p(int(rgba_ptr) or None),
-                                           C.byref(hs) if hs is not None else None,
-                                           C.c_void_p(int(rendered_ptr) or None),
-                                           C.c_void_p(int(stream) or None)))
+                                           r0, r1, camera, _vp(rgba_ptr), _ref(_hits(hit_ptrs)),
+                                           _vp(rendered_ptr), _vp(stream)))
 
     def render_tiled_dev(self, scene, g, pc, W, H, tiling, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE,
                          hit_ptrs=None, rendered_ptr=0, stream=0):
         """Rows owned by ``tiling.part`` only (multi-GPU tiling, include/trt.h ``trt_tiling``)."""
-        hs = None
-        if hit_ptrs:
-            hs = abi.hits_struct({k: (int(v) if v else None) for k, v in hit_ptrs.items()})
         self._check(self._L.trt_render_tiled_dev(self._h, C.byref(g), C.byref(pc), C.byref(scene.c), W, H,
-                                                 C.byref(tiling), camera, C.c_void_p(int(rgba_ptr) or None),
-                                                 C.byref(hs) if hs is not None else None,
-                                                 C.c_void_p(int(rendered_ptr) or None),
-                                                 C.c_void_p(int(stream) or None)))
+                                                 C.byref(tiling), camera, _vp(rgba_ptr), _ref(_hits(hit_ptrs)),
+                                                 _vp(rendered_ptr), _vp(stream)))
 
     def render_batch_dev(self, scene, frames, W, H, tiling=None, camera=abi.TRT_CAMERA_PINHOLE, stream=0):
         """Up to TRT_MAX_BATCH consecutive frames of a frame loop in ONE pair of launches (trt_render_batch_dev).
         frames: sequence of (g, pc, rgba_ptr, hit_ptrs | None); tiling None = whole frames."""
         n = len(frames)
         arr = (abi.trt_frame * n)()
-        keep = []
-        for dst, (g, pc, rgba_ptr, hit_ptrs) in zip(arr, frames):
+        keep = [_hits(f[3]) for f in frames]   # arr holds bare addresses of these: alive until the call has returned
+        for dst, (g, pc, rgba_ptr, _), hs in zip(arr, frames, keep):
             dst.g, dst.pc = C.pointer(g), C.pointer(pc)
             dst.rgba_dev = int(rgba_ptr) or None
-            if hit_ptrs:
-                hs = abi.hits_struct({k: (int(v) if v else None) for k, v in hit_ptrs.items()})
-                keep.append(hs)
+            if hs is not None:
                 dst.first_hit_dev = C.pointer(hs)
-        self._check(self._L.trt_render_batch_dev(self._h, arr, n, C.byref(scene.c), W, H,
-                                                 C.byref(tiling) if tiling is not None else None, camera,
-                                                 C.c_void_p(int(stream) or None)))
+        self._check(self._L.trt_render_batch_dev(self._h, arr, n, C.byref(scene.c), W, H, _ref(tiling), camera, _vp(stream)))
 
     def tiling_rows(self, tiling, H):
         return int(self._L.trt_tiling_rows(C.byref(tiling), H))
 
     def post_dev(self, rgba_ptr, n_pixels, f32_out_ptr=0, unorm8_out_ptr=0, stream=0):
         """Tonemap pass of post.frag (pow(c, 1/2.2)) on device buffers."""
-        self._check(self._L.trt_post_dev(self._h, C.c_void_p(int(rgba_ptr) or None), int(n_pixels),
-                                         C.c_void_p(int(f32_out_ptr) or None),
-                                         C.c_void_p(int(unorm8_out_ptr) or None),
-                                         C.c_void_p(int(stream) or None)))
+        self._check(self._L.trt_post_dev(self._h, _vp(rgba_ptr), int(n_pixels), _vp(f32_out_ptr), _vp(unorm8_out_ptr),
+                                         _vp(stream)))
 
     def splat_dev(self, points_ptr, n_points, view_proj, W, H, rgba_ptr, clear=(0.8, 0.8, 0.8, 1.0),
                   point_size=2.5, stream=0):
@@ -172,9 +172,8 @@ class Tracer:
         4x4 numpy matrix in math convention (M[row, col]); clear colour as SEC/main.cpp:178."""
         vp = (C.c_float * 16)(*np.asarray(view_proj, np.float32).T.reshape(-1).tolist())
         cc = (C.c_float * 4)(*[float(v) for v in clear])
-        self._check(self._L.trt_splat_dev(self._h, C.c_void_p(int(points_ptr) or None), int(n_points), vp, W, H,
-                                          cc, float(point_size), C.c_void_p(int(rgba_ptr) or None),
-                                          C.c_void_p(int(stream) or None)))
+        self._check(self._L.trt_splat_dev(self._h, _vp(points_ptr), int(n_points), vp, W, H,
+                                          cc, float(point_size), _vp(rgba_ptr), _vp(stream)))
 
     def raytrace(self, scene, g, light, max_depth, clear_color, W, H, rgba_ptr, camera=0, rho=0.0,
                  **kw):
