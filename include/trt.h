@@ -103,9 +103,11 @@ typedef struct trt_material {
   int32_t textureId; /* must be -1: tori are untextured (REFL rchit:100)                */
 } trt_material;      /* 80 bytes                                                        */
 
-/* One analytic torus: centre C, symmetry axis +y (the reference's world-up,
- * REFL/main.cpp:95), major radius R, tube radius r, 0 < r < R.  Replaces one TLAS
- * instance + its ObjDesc (REFL/shaders/host_device.h:57-64). */
+/* One analytic torus: centre C, major radius R, tube radius r, 0 < r < R; symmetry axis +y (the
+ * reference's world-up, REFL/main.cpp:95) unless trt_set_torus_axes names another one.  Replaces one
+ * TLAS instance + its ObjDesc (REFL/shaders/host_device.h:57-64): of the instance's mat4 the
+ * translation is `center`, the uniform scale is folded into R and r, and the rotation is the axis
+ * (INTEGRATION.md shows the arithmetic). */
 typedef struct trt_torus {
   float   center[3];
   float   R;
@@ -173,6 +175,17 @@ int         trt_create(int device, trt_ctx** out);   /* one ctx per device, not 
 void        trt_destroy(trt_ctx* ctx);
 const char* trt_last_error(const trt_ctx* ctx);      /* ctx may be NULL: create errors   */
 int         trt_set_solver(trt_ctx* ctx, int solver);    /* one of TRT_SOLVE_*                 */
+
+/* Axis of symmetry of every torus of the scenes passed to later calls: n_tori x 3 floats, any non-zero finite
+ * length (normalised by the library).  NULL / n_tori == 0: every torus turns about +y again (the default).
+ * A later call whose scene has a different n_tori fails with TRT_E_SCENE (a stale setting never applies
+ * silently).  The floats are copied.  TRT_E_INVALID: ctx == NULL or n_tori > TRT_MAX_TORI; TRT_E_SCENE: an axis
+ * that is zero, NaN or infinite (the message names the torus; the previous setting stays).
+ * A torus whose normalised axis is exactly (0,1,0) takes the same path, bit for bit, as without this call.  For
+ * any other axis the torus is tested in a frame of its own: results agree with FP64 arithmetic to the
+ * library's usual tolerances and are identical between the kernel variants and launch paths, and the enclosure cull
+ * (trt_scene) leaves out every pair of tori in which either one has such an axis (same results, more tests traced). */
+int trt_set_torus_axes(trt_ctx* ctx, const float* axes, uint32_t n_tori);
 
 /* ---- trace(rays_in -> hits_out): closest hit of every ray against the scene -------- */
 /* Host buffers: copies in, launches, copies out, synchronises. */

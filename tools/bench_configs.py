@@ -95,6 +95,24 @@ render_case("C3 with Ferrari FP64", camera.single_torus_scene(), camera.baseline
             variants=("listed",), solver=abi.TRT_SOLVE_FERRARI_F64)
 render_case("C4 8 nested tori, FP64 solve", camera.nested_tori_scene(), camera.baseline_camera(W, W), camera.baseline_push(5), W, W, f64=True)
 render_case("C4' 8 nested tori, FP32 solve", camera.nested_tori_scene(), camera.baseline_camera(W, W), camera.baseline_push(5), W, W)
+# eight interlocking rings, every one on an axis of its own: closest-of-8 with nothing for the enclosure cull to skip
+def traced_case(name, sc, g, pc, W, H, f64):
+    rgba = torch.empty(H, W, 4, device=dev)
+    tr.set_solver(abi.TRT_SOLVE_F64 if f64 else abi.TRT_SOLVE_F32)
+    tr.enable_stats(True)
+    tr.render_dev(sc, g, pc, W, H, rgba.data_ptr(), stream=s.cuda_stream)
+    st = tr.stats()
+    tr.enable_stats(False)
+    ms = timeit(lambda: tr.render_dev(sc, g, pc, W, H, rgba.data_ptr(), stream=s.cuda_stream))
+    tr.set_solver(abi.TRT_SOLVE_F32)
+    tot = st["primary_tests"] + st["bounce_tests"] + st["shadow_tests"]
+    print(f"{name:34s} {'listed':10s} traced_tests_per_s {st['traced_tests'] / ms * 1e3:.4g}  {ms:8.4f} ms  traced {st['traced_tests']}  "
+          f"solved {st['solved_tests']}  all tests {tot} ({tot / ms / 1e6:.1f} Gtests/s)")
+
+
+for f64 in (False, True):
+    traced_case(f"8 linked rings, {'FP64' if f64 else 'FP32'} solve, 4096^2 d5", camera.linked_rings_scene(), camera.linked_rings_camera(W, W),
+                camera.baseline_push(5), W, W, f64)
 pc = camera.baseline_push(5); pc.rho = 4.0
 render_case("toroidal camera, interior R=6", camera.single_torus_scene(R=6.0, r=1.5, material=camera.PLASTIC),
             camera.toroidal_camera(W, W), pc, W, W, cam=1)

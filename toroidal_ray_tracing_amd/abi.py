@@ -110,11 +110,16 @@ RAY_FIELDS = ("ox", "oy", "oz", "dx", "dy", "dz")
 class Scene:
     """Owns the ctypes arrays behind a ``trt_scene`` (keeps them alive)."""
 
-    def __init__(self, tori, materials):
+    def __init__(self, tori, materials, axes=None):
         """tori: iterable of (center(3), R, r, matId); materials: iterable of dicts with the
         WaveFrontMaterial field names (missing fields default to 0, textureId to -1,
-        dissolve/ior to 1)."""
+        dissolve/ior to 1); axes: None (every torus turns about +y) or one axis of symmetry (3 floats, any
+        non-zero length) per torus — they travel beside the trt_scene (trt_set_torus_axes): a Tracer sets them
+        before every call that takes this scene.  The rule, in full: a Scene with axes always renders with its own axes;
+        a Scene without axes renders on +y — unless the caller has set axes on the Tracer with set_torus_axes(), which
+        then hold for every Scene without axes of its own until set_torus_axes(None)."""
         tori = list(tori)
+        self.axes = None if axes is None else axes_array(axes, len(tori))
         materials = list(materials)
         self._tori = (trt_torus * len(tori))()
         for dst, (c, R, r, mid) in zip(self._tori, tori):
@@ -137,6 +142,14 @@ class Scene:
 
     def tori_list(self):
         return [(tuple(t.center), t.R, t.r, t.matId) for t in self._tori]
+
+
+def axes_array(axes, n_tori=None):
+    """(n_tori, 3) float32 array of torus axes as trt_set_torus_axes takes it."""
+    a = np.ascontiguousarray(np.asarray(axes, np.float32).reshape(-1, 3))
+    if n_tori is not None and len(a) != n_tori:
+        raise ValueError(f"{len(a)} axes for {n_tori} tori")
+    return a
 
 
 def make_globals(view_inverse, proj_inverse, view_proj=None, center=(0.0, 0.0, 0.0)):

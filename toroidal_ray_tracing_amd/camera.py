@@ -58,17 +58,32 @@ FLAT = dict(ambient=(0.3, 0.3, 0.3), diffuse=(0.4, 0.4, 0.8), specular=(0.0, 0.0
             shininess=1.0, illum=0)
 
 
-def single_torus_scene(center=(0.0, 0.0, 0.0), R=1.0, r=0.25, material=MIRROR):
-    """BASELINE configs 1-3, 5: single torus R=1.0, r=0.25."""
-    return abi.Scene([(center, R, r, 0)], [material])
+def single_torus_scene(center=(0.0, 0.0, 0.0), R=1.0, r=0.25, material=MIRROR, axis=None):
+    """BASELINE configs 1-3, 5: single torus R=1.0, r=0.25.  axis: its axis of symmetry (None: +y)."""
+    return abi.Scene([(center, R, r, 0)], [material], axes=None if axis is None else [axis])
 
 
-def nested_tori_scene(center=(0.0, 0.0, 0.0)):
+def nested_tori_scene(center=(0.0, 0.0, 0.0), axes=None):
     """BASELINE config 4: 8 nested tori ("tokamak shells"), same centre, R=1,
     r = 0.05…0.40 step 0.05; the inner shells are Phong, the outer ones mirrors
-    (SURVEY.md §8d)."""
+    (SURVEY.md §8d).  axes: one axis per shell (None: +y)."""
     tori = [(center, 1.0, 0.05 * (i + 1), 0 if i < 4 else 1) for i in range(8)]
-    return abi.Scene(tori, [PLASTIC, MIRROR])
+    return abi.Scene(tori, [PLASTIC, MIRROR], axes=axes)
+
+
+def linked_rings_scene(n=8, R=1.0, r=0.2, spacing=1.2):
+    """A chain of n interlocking rings along x, turned 45° about its length: centres `spacing` apart, axes alternately
+    (0,1,1) and (0,-1,1) — perpendicular to the chain and to each other, so each ring passes through the holes of its
+    neighbours (spacing - R inside the hole, more than 2r from the neighbour's centre circle) and none encloses another:
+    every query tests every ring.  Mirrors and Phong rings alternate in pairs."""
+    tori = [(((i - 0.5 * (n - 1)) * spacing, 0.0, 0.0), R, r, (i // 2) % 2) for i in range(n)]
+    axes = [(0.0, 1.0, 1.0) if i % 2 == 0 else (0.0, -1.0, 1.0) for i in range(n)]
+    return abi.Scene(tori, [MIRROR, PLASTIC], axes=axes)
+
+
+def linked_rings_camera(W, H):
+    """Pinhole camera that frames the eight-ring chain: eye (0,3,-11) → origin, up +y, fov 60°."""
+    return globals_for((0.0, 3.0, -11.0), (0.0, 0.0, 0.0), W, H)
 
 
 def baseline_camera(W, H):

@@ -104,8 +104,12 @@ struct trt_ctx {
     uint32_t     n_tori = 0, n_mat = 0;
     trt_torus    tori[TRT_MAX_TORI];
     trt_material mat[TRT_MAX_MATERIALS];
+    double       axis[TRT_MAX_TORI][3];   // the axes K was built with (+y where none was set)
     SceneK       K;
   } scene_cache;
+  // trt_set_torus_axes: unit axes in double, exactly (0,1,0) for a torus that is not oriented; n_axes == 0: none set.
+  uint32_t n_axes = 0;
+  double   axis[TRT_MAX_TORI][3];
   uint64_t scene_gen = 0;   // bumped whenever scene_cache is rebuilt
   uint64_t toro_gen  = 0;   // bumped by every upload of the toroidal tables
 
@@ -245,7 +249,28 @@ void torus_prepare(const trt_torus& t, TorusK<Real>& k)
   k.fourR2 = (Real)4 * R2;
 }
 
-int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, SceneK& out);
+int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], SceneK& out);
+
+// Frame of an oriented torus with unit axis a: h = the world axis x or z along which |a| is smaller (x on a tie — never
+// within 45° of a), u = normalize(h − (h·a)·a), w = u × a.  (u, a, w) is right-handed and plays (x, y, z) of the torus'
+// own frame; for a = +y it would be the identity.  The torus is symmetric about a, so any frame is geometrically right:
+// the rule only has to be deterministic.  Double arithmetic, each entry rounded to FP32 once.
+void torus_frame(const double a[3], TorusRot& out)
+{
+  const int    hi = std::fabs(a[0]) <= std::fabs(a[2]) ? 0 : 2;
+  double       u[3] = {-a[hi] * a[0], -a[hi] * a[1], -a[hi] * a[2]};
+  u[hi] += 1.0;
+  const double ul = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  for(double& c : u) c /= ul;
+  const double w[3] = {u[1] * a[2] - u[2] * a[1], u[2] * a[0] - u[0] * a[2], u[0] * a[1] - u[1] * a[0]};
+  for(int k = 0; k < 3; ++k)
+  {
+    out.m[k]     = (float)u[k];
+    out.m[3 + k] = (float)a[k];
+    out.m[6 + k] = (float)w[k];
+  }
+}
+bool is_plus_y(const double a[3]) { return a[0] == 0.0 && a[1] == 1.0 && a[2] == 0.0; }
 
 // The validated kernel constants of `s` — from the ctx's cache when the caller passes the scene of the previous call
 // again (compared byte for byte, solver included), else built and cached.
@@ -258,14 +283,22 @@ int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
   if(s->n_materials < 1 || s->n_materials > TRT_MAX_MATERIALS)
     return fail(ctx, TRT_E_SCENE, "scene: n_materials=%u outside 1..%d", s->n_materials,
                 TRT_MAX_MATERIALS);
+  if(ctx->n_axes != 0 && ctx->n_axes != s->n_tori)
+    return fail(ctx, TRT_E_SCENE, "scene: n_tori=%u, but trt_set_torus_axes set the axes of %u tori (set the axes of this scene, or NULL)",
+                s->n_tori, ctx->n_axes);
+  double axis[TRT_MAX_TORI][3];
+  for(uint32_t i = 0; i < s->n_tori; ++i)
+    for(int k = 0; k < 3; ++k) axis[i][k] = ctx->n_axes ? ctx->axis[i][k] : (k == 1 ? 1.0 : 0.0);
   auto& c = ctx->scene_cache;
   if(!(c.valid && c.precision == ctx->precision && c.n_tori == s->n_tori && c.n_mat == s->n_materials
        && !std::memcmp(c.tori, s->tori, s->n_tori * sizeof(trt_torus))
-       && !std::memcmp(c.mat, s->materials, s->n_materials * sizeof(trt_material))))
+       && !std::memcmp(c.mat, s->materials, s->n_materials * sizeof(trt_material))
+       && !std::memcmp(c.axis, axis, s->n_tori * sizeof axis[0])))
   {
     c.valid = false;
     ++ctx->scene_gen;
-    if(int rc = build_scene_uncached(ctx, s, c.K)) return rc;
+    if(int rc = build_scene_uncached(ctx, s, axis, c.K)) return rc;
+    std::memcpy(c.axis, axis, s->n_tori * sizeof axis[0]);
     c.precision = ctx->precision;
     c.n_tori = s->n_tori;
     c.n_mat  = s->n_materials;
@@ -277,7 +310,7 @@ int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
   return TRT_OK;
 }
 
-int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, SceneK& out)
+int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], SceneK& out)
 {
   std::memset(&out, 0, sizeof out);
   out.n_tori = (int)s->n_tori;
@@ -296,6 +329,13 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, SceneK& out)
     torus_prepare<float>(t, out.k32[i]);
     torus_prepare<double>(t, out.k64[i]);
     out.shade[i] = {t.center[0], t.center[1], t.center[2], t.R, t.matId};
+    // an oriented torus: its frame; the solver records keep the WORLD centre — the kernels subtract it from the ray
+    // origin before they rotate, and hand the solver a centre of zero (trt_device.hpp, LocalRay)
+    if(!is_plus_y(axis[i]))
+    {
+      out.oriented |= 1u << i;
+      torus_frame(axis[i], out.rot[i]);
+    }
   }
   // test order: largest bounding sphere first (stable insertion sort on the FP32 sum R + r)
   for(uint32_t i = 0; i < s->n_tori; ++i)
@@ -322,6 +362,7 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, SceneK& out)
       const uint32_t k = (uint32_t)out.order[p];
       const trt_torus& K = s->tori[k];
       if(k == j || K.center[0] != J.center[0] || K.center[2] != J.center[2]) continue;
+      if((out.oriented >> j | out.oriented >> k) & 1u) continue;   // the test below is the coaxial one about +y: a pair with an oriented torus is never culled
       const double dR = (double)K.R - (double)J.R, dy = (double)K.center[1] - (double)J.center[1];
       const double D  = std::sqrt(dR * dR + dy * dy);
       if(D + (double)K.r < (double)J.r - (double)J.r * 0.0009765625 && !ctx->tn.no_enclosure) out.inside[j] |= 1u << p;
@@ -544,6 +585,31 @@ extern "C" int trt_set_solver(trt_ctx* ctx, int precision)
   if(precision < TRT_SOLVE_F32 || precision > TRT_SOLVE_FERRARI_F64)
     return fail(ctx, TRT_E_INVALID, "trt_set_solver: %d is not one of the TRT_SOLVE_* constants", precision);
   ctx->precision = precision;
+  return TRT_OK;
+}
+
+extern "C" int trt_set_torus_axes(trt_ctx* ctx, const float* axes, uint32_t n_tori)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(n_tori > TRT_MAX_TORI)
+    return fail(ctx, TRT_E_INVALID, "trt_set_torus_axes: n_tori=%u exceeds %d", n_tori, TRT_MAX_TORI);
+  if(!axes || n_tori == 0)
+  {
+    ctx->n_axes = 0;
+    return TRT_OK;
+  }
+  double unit[TRT_MAX_TORI][3];
+  for(uint32_t i = 0; i < n_tori; ++i)
+  {
+    const double x = axes[3 * i], y = axes[3 * i + 1], z = axes[3 * i + 2];
+    const double len = std::sqrt(x * x + y * y + z * z);
+    if(!(len > 0.0) || !std::isfinite(len))   // (NaN fails both; the squares of finite floats cannot overflow a double)
+      return fail(ctx, TRT_E_SCENE, "trt_set_torus_axes: the axis of torus %u, (%g, %g, %g), is zero or not finite", i, x, y, z);
+    unit[i][0] = x / len; unit[i][1] = y / len; unit[i][2] = z / len;
+    if(is_plus_y(unit[i])) { unit[i][0] = 0.0; unit[i][2] = 0.0; }   // (-0 → +0: the scene cache compares bytes)
+  }
+  std::memcpy(ctx->axis, unit, sizeof unit[0] * n_tori);   // (only after every axis has passed: an error leaves the setting as it was)
+  ctx->n_axes = n_tori;
   return TRT_OK;
 }
 

@@ -85,6 +85,11 @@ struct TorusShade {  // what the closest-hit stage needs: centre, R, material in
   int   matId;
 };
 
+// World → torus-frame rotation of an oriented torus, row-major: rows u, a, w with a the unit axis of symmetry and
+// (u, a, w) right-handed, so that the torus turns about the frame's +y like every other one (the frame rule is
+// trt_api.hip: torus_frame).  local = m · world; m is orthonormal to FP32 rounding, its transpose rotates back.
+struct TorusRot { float m[9]; };
+
 struct MaterialK {  // the WaveFrontMaterial fields the Phong model reads (rchit:95-155)
   float ambient[3];
   float diffuse[3];
@@ -105,39 +110,55 @@ struct SceneK {
   int            order[TRT_MAX_TORI];  // test order: descending bounding radius R + r, ties by index
   uint32_t       inside[TRT_MAX_TORI]; // inside[i]: the tori whose tube lies strictly inside torus i's tube, as a mask over TEST-ORDER
                                        // positions (bit k = order[k]) — what a ray that leaves i's surface outwards cannot hit first
+  uint32_t       oriented;             // bit i: torus i turns about an axis other than +y (trt_set_torus_axes) and has a TorusRot record;
+                                       // zero: the scene runs the kernels without ORIENT, which know nothing of all this
+  uint32_t       reserved;
   TorusK<float>  k32[TRT_MAX_TORI];
   TorusK<double> k64[TRT_MAX_TORI];
   TorusShade     shade[TRT_MAX_TORI];
   MaterialK      mat[TRT_MAX_MATERIALS];
+  TorusRot       rot[TRT_MAX_TORI];    // read for the tori of `oriented` only
 };
 
 // Copy the scene constants from the kernel-argument segment into LDS — only the records in use
 // (header + test order + enclosure masks, n_tori solver records of the active precision, n_tori shading records,
-// n_mat materials): 46 dwords for one FP32 torus instead of the 388 of the full struct, one load per thread.
+// n_mat materials, and — in the ORIENT kernels, which run only when some torus is oriented — n_tori rotation records):
+// 48 dwords for one FP32 torus instead of the 462 of the full struct, one load per thread.
 // Reads in the hot loops then hit LDS at wave-uniform (broadcast) or material-indexed addresses.
 // The dwords of a SceneK that are in use, numbered 0 .. scene_words() - 1: word i of them sits at dword scene_word(i) of the struct.
-constexpr uint32_t kSceneHdr = 20, kSceneK32 = kSceneHdr, kSceneK64 = kSceneK32 + 80, kSceneShade = kSceneK64 + 160, kSceneMat = kSceneShade + 40;
+constexpr uint32_t kSceneHdr = 22, kSceneK32 = kSceneHdr, kSceneK64 = kSceneK32 + 80, kSceneShade = kSceneK64 + 160, kSceneMat = kSceneShade + 40,
+                   kSceneRot = kSceneMat + 88;
+template <bool ORIENT = false>
 __device__ __forceinline__ uint32_t scene_words(const SceneK& arg)
 {
-  return kSceneHdr + (arg.f64 ? 20u : 10u) * (uint32_t)arg.n_tori + 5u * (uint32_t)arg.n_tori + 11u * (uint32_t)arg.n_mat;
+  return kSceneHdr + (arg.f64 ? 20u : 10u) * (uint32_t)arg.n_tori + 5u * (uint32_t)arg.n_tori + 11u * (uint32_t)arg.n_mat
+         + (ORIENT ? 9u * (uint32_t)arg.n_tori : 0u);
 }
+template <bool ORIENT = false>
 __device__ __forceinline__ uint32_t scene_word(const SceneK& arg, uint32_t i)
 {
   const uint32_t n = (uint32_t)arg.n_tori;
   const uint32_t c0 = kSceneHdr, c1 = c0 + (arg.f64 ? 0u : 10u * n), c2 = c1 + (arg.f64 ? 20u * n : 0u), c3 = c2 + 5u * n;
+  if(ORIENT)
+  {
+    const uint32_t c4 = c3 + 11u * (uint32_t)arg.n_mat;
+    if(i >= c4) return kSceneRot + (i - c4);
+  }
   return i < c0 ? i : i < c1 ? kSceneK32 + (i - c0) : i < c2 ? kSceneK64 + (i - c1) : i < c3 ? kSceneShade + (i - c2) : kSceneMat + (i - c3);
 }
+template <bool ORIENT = false>
 __device__ __forceinline__ void stage_scene(SceneK* lds, const SceneK& arg)
 {
-  static_assert(sizeof(SceneK) == 4 * (kSceneMat + 88) && sizeof(TorusK<float>) == 40 && sizeof(TorusShade) == 20
-                    && sizeof(MaterialK) == 44 && offsetof(SceneK, k32) == 4 * kSceneK32 && offsetof(SceneK, k64) == 4 * kSceneK64
-                    && offsetof(SceneK, shade) == 4 * kSceneShade && offsetof(SceneK, mat) == 4 * kSceneMat, "SceneK layout");
+  static_assert(sizeof(SceneK) == 4 * (kSceneRot + 72) && sizeof(TorusK<float>) == 40 && sizeof(TorusShade) == 20
+                    && sizeof(MaterialK) == 44 && sizeof(TorusRot) == 36 && offsetof(SceneK, k32) == 4 * kSceneK32
+                    && offsetof(SceneK, k64) == 4 * kSceneK64 && offsetof(SceneK, shade) == 4 * kSceneShade
+                    && offsetof(SceneK, mat) == 4 * kSceneMat && offsetof(SceneK, rot) == 4 * kSceneRot, "SceneK layout");
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&arg);
   uint32_t*       dst = reinterpret_cast<uint32_t*>(lds);
-  const uint32_t  c4 = scene_words(arg);
+  const uint32_t  c4 = scene_words<ORIENT>(arg);
   for(uint32_t i = threadIdx.x; i < c4; i += blockDim.x)
   {
-    const uint32_t off = scene_word(arg, i);
+    const uint32_t off = scene_word<ORIENT>(arg, i);
     dst[off] = src[off];
   }
   __syncthreads();
@@ -672,11 +693,74 @@ __device__ __forceinline__ bool round_t(double t, float tmin, float tmax, float&
   return true;
 }
 
+// Oriented tori (SceneK::oriented, ORIENT kernels).  A test against an oriented torus runs in the torus' own frame, where it
+// turns about +y and TorusTest applies as it stands: e = O − C is formed in world space (exact in FP64, one rounding
+// in FP32 — the same subtraction setup() makes for an unoriented torus), e and D are rotated by the torus' TorusRot in
+// the solver precision, and setup() is handed a centre of zero.  Rotating O and a pre-rotated centre separately would
+// cancel two independently rounded vectors: an error that grows with the scene's distance from the world origin
+// instead of the ray's distance from the torus.  |d|² and its reciprocal are taken from the rotated direction, so the
+// local ray is self-consistent; t is the same number in both frames, and P = O + t·D stays in world space.
+__device__ __forceinline__ bool is_oriented(const SceneK& S, int i) { return ((S.oriented >> i) & 1u) != 0u; }
+
+template <class Real>
+__device__ __forceinline__ void rotate_to_local(const TorusRot& M, Real x, Real y, Real z, Real& lx, Real& ly, Real& lz)
+{
+  lx = fma_((Real)M.m[2], z, fma_((Real)M.m[1], y, (Real)M.m[0] * x));
+  ly = fma_((Real)M.m[5], z, fma_((Real)M.m[4], y, (Real)M.m[3] * x));
+  lz = fma_((Real)M.m[8], z, fma_((Real)M.m[7], y, (Real)M.m[6] * x));
+}
+__device__ __forceinline__ v3 rotate_to_world(const TorusRot& M, v3 l)
+{
+  return {fma_(M.m[6], l.z, fma_(M.m[3], l.y, M.m[0] * l.x)), fma_(M.m[7], l.z, fma_(M.m[4], l.y, M.m[1] * l.x)),
+          fma_(M.m[8], l.z, fma_(M.m[5], l.y, M.m[2] * l.x))};
+}
+
+// The ray of a query in the frame of oriented torus i, and that torus' solver constants with the centre at the
+// frame's origin: what setup() / finish() take in place of the world ray and torus_k().
+template <class Real>
+struct LocalRay {
+  Real ox, oy, oz, dx, dy, dz, dd, inv_dd;
+  __device__ __forceinline__ void direction(const TorusRot& M, float wx, float wy, float wz)
+  {
+    rotate_to_local<Real>(M, (Real)wx, (Real)wy, (Real)wz, dx, dy, dz);
+  }
+  __device__ __forceinline__ void set(const SceneK& S, int i, float wox, float woy, float woz, float wdx, float wdy, float wdz)
+  {
+    const TorusShade& C = S.shade[i];   // the world centre (FP32, as the caller passed it)
+    rotate_to_local<Real>(S.rot[i], (Real)wox - (Real)C.cx, (Real)woy - (Real)C.cy, (Real)woz - (Real)C.cz, ox, oy, oz);
+    direction(S.rot[i], wdx, wdy, wdz);
+    dd     = fma_(dz, dz, fma_(dy, dy, dx * dx));
+    inv_dd = Real(1) / dd;
+  }
+};
+template <class Real>
+__device__ __forceinline__ TorusK<Real> centred(const TorusK<Real>& T)
+{
+  TorusK<Real> c = T;
+  c.cx = Real(0); c.cy = Real(0); c.cz = Real(0);
+  return c;
+}
+
 // One ray against torus i over the open interval (tmin, tmax); t rounded to FP32.
-template <class Real, bool ALT = false, int WALK = kRenderWalk>
+template <class Real, bool ALT = false, int WALK = kRenderWalk, bool ORIENT = false>
 __device__ __forceinline__ bool torus_hit(const SceneK& S, int i, const RayK<Real>& r, float tmin, float tmax, float& t, WorkCount& wc)
 {
   Real tt;
+  if constexpr(ORIENT)
+  {
+    // one copy of the solver for both kinds of torus: the world ray and torus_k(), or — wave-uniform, every lane of a
+    // query loop is at the same torus — the local ray and the centred constants
+    LocalRay<Real> l = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+    TorusK<Real>   T = torus_k<Real>(S, i);
+    if(is_oriented(S, i))
+    {
+      l.set(S, i, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+      T = centred(T);
+    }
+    if(!torus_first_hit<Real, ALT, WALK>(l.ox, l.oy, l.oz, l.dx, l.dy, l.dz, l.dd, l.inv_dd, (Real)r.tmin, (Real)tmax, T, tt, wc, S.alt_solver))
+      return false;
+    return round_t(tt, tmin, tmax, t);
+  }
   if(!torus_first_hit<Real, ALT, WALK>((Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd, (Real)r.tmin, (Real)tmax,
                                        torus_k<Real>(S, i), tt, wc, S.alt_solver))
     return false;
@@ -690,7 +774,7 @@ __device__ __forceinline__ bool torus_hit(const SceneK& S, int i, const RayK<Rea
 // `skip` (a mask over test-order positions) names the tori this ray cannot hit first: tubes that lie strictly inside a
 // tube the ray's origin is known to be OUTSIDE of (enclosure cull) — they count as tests and cost nothing.
 // Returns the torus index or -1; `tests` counts ray–torus tests.
-template <class Real, bool ALT = false, int WALK = kRenderWalk>
+template <class Real, bool ALT = false, int WALK = kRenderWalk, bool ORIENT = false>
 __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
                                            float& t_out, uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
 {
@@ -706,9 +790,9 @@ __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tm
     if((skip >> k) & 1u)
       continue;
 #ifdef TRT_FULL_WINDOW   // timing experiment only (the tail of config 4): every torus over the FULL interval, minimum afterwards
-    if(torus_hit<Real, ALT, WALK>(S, i, r, tmin, tmax, t, wc) && t < best)
+    if(torus_hit<Real, ALT, WALK, ORIENT>(S, i, r, tmin, tmax, t, wc) && t < best)
 #else
-    if(torus_hit<Real, ALT, WALK>(S, i, r, tmin, min_(tmax, best), t, wc))
+    if(torus_hit<Real, ALT, WALK, ORIENT>(S, i, r, tmin, min_(tmax, best), t, wc))
 #endif
     {
       best = t;
@@ -720,7 +804,7 @@ __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tm
 }
 
 // Any hit — the shadow query with gl_RayFlagsTerminateOnFirstHitEXT (REFL/shaders/raytrace.rchit:114-131).
-template <class Real, bool ALT = false>
+template <class Real, bool ALT = false, bool ORIENT = false>
 __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
                                         uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
 {
@@ -732,7 +816,7 @@ __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin,
     ++tests;
     if((skip >> k) & 1u)
       continue;
-    if(torus_hit<Real, ALT>(S, S.order[k], r, tmin, tmax, t, wc))
+    if(torus_hit<Real, ALT, kRenderWalk, ORIENT>(S, S.order[k], r, tmin, tmax, t, wc))
       return true;
   }
   return false;
@@ -746,6 +830,23 @@ __device__ __forceinline__ v3 torus_normal(const TorusShade& T, v3 P)
   const float rho = sqrt_(fma_(pl.z, pl.z, pl.x * pl.x));
   const float k   = (rho - T.R) / rho;
   return normalize3(v3{pl.x * k, pl.y, pl.z * k});
+}
+// The same for torus i of the scene; an oriented torus: P − C rotated into its frame, the normal formed there as above
+// and rotated back before it is normalised (so |N| = 1 to one rounding, as for every other torus).
+template <bool ORIENT>
+__device__ __forceinline__ v3 torus_normal(const SceneK& S, int i, v3 P)
+{
+  const TorusShade& T = S.shade[i];
+  if(ORIENT && is_oriented(S, i))
+  {
+    const v3 pw = sub3(P, v3{T.cx, T.cy, T.cz});
+    v3 pl;
+    rotate_to_local<float>(S.rot[i], pw.x, pw.y, pw.z, pl.x, pl.y, pl.z);
+    const float rho = sqrt_(fma_(pl.z, pl.z, pl.x * pl.x));
+    const float k   = (rho - T.R) / rho;
+    return normalize3(rotate_to_world(S.rot[i], v3{pl.x * k, pl.y, pl.z * k}));
+  }
+  return torus_normal(T, P);
 }
 
 // ------------------------------------------------------------------------------------------

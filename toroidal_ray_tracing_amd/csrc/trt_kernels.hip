@@ -75,12 +75,13 @@ struct HitState {
   bool  wantShadow;  // dot(N,L) > 0  (rchit:112)
 };
 
+template <bool ORIENT = false>
 __device__ __forceinline__ void hit_begin(const SceneK& S, const trt_push& pc, int id, float t, v3 o,
                                           v3 d, HitState& h)
 {
   h.matId = S.shade[id].matId;                                               // rchit:95-96
   h.P     = {fma_(t, d.x, o.x), fma_(t, d.y, o.y), fma_(t, d.z, o.z)};       // BEF rchit:134
-  h.N     = torus_normal(S.shade[id], h.P);
+  h.N     = torus_normal<ORIENT>(S, id, h.P);
   const v3 lp = {pc.lightPosition[0], pc.lightPosition[1], pc.lightPosition[2]};
   h.lightIntensity = pc.lightIntensity;                                      // rchit:79
   h.lightDistance  = 100000.0f;                                              // rchit:80
@@ -250,6 +251,7 @@ __device__ __forceinline__ void stage_args(RenderArgs* lds, const RenderArgs& ar
 // the threads from 128 on copy the scene records in use — one load per thread and one barrier.  (The general loops above
 // compile to ≈200 instructions per wave with an unknown block size; a wave of the listed kernel lives for one tile, so
 // its prologue was 40 % of all instructions the LIVE part of config 3 issued — tools/timeline.py)
+template <bool ORIENT = false>
 __device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const SceneK& scene, const RenderArgs& arg)
 {
   constexpr uint32_t NA = sizeof(RenderArgs) / 4;
@@ -261,11 +263,11 @@ __device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const S
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&scene);
     uint32_t*       dst = reinterpret_cast<uint32_t*>(S);
-    const uint32_t  c4 = scene_words(scene);
+    const uint32_t  c4 = scene_words<ORIENT>(scene);
 #pragma unroll 1
     for(uint32_t i = tid - 128u; i < c4; i += 128u)
     {
-      const uint32_t off = scene_word(scene, i);
+      const uint32_t off = scene_word<ORIENT>(scene, i);
       dst[off] = src[off];
     }
   }
@@ -278,11 +280,11 @@ constexpr float kTMax = 10000.0f;  // rgen:52
 // ------------------------------------------------------------------------------------------
 // trace(rays_in → hits_out)
 // ------------------------------------------------------------------------------------------
-template <class Real, bool ALT>
+template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void trace_kernel(const SceneK scene, const TraceArgs a)
 {
   __shared__ SceneK S;
-  stage_scene(&S, scene);
+  stage_scene<ORIENT>(&S, scene);
 
   uint32_t       tests  = 0;
   WorkCount      wc;
@@ -292,12 +294,12 @@ __global__ __launch_bounds__(256) void trace_kernel(const SceneK scene, const Tr
     const v3 o = {a.rays.ox[i], a.rays.oy[i], a.rays.oz[i]};
     const v3 d = {a.rays.dx[i], a.rays.dy[i], a.rays.dz[i]};
     float     t;
-    const int id = closest_hit<Real, ALT, kWalkTable>(S, o, d, a.tmin, a.tmax, t, tests, wc);   // incoherent rays: trt_device.hpp
+    const int id = closest_hit<Real, ALT, kWalkTable, ORIENT>(S, o, d, a.tmin, a.tmax, t, tests, wc);   // incoherent rays: trt_device.hpp
     v3 P = {0.0f, 0.0f, 0.0f}, N = {0.0f, 0.0f, 0.0f};
     if(id >= 0)
     {
       P = {fma_(t, d.x, o.x), fma_(t, d.y, o.y), fma_(t, d.z, o.z)};
-      N = torus_normal(S.shade[id], P);
+      N = torus_normal<ORIENT>(S, id, P);
     }
     if(a.hits.t) a.hits.t[i] = t;
     if(a.hits.px) a.hits.px[i] = P.x;
@@ -383,7 +385,7 @@ __device__ __forceinline__ void rd_miss_tile(const RenderArgs& a, float4* tile, 
   rd_flush(a, tile, tx, ty, lane);
 }
 
-template <class Real, bool ALT>
+template <class Real, bool ALT, bool ORIENT = false>
 __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a, uint32_t x, uint32_t y, uint32_t ly, const RdSink rd,
                                             uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
 {
@@ -410,7 +412,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
   {
     v3    prdHit, nextO = origin, nextD = direction;
     float t;
-    const int id = closest_hit<Real, ALT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
+    const int id = closest_hit<Real, ALT, kRenderWalk, ORIENT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
     if(id < 0)
     {
       prdHit = miss_colour(a.pc);
@@ -429,7 +431,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
     else
     {
       HitState h;
-      hit_begin(S, a.pc, id, t, origin, direction, h);
+      hit_begin<ORIENT>(S, a.pc, id, t, origin, direction, h);
       if(depth == 0)                                                       // BEF rgen:94-97
       {
         store_first_hit(a, oi, t, h.P, h.N, id);
@@ -438,7 +440,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
       bool shadowed = false;
       const uint32_t inside = S.inside[id];
       if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
-        shadowed = any_hit<Real, ALT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
+        shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
       if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
         skip |= inside;
       prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
@@ -462,11 +464,11 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
   if(rd) rd.put(1, c);                                                     // BEF rgen:111
 }
 
-template <class Real, int TW, bool ALT>
+template <class Real, int TW, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void render_static_kernel(const SceneK scene, const RenderArgs a)
 {
   __shared__ SceneK S;
-  stage_scene(&S, scene);
+  stage_scene<ORIENT>(&S, scene);
 
   // TW×TH pixel tile per wavefront (TW·TH = 64): neighbouring lanes trace neighbouring rays;
   // a row of the tile is TW·16 B of rgba and TW·4 B of every first-hit stream
@@ -482,7 +484,7 @@ __global__ __launch_bounds__(256) void render_static_kernel(const SceneK scene, 
   {
     const uint32_t y = image_row(a, ly);
     const RdSink rd{nullptr, a.rendered ? rendered_record(a.rendered, a.H, x, y) : nullptr};
-    trace_pixel<Real, ALT>(S, a, x, y, ly, rd, n_primary, n_bounce, n_shadow, wc);
+    trace_pixel<Real, ALT, ORIENT>(S, a, x, y, ly, rd, n_primary, n_bounce, n_shadow, wc);
   }
   if(a.stats)
   {
@@ -536,7 +538,7 @@ __device__ __forceinline__ void raygen_fast(const trt_globals& g, const ToroCam&
   dir          = fnormalize(mat4_mul(g.viewInverse, tn.x, tn.y, tn.z, 0.0f));
 }
 
-template <bool MARCH>
+template <bool MARCH, bool ORIENT = false>
 __device__ __forceinline__ bool tile_is_clear(const SceneK& S, const RenderArgs& a, uint32_t x0, uint32_t ty, uint32_t width)
 {
   const uint32_t x1 = min(x0 + width - 1, a.W - 1);
@@ -578,9 +580,17 @@ __device__ __forceinline__ bool tile_is_clear(const SceneK& S, const RenderArgs&
     //     the sphere can be met (t <= L + rb): delta = Δo + (L + rb)·θ
     const float delta = 1.02f * (dO + (L + rb) * theta) + 1e-5f * (L + 1.0f);
     const float Rc = rb * 1.015625f + delta, hs = S.k32[i].rs * 1.015625f + delta;
-    const float ex = -v.x, ey = -v.y, ez = -v.z;
+    // Tests (2) and (3) are stated in the torus' frame (axis +y): for an oriented torus the centre ray is rotated into it
+    // first — e and d below.  Distances, and with them every Lipschitz bound above, are the same in both frames.
+    float ex = -v.x, ey = -v.y, ez = -v.z;
+    v3    d  = dc;
+    if(ORIENT && is_oriented(S, i))
+    {
+      rotate_to_local<float>(S.rot[i], -v.x, -v.y, -v.z, ex, ey, ez);
+      rotate_to_local<float>(S.rot[i], dc.x, dc.y, dc.z, d.x, d.y, d.z);
+    }
     float t_lo = 0.0f, t_hi = L + rb + delta;   // forward half-line only, inside the sphere's reach
-    const float ca = fma_(dc.z, dc.z, dc.x * dc.x), cb = fma_(ez, dc.z, ex * dc.x), cc = fma_(ez, ez, ex * ex);
+    const float ca = fma_(d.z, d.z, d.x * d.x), cb = fma_(ez, d.z, ex * d.x), cc = fma_(ez, ez, ex * ex);
     bool miss = false;
     if(ca > 1e-12f)
     {
@@ -596,9 +606,9 @@ __device__ __forceinline__ bool tile_is_clear(const SceneK& S, const RenderArgs&
     else if(cc > Rc * Rc) miss = true;
     if(!miss)
     {
-      if(abs_(dc.y) > 1e-6f)
+      if(abs_(d.y) > 1e-6f)
       {
-        const float iy = frcp(dc.y), u0 = (-hs - ey) * iy, u1 = (hs - ey) * iy;
+        const float iy = frcp(d.y), u0 = (-hs - ey) * iy, u1 = (hs - ey) * iy;
         t_lo = max_(t_lo, min_(u0, u1) - delta);
         t_hi = min_(t_hi, max_(u0, u1) + delta);
       }
@@ -620,7 +630,7 @@ __device__ __forceinline__ bool tile_is_clear(const SceneK& S, const RenderArgs&
       bool  passed = false;
       for(int it = 0; it < 16; ++it)
       {
-        const float px = fma_(sArc, dc.x, ex), py = fma_(sArc, dc.y, ey), pz = fma_(sArc, dc.z, ez);
+        const float px = fma_(sArc, d.x, ex), py = fma_(sArc, d.y, ey), pz = fma_(sArc, d.z, ez);
         const float e  = fsqrt(fma_(pz, pz, px * px)) - R;
         const float dist  = fsqrt(fma_(e, e, py * py)) - r;
         const float slack = dist - (1.02f * (dO + sArc * theta) + pad);
@@ -817,7 +827,7 @@ __device__ __forceinline__ void classify_reserve(const RenderArgs& a, uint32_t (
 // A clear macro tile becomes ONE entry of the CLEAR list (written later with full-line
 // dwordx4 stores); any other macro tile contributes its 8×8 tiles to the LIVE list.
 // (Ordering the LIVE list heavy-tiles-first was tried: render +10 %, classify 8 → 26 µs.)
-template <bool FB, bool BATCH = false>
+template <bool FB, bool BATCH = false, bool ORIENT = false>
 __global__ __launch_bounds__(kClassifyThreads) void tile_classify_kernel(const SceneK scene, const typename LaunchArgs<BATCH>::type args)
 {
   // per-block counts, per-wave offsets inside the block's reservation: ONE device-scope atomic
@@ -844,7 +854,7 @@ __global__ __launch_bounds__(kClassifyThreads) void tile_classify_kernel(const S
   const uint32_t mx = t % macro_x, ty = t / macro_x;
   const uint32_t tx0 = mx * kMacroTiles;
   const uint32_t ntile = valid ? min(kMacroTiles, tiles_x - tx0) : 0u;   // 8×8 tiles inside the image
-  const bool     clear = valid && a.tile_cull && tile_is_clear<false>(scene, a, tx0 * 8, ty, kMacroTiles * 8);
+  const bool     clear = valid && a.tile_cull && tile_is_clear<false, ORIENT>(scene, a, tx0 * 8, ty, kMacroTiles * 8);
   const uint32_t nlive = clear ? 0u : ntile;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // cost feedback: what the previous frame's slowest wave spent on this macro tile (read and reset)
@@ -878,7 +888,7 @@ __global__ __launch_bounds__(kClassifyThreads) void tile_classify_kernel(const S
 // miss records without tracing (the other kernels ignore the flag and trace it — same result).
 // (Ordering the LIVE list heavy-tiles-first was tried: render +10 %, classify 8 → 26 µs.)
 
-template <bool FB, bool BATCH = false>
+template <bool FB, bool BATCH = false, bool ORIENT = false>
 __global__ __launch_bounds__(kClassifyThreads) void tile_classify_fine_kernel(const SceneK scene, const typename LaunchArgs<BATCH>::type args)
 {
   // per-block counts, per-wave offsets inside the block's reservation: ONE device-scope atomic
@@ -903,7 +913,7 @@ __global__ __launch_bounds__(kClassifyThreads) void tile_classify_fine_kernel(co
   const uint32_t mx = m % macro_x, ty = m / macro_x;
   const uint32_t tx = mx * kMacroTiles + j;
   const bool     valid = in_batch && ty < tiles_y && tx < tiles_x;
-  const bool     clear = valid && a.tile_cull && tile_is_clear<true>(scene, a, tx * 8, ty, 8);
+  const bool     clear = valid && a.tile_cull && tile_is_clear<true, ORIENT>(scene, a, tx * 8, ty, 8);
   // all four tiles of the macro tile clear (tiles outside the image count as clear)
   uint32_t c4 = (clear || !valid) ? 1u : 0u;
   c4 &= (uint32_t)__shfl_xor((int)c4, 1, 64);
@@ -1020,13 +1030,13 @@ __device__ __forceinline__ uint32_t clear_macro(const RenderArgs& a, uint32_t tx
   return n;
 }
 
-template <class Real>
-__global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persistent_kernel(const SceneK scene, const RenderArgs a_arg)
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256, (sizeof(Real) == 4 ? (ORIENT ? 3 : 4) : 2)) void render_persistent_kernel(const SceneK scene, const RenderArgs a_arg)
 {
   __shared__ SceneK     S;
   __shared__ RenderArgs A_lds;
   stage_args(&A_lds, a_arg);
-  stage_scene(&S, scene);
+  stage_scene<ORIENT>(&S, scene);
   const RenderArgs& a = A_lds;
 
   const uint32_t lane    = threadIdx.x & 63;
@@ -1125,7 +1135,7 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
           else
           {
             HitState h;
-            hit_begin(S, a.pc, best_id, best_t, qo, qd, h);
+            hit_begin<ORIENT>(S, a.pc, best_id, best_t, qo, qd, h);
             if(depth == 0)                                                   // BEF rgen:94-97
             {
               store_first_hit(a, oi, best_t, h.P, h.N, best_id);
@@ -1254,8 +1264,25 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
         {
         ++wc.traced;
         // closest-hit queries end the interval of every later test at the closest hit so far
-        if(tst.setup((Real)rk.ox, (Real)rk.oy, (Real)rk.oz, (Real)rk.dx, (Real)rk.dy, (Real)rk.dz, rk.dd, rk.inv_dd, (Real)rk.tmin,
-                     (Real)(kind == K_CLOSEST ? min_(q_tmax, best_t) : q_tmax), torus_k<Real>(S, S.order[ti])))
+        const Real tm = (Real)(kind == K_CLOSEST ? min_(q_tmax, best_t) : q_tmax);
+        bool pass;
+        if constexpr(ORIENT)
+        {
+          // (torus_hit: an oriented torus is tested in its own frame; the lanes of a wave sit at different tori here)
+          const int      i = S.order[ti];
+          LocalRay<Real> l = {(Real)rk.ox, (Real)rk.oy, (Real)rk.oz, (Real)rk.dx, (Real)rk.dy, (Real)rk.dz, rk.dd, rk.inv_dd};
+          TorusK<Real>   T = torus_k<Real>(S, i);
+          if(is_oriented(S, i))
+          {
+            l.set(S, i, rk.ox, rk.oy, rk.oz, rk.dx, rk.dy, rk.dz);
+            T = centred(T);
+          }
+          pass = tst.setup(l.ox, l.oy, l.oz, l.dx, l.dy, l.dz, l.dd, l.inv_dd, (Real)rk.tmin, tm, T);
+        }
+        else
+          pass = tst.setup((Real)rk.ox, (Real)rk.oy, (Real)rk.oz, (Real)rk.dx, (Real)rk.dy, (Real)rk.dz, rk.dd, rk.inv_dd, (Real)rk.tmin,
+                           tm, torus_k<Real>(S, S.order[ti]));
+        if(pass)
         {
           inflight = true;
           ++wc.solved;
@@ -1291,7 +1318,10 @@ __global__ __launch_bounds__(256, (sizeof(Real) == 4 ? 4 : 2)) void render_persi
       Real  tt;
       float t;
       const float tm = kind == K_CLOSEST ? min_(q_tmax, best_t) : q_tmax;   // the interval setup() used
-      if(tst.finish((Real)rk.dx, (Real)rk.dy, (Real)rk.dz, (Real)rk.tmin, (Real)tm, torus_k<Real>(S, S.order[ti]), tt)
+      Real fdx = (Real)rk.dx, fdy = (Real)rk.dy, fdz = (Real)rk.dz;   // the direction setup() saw: rotated again, not kept
+      if(ORIENT && is_oriented(S, S.order[ti]))
+        rotate_to_local<Real>(S.rot[S.order[ti]], (Real)rk.dx, (Real)rk.dy, (Real)rk.dz, fdx, fdy, fdz);
+      if(tst.finish(fdx, fdy, fdz, (Real)rk.tmin, (Real)tm, torus_k<Real>(S, S.order[ti]), tt)
          && round_t(tt, kTMin, tm, t))
       {
         if(kind == K_SHADOW) shadow_hit = true;
@@ -1325,14 +1355,15 @@ constexpr uint32_t kListedThreads = 256;   // block size of the listed kernel: s
 // Waves per SIMD the register allocation aims at: 6 for the plain FP32 kernel (80 VGPRs, no scratch: LIVE part
 // −3.6 %, eight nested tori FP32 −4.5 % against 5 waves), 4 for FP64.  The counted (STATS) instantiations carry six
 // counters per lane and run only in the untimed counted pass, the RD instantiations stage RenderedData through LDS:
-// each gets one wave less instead of scratch.
+// each gets one wave less instead of scratch.  So do the ORIENT instantiations (a scene with an oriented torus): a test
+// holds the ray twice, in world space for the next torus and in the torus' frame for this one (8 / 16 VGPRs more).
 // RD: the launch exports RenderedData (a.rendered != nullptr); every wave then owns a 4-KB LDS image.
 // FB: the launch takes part in the cost feedback (RenderArgs::tile_cost): heavy tiles first, every traced tile timed.
 // BATCH: the launch renders up to kMaxBatch frames (RenderBatch, trt_render_batch_dev): every list entry names its frame,
 // whose arguments the wave takes from the block's LDS copy of the batch.  The single-frame instantiations are the code they
 // were before batches existed.
-template <class Real, bool STATS, bool ALT, bool RD, bool FB = false, bool BATCH = false>
-__global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAVES : TRT_LISTED_WAVES_F64) - (STATS ? 1 : 0) - (RD ? 1 : 0))) void render_listed_kernel(const SceneK scene, const typename LaunchArgs<BATCH>::type args)
+template <class Real, bool STATS, bool ALT, bool RD, bool FB = false, bool BATCH = false, bool ORIENT = false>
+__global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAVES : TRT_LISTED_WAVES_F64) - (STATS ? 1 : 0) - (RD ? 1 : 0) - (ORIENT ? 1 : 0))) void render_listed_kernel(const SceneK scene, const typename LaunchArgs<BATCH>::type args)
 {
   static_assert(!(BATCH && (RD || ALT)), "batches: default solver, no RenderedData");
   __shared__ SceneK     S;
@@ -1366,18 +1397,18 @@ __global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAV
     {
       const uint32_t* ssrc = reinterpret_cast<const uint32_t*>(&scene);
       uint32_t*       sdst = reinterpret_cast<uint32_t*>(&S);
-      const uint32_t  c4 = scene_words(scene);
+      const uint32_t  c4 = scene_words<ORIENT>(scene);
 #pragma unroll 1
       for(uint32_t i = threadIdx.x - 128u; i < c4; i += 128u)
       {
-        const uint32_t off = scene_word(scene, i);
+        const uint32_t off = scene_word<ORIENT>(scene, i);
         sdst[off] = ssrc[off];
       }
     }
     __syncthreads();
   }
   else
-    stage_block256(&S, &A_lds[0], scene, args);
+    stage_block256<ORIENT>(&S, &A_lds[0], scene, args);
   TRT_STAMP(5, wall_clock64());
   const RenderArgs& a0 = A_lds[0];
   const uint32_t lane    = threadIdx.x & 63;
@@ -1445,7 +1476,7 @@ __global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAV
           n_primary += (uint32_t)S.n_tori;
         }
         else
-          trace_pixel<Real, ALT>(S, a, x, image_row(a, ly), ly, RdSink{RD ? rd_tile + rd_unit(ln & 7, ln >> 3, 0) : nullptr, nullptr},
+          trace_pixel<Real, ALT, ORIENT>(S, a, x, image_row(a, ly), ly, RdSink{RD ? rd_tile + rd_unit(ln & 7, ln >> 3, 0) : nullptr, nullptr},
                                 n_primary, n_bounce, n_shadow, wc);
       }
       // cost feedback (RenderArgs::tile_cost): what this wave spent on the tile, kept per macro tile as the maximum over its tiles
@@ -1470,17 +1501,30 @@ __global__ __launch_bounds__(256, (ALT ? 2 : (sizeof(Real) == 4 ? TRT_LISTED_WAV
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 namespace {
-// The one place that maps the scene's precision and solver family to <Real, ALT>: returns f(Real{}, Alt<ALT>{}).  The
-// callers instantiate only the kernels they launch (if constexpr on the tags).
+// The one place that maps the scene's precision, solver family and orientation to <Real, ALT, ORIENT>: returns
+// f(Real{}, Alt<ALT>{}, Orient<ORIENT>{}).  The callers instantiate only the kernels they launch (if constexpr on the tags).
+// ORIENT: some torus of the scene turns about an axis other than +y (SceneK::oriented).  A template flag and not a
+// branch in the one kernel: the kernels of a scene without such a torus are then the code they were before oriented
+// tori existed (the plain FP32 listed kernel sits exactly on its 80-VGPR / 6-wave boundary), and inside
+// the ORIENT kernels a wave-uniform branch per test keeps the +y tori of a mixed scene on that same arithmetic.
 template <bool ALT> using Alt = std::integral_constant<bool, ALT>;
+template <bool ORIENT> using Orient = std::integral_constant<bool, ORIENT>;
+template <class F>
+hipError_t with_orient(const SceneK& scene, F&& f)
+{
+  if(scene.oriented != 0u) return f(Orient<true>{});
+  return f(Orient<false>{});
+}
 template <class F>
 hipError_t with_solver(const SceneK& scene, F&& f)
 {
   const bool alt = scene.alt_solver != kSolverWalk;
-  if(scene.f64 && alt) return f(double{}, Alt<true>{});
-  if(scene.f64) return f(double{}, Alt<false>{});
-  if(alt) return f(float{}, Alt<true>{});
-  return f(float{}, Alt<false>{});
+  return with_orient(scene, [&](auto ori) {
+    if(scene.f64 && alt) return f(double{}, Alt<true>{}, ori);
+    if(scene.f64) return f(double{}, Alt<false>{}, ori);
+    if(alt) return f(float{}, Alt<true>{}, ori);
+    return f(float{}, Alt<false>{}, ori);
+  });
 }
 }  // namespace
 
@@ -1493,8 +1537,8 @@ hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& t
   if(tn.trace_blocks) cap = tn.trace_blocks;
   if(cap == 0) cap = 1;
   const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-  return with_solver(scene, [&](auto real, auto alt) {
-    hipLaunchKernelGGL((trace_kernel<decltype(real), decltype(alt)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    hipLaunchKernelGGL((trace_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();
   });
 }
@@ -1559,11 +1603,11 @@ hipError_t launch_static(const SceneK& scene, const RenderArgs& a, const Tuning&
   if(tw != 8 && tw != 16 && tw != 32 && tw != 64) tw = 8;
   const uint64_t stiles = (uint64_t)((a.W + tw - 1) / tw) * ((a.n_local_rows + 64 / tw - 1) / (64 / tw));
   const dim3 grid((uint32_t)((stiles + 3) / 4)), block(256);
-  return with_solver(scene, [&](auto real, auto alt) {
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
     using Real = decltype(real);
-    constexpr bool ALT = decltype(alt)::value;
+    constexpr bool ALT = decltype(alt)::value, ORIENT = decltype(ori)::value;
 #ifdef TRT_TUNING
-    if constexpr(std::is_same<Real, float>::value && !ALT)
+    if constexpr(std::is_same<Real, float>::value && !ALT && !ORIENT)
     {
       if(tw == 16) hipLaunchKernelGGL((render_static_kernel<float, 16, false>), grid, block, 0, stream, scene, a);
       else if(tw == 32) hipLaunchKernelGGL((render_static_kernel<float, 32, false>), grid, block, 0, stream, scene, a);
@@ -1571,7 +1615,7 @@ hipError_t launch_static(const SceneK& scene, const RenderArgs& a, const Tuning&
       if(tw != 8) return hipGetLastError();
     }
 #endif
-    hipLaunchKernelGGL((render_static_kernel<Real, 8, ALT>), grid, block, 0, stream, scene, a);
+    hipLaunchKernelGGL((render_static_kernel<Real, 8, ALT, ORIENT>), grid, block, 0, stream, scene, a);
     return hipGetLastError();
   });
 }
@@ -1583,10 +1627,14 @@ void launch_classify(bool fine, bool fb, uint64_t lanes, const SceneK& scene, co
                      hipStream_t stream)
 {
   const dim3 grid((uint32_t)((lanes + kClassifyThreads - 1) / kClassifyThreads)), block(kClassifyThreads);
-  if(fine && fb) hipLaunchKernelGGL((tile_classify_fine_kernel<true, BATCH>), grid, block, 0, stream, scene, args);
-  else if(fine) hipLaunchKernelGGL((tile_classify_fine_kernel<false, BATCH>), grid, block, 0, stream, scene, args);
-  else if(fb) hipLaunchKernelGGL((tile_classify_kernel<true, BATCH>), grid, block, 0, stream, scene, args);
-  else hipLaunchKernelGGL((tile_classify_kernel<false, BATCH>), grid, block, 0, stream, scene, args);
+  (void)with_orient(scene, [&](auto ori) {
+    constexpr bool ORIENT = decltype(ori)::value;
+    if(fine && fb) hipLaunchKernelGGL((tile_classify_fine_kernel<true, BATCH, ORIENT>), grid, block, 0, stream, scene, args);
+    else if(fine) hipLaunchKernelGGL((tile_classify_fine_kernel<false, BATCH, ORIENT>), grid, block, 0, stream, scene, args);
+    else if(fb) hipLaunchKernelGGL((tile_classify_kernel<true, BATCH, ORIENT>), grid, block, 0, stream, scene, args);
+    else hipLaunchKernelGGL((tile_classify_kernel<false, BATCH, ORIENT>), grid, block, 0, stream, scene, args);
+    return hipSuccess;
+  });
 }
 
 // Grid of the listed kernel: one wave per 16 tiles (4096²: 16,384 blocks = 64 per CU), at least 4 blocks per CU, never
@@ -1601,16 +1649,16 @@ uint32_t listed_grid(uint64_t tiles, int n_cus, const Tuning& tn)
   return (uint32_t)((tiles + wpb - 1) / wpb < cap ? (tiles + wpb - 1) / wpb : cap);
 }
 
-template <class Real, bool STATS, bool ALT, bool RD, bool FB, bool BATCH>
+template <class Real, bool STATS, bool ALT, bool RD, bool FB, bool BATCH, bool ORIENT>
 void launch_listed_kernel(const SceneK& scene, const typename LaunchArgs<BATCH>::type& args, uint32_t grid, hipStream_t stream)
 {
-  hipLaunchKernelGGL((render_listed_kernel<Real, STATS, ALT, RD, FB, BATCH>), dim3(grid), dim3(kListedThreads), 0, stream,
+  hipLaunchKernelGGL((render_listed_kernel<Real, STATS, ALT, RD, FB, BATCH, ORIENT>), dim3(grid), dim3(kListedThreads), 0, stream,
                      scene, args);
 }
 
 // The one place that picks the listed instantiation.  Cost feedback (fb) runs with the walk and without counters only
 // (the callers decide); RenderedData (rd) exists for single frames only — in a batch its instantiations are the plain ones.
-template <class Real, bool ALT, bool BATCH>
+template <class Real, bool ALT, bool BATCH, bool ORIENT>
 void launch_listed(const SceneK& scene, const typename LaunchArgs<BATCH>::type& args, bool fb, bool rd, bool stats,
                    uint32_t grid, hipStream_t stream)
 {
@@ -1620,15 +1668,15 @@ void launch_listed(const SceneK& scene, const typename LaunchArgs<BATCH>::type& 
   {
     if(fb)
     {
-      if(rd) launch_listed_kernel<Real, false, false, RD, true, BATCH>(scene, args, grid, stream);
-      else launch_listed_kernel<Real, false, false, false, true, BATCH>(scene, args, grid, stream);
+      if(rd) launch_listed_kernel<Real, false, false, RD, true, BATCH, ORIENT>(scene, args, grid, stream);
+      else launch_listed_kernel<Real, false, false, false, true, BATCH, ORIENT>(scene, args, grid, stream);
       return;
     }
   }
-  if(rd && stats) launch_listed_kernel<Real, true, ALT, RD, false, BATCH>(scene, args, grid, stream);
-  else if(rd) launch_listed_kernel<Real, false, ALT, RD, false, BATCH>(scene, args, grid, stream);
-  else if(stats) launch_listed_kernel<Real, true, ALT, false, false, BATCH>(scene, args, grid, stream);
-  else launch_listed_kernel<Real, false, ALT, false, false, BATCH>(scene, args, grid, stream);
+  if(rd && stats) launch_listed_kernel<Real, true, ALT, RD, false, BATCH, ORIENT>(scene, args, grid, stream);
+  else if(rd) launch_listed_kernel<Real, false, ALT, RD, false, BATCH, ORIENT>(scene, args, grid, stream);
+  else if(stats) launch_listed_kernel<Real, true, ALT, false, false, BATCH, ORIENT>(scene, args, grid, stream);
+  else launch_listed_kernel<Real, false, ALT, false, false, BATCH, ORIENT>(scene, args, grid, stream);
 }
 
 // Persistent wavefronts: kPersistentBlocksPerCU blocks of 4 waves per CU, never more waves than tiles; the walk only.
@@ -1638,12 +1686,12 @@ hipError_t launch_persistent(const SceneK& scene, const RenderArgs& a, uint64_t 
   uint64_t cap = (uint64_t)n_cus * kPersistentBlocksPerCU;
   if(tn.persist_blocks) cap = tn.persist_blocks;
   const uint32_t grid = (uint32_t)((tiles + 3) / 4 < cap ? (tiles + 3) / 4 : cap);
-  return with_solver(scene, [&](auto real, auto alt) {
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
     if constexpr(decltype(alt)::value)
       return hipErrorInvalidValue;   // (trt_api.hip refuses this before)
     else
     {
-      hipLaunchKernelGGL(render_persistent_kernel<decltype(real)>, dim3(grid), dim3(256), 0, stream, scene, a);
+      hipLaunchKernelGGL((render_persistent_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
       return hipGetLastError();
     }
   });
@@ -1673,8 +1721,8 @@ hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant
   if(v == kRenderPersistent)
     return launch_persistent(scene, a, tiles, n_cus, tn, stream);
   const uint32_t grid = listed_grid(tiles, n_cus, tn);
-  return with_solver(scene, [&](auto real, auto alt) {
-    launch_listed<decltype(real), decltype(alt)::value, false>(scene, a, fb, a.rendered != nullptr, a.stats != nullptr, grid, stream);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    launch_listed<decltype(real), decltype(alt)::value, false, decltype(ori)::value>(scene, a, fb, a.rendered != nullptr, a.stats != nullptr, grid, stream);
     return hipGetLastError();
   });
 }
@@ -1693,9 +1741,12 @@ hipError_t launch_render_batch(const SceneK& scene, const RenderBatch& b, bool c
   const bool fb = render_feedback(scene, a, kRenderListed);
   if(classify) launch_classify<true>(a.fine, fb, (uint64_t)b.per_frame * b.n_frames, scene, b, stream);
   const uint32_t grid = listed_grid(tiles, n_cus, tn);
-  if(scene.f64) launch_listed<double, false, true>(scene, b, fb, false, a.stats != nullptr, grid, stream);
-  else launch_listed<float, false, true>(scene, b, fb, false, a.stats != nullptr, grid, stream);
-  return hipGetLastError();
+  return with_orient(scene, [&](auto ori) {
+    constexpr bool ORIENT = decltype(ori)::value;
+    if(scene.f64) launch_listed<double, false, true, ORIENT>(scene, b, fb, false, a.stats != nullptr, grid, stream);
+    else launch_listed<float, false, true, ORIENT>(scene, b, fb, false, a.stats != nullptr, grid, stream);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace trt

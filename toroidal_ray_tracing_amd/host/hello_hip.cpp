@@ -126,6 +126,11 @@ void HelloHip::addTorus(const float center[3], float R, float r, int matId)
   m_tori.push_back(trt_torus{{center[0], center[1], center[2]}, R, r, matId});
 }
 
+void HelloHip::setTorusAxes(const float* axes)
+{
+  check(trt_set_torus_axes(m_ctx, axes, (uint32_t)m_tori.size()), "HelloHip::setTorusAxes");
+}
+
 void HelloHip::destroyResources()
 {
   if(m_dColor) (void)hipFree(m_dColor);

@@ -37,6 +37,10 @@ public:
   void createOffscreenRender(uint32_t w, uint32_t h);  // rgba32f image + RenderedData buffer on the device
   int  addMaterial(const trt_material& m);             // returns the material index
   void addTorus(const float center[3], float R, float r, int matId);
+  // Axis of symmetry of every torus added so far (trt_set_torus_axes): 3 floats per torus in addTorus order, any
+  // non-zero length — the rotation part of the instance transform loadModel(filename, transform) takes in the
+  // reference.  nullptr: every torus turns about +y again.  Call it after the last addTorus.
+  void setTorusAxes(const float* axes);
   void destroyResources();
   ~HelloHip() { destroyResources(); }
 

@@ -19,6 +19,7 @@ SYMBOLS = {
     "trt_destroy": (None, [C.c_void_p]),
     "trt_last_error": (C.c_char_p, [C.c_void_p]),
     "trt_set_solver": (C.c_int, [C.c_void_p, C.c_int]),
+    "trt_set_torus_axes": (C.c_int, [C.c_void_p, abi.f32p, C.c_uint32]),
     "trt_trace": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.POINTER(abi.trt_scene),
                             C.c_float, C.c_float, C.POINTER(abi.trt_hits)]),
     "trt_trace_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.POINTER(abi.trt_scene),

@@ -46,6 +46,7 @@ class Tracer:
             raise TrtError(rc, (self._L.trt_last_error(None) or b"").decode())
         self._h = h
         self.device = int(device)
+        self._scene_axes = False   # the axes in force came from a Scene (and go when a Scene without axes follows)
 
     # -- lifetime ----------------------------------------------------------------------
     def close(self):
@@ -72,6 +73,29 @@ class Tracer:
     # -- configuration -----------------------------------------------------------------
     def set_solver(self, precision):
         self._check(self._L.trt_set_solver(self._h, int(precision)))
+
+    def set_torus_axes(self, axes):
+        """Axis of symmetry of every torus of the scenes passed to later calls (trt_set_torus_axes): an (n_tori, 3) array
+        of any non-zero lengths, or None for +y everywhere.  A scene with a different number of tori is then refused.
+        They hold for every Scene that carries no axes of its own; a Scene with axes renders with those and ends this
+        setting (abi.Scene states the rule in full)."""
+        self._scene_axes = False
+        if axes is None:
+            self._check(self._L.trt_set_torus_axes(self._h, None, 0))
+        else:
+            a = abi.axes_array(axes)
+            self._check(self._L.trt_set_torus_axes(self._h, a.ctypes.data_as(abi.f32p), len(a)))
+
+    def _scene(self, scene):
+        """The trt_scene of ``scene`` for a call, after the axes the Scene carries have been put in force.  A Scene without
+        axes leaves axes set through set_torus_axes() alone, and removes those of an earlier Scene."""
+        axes = getattr(scene, "axes", None)
+        if axes is not None:
+            self.set_torus_axes(axes)
+            self._scene_axes = True
+        elif self._scene_axes:
+            self.set_torus_axes(None)
+        return C.byref(scene.c)
 
     def set_render_variant(self, name):
         self._check(self._L.trt_set_render_variant(self._h, name.encode()))
@@ -110,14 +134,14 @@ class Tracer:
         rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
         out = abi.alloc_hits(n)
         hs = abi.hits_struct(out)
-        self._check(self._L.trt_trace(self._h, C.byref(rays), C.byref(scene.c), tmin, tmax, C.byref(hs)))
+        self._check(self._L.trt_trace(self._h, C.byref(rays), self._scene(scene), tmin, tmax, C.byref(hs)))
         return out
 
     def trace_dev(self, scene, ray_ptrs, n, hit_ptrs, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses, hit_ptrs = dict name -> address."""
         rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
         hs = _hits(hit_ptrs) or abi.trt_hits()   # (an empty dict: every stream null, for the library to refuse)
-        self._check(self._L.trt_trace_dev(self._h, C.byref(rays), C.byref(scene.c), tmin, tmax,
+        self._check(self._L.trt_trace_dev(self._h, C.byref(rays), self._scene(scene), tmin, tmax,
                                           C.byref(hs), _vp(stream)))
 
     # -- render -------------------------------------------------------------------------
@@ -126,7 +150,7 @@ class Tracer:
         rgba = np.empty((H, W, 4), np.float32)
         hits = abi.alloc_hits(W * H) if want_hits else None
         hs = abi.hits_struct(hits) if hits is not None else None
-        self._check(self._L.trt_render(self._h, C.byref(g), C.byref(pc), C.byref(scene.c), W, H,
+        self._check(self._L.trt_render(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H,
                                        camera, abi.ptr(rgba), _ref(hs)))
         return rgba, hits
 
@@ -134,14 +158,14 @@ class Tracer:
                    hit_ptrs=None, rendered_ptr=0, stream=0):
         """Device buffers, asynchronous on ``stream``; rows = (begin, end) of the band to render."""
         r0, r1 = (0, H) if rows is None else rows
-        self._check(self._L.trt_render_dev(self._h, C.byref(g), C.byref(pc), C.byref(scene.c), W, H,
+        self._check(self._L.trt_render_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H,
                                            r0, r1, camera, _vp(rgba_ptr), _ref(_hits(hit_ptrs)),
                                            _vp(rendered_ptr), _vp(stream)))
 
     def render_tiled_dev(self, scene, g, pc, W, H, tiling, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE,
                          hit_ptrs=None, rendered_ptr=0, stream=0):
         """Rows owned by ``tiling.part`` only (multi-GPU tiling, include/trt.h ``trt_tiling``)."""
-        self._check(self._L.trt_render_tiled_dev(self._h, C.byref(g), C.byref(pc), C.byref(scene.c), W, H,
+        self._check(self._L.trt_render_tiled_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H,
                                                  C.byref(tiling), camera, _vp(rgba_ptr), _ref(_hits(hit_ptrs)),
                                                  _vp(rendered_ptr), _vp(stream)))
 
@@ -156,7 +180,7 @@ class Tracer:
             dst.rgba_dev = int(rgba_ptr) or None
             if hs is not None:
                 dst.first_hit_dev = C.pointer(hs)
-        self._check(self._L.trt_render_batch_dev(self._h, arr, n, C.byref(scene.c), W, H, _ref(tiling), camera, _vp(stream)))
+        self._check(self._L.trt_render_batch_dev(self._h, arr, n, self._scene(scene), W, H, _ref(tiling), camera, _vp(stream)))
 
     def tiling_rows(self, tiling, H):
         return int(self._L.trt_tiling_rows(C.byref(tiling), H))
@@ -176,10 +200,13 @@ class Tracer:
                                           cc, float(point_size), _vp(rgba_ptr), _vp(stream)))
 
     def raytrace(self, scene, g, light, max_depth, clear_color, W, H, rgba_ptr, camera=0, rho=0.0,
-                 **kw):
+                 axes=None, **kw):
         """Mirror of ``HelloVulkan::raytrace(cmdBuf, clearColor)``: fills PushConstantRay from
         the light state (``light`` = dict position/intensity/type, the m_pcRaster fields) and
-        the clear colour, then launches W×H (hello_vulkan.cpp:917-931)."""
+        the clear colour, then launches W×H (hello_vulkan.cpp:917-931).  axes: torus axes to put in force
+        first (set_torus_axes; they stay in force afterwards)."""
+        if axes is not None:
+            self.set_torus_axes(axes)
         pc = abi.make_push(clear=clear_color, light_pos=light["position"],
                            light_intensity=light["intensity"], light_type=light["type"],
                            max_depth=max_depth, rho=rho)
