@@ -305,6 +305,34 @@ int trt_splat_dev(trt_ctx* ctx, const trt_point* points_dev, uint64_t n_points, 
                   uint32_t W, uint32_t H, const float* clearColor, float point_size, float* rgba_dev,
                   void* stream);
 
+/* ---- capture -> point cloud: the step between trt_render_dev's RenderedData and trt_splat_dev ------------------ */
+/* The reference takes a capture to its re-projection through text files (BEF writeRenderedPosition / writeColorImage,
+ * SEC loadPoints + createCloudDataBuffer, SEC/hello_vulkan.cpp:496-660).  trt_cloud_dev does it on the device, exactly:
+ * records are taken in buffer order, i = 0 .. n_records-1 (for a capture x*H + y, the order in which the reference pairs
+ * and draws them; trt_splat_dev lets the earlier point win equal depths).  Per record:
+ *   point pos.xyz = record pos.xyz, point color.xyz = record color.xyz, both .w = 0 (SEC :646-647);
+ *   any NaN component of pos or color becomes -FLT_MAX (loadPoints' "-nan -> lowest()", here for EITHER sign of NaN);
+ *   everything else is copied bit for bit (rayOrigin / rayDir are never read).
+ * A record is a MISS iff pos[0], pos[1] and pos[2] all compare equal to 0.0f (-0.0f counts; BEF/shaders/raytrace.rmiss:21
+ * leaves that value, and pos.w is 1 for hits and misses alike).  A record with a NaN in pos is not a miss.
+ *   TRT_CLOUD_KEEP_ALL     every record becomes a point (what the reference does);
+ *   TRT_CLOUD_MARK_MISSES  every record becomes a point, a miss with pos.xyz = -FLT_MAX, which trt_splat_dev discards by
+ *                          its clip test: the point count is known on the host without a read-back;
+ *   TRT_CLOUD_COMPACT      misses are dropped, the kept points keep their relative order.
+ * append == 0: the output starts at point 0.  append != 0: it starts at the counts_dev[0] found on the device when the
+ * kernels run, so consecutive calls on one stream build one cloud from several captures with no synchronisation (pass the
+ * same points_dev and capacity).  Nothing is ever written at or beyond `capacity`.
+ * counts_dev: two uint64 on the device, 8-byte aligned.  After the call [0] = min(first point + points of this call,
+ * capacity), the points in points_dev; [1] = the points the call wanted to put there, added to the [1] found when
+ * appending (> [0] only if capacity was too small).
+ * TRT_E_INVALID: NULL ctx; NULL rendered_dev or points_dev with n_records > 0; NULL counts_dev; an unknown mode; buffers
+ * not 16-byte aligned; n_records or capacity above 0xffffffff; input and output ranges that overlap.  n_records == 0 is
+ * valid and only updates the counts.  Launch contract: that of the *_dev entry points above (kernel nodes only; the ctx's
+ * grow-only scratch is sized by n_records). */
+enum { TRT_CLOUD_KEEP_ALL = 0, TRT_CLOUD_MARK_MISSES = 1, TRT_CLOUD_COMPACT = 2 };
+int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t n_records, int mode, int append,
+                  trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
+
 /* Counters of the last render or trace call made with counting enabled. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */

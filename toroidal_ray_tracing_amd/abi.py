@@ -20,6 +20,9 @@ TRT_CAMERA_PINHOLE, TRT_CAMERA_TOROIDAL = 0, 1
 TRT_CLASSIFY_AUTO, TRT_CLASSIFY_MACRO, TRT_CLASSIFY_TILE = -1, 0, 1
 TRT_SOLVE_F32, TRT_SOLVE_F64, TRT_SOLVE_DK_F32, TRT_SOLVE_DK_F64 = 0, 1, 2, 3
 TRT_SOLVE_FERRARI_F32, TRT_SOLVE_FERRARI_F64 = 4, 5
+TRT_CLOUD_KEEP_ALL, TRT_CLOUD_MARK_MISSES, TRT_CLOUD_COMPACT = 0, 1, 2
+#: records one block of trt_cloud_dev's count and scatter passes owns (kCloudChunk, csrc/trt_cloud.hpp): 256 lanes x 4
+TRT_CLOUD_CHUNK = 1024
 
 ERROR_NAMES = {
     TRT_E_INVALID: "TRT_E_INVALID", TRT_E_NO_DEVICE: "TRT_E_NO_DEVICE", TRT_E_HIP: "TRT_E_HIP",

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "trt_kernels.hpp"
+#include "trt_cloud.hpp"
 #include "trt_splat.hpp"
 
 using namespace trt;
@@ -93,6 +94,7 @@ struct trt_ctx {
   DevBuf d_keys;   // depth|index keys of trt_splat_dev (one-pass form)
   DevBuf d_bins;   // … binned form: per-bin count / offset / cursor words (count zero between calls)
   DevBuf d_recs;   // … binned form: point records sorted by bin
+  DevBuf d_cloud;  // trt_cloud_dev: the header words and the chunk table (CloudWord, trt_cloud.hpp)
   std::vector<void*> retired;   // scratch blocks replaced by larger ones: a hipGraph captured earlier may still use them
   bool               bins_dirty = false;   // a re-projection failed between its count and its resolve: zero d_bins before the next one
 
@@ -546,7 +548,7 @@ extern "C" void trt_destroy(trt_ctx* ctx)
   if(ctx->d_stats) (void)hipFree(ctx->d_stats);
   if(ctx->d_queue) (void)hipFree(ctx->d_queue);
   if(ctx->h_toro) (void)hipHostFree(ctx->h_toro);
-  DevBuf* all[] = {&ctx->d_toro, &ctx->d_rgba, &ctx->d_rendered, &ctx->d_tiles, &ctx->d_cost, &ctx->d_keys, &ctx->d_bins, &ctx->d_recs};
+  DevBuf* all[] = {&ctx->d_toro, &ctx->d_rgba, &ctx->d_rendered, &ctx->d_tiles, &ctx->d_cost, &ctx->d_keys, &ctx->d_bins, &ctx->d_recs, &ctx->d_cloud};
   for(DevBuf* b : all)
     if(b->p) (void)hipFree(b->p);
   for(DevBuf& b : ctx->d_in)
@@ -1071,6 +1073,38 @@ extern "C" int trt_post_dev(trt_ctx* ctx, const float* rgba_in, uint64_t n_pixel
     return fail(ctx, TRT_E_INVALID, "trt_post: images must be 16-byte (float) / 4-byte (unorm8) aligned");
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   TRT_HIP(ctx, launch_post(rgba_in, n_pixels, f32_out, unorm8_out, ctx->n_cus, ctx->tn, (hipStream_t)stream));
+  return TRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// capture -> point cloud
+// ------------------------------------------------------------------------------------------
+extern "C" int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered, uint64_t n_records, int mode, int append,
+                             trt_point* points, uint64_t capacity, uint64_t* counts, void* stream)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(!counts || (n_records && (!rendered || !points)))
+    return fail(ctx, TRT_E_INVALID, "trt_cloud: NULL argument");
+  if(mode != TRT_CLOUD_KEEP_ALL && mode != TRT_CLOUD_MARK_MISSES && mode != TRT_CLOUD_COMPACT)
+    return fail(ctx, TRT_E_INVALID, "trt_cloud: %d is not one of the TRT_CLOUD_* constants", mode);
+  if((((uintptr_t)rendered | (uintptr_t)points) & 15) || ((uintptr_t)counts & 7))
+    return fail(ctx, TRT_E_INVALID, "trt_cloud: the capture and the point buffer must be 16-byte aligned (float4 accesses), the counts 8-byte");
+  if(n_records > 0xffffffffull || capacity > 0xffffffffull)
+    return fail(ctx, TRT_E_INVALID, "trt_cloud: n_records=%llu / capacity=%llu above 2^32-1", (unsigned long long)n_records,
+                (unsigned long long)capacity);
+  const uintptr_t in0 = (uintptr_t)rendered, in1 = in0 + n_records * sizeof(trt_rendered_data);
+  const uintptr_t out0 = (uintptr_t)points, out1 = out0 + capacity * sizeof(trt_point);
+  if(n_records && capacity && in0 < out1 && out0 < in1)
+    return fail(ctx, TRT_E_INVALID, "trt_cloud: the capture and the point buffer overlap (records are not read before points are written)");
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if(int rc = grow(ctx, ctx->d_cloud, cloud_scratch_bytes(n_records, mode), st)) return rc;
+  CloudArgs a{};
+  a.rendered = rendered; a.n_records = n_records; a.mode = mode; a.append = append;
+  a.points = points; a.capacity = capacity; a.counts = counts;
+  a.header = (uint64_t*)ctx->d_cloud.p;
+  a.table  = (uint32_t*)(a.header + kCloudHeaderWords);
+  TRT_HIP(ctx, launch_cloud(a, st));
   return TRT_OK;
 }
 

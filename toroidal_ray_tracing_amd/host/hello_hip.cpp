@@ -137,7 +137,9 @@ void HelloHip::destroyResources()
   if(m_dRendered) (void)hipFree(m_dRendered);
   if(m_dPost) (void)hipFree(m_dPost);
   if(m_dCloud) (void)hipFree(m_dCloud);
-  m_dColor = nullptr; m_dRendered = nullptr; m_dPost = nullptr; m_dCloud = nullptr;
+  if(m_dCloudCounts) (void)hipFree(m_dCloudCounts);
+  m_dColor = nullptr; m_dRendered = nullptr; m_dPost = nullptr; m_dCloud = nullptr; m_dCloudCounts = nullptr;
+  m_cloudCapacity = 0; m_cloudFromCapture = false;
   if(m_ctx) trt_destroy(m_ctx);
   m_ctx = nullptr;
 }
@@ -300,6 +302,8 @@ void HelloHip::createCloudDataBuffer()
                                {m_colors[i][0], m_colors[i][1], m_colors[i][2], 0.f}};   // vec4(…, 0), :646-647
   if(m_dCloud) hipCheck(hipFree(m_dCloud), "hipFree");
   m_dCloud = nullptr;
+  m_cloudCapacity = m_cloudData.size();
+  m_cloudFromCapture = false;
   if(!m_cloudData.empty())
   {
     hipCheck(hipMalloc((void**)&m_dCloud, m_cloudData.size() * sizeof(trt_point)), "hipMalloc(cloud)");
@@ -307,10 +311,54 @@ void HelloHip::createCloudDataBuffer()
   }
 }
 
+void HelloHip::reserveCloud(size_t capacity)
+{
+  hipCheck(hipSetDevice(m_device), "hipSetDevice");
+  if(m_dCloud) hipCheck(hipFree(m_dCloud), "hipFree");   // (waits for the device: nothing reads the old cloud any more)
+  m_dCloud = nullptr;
+  m_cloudCapacity = 0;
+  if(capacity) hipCheck(hipMalloc((void**)&m_dCloud, capacity * sizeof(trt_point)), "hipMalloc(cloud)");
+  m_cloudCapacity = capacity;
+  if(!m_dCloudCounts) hipCheck(hipMalloc((void**)&m_dCloudCounts, 2 * sizeof(uint64_t)), "hipMalloc(cloud counts)");
+  hipCheck(hipMemset(m_dCloudCounts, 0, 2 * sizeof(uint64_t)), "hipMemset(cloud counts)");
+  m_cloudFromCapture = true;   // an empty cloud of the device path
+  m_cloudStream = nullptr;
+}
+
+void HelloHip::createCloudDataBufferFromCapture(int mode, bool append, void* stream)
+{
+  const size_t n = (size_t)m_size.width * m_size.height;
+  // a cloud of the text path is not appended to (its count lives on the host), and one capture must fit
+  if(!m_cloudFromCapture || !m_dCloudCounts || (!append && m_cloudCapacity < n)) reserveCloud(n > m_cloudCapacity ? n : m_cloudCapacity);
+  check(trt_cloud_dev(m_ctx, m_dRendered, n, mode, append ? 1 : 0, m_dCloud, m_cloudCapacity, m_dCloudCounts, stream),
+        "HelloHip::createCloudDataBufferFromCapture");
+  m_cloudStream = stream;
+}
+
+namespace {
+uint64_t cloudCount(const uint64_t* dCounts, void* stream, int word)
+{
+  uint64_t h[2] = {0, 0};
+  hipCheck(hipStreamSynchronize((hipStream_t)stream), "cloud counts");
+  hipCheck(hipMemcpy(h, dCounts, sizeof h, hipMemcpyDeviceToHost), "cloud counts");
+  return h[word];
+}
+}  // namespace
+
+size_t HelloHip::numPoints() const
+{
+  return m_cloudFromCapture ? (size_t)cloudCount(m_dCloudCounts, m_cloudStream, 0) : m_cloudData.size();
+}
+
+size_t HelloHip::wantedPoints() const
+{
+  return m_cloudFromCapture ? (size_t)cloudCount(m_dCloudCounts, m_cloudStream, 1) : m_cloudData.size();
+}
+
 void HelloHip::rasterize(void* stream, const std::array<float, 4>& clearColor)
 {
   // vkCmdDraw(numPoints, 1, 0, 0) on the POINT_LIST pipeline, gl_PointSize = 2.5 (SEC :313-330)
-  check(trt_splat_dev(m_ctx, m_dCloud, m_cloudData.size(), m_globals.viewProj, m_size.width, m_size.height,
+  check(trt_splat_dev(m_ctx, m_dCloud, numPoints(), m_globals.viewProj, m_size.width, m_size.height,
                       clearColor.data(), 2.5f, m_dColor, stream),
         "HelloHip::rasterize");
 }

@@ -78,7 +78,15 @@ public:
   void loadPoints(const std::string& positionFile, const std::string& colorFile);
   void createCloudDataBuffer();             // :633-660 — throws if the two files disagree in length
   void rasterize(void* stream, const std::array<float, 4>& clearColor);  // :313-330, POINT_LIST draw into m_dColor
-  size_t numPoints() const { return m_cloudData.size(); }
+  // The same cloud built on the device from the capture raytrace() left in the RenderedData buffer (trt_cloud_dev): no
+  // text files, no host round trip, any width and height.  mode: TRT_CLOUD_KEEP_ALL (what the text path builds, exactly
+  // instead of to six digits) | TRT_CLOUD_MARK_MISSES | TRT_CLOUD_COMPACT.  append: behind the points already there, so
+  // the captures of a rho sweep make one cloud — call reserveCloud() first with room for all of them (without it the
+  // cloud holds one capture; what does not fit is dropped and wantedPoints() tells).  Only enqueues on `stream`.
+  void   reserveCloud(size_t capacity);
+  void   createCloudDataBufferFromCapture(int mode = TRT_CLOUD_COMPACT, bool append = false, void* stream = nullptr);
+  size_t numPoints() const;      // either path; after the device path it waits for the stream and reads the count back
+  size_t wantedPoints() const;   // device path: points the calls wanted to store (> numPoints(): the reserve was too small)
 
   // --- state, named as in the reference -----------------------------------------------------
   PushConstantRaster m_pcRaster;
@@ -109,4 +117,8 @@ private:
   std::vector<std::array<float, 3>> m_positions, m_colors;   // SEC: m_positions / m_colors
   std::vector<trt_point>         m_cloudData;                // SEC: m_cloudData
   trt_point*                     m_dCloud{nullptr};
+  size_t                         m_cloudCapacity{0};         // points m_dCloud has room for
+  uint64_t*                      m_dCloudCounts{nullptr};    // counts_dev of trt_cloud_dev
+  bool                           m_cloudFromCapture{false};  // m_dCloud was built by createCloudDataBufferFromCapture
+  void*                          m_cloudStream{nullptr};     // … on this stream
 };

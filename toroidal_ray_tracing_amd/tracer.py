@@ -199,6 +199,28 @@ class Tracer:
         self._check(self._L.trt_splat_dev(self._h, _vp(points_ptr), int(n_points), vp, W, H,
                                           cc, float(point_size), _vp(rgba_ptr), _vp(stream)))
 
+    def cloud_dev(self, rendered_ptr, n_records, points_ptr, capacity, counts_ptr, mode=abi.TRT_CLOUD_KEEP_ALL,
+                  append=False, stream=0):
+        """Capture -> point cloud on the device (trt_cloud_dev): the first n_records RenderedData records at rendered_ptr,
+        in buffer order, become trt_points at points_ptr (room for ``capacity`` points).  mode: abi.TRT_CLOUD_KEEP_ALL |
+        _MARK_MISSES | _COMPACT; append: continue at the count found in counts_ptr[0] on the device.  counts_ptr: two
+        uint64 on the device, [0] points in the buffer, [1] points wanted.  Asynchronous on ``stream``."""
+        self._check(self._L.trt_cloud_dev(self._h, _vp(rendered_ptr), int(n_records), int(mode), int(bool(append)),
+                                          _vp(points_ptr), int(capacity), _vp(counts_ptr), _vp(stream)))
+
+    def cloud(self, rendered, points, mode=abi.TRT_CLOUD_COMPACT, append=False, counts=None, stream=0):
+        """cloud_dev on torch tensors, then a wait for ``stream`` and the two counts as ints: rendered (n, 16) float32,
+        points (capacity, 8) float32, counts a (2,) int64 device tensor (needed to append; made when None).
+        Returns (points in the buffer, points wanted)."""
+        import torch
+        if counts is None:
+            counts = torch.zeros(2, dtype=torch.int64, device=points.device)
+        self.cloud_dev(rendered.data_ptr(), rendered.shape[0], points.data_ptr(), points.shape[0], counts.data_ptr(),
+                       mode=mode, append=append, stream=stream)
+        torch.cuda.synchronize(points.device)
+        have, wanted = counts.tolist()
+        return int(have), int(wanted)
+
     def raytrace(self, scene, g, light, max_depth, clear_color, W, H, rgba_ptr, camera=0, rho=0.0,
                  axes=None, **kw):
         """Mirror of ``HelloVulkan::raytrace(cmdBuf, clearColor)``: fills PushConstantRay from
