@@ -13,8 +13,8 @@
  *                                  BEF/hello_vulkan.cpp:936-958          trt_render*
  *   raygen binding contract        REFL/shaders/raytrace.rgen:30-35,
  *                                  BEF/shaders/raytrace.rgen:10-17       trt_globals/trt_push/outputs
- *   traceRayEXT closest/any hit    REFL/shaders/raytrace.rgen:64-75,
- *                                  REFL/shaders/raytrace.rchit:120-131   trt_trace*
+ *   traceRayEXT closest hit        REFL/shaders/raytrace.rgen:64-75      trt_trace*
+ *   traceRayEXT any hit (shadow)   REFL/shaders/raytrace.rchit:114-131   trt_occluded*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -195,6 +195,28 @@ int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene,
 int trt_trace_dev(trt_ctx* ctx, const trt_rays* in_dev, const trt_scene* scene,
                   float tmin, float tmax, trt_hits* out_dev, void* stream);
 
+/* ---- occluded(rays_in -> one bit per ray): is anything in the way? --------------------- */
+/* Any-hit query (the shadow ray of REFL/shaders/raytrace.rchit:114-131, gl_RayFlagsTerminateOnFirstHitEXT): is there a
+ * torus surface on ray i inside the open interval (tmin, tmax_i)?  tmax_i = tmax_per_ray[i] when tmax_per_ray != NULL
+ * (n floats: the distance to the light, rchit:114), else tmax.
+ * Ray i is occluded exactly when trt_trace, given the same ray, scene, axes, solver and (tmin, tmax_i), reports
+ * id >= 0 — bit for bit, for every TRT_SOLVE_* and for oriented tori; like trt_trace it tests every
+ * torus.  Directions may have any non-zero length and t is in units of |d|: "is B visible from A" is d = B - A,
+ * tmax = 1.  A ray with !(tmax_i > tmin) — an empty window, a NaN bound — is not occluded and executes no test.
+ * Zero, NaN and infinite ray components behave as in trt_trace.
+ * flag_out: n bytes, each 0 or 1.  mask_out: (n + 63) / 64 words, 8-byte aligned; bit (i & 63) of word (i >> 6) belongs
+ * to ray i and the unused high bits of the last word are written as zero.  Either may be NULL, not both.
+ * TRT_E_INVALID: NULL ctx or rays; a NULL ray stream with n > 0; both outputs NULL; a misaligned mask.  n == 0 is valid
+ * and launches nothing.  Stats (trt_enable_stats): the tests executed are shadow_tests — a ray stops counting at its
+ * first hit — and primary_tests = bounce_tests = 0.
+ * Host buffers: copies in, launches, copies out, synchronises. */
+int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                 float tmin, float tmax, uint8_t* flag_out, uint64_t* mask_out);
+/* Device-resident buffers, asynchronous on `stream`; launch contract of the *_dev entry points below (kernel nodes
+ * only, may be captured; it uses no scratch of the ctx). */
+int trt_occluded_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                     float tmin, float tmax, uint8_t* flag_dev, uint64_t* mask_dev, void* stream);
+
 /* ---- render: the faithful equivalent of HelloVulkan::raytrace ---------------------- */
 /* rgba_out: W*H*4 floats, row-major, image[y][x] = (hitValue, 1)  (rgen:87); 16-byte aligned.
  * first_hit_out: optional SoA record of the depth-0 hit per pixel, row-major y*W+x. */
@@ -333,7 +355,7 @@ enum { TRT_CLOUD_KEEP_ALL = 0, TRT_CLOUD_MARK_MISSES = 1, TRT_CLOUD_COMPACT = 2 
 int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t n_records, int mode, int append,
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
-/* Counters of the last render or trace call made with counting enabled. */
+/* Counters of the last render, trace or occluded call made with counting enabled. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

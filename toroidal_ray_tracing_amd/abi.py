@@ -207,3 +207,15 @@ def alloc_hits(n):
     d = {k: np.empty(n, np.float32) for k in HIT_FIELDS[:-1]}
     d["id"] = np.empty(n, np.int32)
     return d
+
+
+def mask_words(n):
+    """Words of a trt_occluded mask over n rays."""
+    return (int(n) + 63) // 64
+
+
+def unpack_mask(words, n):
+    """The first n bits of a trt_occluded mask (uint64 words; bit i & 63 of word i >> 6 is ray i) as a bool array."""
+    w = np.ascontiguousarray(words, np.uint64)[:mask_words(n)]
+    bits = (w[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)
+    return bits.reshape(-1)[:n].astype(bool)

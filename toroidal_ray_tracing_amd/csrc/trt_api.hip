@@ -89,6 +89,7 @@ struct trt_ctx {
 
   // staging for the host-pointer entry points (grow-only, freed in trt_destroy)
   DevBuf d_in[6], d_out[8], d_rgba, d_rendered;
+  DevBuf d_tmax;   // trt_occluded: the per-ray bounds (host-pointer form only)
   DevBuf d_tiles;  // LIVE + CLEAR tile lists of the listed and the persistent kernel
   DevBuf d_cost;   // cost feedback: one word per macro tile (zero = no history)
   DevBuf d_keys;   // depth|index keys of trt_splat_dev (one-pass form)
@@ -548,7 +549,7 @@ extern "C" void trt_destroy(trt_ctx* ctx)
   if(ctx->d_stats) (void)hipFree(ctx->d_stats);
   if(ctx->d_queue) (void)hipFree(ctx->d_queue);
   if(ctx->h_toro) (void)hipHostFree(ctx->h_toro);
-  DevBuf* all[] = {&ctx->d_toro, &ctx->d_rgba, &ctx->d_rendered, &ctx->d_tiles, &ctx->d_cost, &ctx->d_keys, &ctx->d_bins, &ctx->d_recs, &ctx->d_cloud};
+  DevBuf* all[] = {&ctx->d_toro, &ctx->d_rgba, &ctx->d_rendered, &ctx->d_tiles, &ctx->d_cost, &ctx->d_keys, &ctx->d_bins, &ctx->d_recs, &ctx->d_cloud, &ctx->d_tmax};
   for(DevBuf* b : all)
     if(b->p) (void)hipFree(b->p);
   for(DevBuf& b : ctx->d_in)
@@ -741,6 +742,94 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
   if(int rc = stage_hits(ctx, *out, bytes, dout)) return rc;
   if(int rc = trt_trace_dev(ctx, &din, scene, tmin, tmax, &dout, nullptr)) return rc;
   return fetch_hits(ctx, *out, bytes);
+}
+
+// ------------------------------------------------------------------------------------------
+// occluded: the any-hit query
+// ------------------------------------------------------------------------------------------
+static int check_occluded(trt_ctx* ctx, const trt_rays* in, const uint8_t* flag, const uint64_t* mask)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(!in) return fail(ctx, TRT_E_INVALID, "trt_occluded: NULL rays");
+  if(in->n && (!in->ox || !in->oy || !in->oz || !in->dx || !in->dy || !in->dz))
+    return fail(ctx, TRT_E_INVALID, "trt_occluded: NULL ray stream");
+  if(!flag && !mask) return fail(ctx, TRT_E_INVALID, "trt_occluded: no output (flag and mask both NULL)");
+  if((uintptr_t)mask & 7) return fail(ctx, TRT_E_INVALID, "trt_occluded: the mask must be 8-byte aligned (64-bit stores)");
+  return TRT_OK;
+}
+extern "C" int trt_occluded_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
+                                float tmax, uint8_t* flag, uint64_t* mask, void* stream)
+{
+  if(int rc = check_occluded(ctx, in, flag, mask)) return rc;
+  const SceneK* Sp = nullptr;
+  if(int rc = build_scene(ctx, scene, Sp)) return rc;
+  const SceneK& S = *Sp;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t  st = (hipStream_t)stream;
+  OccludedArgs a;
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.flag         = flag;
+  a.mask         = (unsigned long long*)mask;
+  a.stats        = nullptr;
+  if(ctx->stats_on)
+  {
+    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 2 * kStatWords, st));
+    a.stats           = ctx->d_stats;
+    ctx->stats_pixels = in->n;
+  }
+  TRT_HIP(ctx, launch_occluded(S, a, ctx->tn, st));
+  if(ctx->stats_on && !capturing(st))
+  {
+    TRT_HIP(ctx, hipEventRecord(ctx->ev_stats, st));
+    ctx->ev_stats_set = true;
+  }
+  return TRT_OK;
+}
+
+// Host buffers: the rays through d_in[0..5] like trt_trace, the bounds through d_tmax, flag and mask through d_out[0] / d_out[1].
+extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
+                            float tmax, uint8_t* flag, uint64_t* mask)
+{
+  if(int rc = check_occluded(ctx, in, flag, mask)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)in->n, bytes = n * sizeof(float), mask_bytes = (n + 63) / 64 * sizeof(uint64_t);
+  if(n == 0) return trt_occluded_dev(ctx, in, nullptr, scene, tmin, tmax, flag, mask, nullptr);   // validates, launches and writes nothing
+  const float* src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
+  trt_rays din = *in;
+  const float** dptr_in[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
+  for(int k = 0; k < 6; ++k)
+  {
+    if(int rc = grow(ctx, ctx->d_in[k], bytes, nullptr, false)) return rc;
+    TRT_HIP(ctx, hipMemcpyAsync(ctx->d_in[k].p, src[k], bytes, hipMemcpyHostToDevice, nullptr));
+    *dptr_in[k] = (const float*)ctx->d_in[k].p;
+  }
+  const float* d_tmax = nullptr;
+  uint8_t*     d_flag = nullptr;
+  uint64_t*    d_mask = nullptr;
+  if(tmax_per_ray)
+  {
+    if(int rc = grow(ctx, ctx->d_tmax, bytes, nullptr, false)) return rc;
+    TRT_HIP(ctx, hipMemcpyAsync(ctx->d_tmax.p, tmax_per_ray, bytes, hipMemcpyHostToDevice, nullptr));
+    d_tmax = (const float*)ctx->d_tmax.p;
+  }
+  if(flag)
+  {
+    if(int rc = grow(ctx, ctx->d_out[0], n, nullptr, false)) return rc;
+    d_flag = (uint8_t*)ctx->d_out[0].p;
+  }
+  if(mask)
+  {
+    if(int rc = grow(ctx, ctx->d_out[1], mask_bytes, nullptr, false)) return rc;
+    d_mask = (uint64_t*)ctx->d_out[1].p;
+  }
+  if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, d_flag, d_mask, nullptr)) return rc;
+  if(flag) TRT_HIP(ctx, hipMemcpyAsync(flag, d_flag, n, hipMemcpyDeviceToHost, nullptr));
+  if(mask) TRT_HIP(ctx, hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, nullptr));
+  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
+  return TRT_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -617,6 +617,9 @@ constexpr int kRenderWalk = kWalkTable;
 #else
 constexpr int kRenderWalk = kWalkNested;
 #endif
+// occluded_kernel (trt_occluded*): caller-supplied rays of unknown coherence, like trace_kernel's — the table
+// (not measured against the nested form yet).
+constexpr int kOccludedWalk = kWalkTable;
 
 template <class Real, bool ALT = false, int WALK = kRenderWalk>
 __device__ __forceinline__ bool torus_first_hit(Real ox, Real oy, Real oz, Real dx_, Real dy_,
@@ -804,7 +807,10 @@ __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tm
 }
 
 // Any hit — the shadow query with gl_RayFlagsTerminateOnFirstHitEXT (REFL/shaders/raytrace.rchit:114-131).
-template <class Real, bool ALT = false, bool ORIENT = false>
+// Up to and including the first torus (in S.order) with a root in the window this runs the torus_hit calls of
+// closest_hit with the same arguments — closest_hit's interval shrinks only after that torus — so, for the same WALK or
+// any other (the forms are bit-identical), any_hit() == (closest_hit() >= 0) bit for bit.
+template <class Real, bool ALT = false, bool ORIENT = false, int WALK = kRenderWalk>
 __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
                                         uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
 {
@@ -816,7 +822,7 @@ __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin,
     ++tests;
     if((skip >> k) & 1u)
       continue;
-    if(torus_hit<Real, ALT, kRenderWalk, ORIENT>(S, S.order[k], r, tmin, tmax, t, wc))
+    if(torus_hit<Real, ALT, WALK, ORIENT>(S, S.order[k], r, tmin, tmax, t, wc))
       return true;
   }
   return false;

@@ -1,6 +1,7 @@
 // trt_kernels.hip — gfx950 (MI355X / CDNA4) render path of the toroidal ray tracer (trt_trace*, trt_render*).
 //
 //   trace_kernel              trace(rays_in → hits_out): SoA rays in, closest hit out.
+//   occluded_kernel           occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
 //   render_static_kernel      one lane per pixel, 8×8 pixel tile per wavefront; each lane runs the
 //                             reference's raygen bounce loop (REFL/shaders/raytrace.rgen:62-85).
 //   tile_classify[_fine]_kernel  which 8×8 tiles can be answered without tracing a ray: the CLEAR list (32×8 macro tiles,
@@ -312,6 +313,46 @@ __global__ __launch_bounds__(256) void trace_kernel(const SceneK scene, const Tr
   }
   if(a.stats)
     block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
+// occluded(rays_in → one bit per ray): the any-hit query
+// ------------------------------------------------------------------------------------------
+// A wave owns the 64 consecutive rays from a multiple of 64 on, so its mask word is one __ballot.  The grid-stride loop
+// therefore runs on the WAVE's base index (a scalar: every lane of the wave makes the same trips and meets the ballot
+// with the whole wave converged); the lanes at or beyond n load nothing and vote 0, which also zeroes the unused high
+// bits of the last word.  A ray whose window is empty — !(tmax_i > tmin), a NaN bound included — executes no test.
+template <class Real, bool ALT, bool ORIENT = false, int WALK = kOccludedWalk>
+__global__ __launch_bounds__(256) void occluded_kernel(const SceneK scene, const OccludedArgs a)
+{
+  __shared__ SceneK S;
+  stage_scene<ORIENT>(&S, scene);
+
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint32_t lane   = threadIdx.x & 63u;
+  const uint32_t wave   = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  for(uint64_t base = (uint64_t)blockIdx.x * 256u + wave * 64u; base < a.rays.n; base += stride)
+  {
+    const uint64_t i   = base + lane;
+    bool           hit = false;
+    if(i < a.rays.n)
+    {
+      const float tmax = a.tmax_per_ray ? a.tmax_per_ray[i] : a.tmax;
+      if(tmax > a.tmin)
+      {
+        const v3 o = {a.rays.ox[i], a.rays.oy[i], a.rays.oz[i]};
+        const v3 d = {a.rays.dx[i], a.rays.dy[i], a.rays.dz[i]};
+        hit = any_hit<Real, ALT, ORIENT, WALK>(S, o, d, a.tmin, tmax, tests, wc);
+      }
+      if(a.flag) a.flag[i] = hit ? 1 : 0;
+    }
+    const unsigned long long word = __ballot(hit);
+    if(a.mask && lane == 0u) a.mask[base >> 6] = word;
+  }
+  if(a.stats)
+    block_add_stats(a.stats, 0u, 0u, tests, wc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1543,6 +1584,31 @@ hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& t
   });
 }
 
+hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint64_t want = (a.rays.n + 255) / 256;
+  uint64_t cap = 256u * 16u;
+  if(tn.trace_blocks) cap = tn.trace_blocks;
+  if(cap == 0) cap = 1;
+  const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    using Real = decltype(real);
+    constexpr bool ALT = decltype(alt)::value, ORIENT = decltype(ori)::value;
+#ifdef TRT_TUNING   // TRT_OCCLUDED_WALK: the other form of the walk (bit-identical; tools/bench_occluded.py times both)
+    if constexpr(!ALT)
+      if(tn.occluded_walk != kOccludedWalk)
+      {
+        hipLaunchKernelGGL((occluded_kernel<Real, ALT, ORIENT, kOccludedWalk == kWalkTable ? kWalkNested : kWalkTable>), dim3(grid), dim3(256), 0, stream, scene, a);
+        return hipGetLastError();
+      }
+#endif
+    hipLaunchKernelGGL((occluded_kernel<Real, ALT, ORIENT>), dim3(grid), dim3(256), 0, stream, scene, a);
+    return hipGetLastError();
+  });
+}
+
 // Zeroes up to 64 words (the query counters of a counted launch) with a one-wave kernel: a kernel
 // node when the stream is being captured — the *_dev entry points put no memset node into a graph
 // (32 memset nodes between 64 kernel nodes faulted on replay under ROCm 7.2).
@@ -1585,6 +1651,7 @@ Tuning tuning_from_env()
   u64("TRT_LISTED_BLOCKS", t.listed_blocks);
   i32("TRT_TILE", t.static_tile);
   u64("TRT_TRACE_BLOCKS", t.trace_blocks);
+  i32("TRT_OCCLUDED_WALK", t.occluded_walk);
   u64("TRT_POST_BLOCKS_PER_CU", t.post_blocks_per_cu);
   u64("TRT_SPLAT_BLOCKS_PER_CU", t.splat_blocks_per_cu);
   i32("TRT_SPLAT_VARIANT", t.splat_variant);

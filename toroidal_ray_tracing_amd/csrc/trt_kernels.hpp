@@ -129,7 +129,8 @@ struct Tuning {
   uint64_t persist_blocks     = 0;    // TRT_PERSIST_BLOCKS   (0 = default)
   uint64_t listed_blocks      = 0;    // TRT_LISTED_BLOCKS
   int      static_tile        = 8;    // TRT_TILE
-  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS
+  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel and occluded_kernel)
+  int      occluded_walk      = kOccludedWalk;   // TRT_OCCLUDED_WALK: kWalkNested (0) | kWalkTable (1), occluded_kernel only
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
   uint64_t splat_blocks_per_cu = 0;   // TRT_SPLAT_BLOCKS_PER_CU
   int      splat_variant      = -1;   // TRT_SPLAT_VARIANT
@@ -143,12 +144,24 @@ struct TraceArgs {
   unsigned long long* stats;
 };
 
+// trt_occluded*: the any-hit query.  flag (one byte per ray) and mask (bit i & 63 of word i >> 6, (n + 63) / 64 words,
+// the unused high bits of the last word zero) are each optional; tmax_per_ray == nullptr: every ray ends at tmax.
+struct OccludedArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  uint8_t*            flag;
+  unsigned long long* mask;
+  unsigned long long* stats;
+};
+
 enum RenderVariant { kRenderStatic = 0, kRenderPersistent = 1, kRenderListed = 2 };
 constexpr int kPersistentBlocksPerCU = 16;  // 4× the resident 4 blocks/CU: the dispatcher evens out the tile costs
 
 hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_out, int n_cus, const Tuning& tn,
                        hipStream_t stream);
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

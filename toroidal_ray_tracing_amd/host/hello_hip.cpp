@@ -176,6 +176,13 @@ void HelloHip::raytrace(void* stream, const std::array<float, 4>& clearColor)
         "HelloHip::raytrace");
 }
 
+void HelloHip::occluded(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax,
+                        uint8_t* flagDev, uint64_t* maskDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_occluded_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, flagDev, maskDev, stream), "HelloHip::occluded");
+}
+
 void HelloHip::copyRenderedPosition(void* stream)
 {
   hipCheck(hipMemcpyAsync(m_hostRendered.data(), m_dRendered, m_hostRendered.size() * sizeof(trt_rendered_data),

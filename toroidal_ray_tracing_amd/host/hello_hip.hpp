@@ -54,6 +54,11 @@ public:
   // push constants from m_pcRaster and clearColor, then launch width × height rays.
   void raytrace(void* stream, const std::array<float, 4>& clearColor);
 
+  // The shadow query on its own (traceRayEXT with gl_RayFlagsTerminateOnFirstHitEXT, REFL/shaders/raytrace.rchit:114-131)
+  // against the tori added so far: device streams in, one byte and / or one mask bit per ray out (trt_occluded_dev).
+  void occluded(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax,
+                uint8_t* flagDev, uint64_t* maskDev);
+
   // --- readback + text dumps (ray_tracing__before/hello_vulkan.cpp:991-1259) ----------------
   void copyRenderedPosition(void* stream);  // RenderedData device → host
   void copyColorImage(void* stream);        // rgba32f image device → host

@@ -144,6 +144,27 @@ class Tracer:
         self._check(self._L.trt_trace_dev(self._h, C.byref(rays), self._scene(scene), tmin, tmax,
                                           C.byref(hs), _vp(stream)))
 
+    # -- occluded(rays_in -> one bit per ray) ------------------------------------------
+    def occluded(self, scene, o, d, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """Any-hit query on host arrays (trt_occluded): o, d of shape (n,3); tmax_per_ray: None or n bounds, one per ray
+        (a segment query "is B visible from A": d = B - A, tmax = 1).  Returns a bool array."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        flag = np.empty(n, np.uint8)
+        self._check(self._L.trt_occluded(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), tmin, tmax,
+                                         abi.ptr(flag), None))
+        return flag.astype(bool)
+
+    def occluded_dev(self, scene, ray_ptrs, n, flag_ptr=0, mask_ptr=0, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses; flag_ptr: n bytes and / or mask_ptr: abi.mask_words(n) uint64
+        (abi.unpack_mask reads them); tmax_ptr: n per-ray bounds or 0.  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_occluded_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
+                                             _vp(flag_ptr), _vp(mask_ptr), _vp(stream)))
+
     # -- render -------------------------------------------------------------------------
     def render(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, want_hits=True):
         """Host buffers.  Returns (rgba (H,W,4), hits dict | None)."""
