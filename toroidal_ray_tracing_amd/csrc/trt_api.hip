@@ -1,8 +1,9 @@
 // trt_api.hip — implementation of the C ABI declared in include/trt.h.
 //
 // Host side of the drop-in boundary: validates arguments, derives the per-torus solver
-// constants and the toroidal camera frame, owns grow-only device staging buffers for the
-// host-pointer entry points, and launches the gfx950 kernels.  Replaces what
+// constants and the toroidal camera frame, owns the grow-only device scratch (one table, Buf:
+// staging of the host-pointer entry points, and what the *_dev ones hand to kernels), and
+// launches the gfx950 kernels.  Replaces what
 // HelloVulkan::raytrace + the descriptor-set / push-constant plumbing do in the reference
 // (REFL/hello_vulkan.cpp:913-935, BEF/hello_vulkan.cpp:936-958).  Nothing in here computes
 // a ray on the CPU: without a HIP device trt_create fails.
@@ -29,11 +30,31 @@ thread_local std::string g_create_error;
 struct DevBuf {
   void*  p   = nullptr;
   size_t cap = 0;
+  bool   graph_visible = false;   // what grow() does with a block it replaces: retire it (true) or free it at once
+};
+
+// The ctx's device scratch, trt_ctx::buf[]: one line here per buffer, and trt_destroy frees whatever the table holds.
+// Before kBufGraphVisible: staging of the host-pointer entry points, which synchronise before they return and cannot be
+// captured.  From it on: scratch that a *_dev entry point hands to a kernel (DevBuf::graph_visible, grow()).
+enum Buf {
+  kBufIn,                       // [6] trt_trace, trt_occluded: the ray streams
+  kBufOut  = kBufIn + 6,        // [8] trt_trace, trt_render: the first-hit streams; trt_occluded: flag and mask in [0], [1]
+  kBufRgba = kBufOut + 8,       // trt_render: the image
+  kBufTmax,                     // trt_occluded: the per-ray bounds
+  kBufGraphVisible,
+  kBufToro = kBufGraphVisible,  // the toroidal camera's trigonometry tables
+  kBufTiles,                    // LIVE + CLEAR tile lists of the listed and the persistent kernel
+  kBufCost,                     // cost feedback: one word per macro tile (zero = no history)
+  kBufKeys,                     // depth|index keys of trt_splat_dev (one-pass form)
+  kBufBins,                     // … binned form: per-bin count / offset / cursor words (count zero between calls)
+  kBufRecs,                     // … binned form: point records sorted by bin
+  kBufCloud,                    // trt_cloud_dev: the header words and the chunk table (CloudWord, trt_cloud.hpp)
+  kBufCount
 };
 
 // Everything the classification of a call read, and where it wrote: the key of the ctx's tile lists (ListCache below).
 // The tile lists and their lengths are a function of the view, the tori, the frame shape and the camera model; a call
-// whose key equals the one of the classification that ran last finds in d_tiles and d_queue exactly what its own
+// whose key equals the one of the classification that ran last finds in the tile lists and d_queue exactly what its own
 // classification would write (the render kernels read the lists and the counts and never write them; the
 // classification's last block leaves the accumulators zero), and launches the render kernel alone.
 // g and pc are keyed WHOLE, shading-only fields included (light, clear colour, maxDepth): a frame that moves only the
@@ -81,23 +102,15 @@ struct trt_ctx {
   unsigned int*       d_queue = nullptr;  // [kQueueWords]: the classification's accumulators and published counts (QueueWord)
   uint64_t            stats_pixels = 0;
 
-  // toroidal camera tables: device copy + pinned host staging + cache key
-  DevBuf d_toro;
+  // toroidal camera tables (buf[kBufToro]): pinned host staging + cache key
   float* h_toro     = nullptr;
   size_t h_toro_cap = 0;
   struct { uint32_t W = 0, H = 0; float omega = 0, theta = 0; bool valid = false; } toro_key;
 
-  // staging for the host-pointer entry points (grow-only, freed in trt_destroy)
-  DevBuf d_in[6], d_out[8], d_rgba, d_rendered;
-  DevBuf d_tmax;   // trt_occluded: the per-ray bounds (host-pointer form only)
-  DevBuf d_tiles;  // LIVE + CLEAR tile lists of the listed and the persistent kernel
-  DevBuf d_cost;   // cost feedback: one word per macro tile (zero = no history)
-  DevBuf d_keys;   // depth|index keys of trt_splat_dev (one-pass form)
-  DevBuf d_bins;   // … binned form: per-bin count / offset / cursor words (count zero between calls)
-  DevBuf d_recs;   // … binned form: point records sorted by bin
-  DevBuf d_cloud;  // trt_cloud_dev: the header words and the chunk table (CloudWord, trt_cloud.hpp)
+  DevBuf buf[kBufCount];        // grow-only device scratch (Buf), freed in trt_destroy
+  trt_ctx() { for(int k = kBufGraphVisible; k < kBufCount; ++k) buf[k].graph_visible = true; }
   std::vector<void*> retired;   // scratch blocks replaced by larger ones: a hipGraph captured earlier may still use them
-  bool               bins_dirty = false;   // a re-projection failed between its count and its resolve: zero d_bins before the next one
+  bool               bins_dirty = false;   // a re-projection failed between its count and its resolve: zero the bin words before the next one
 
   // The scene the caller passed last, validated and turned into kernel constants: a frame loop passes the same few
   // hundred bytes every frame, and a 1/8-part frame is short enough for the host's share of a launch to show.
@@ -116,11 +129,11 @@ struct trt_ctx {
   uint64_t scene_gen = 0;   // bumped whenever scene_cache is rebuilt
   uint64_t toro_gen  = 0;   // bumped by every upload of the toroidal tables
 
-  // The tile lists the last classification left in d_tiles / d_queue, by what it read (ListKey): the third product a
+  // The tile lists the last classification left in buf[kBufTiles] / d_queue, by what it read (ListKey): the third product a
   // frame loop recomputes for nothing, and the only one that costs GPU time (8 µs of a 116-µs frame at 4096²).
   // Cleared by: any error between a classification and the end of its call, trt_set_list_reuse, a reload of the tuning
   // knobs; everything else that changes a launch input (variant, classification level, solver and scene through
-  // scene_gen, growth of d_tiles / d_cost and a new upload of the toroidal tables through their addresses and toro_gen)
+  // scene_gen, growth of the tile lists / the cost words and a new upload of the toroidal tables through their addresses and toro_gen)
   // is part of the key.  A ctx that has recorded a frame into a hipGraph stops reusing for good (`captured`): a replay
   // rewrites the lists at a time the host cannot see.
   struct ListCache {
@@ -166,27 +179,27 @@ bool capturing(hipStream_t st)
 
 
 // Grow-only scratch.  Scratch that a *_dev entry point hands to a kernel (tile lists, cost words, toroidal tables,
-// re-projection keys / bins / records: `graph_visible`) is RETIRED when a larger block replaces it, not freed, until
+// re-projection keys / bins / records: DevBuf::graph_visible) is RETIRED when a larger block replaces it, not freed, until
 // trt_destroy: a hipGraph captured earlier keeps replaying on the old block (its kernel arguments hold the old address
 // and capacity), and work still in flight on another stream may be using it; such blocks grow by at least half, so that
 // a ctx driven through increasing sizes retains at most ≈3× its peak.  The staging buffers of the host-pointer entry
 // points (which synchronise before they return and cannot be captured) are freed at once.  hipMalloc is illegal while
 // `st` is being captured — then the call is refused instead (include/trt.h: size the ctx with an eager call first).
-int grow(trt_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t st = nullptr, bool graph_visible = true)
+int grow(trt_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t st = nullptr)
 {
   if(bytes <= b.cap) return TRT_OK;
   if(capturing(st))
     return fail(ctx, TRT_E_INVALID, "the ctx's scratch would have to grow (%zu -> %zu bytes) while the stream is being "
                 "captured into a hipGraph: make one eager call with the same sizes first", b.cap, bytes);
   void* const old = b.p;
-  if(old && graph_visible)
+  if(old && b.graph_visible)
   {
     ctx->retired.push_back(old);
     if(bytes < b.cap + b.cap / 2) bytes = b.cap + b.cap / 2;
   }
   b.p = nullptr;   // before any error return: the ctx must not keep (and trt_destroy free again) a freed block
   b.cap = 0;
-  if(old && !graph_visible)
+  if(old && !b.graph_visible)
     TRT_HIP(ctx, hipFree(old));   // (synchronises with the device: nothing is using the block any more)
   TRT_HIP(ctx, hipMalloc(&b.p, bytes));
   b.cap = bytes;
@@ -200,19 +213,25 @@ std::array<void**, 8> hit_streams(trt_hits& h)
   return {{(void**)&h.t, (void**)&h.px, (void**)&h.py, (void**)&h.pz, (void**)&h.nx, (void**)&h.ny, (void**)&h.nz, (void**)&h.id}};
 }
 
-// Host staging of the hit streams for the entry points that take host pointers (trt_trace, trt_render).  stage_hits()
-// points every stream of `dev` that the caller wants (non-NULL in `want`) at ctx->d_out[k], grown to `bytes`, and leaves
-// the others NULL; fetch_hits() copies those streams back and waits for the default stream.
+// Host staging of the entry points that take host pointers; all of it runs on the default stream.
+// stage_out(): one output the caller wants (`host` non-NULL) gets buf[which], grown to `bytes`, as its device address
+// `*dev`; one it does not want, NULL.
+int stage_out(trt_ctx* ctx, int which, const void* host, size_t bytes, void** dev)
+{
+  *dev = nullptr;
+  if(!host || !bytes) return TRT_OK;
+  if(int rc = grow(ctx, ctx->buf[which], bytes)) return rc;
+  *dev = ctx->buf[which].p;
+  return TRT_OK;
+}
+
+// The hit streams (trt_trace, trt_render): stage_hits() stages every stream of `want` into the same stream of `dev`,
+// fetch_hits() copies those streams back and waits for the default stream.
 int stage_hits(trt_ctx* ctx, trt_hits& want, size_t bytes, trt_hits& dev)
 {
-  std::memset(&dev, 0, sizeof dev);
   const auto dst = hit_streams(want), dptr = hit_streams(dev);
   for(int k = 0; k < 8; ++k)
-    if(*dst[k] && bytes)
-    {
-      if(int rc = grow(ctx, ctx->d_out[k], bytes, nullptr, false)) return rc;
-      *dptr[k] = ctx->d_out[k].p;
-    }
+    if(int rc = stage_out(ctx, kBufOut + k, *dst[k], bytes, dptr[k])) return rc;
   return TRT_OK;
 }
 
@@ -220,8 +239,49 @@ int fetch_hits(trt_ctx* ctx, trt_hits& want, size_t bytes)
 {
   const auto dst = hit_streams(want);
   for(int k = 0; k < 8 && bytes; ++k)
-    if(*dst[k]) TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->d_out[k].p, bytes, hipMemcpyDeviceToHost, nullptr));
+    if(*dst[k]) TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->buf[kBufOut + k].p, bytes, hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
+  return TRT_OK;
+}
+
+// stage_in(): one input stream uploaded through buf[which], with `*dev` pointed at the copy.  stage_rays(): the six
+// streams of `in` (trt_trace, trt_occluded) through buf[kBufIn ..], with `din` pointed at them; no rays, nothing staged.
+int stage_in(trt_ctx* ctx, int which, const float* host, size_t bytes, const float** dev)
+{
+  DevBuf& b = ctx->buf[which];
+  if(int rc = grow(ctx, b, bytes)) return rc;
+  TRT_HIP(ctx, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, nullptr));
+  *dev = (const float*)b.p;
+  return TRT_OK;
+}
+
+int stage_rays(trt_ctx* ctx, const trt_rays* in, trt_rays& din)
+{
+  din = *in;
+  const float*  src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
+  const float** dst[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
+  for(int k = 0; k < 6 && in->n; ++k)
+    if(int rc = stage_in(ctx, kBufIn + k, src[k], (size_t)in->n * sizeof(float), dst[k])) return rc;
+  return TRT_OK;
+}
+
+// The bracket of a counted launch on `st`.  stats_begin() zeroes the query counters (a kernel node when captured) and
+// gives in `stats` what the launch is to be passed: d_stats, or NULL with the statistics off.  stats_end() records the
+// event trt_get_stats waits for — not into a capture: that event would belong to the graph, no wait for the host.
+int stats_begin(trt_ctx* ctx, hipStream_t st, uint64_t pixels, unsigned long long*& stats)
+{
+  stats = ctx->stats_on ? ctx->d_stats : nullptr;
+  if(!stats) return TRT_OK;
+  TRT_HIP(ctx, launch_zero_words((unsigned int*)stats, 2 * kStatWords, st));
+  ctx->stats_pixels = pixels;
+  return TRT_OK;
+}
+
+int stats_end(trt_ctx* ctx, hipStream_t st)
+{
+  if(!ctx->stats_on || capturing(st)) return TRT_OK;
+  TRT_HIP(ctx, hipEventRecord(ctx->ev_stats, st));
+  ctx->ev_stats_set = true;
   return TRT_OK;
 }
 
@@ -318,8 +378,9 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[
   std::memset(&out, 0, sizeof out);
   out.n_tori = (int)s->n_tori;
   out.n_mat  = (int)s->n_materials;
-  out.f64        = solver_of(ctx->precision).f64;
-  out.alt_solver = solver_of(ctx->precision).alt;
+  const Solver solver = solver_of(ctx->precision);
+  out.f64        = solver.f64;
+  out.alt_solver = solver.alt;
   for(uint32_t i = 0; i < s->n_tori; ++i)
   {
     const trt_torus& t = s->tori[i];
@@ -440,7 +501,7 @@ int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t 
     if(ty < 0.0f) theta = 360.0f - theta;                                    // :50-52
   }
   const size_t n = 2 * ((size_t)W + H);
-  if(int rc = grow(ctx, ctx->d_toro, n * sizeof(float), stream)) return rc;
+  if(int rc = grow(ctx, ctx->buf[kBufToro], n * sizeof(float), stream)) return rc;
   auto& key = ctx->toro_key;
   // bit-compare the angles so that a NaN frame (eye above centre) still caches
   const bool same = key.valid && key.W == W && key.H == H && !std::memcmp(&key.omega, &omega, 4)
@@ -478,7 +539,7 @@ int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t 
       cb[y] = std::cos(bt);
       sb[y] = std::sin(bt);
     }
-    TRT_HIP(ctx, hipMemcpyAsync(ctx->d_toro.p, ctx->h_toro, n * sizeof(float), hipMemcpyHostToDevice,
+    TRT_HIP(ctx, hipMemcpyAsync(ctx->buf[kBufToro].p, ctx->h_toro, n * sizeof(float), hipMemcpyHostToDevice,
                                 stream));
     TRT_HIP(ctx, hipEventRecord(ctx->ev_toro, stream));
     ctx->ev_toro_set = true;
@@ -487,7 +548,7 @@ int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t 
   }
   out.eye[0] = eye[0]; out.eye[1] = eye[1]; out.eye[2] = eye[2];
   out.rho   = pc.rho;
-  out.cos_a = (const float*)ctx->d_toro.p;
+  out.cos_a = (const float*)ctx->buf[kBufToro].p;
   out.sin_a = out.cos_a + W;
   out.cos_b = out.sin_a + W;
   out.sin_b = out.cos_b + H;
@@ -549,12 +610,7 @@ extern "C" void trt_destroy(trt_ctx* ctx)
   if(ctx->d_stats) (void)hipFree(ctx->d_stats);
   if(ctx->d_queue) (void)hipFree(ctx->d_queue);
   if(ctx->h_toro) (void)hipHostFree(ctx->h_toro);
-  DevBuf* all[] = {&ctx->d_toro, &ctx->d_rgba, &ctx->d_rendered, &ctx->d_tiles, &ctx->d_cost, &ctx->d_keys, &ctx->d_bins, &ctx->d_recs, &ctx->d_cloud, &ctx->d_tmax};
-  for(DevBuf* b : all)
-    if(b->p) (void)hipFree(b->p);
-  for(DevBuf& b : ctx->d_in)
-    if(b.p) (void)hipFree(b.p);
-  for(DevBuf& b : ctx->d_out)
+  for(DevBuf& b : ctx->buf)
     if(b.p) (void)hipFree(b.p);
   for(void* q : ctx->retired) (void)hipFree(q);
   delete ctx;
@@ -685,18 +741,24 @@ extern "C" int trt_get_stats(trt_ctx* ctx, trt_stats* out)
 // ------------------------------------------------------------------------------------------
 // trace
 // ------------------------------------------------------------------------------------------
-static int check_rays(trt_ctx* ctx, const trt_rays* in, const trt_hits* out)
+// `in` and its six streams, for the entry point `who` (trt_trace, trt_occluded)
+static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 {
   if(!ctx) return TRT_E_INVALID;
-  if(!in || !out) return fail(ctx, TRT_E_INVALID, "trt_trace: NULL rays or hits");
+  if(!in) return fail(ctx, TRT_E_INVALID, "%s: NULL rays", who);
   if(in->n && (!in->ox || !in->oy || !in->oz || !in->dx || !in->dy || !in->dz))
-    return fail(ctx, TRT_E_INVALID, "trt_trace: NULL ray stream");
+    return fail(ctx, TRT_E_INVALID, "%s: NULL ray stream", who);
   return TRT_OK;
+}
+static int check_trace(trt_ctx* ctx, const trt_rays* in, const trt_hits* out)
+{
+  if(ctx && (!in || !out)) return fail(ctx, TRT_E_INVALID, "trt_trace: NULL rays or hits");
+  return check_rays(ctx, in, "trt_trace");
 }
 extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin,
                              float tmax, trt_hits* out, void* stream)
 {
-  if(int rc = check_rays(ctx, in, out)) return rc;
+  if(int rc = check_trace(ctx, in, out)) return rc;
   const SceneK* Sp = nullptr;
   if(int rc = build_scene(ctx, scene, Sp)) return rc;
   const SceneK& S = *Sp;
@@ -707,38 +769,20 @@ extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
   a.hits  = *out;
   a.tmin  = tmin;
   a.tmax  = tmax;
-  a.stats = nullptr;
-  if(ctx->stats_on)
-  {
-    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 2 * kStatWords, st));
-    a.stats           = ctx->d_stats;
-    ctx->stats_pixels = in->n;
-  }
+  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
   TRT_HIP(ctx, launch_trace(S, a, ctx->tn, st));
-  if(ctx->stats_on)
-  {
-    TRT_HIP(ctx, hipEventRecord(ctx->ev_stats, st));
-    ctx->ev_stats_set = true;
-  }
-  return TRT_OK;
+  return stats_end(ctx, st);
 }
 
 extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin,
                          float tmax, trt_hits* out)
 {
-  if(int rc = check_rays(ctx, in, out)) return rc;
+  if(int rc = check_trace(ctx, in, out)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)in->n * sizeof(float);
-  const float* src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
-  trt_rays din = *in;
+  trt_rays din;
   trt_hits dout;
-  const float** dptr_in[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
-  for(int k = 0; k < 6 && in->n; ++k)
-  {
-    if(int rc = grow(ctx, ctx->d_in[k], bytes, nullptr, false)) return rc;
-    TRT_HIP(ctx, hipMemcpyAsync(ctx->d_in[k].p, src[k], bytes, hipMemcpyHostToDevice, nullptr));
-    *dptr_in[k] = (const float*)ctx->d_in[k].p;
-  }
+  if(int rc = stage_rays(ctx, in, din)) return rc;
   if(int rc = stage_hits(ctx, *out, bytes, dout)) return rc;
   if(int rc = trt_trace_dev(ctx, &din, scene, tmin, tmax, &dout, nullptr)) return rc;
   return fetch_hits(ctx, *out, bytes);
@@ -749,10 +793,7 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
 // ------------------------------------------------------------------------------------------
 static int check_occluded(trt_ctx* ctx, const trt_rays* in, const uint8_t* flag, const uint64_t* mask)
 {
-  if(!ctx) return TRT_E_INVALID;
-  if(!in) return fail(ctx, TRT_E_INVALID, "trt_occluded: NULL rays");
-  if(in->n && (!in->ox || !in->oy || !in->oz || !in->dx || !in->dy || !in->dz))
-    return fail(ctx, TRT_E_INVALID, "trt_occluded: NULL ray stream");
+  if(int rc = check_rays(ctx, in, "trt_occluded")) return rc;
   if(!flag && !mask) return fail(ctx, TRT_E_INVALID, "trt_occluded: no output (flag and mask both NULL)");
   if((uintptr_t)mask & 7) return fail(ctx, TRT_E_INVALID, "trt_occluded: the mask must be 8-byte aligned (64-bit stores)");
   return TRT_OK;
@@ -773,23 +814,12 @@ extern "C" int trt_occluded_dev(trt_ctx* ctx, const trt_rays* in, const float* t
   a.tmax         = tmax;
   a.flag         = flag;
   a.mask         = (unsigned long long*)mask;
-  a.stats        = nullptr;
-  if(ctx->stats_on)
-  {
-    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 2 * kStatWords, st));
-    a.stats           = ctx->d_stats;
-    ctx->stats_pixels = in->n;
-  }
+  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
   TRT_HIP(ctx, launch_occluded(S, a, ctx->tn, st));
-  if(ctx->stats_on && !capturing(st))
-  {
-    TRT_HIP(ctx, hipEventRecord(ctx->ev_stats, st));
-    ctx->ev_stats_set = true;
-  }
-  return TRT_OK;
+  return stats_end(ctx, st);
 }
 
-// Host buffers: the rays through d_in[0..5] like trt_trace, the bounds through d_tmax, flag and mask through d_out[0] / d_out[1].
+// Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], flag and mask through buf[kBufOut], [kBufOut + 1].
 extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
                             float tmax, uint8_t* flag, uint64_t* mask)
 {
@@ -797,35 +827,15 @@ extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n = (size_t)in->n, bytes = n * sizeof(float), mask_bytes = (n + 63) / 64 * sizeof(uint64_t);
   if(n == 0) return trt_occluded_dev(ctx, in, nullptr, scene, tmin, tmax, flag, mask, nullptr);   // validates, launches and writes nothing
-  const float* src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
-  trt_rays din = *in;
-  const float** dptr_in[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
-  for(int k = 0; k < 6; ++k)
-  {
-    if(int rc = grow(ctx, ctx->d_in[k], bytes, nullptr, false)) return rc;
-    TRT_HIP(ctx, hipMemcpyAsync(ctx->d_in[k].p, src[k], bytes, hipMemcpyHostToDevice, nullptr));
-    *dptr_in[k] = (const float*)ctx->d_in[k].p;
-  }
+  trt_rays din;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
   const float* d_tmax = nullptr;
-  uint8_t*     d_flag = nullptr;
-  uint64_t*    d_mask = nullptr;
+  void *d_flag, *d_mask;
   if(tmax_per_ray)
-  {
-    if(int rc = grow(ctx, ctx->d_tmax, bytes, nullptr, false)) return rc;
-    TRT_HIP(ctx, hipMemcpyAsync(ctx->d_tmax.p, tmax_per_ray, bytes, hipMemcpyHostToDevice, nullptr));
-    d_tmax = (const float*)ctx->d_tmax.p;
-  }
-  if(flag)
-  {
-    if(int rc = grow(ctx, ctx->d_out[0], n, nullptr, false)) return rc;
-    d_flag = (uint8_t*)ctx->d_out[0].p;
-  }
-  if(mask)
-  {
-    if(int rc = grow(ctx, ctx->d_out[1], mask_bytes, nullptr, false)) return rc;
-    d_mask = (uint64_t*)ctx->d_out[1].p;
-  }
-  if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, d_flag, d_mask, nullptr)) return rc;
+    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, &d_tmax)) return rc;
+  if(int rc = stage_out(ctx, kBufOut, flag, n, &d_flag)) return rc;
+  if(int rc = stage_out(ctx, kBufOut + 1, mask, mask_bytes, &d_mask)) return rc;
+  if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, (uint8_t*)d_flag, (uint64_t*)d_mask, nullptr)) return rc;
   if(flag) TRT_HIP(ctx, hipMemcpyAsync(flag, d_flag, n, hipMemcpyDeviceToHost, nullptr));
   if(mask) TRT_HIP(ctx, hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
@@ -938,16 +948,16 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
       return fail(ctx, TRT_E_INVALID, "trt_render: the tile lists pack tile coordinates in 16 + 15 bits (W <= 524280, rows <= 262136)");
     if(n_tiles * n_frames > 0x7fffffffull)
       return fail(ctx, TRT_E_INVALID, "trt_render_batch: %zu tiles in the batch exceed the tile lists", n_tiles * n_frames);
-    if(int rc = grow(ctx, ctx->d_tiles, 2 * n_tiles * n_frames * sizeof(uint32_t), st)) return rc;
+    if(int rc = grow(ctx, ctx->buf[kBufTiles], 2 * n_tiles * n_frames * sizeof(uint32_t), st)) return rc;
   }
   // cost feedback of the listed kernel (scheduling only): one word per macro tile (and frame of a batch), zero when the buffer is
   // new.  It pays where the cost of a tile varies much and the frame is bound by the tracing: eight nested tori −11 % (FP64) /
   // −15 % (FP32); a single torus' frame is bound by its stores and LOSES 2–3 % to the bookkeeping — scenes of one torus go without
   const bool cost_fb = lists && ctx->variant == kRenderListed && ctx->tn.heavy_x16 && (uint32_t)S.n_tori >= ctx->tn.heavy_min_tori;
-  if(cost_fb && ctx->d_cost.cap < n_macro * n_frames * sizeof(uint32_t))
+  if(cost_fb && ctx->buf[kBufCost].cap < n_macro * n_frames * sizeof(uint32_t))
   {
-    if(int rc = grow(ctx, ctx->d_cost, n_macro * n_frames * sizeof(uint32_t), st)) return rc;
-    TRT_HIP(ctx, hipMemsetAsync(ctx->d_cost.p, 0, ctx->d_cost.cap, st));   // never inside a capture: grow() refuses there
+    if(int rc = grow(ctx, ctx->buf[kBufCost], n_macro * n_frames * sizeof(uint32_t), st)) return rc;
+    TRT_HIP(ctx, hipMemsetAsync(ctx->buf[kBufCost].p, 0, ctx->buf[kBufCost].cap, st));   // never inside a capture: grow() refuses there
   }
   uint32_t fine_any = 0;
   for(uint32_t f = 0; f < n_frames; ++f)
@@ -973,18 +983,17 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     a.counts   = ctx->d_queue + kQueueCounts;
     if(camera == TRT_CAMERA_TOROIDAL)
       if(int rc = build_toro(ctx, *fr.g, *fr.pc, W, H, st, a.toro, f > 0)) return rc;
-    if(ctx->stats_on) a.stats = ctx->d_stats;
     float eye[3];   // the frame's eye: the enclosure cull here, the choice of the classification below
     mat4_origin(fr.g->viewInverse, eye);
     a.skip_primary = primary_skip_mask(scene, S, eye, camera == TRT_CAMERA_TOROIDAL ? fr.pc->rho : 0.0f);
     if(!lists) continue;
-    a.tiles_live  = (uint32_t*)ctx->d_tiles.p;
+    a.tiles_live  = (uint32_t*)ctx->buf[kBufTiles].p;
     a.tiles_clear = a.tiles_live + n_tiles * n_frames;
     a.cap_live    = (uint32_t)(n_tiles * n_frames);
     a.cap_clear   = (uint32_t)(n_tiles * n_frames);
     if(cost_fb)
     {
-      a.tile_cost = (uint32_t*)ctx->d_cost.p + (size_t)f * n_macro;
+      a.tile_cost = (uint32_t*)ctx->buf[kBufCost].p + (size_t)f * n_macro;
       a.heavy_x16 = ctx->tn.heavy_x16;
     }
     // tile culling needs tiles that are 8 contiguous image rows; with a RenderedData export the listed
@@ -1017,11 +1026,8 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     for(void** q : hit_streams(a.hits)) bits |= (uintptr_t)*q;
     a.vec4_ok = (W % 4 == 0 && (bits & 15) == 0) ? 1u : 0u;
   }
-  if(ctx->stats_on)
-  {
-    TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_stats, 2 * kStatWords, st));
-    ctx->stats_pixels = (uint64_t)n_local_rows * W * n_frames;
-  }
+  if(int rc = stats_begin(ctx, st, (uint64_t)n_local_rows * W * n_frames, B.fr[0].stats)) return rc;
+  for(uint32_t f = 1; f < n_frames; ++f) B.fr[f].stats = B.fr[0].stats;
   if(batch)
   {
     for(uint32_t f = 0; f < n_frames; ++f) B.fr[f].fine = fine_any;   // one classification kernel for the whole batch
@@ -1041,7 +1047,7 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     if(camera == TRT_CAMERA_TOROIDAL)
     {
       key.toro_gen = ctx->toro_gen;
-      key.toro_tab = ctx->d_toro.p;
+      key.toro_tab = ctx->buf[kBufToro].p;
     }
     key.tiles = a.tiles_live;
     key.queue = a.counters;
@@ -1068,11 +1074,7 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     TRT_HIP(ctx, launch_render_batch(S, B, !reuse, ctx->n_cus, ctx->tn, st));
   else
     TRT_HIP(ctx, launch_render(S, B.fr[0], ctx->variant, !reuse, ctx->n_cus, ctx->tn, st));
-  if(ctx->stats_on && !capturing(st))
-  {
-    TRT_HIP(ctx, hipEventRecord(ctx->ev_stats, st));
-    ctx->ev_stats_set = true;
-  }
+  if(int rc = stats_end(ctx, st)) return rc;
   if(lists && ctx->tn.debug_tiles)
   {
     unsigned int q[kCountWords];
@@ -1133,17 +1135,12 @@ extern "C" int trt_render(trt_ctx* ctx, const trt_globals* g, const trt_push* pc
   if(!ctx) return TRT_E_INVALID;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t npx = (size_t)W * H;
-  float*       d_rgba = nullptr;
-  if(rgba_out)
-  {
-    if(int rc = grow(ctx, ctx->d_rgba, npx * 16, nullptr, false)) return rc;
-    d_rgba = (float*)ctx->d_rgba.p;
-  }
-  trt_hits dh, want;
-  std::memset(&want, 0, sizeof want);
+  void*        d_rgba;
+  if(int rc = stage_out(ctx, kBufRgba, rgba_out, npx * 16, &d_rgba)) return rc;
+  trt_hits dh, want{};
   if(first_hit_out) want = *first_hit_out;
   if(int rc = stage_hits(ctx, want, npx * 4, dh)) return rc;
-  if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, d_rgba, first_hit_out ? &dh : nullptr,
+  if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, (float*)d_rgba, first_hit_out ? &dh : nullptr,
                              nullptr, nullptr))
     return rc;
   if(rgba_out) TRT_HIP(ctx, hipMemcpyAsync(rgba_out, d_rgba, npx * 16, hipMemcpyDeviceToHost, nullptr));
@@ -1187,11 +1184,11 @@ extern "C" int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered, ui
     return fail(ctx, TRT_E_INVALID, "trt_cloud: the capture and the point buffer overlap (records are not read before points are written)");
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  if(int rc = grow(ctx, ctx->d_cloud, cloud_scratch_bytes(n_records, mode), st)) return rc;
+  if(int rc = grow(ctx, ctx->buf[kBufCloud], cloud_scratch_bytes(n_records, mode), st)) return rc;
   CloudArgs a{};
   a.rendered = rendered; a.n_records = n_records; a.mode = mode; a.append = append;
   a.points = points; a.capacity = capacity; a.counts = counts;
-  a.header = (uint64_t*)ctx->d_cloud.p;
+  a.header = (uint64_t*)ctx->buf[kBufCloud].p;
   a.table  = (uint32_t*)(a.header + kCloudHeaderWords);
   TRT_HIP(ctx, launch_cloud(a, st));
   return TRT_OK;
@@ -1225,24 +1222,24 @@ extern "C" int trt_splat_dev(trt_ctx* ctx, const trt_point* points, uint64_t n_p
   {
     // sized for the largest bin count once: the count, state, pool and ticket words must be zero between calls — the
     // kernels leave them so; a call that failed in between marks them dirty
-    if(ctx->d_bins.cap < kSplatBinWords * sizeof(uint32_t))
+    if(ctx->buf[kBufBins].cap < kSplatBinWords * sizeof(uint32_t))
     {
-      if(int rc = grow(ctx, ctx->d_bins, kSplatBinWords * sizeof(uint32_t), st)) return rc;
+      if(int rc = grow(ctx, ctx->buf[kBufBins], kSplatBinWords * sizeof(uint32_t), st)) return rc;
       ctx->bins_dirty = true;
     }
     if(ctx->bins_dirty)
     {
-      TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->d_bins.p, (uint32_t)kSplatBinWords, st));   // a kernel node when captured
+      TRT_HIP(ctx, launch_zero_words((unsigned int*)ctx->buf[kBufBins].p, (uint32_t)kSplatBinWords, st));   // a kernel node when captured
       ctx->bins_dirty = false;
     }
-    if(int rc = grow(ctx, ctx->d_recs, sc.plan.total(), st)) return rc;
-    sc.bin_words = (uint32_t*)ctx->d_bins.p;
-    sc.records   = ctx->d_recs.p;
+    if(int rc = grow(ctx, ctx->buf[kBufRecs], sc.plan.total(), st)) return rc;
+    sc.bin_words = (uint32_t*)ctx->buf[kBufBins].p;
+    sc.records   = ctx->buf[kBufRecs].p;
   }
   else
   {
-    if(int rc = grow(ctx, ctx->d_keys, (size_t)W * H * sizeof(unsigned long long), st)) return rc;
-    sc.keys = (unsigned long long*)ctx->d_keys.p;
+    if(int rc = grow(ctx, ctx->buf[kBufKeys], (size_t)W * H * sizeof(unsigned long long), st)) return rc;
+    sc.keys = (unsigned long long*)ctx->buf[kBufKeys].p;
   }
   if(sc.plan.mode != kSplatOnePass) ctx->bins_dirty = true;   // until every kernel of the call is enqueued
   TRT_HIP(ctx, launch_splat(points, n_points, viewProj, W, H, clearColor, point_size, sc, rgba, ctx->n_cus, ctx->tn, st));

@@ -1567,17 +1567,21 @@ hipError_t with_solver(const SceneK& scene, F&& f)
     return f(float{}, Alt<false>{}, ori);
   });
 }
+
+// The grid of the ray-stream kernels (trace_kernel, occluded_kernel; grid-stride loops): one block per 256 rays, at
+// most 4096 blocks (TRT_TRACE_BLOCKS).
+uint32_t stream_grid(uint64_t n, const Tuning& tn)
+{
+  const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;
+  return (uint32_t)(want < cap ? want : cap);
+}
 }  // namespace
 
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream)
 {
   if(a.rays.n == 0)
     return hipSuccess;
-  const uint64_t want = (a.rays.n + 255) / 256;
-  uint64_t cap = 256u * 16u;
-  if(tn.trace_blocks) cap = tn.trace_blocks;
-  if(cap == 0) cap = 1;
-  const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+  const uint32_t grid = stream_grid(a.rays.n, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     hipLaunchKernelGGL((trace_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();
@@ -1588,11 +1592,7 @@ hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tun
 {
   if(a.rays.n == 0)
     return hipSuccess;
-  const uint64_t want = (a.rays.n + 255) / 256;
-  uint64_t cap = 256u * 16u;
-  if(tn.trace_blocks) cap = tn.trace_blocks;
-  if(cap == 0) cap = 1;
-  const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+  const uint32_t grid = stream_grid(a.rays.n, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     using Real = decltype(real);
     constexpr bool ALT = decltype(alt)::value, ORIENT = decltype(ori)::value;
