@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
-"""Per-kernel comparison of two `make asm` outputs:  tools/isa_diff.py OLD.s NEW.s
+"""Per-kernel comparison of two `make asm` outputs:  tools/isa_diff.py OLD.s NEW.s  |  tools/isa_diff.py OLD_DIR NEW_DIR
 
 A kernel is its instruction body, its .amdhsa_* descriptor, its `.set <kernel>.*` resource symbols and its entry in the
 amdhsa.kernels metadata.  Comment lines and trailing comments are dropped, local labels (.LBB3_12, .Lfunc_end3, ...) are
 renumbered in order of appearance inside the kernel, and the per-build __hip_cuid_<hash> symbol is masked, so that two
 builds of the same code compare equal wherever the kernel sits in the file.  Whatever belongs to no kernel (device
-variables, target lines) is compared as `<file scope>`.  Exit status 1 when anything differs or a kernel is missing."""
+variables, target lines) is compared as `<file scope>`.  Exit status 1 when anything differs or a kernel is missing.
+
+Given two directories, the kernels of every .s inside each are pooled and compared by name: a kernel that moved to another
+file is `same` when nothing of it changed.  The pooled `<file scope>` lines are compared as sorted sets and reported, but
+the exit status then rests on the kernels alone: device variables and target lines regroup with the files."""
+import glob
+import os
 import re
 import sys
 
@@ -46,6 +52,22 @@ def kernels(path):
     return out
 
 
+def pooled(path):
+    """kernels() of a file, or of every .s of a directory pooled (file scope: the distinct lines, sorted)."""
+    if not os.path.isdir(path):
+        return kernels(path)
+    out, scope = {}, set()
+    for f in sorted(glob.glob(os.path.join(path, "*.s"))):
+        k = kernels(f)
+        scope.update(k.pop("<file scope>"))
+        dup = set(k) & set(out)
+        if dup:
+            sys.exit("%s: %s is in another file of %s too" % (f, sorted(dup)[0], path))
+        out.update(k)
+    out["<file scope>"] = sorted(scope)
+    return out
+
+
 def figures(body):
     f = {n: next((int(ln.split()[1]) for ln in body if ln.split()[0] == key), None) for n, key in FIELDS}
     f["insts"] = sum(1 for ln in body if re.match(r"\t[a-z]\w+", ln))   # instructions: tab, mnemonic (directives start with '.')
@@ -55,7 +77,10 @@ def figures(body):
 def main():
     if len(sys.argv) != 3:
         sys.exit(__doc__)
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    old, new = pooled(sys.argv[1]), pooled(sys.argv[2])
+    if os.path.isdir(sys.argv[1]) and os.path.isdir(sys.argv[2]) and old["<file scope>"] != new["<file scope>"]:
+        print("differs  <file scope> (not counted: the files regrouped)")
+        old.pop("<file scope>"), new.pop("<file scope>")
     n_same = n_kernels = 0
     for k in sorted(set(old) | set(new)):
         n_kernels += k != "<file scope>"

@@ -11,6 +11,9 @@ mkdir -p $OUT
 # files of their own and are not in it): bench.py reports `roofline.traffic` only while they are unchanged
 cat $R/toroidal_ray_tracing_amd/csrc/trt_kernels.hip $R/toroidal_ray_tracing_amd/csrc/trt_device.hpp $R/toroidal_ray_tracing_amd/csrc/trt_kernels.hpp \
     $R/toroidal_ray_tracing_amd/csrc/trt_api.hip | sha256sum | cut -d" " -f1 > $OUT/kernel_sources.sha256
+# Since the render path has one file per kernel family, that hash no longer covers the kernels moved out of trt_kernels.hip
+# (trt_rays.hip, trt_classify.hip, trt_persistent.hip, trt_render.hpp); for the reader, a second one over every source:
+cat $R/toroidal_ray_tracing_amd/csrc/*.hip $R/toroidal_ray_tracing_amd/csrc/*.hpp | sha256sum | cut -d" " -f1 > $OUT/all_sources.sha256
 cd /tmp && export TMPDIR=/tmp
 # 1. per-kernel time of the command the driver runs, with the timed loop itself rotating over FOUR output sets (--output-sets 4:
 #    what bench.py's roofline pass does — no Infinity-Cache reuse between frames): `roofline.frac` of the bench line must be

@@ -25,7 +25,7 @@ template <class T> using gptr = __attribute__((address_space(1))) T*;
 typedef float f4v __attribute__((ext_vector_type(4)));
 
 // The capture is read once by the pass that turns it into points and the cloud is written once: non-temporal, like the
-// constant fills of the render path (st4c, trt_kernels.hip) — the re-projection that follows reads the cloud from HBM
+// constant fills of the render path (st4c, trt_render.hpp) — the re-projection that follows reads the cloud from HBM
 // whatever the policy (268 MB at 4096×2048), and the lines would only displace what the neighbouring passes keep.
 // The count pass reads with the default policy: the scatter pass wants the same lines next.
 __device__ __forceinline__ f4v  ld4(const float* p) { return *(gptr<const f4v>)p; }

@@ -1,6 +1,7 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_kernels.hip, trt_post.hip; the re-projection's half is trt_splat.hpp).  Host-side only types;
-// no HIP runtime types leak past this header except hipStream_t / hipError_t.
+// (trt_rays.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
+// What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,7 +10,7 @@
 
 namespace trt {
 
-// ---- The contract between the host (trt_api.hip) and the render kernels (trt_kernels.hip) -----------------------------
+// ---- The contract between the host (trt_api.hip) and the render kernels (trt_classify.hip, trt_persistent.hip, trt_kernels.hip)
 // Every layout both sides index is stated here once; the kernels' own arithmetic on these indices is pinned by
 // static_asserts next to it.
 
@@ -51,7 +52,7 @@ constexpr uint32_t kTile       = 8;
 constexpr uint32_t kMacroTiles = 4;
 __host__ __device__ constexpr uint32_t tile_count(uint32_t pixels) { return (pixels + kTile - 1) / kTile; }
 __host__ __device__ constexpr uint32_t macro_count(uint32_t tiles) { return (tiles + kMacroTiles - 1) / kMacroTiles; }
-// Tile-list entries (TileCode in trt_kernels.hip).  One frame per launch: tx | ty << kTileXBits [| kTileMissFlag].
+// Tile-list entries (TileCode in trt_render.hpp).  One frame per launch: tx | ty << kTileXBits [| kTileMissFlag].
 // A batch of frames: tx | ty << kBatchTileXBits | frame << kBatchFrameShift [| kTileMissFlag].
 constexpr uint32_t kTileXBits = 16, kTileYBits = 15;
 constexpr uint32_t kBatchTileXBits = 13, kBatchFrameShift = 28, kBatchFrameBits = 3;
@@ -106,7 +107,7 @@ struct RenderArgs {
 // A batch of frames rendered by ONE pair of launches (trt_render_batch_dev): the frames share the scene, the size, the
 // tiling, the camera model, the tile lists and their counters; everything else — uniforms, push constants, toroidal
 // frame, output pointers, cost words — is per frame.  Tile-list entries of a batch carry the frame in three bits
-// (TileCode<true> in trt_kernels.hip).  per_frame: classification lanes per frame, a multiple of 64, so that a wave of
+// (TileCode<true> in trt_render.hpp).  per_frame: classification lanes per frame, a multiple of 64, so that a wave of
 // the classification kernels belongs to one frame.
 constexpr uint32_t kMaxBatch = TRT_MAX_BATCH;
 struct RenderBatch {
@@ -167,6 +168,14 @@ hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of
 // tiles_live.  The launchers and the host's list key (trt_api.hip) ask this one function.
 bool render_feedback(const SceneK& scene, const RenderArgs& a, RenderVariant v);
+// The two steps of launch_render / launch_render_batch that have translation units of their own (trt_classify.hip,
+// trt_persistent.hip).  Hidden: they are called from trt_kernels.hip only, and the library exports what it did before.
+// launch_classify: `lanes` = one per macro tile, or per 8×8 tile when `fine`; fb: with the cost feedback of the listed kernel.
+#define TRT_INTERNAL __attribute__((visibility("hidden")))
+TRT_INTERNAL void launch_classify(bool fine, bool fb, uint64_t lanes, const SceneK& scene, const RenderArgs& a, hipStream_t stream);
+TRT_INTERNAL void launch_classify(bool fine, bool fb, uint64_t lanes, const SceneK& scene, const RenderBatch& b, hipStream_t stream);
+TRT_INTERNAL hipError_t launch_persistent(const SceneK& scene, const RenderArgs& a, uint64_t tiles, int n_cus, const Tuning& tn,
+                                          hipStream_t stream);
 // classify = false: the lists and counts of the ctx already hold what this launch's classification would write (the
 // host's list key, trt_api.hip) — only the render kernel is launched, with the same grid and instantiation.
 hipError_t launch_render(const SceneK& scene, const RenderArgs& a, RenderVariant v, bool classify, int n_cus,

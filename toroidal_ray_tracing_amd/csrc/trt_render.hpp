@@ -1,0 +1,397 @@
+// trt_render.hpp — what more than one kernel family of the render path uses.  Device side: included only by
+// trt_rays.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
+//
+//   gptr, st1 / st4 / st4c, ld1           global-memory accessors
+//   HitState, hit_begin, hit_end          the closest-hit shader body, split at the shadow query
+//   image_row, out_index, rendered_record pixel addressing
+//   miss_id, miss_colour, miss_rgba, store_first_hit, store_first_miss   the first-hit record and the miss record
+//   block_add_stats                       the query counters of a block → the global totals
+//   settle_loads, stage_args, stage_block256   staging into LDS
+//   kTMin, kTMax                          the ray window of the render kernels
+//   live_slot, list_counts, TileCode, tile_x / tile_y, frame_args, LaunchArgs   the tile-list layout
+//   clear_macro                           the constant fill of one CLEAR macro tile
+//   with_orient, with_solver              launch dispatch: scene → <Real, ALT, ORIENT>
+//
+// Everything here is __forceinline__ (or a host template): no device function is called across translation units.
+#pragma once
+
+#include "trt_kernels.hpp"
+
+#include <type_traits>
+
+namespace trt {
+
+// ------------------------------------------------------------------------------------------
+// global-memory accessors
+// ------------------------------------------------------------------------------------------
+// The long kernels read their arguments (and thus their output POINTERS) from LDS, so hipcc no
+// longer knows that those pointers address global memory and would emit flat_load/flat_store —
+// slower, and counted on lgkmcnt as well, so that every LDS wait would also wait for them.
+// These helpers cast to the global address space: global_load / global_store.
+template <class T> using gptr = __attribute__((address_space(1))) T*;
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef int   i4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void st1(float* base, size_t i, float v) { ((gptr<float>)base)[i] = v; }
+__device__ __forceinline__ void st1(int32_t* base, size_t i, int32_t v) { ((gptr<int32_t>)base)[i] = v; }
+__device__ __forceinline__ void st4(float* p, float4 v) { *((gptr<f4v>)p) = f4v{v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ void st4(int32_t* p, int x, int y, int z, int w) { *((gptr<i4v>)p) = i4v{x, y, z, w}; }
+// Non-temporal (`nt`) dwordx4 stores for the FULL-LINE streams that nothing reads again inside the frame: the constant
+// fills of CLEAR macro tiles (85 % of the baseline frame).  Measured (config 3, one box, alternating processes): frame
+// 0.131 → 0.119 ms when the chip is in its fast state and 0.156 → 0.124 ms in its slow one — the fills no longer
+// compete for L2 / Infinity-Cache lines with the partial-line stores of the traced tiles, which need them to merge.
+// Applied to EVERY store the frame got slower (0.185 ms): the traced tiles' dword stores must stay temporal.
+#ifdef TRT_NO_NT_CLEAR   // timing builds
+#define st4c st4
+#else
+__device__ __forceinline__ void st4c(float* p, float4 v) { __builtin_nontemporal_store(f4v{v.x, v.y, v.z, v.w}, (gptr<f4v>)p); }
+__device__ __forceinline__ void st4c(int32_t* p, int x, int y, int z, int w) { __builtin_nontemporal_store(i4v{x, y, z, w}, (gptr<i4v>)p); }
+#endif
+
+__device__ __forceinline__ uint32_t ld1(const uint32_t* base, size_t i) { return ((gptr<const uint32_t>)base)[i]; }
+
+// ------------------------------------------------------------------------------------------
+// closest-hit shader body, split at the shadow query (REFL/shaders/raytrace.rchit:50-156)
+// ------------------------------------------------------------------------------------------
+struct HitState {
+  v3    P, N, L;
+  v3    diffuse;
+  float lightIntensity, lightDistance;
+  int   matId;
+  bool  wantShadow;  // dot(N,L) > 0  (rchit:112)
+};
+
+template <bool ORIENT = false>
+__device__ __forceinline__ void hit_begin(const SceneK& S, const trt_push& pc, int id, float t, v3 o,
+                                          v3 d, HitState& h)
+{
+  h.matId = S.shade[id].matId;                                               // rchit:95-96
+  h.P     = {fma_(t, d.x, o.x), fma_(t, d.y, o.y), fma_(t, d.z, o.z)};       // BEF rchit:134
+  h.N     = torus_normal<ORIENT>(S, id, h.P);
+  const v3 lp = {pc.lightPosition[0], pc.lightPosition[1], pc.lightPosition[2]};
+  h.lightIntensity = pc.lightIntensity;                                      // rchit:79
+  h.lightDistance  = 100000.0f;                                              // rchit:80
+  if(pc.lightType == 0)                                                      // rchit:82
+  {
+    const v3 lDir    = sub3(lp, h.P);
+    h.lightDistance  = sqrt_(dot3(lDir, lDir));
+    h.lightIntensity = pc.lightIntensity / (h.lightDistance * h.lightDistance);
+    h.L              = scale3(lDir, 1.0f / h.lightDistance);
+  }
+  else
+    h.L = normalize3(lp);                                                    // rchit:91
+  h.diffuse    = compute_diffuse(S.mat[h.matId], h.L, h.N);                  // rchit:100
+  h.wantShadow = dot3(h.N, h.L) > 0.0f;                                      // rchit:112
+}
+
+// Finishes the closest-hit shader once the shadow query is answered; returns prd.hitValue and
+// updates the payload (attenuation, done, next ray) exactly as rchit:133-155.
+__device__ __forceinline__ v3 hit_end(const SceneK& S, const HitState& h, v3 d, bool shadowed,
+                                      v3& attenuation, int& done, v3& nextO, v3& nextD)
+{
+  const MaterialK& mat = S.mat[h.matId];
+  v3    specular     = {0.0f, 0.0f, 0.0f};
+  float attenuation1 = 1.0f;
+  if(h.wantShadow)
+  {
+    if(shadowed) attenuation1 = 0.3f;                                        // rchit:135
+    else specular = compute_specular(mat, d, h.L, h.N);                      // rchit:140
+  }
+  if(mat.illum == 3)                                                         // rchit:145
+  {
+    attenuation.x *= mat.specular[0];
+    attenuation.y *= mat.specular[1];
+    attenuation.z *= mat.specular[2];
+    done  = 0;
+    nextO = h.P;
+    nextD = reflect3(d, h.N);
+  }
+  const float k = attenuation1 * h.lightIntensity;                           // rchit:155
+  return {k * (h.diffuse.x + specular.x), k * (h.diffuse.y + specular.y),
+          k * (h.diffuse.z + specular.z)};
+}
+
+// ------------------------------------------------------------------------------------------
+// pixel addressing: local rows (row band, or interleaved row groups of a multi-GPU tiling)
+// ------------------------------------------------------------------------------------------
+// local row ly of this launch → image row y
+__device__ __forceinline__ uint32_t image_row(const RenderArgs& a, uint32_t ly)
+{
+  if(a.tile_parts <= 1)
+    return a.row_begin + ly;
+  return ((ly / a.tile_group) * a.tile_parts + a.tile_part) * a.tile_group + ly % a.tile_group;
+}
+// index of pixel (x, row) in the rgba / first-hit streams
+__device__ __forceinline__ size_t out_index(const RenderArgs& a, uint32_t x, uint32_t y, uint32_t ly)
+{
+  return (size_t)(a.compact ? ly : y) * a.W + x;
+}
+
+// The RenderedData record of pixel (x, image row y): AoS at x·H + y (BEF rgen:72).  It takes a.rendered and a.H, not
+// the RenderArgs: rd_flush() passes image_row() for y, and with `a` as the parameter the two LDS loads come after that
+// call instead of before it — the RD instantiations of render_listed_kernel then grow by 24 instructions.
+__device__ __forceinline__ float* rendered_record(trt_rendered_data* rendered, uint32_t H, uint32_t x, uint32_t y)
+{
+  return reinterpret_cast<float*>(&rendered[(size_t)x * H + y]);
+}
+
+// The id of a miss, materialised at the store: as a plain constant hipcc hoists (-1,-1,-1,-1) out of the
+// tile loop, keeps it live across the whole solve and — in the FP64 kernels at 128 VGPRs — spills it
+// (20 B of scratch whose every reload is a vector-memory load that drains the output stores).
+__device__ __forceinline__ int miss_id()
+{
+  int m;
+  asm volatile("v_mov_b32 %0, -1" : "=v"(m));
+  return m;
+}
+
+__device__ __forceinline__ void store_first_hit(const RenderArgs& a, size_t i_, float t, v3 P, v3 N, int id)
+{
+  // The pixel index passes through an opaque copy so that the eight stream addresses are formed
+  // HERE, at the store, and not at the top of the pixel's bounce loop — where they would sit in
+  // 16 VGPRs across the whole solve (and get spilled).  W·H < 2³¹ (trt_render checks it).
+  uint32_t i32 = (uint32_t)i_;
+  asm volatile("" : "+v"(i32));
+  const size_t i = i32;
+  if(a.hits.t) st1(a.hits.t, i, t);
+  if(a.hits.px) st1(a.hits.px, i, P.x);
+  if(a.hits.py) st1(a.hits.py, i, P.y);
+  if(a.hits.pz) st1(a.hits.pz, i, P.z);
+  if(a.hits.nx) st1(a.hits.nx, i, N.x);
+  if(a.hits.ny) st1(a.hits.ny, i, N.y);
+  if(a.hits.nz) st1(a.hits.nz, i, N.z);
+  if(a.hits.id) st1(a.hits.id, i, id);
+}
+
+// What a pixel that misses at depth 0 gets, stated once for its five writers (trace_pixel, the persistent kernel's miss
+// shader, the listed kernel's miss-flagged tiles, clear_macro, rd_miss_tile).  The colour of a miss is clearColor·0.8
+// (REFL rmiss:37; at depth 0 it is the pixel's colour: rgen:76 with attenuation 1 and hitValue 0 → rgen:87), alpha 1; the
+// first-hit record is t = +inf, position and normal 0, id -1 (BEF rmiss:21).  A writer that has +inf, 0 or 1 in registers
+// of its own (materialised where hoisting would spill them) passes them in.
+__device__ __forceinline__ v3 miss_colour(const trt_push& pc)
+{
+  return {pc.clearColor[0] * 0.8f, pc.clearColor[1] * 0.8f, pc.clearColor[2] * 0.8f};
+}
+__device__ __forceinline__ float4 miss_rgba(const trt_push& pc, float one = 1.0f)
+{
+  const v3 c = miss_colour(pc);
+  return make_float4(c.x, c.y, c.z, one);
+}
+__device__ __forceinline__ void store_first_miss(const RenderArgs& a, size_t i, float inf = __builtin_inff(), float zero = 0.0f)
+{
+  store_first_hit(a, i, inf, {zero, zero, zero}, {zero, zero, zero}, miss_id());
+}
+
+// Query counters of a block → the three global totals: wave sums by shuffles, block sums by LDS
+// atomics, then ONE global atomic per counter per block (65,536 waves adding to three words one
+// by one made the counted pass of the listed kernel 1.2 ms long).  Every thread of the block must
+// call it (it contains barriers); `stats` is kernel-uniform.
+// Layout of the totals: StatWord (trt_kernels.hpp) — the three ray classes at k, the WorkCount fields at k + 1.
+static_assert(kStatPrimary == 0 && kStatBounce == 1 && kStatShadow == 2 && kStatTraced == 4 && kStatSolved == 5 &&
+              kStatEvals == 6 && kStatWords == 8, "block_add_stats: acc[k < 3 ? k : k + 1], 8 words");
+__device__ __forceinline__ void block_add_stats(unsigned long long* stats, uint32_t v0, uint32_t v1, uint32_t v2, const WorkCount& wc)
+{
+  __shared__ unsigned int acc[8];
+  if(threadIdx.x < 8) acc[threadIdx.x] = 0u;
+  __syncthreads();
+  uint32_t v[6] = {v0, v1, v2, wc.traced, wc.solved, wc.evals};
+  for(int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for(int k = 0; k < 6; ++k)
+      v[k] += __shfl_down(v[k], off, 64);
+  if((threadIdx.x & 63) == 0)
+  {
+#pragma unroll
+    for(int k = 0; k < 6; ++k)
+      if(v[k]) atomicAdd(&acc[k < 3 ? k : k + 1], v[k]);
+  }
+  __syncthreads();
+  if(threadIdx.x < 8 && acc[threadIdx.x])
+    atomicAdd(&stats[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+// Retire every outstanding load of this wave, then hide the given registers from hipcc's
+// s_waitcnt bookkeeping.  Without this, a value loaded once per batch and read in a loop (the
+// per-lane tile-list caches) gets an `s_waitcnt vmcnt(0)` in front of EVERY read — and since
+// stores share the counter, each of those waits drains the wave's whole stream of output
+// stores (measured: the clear tiles then serialise with the traced tiles instead of
+// draining behind them).
+__device__ __forceinline__ void settle_loads(uint32_t& a, uint32_t& b)
+{
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("" : "+v"(a), "+v"(b));
+}
+
+// Stage the launch arguments into LDS next to the scene.  Kept in the kernel-argument segment
+// they would be pinned in ~150 SGPRs for the whole persistent loop (hipcc loads kernargs once
+// and never rematerialises them), and the spills cost a dozen v_readlane per output store.
+__device__ __forceinline__ void stage_args(RenderArgs* lds, const RenderArgs& arg)
+{
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&arg);
+  uint32_t*       dst = reinterpret_cast<uint32_t*>(lds);
+  for(uint32_t i = threadIdx.x; i < sizeof(RenderArgs) / 4; i += blockDim.x)
+    dst[i] = src[i];
+}
+
+// Both stagings in ONE pass for a block of exactly 256 threads: thread t < sizeof(RenderArgs)/4 copies argument dword t,
+// the threads from 128 on copy the scene records in use — one load per thread and one barrier.  (The general loops above
+// compile to ≈200 instructions per wave with an unknown block size; a wave of the listed kernel lives for one tile, so
+// its prologue was 40 % of all instructions the LIVE part of config 3 issued — tools/timeline.py)
+template <bool ORIENT = false>
+__device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const SceneK& scene, const RenderArgs& arg)
+{
+  constexpr uint32_t NA = sizeof(RenderArgs) / 4;
+  static_assert(NA <= 128 && sizeof(RenderArgs) % 4 == 0, "RenderArgs must fit the lower half of the block");
+  const uint32_t tid = threadIdx.x;
+  if(tid < NA)
+    reinterpret_cast<uint32_t*>(A)[tid] = reinterpret_cast<const uint32_t*>(&arg)[tid];
+  else if(tid >= 128u)
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&scene);
+    uint32_t*       dst = reinterpret_cast<uint32_t*>(S);
+    const uint32_t  c4 = scene_words<ORIENT>(scene);
+#pragma unroll 1
+    for(uint32_t i = tid - 128u; i < c4; i += 128u)
+    {
+      const uint32_t off = scene_word<ORIENT>(scene, i);
+      dst[off] = src[off];
+    }
+  }
+  __syncthreads();
+}
+
+constexpr float kTMin = 0.001f;    // rgen:51, rchit:114
+constexpr float kTMax = 10000.0f;  // rgen:52
+
+// ------------------------------------------------------------------------------------------
+// tile lists: what the classification writes and the list kernels read
+// ------------------------------------------------------------------------------------------
+// Logical LIVE entry L → position in tiles_live (RenderArgs::tile_cost): the heavy tiles come first.
+__device__ __forceinline__ size_t live_slot(uint32_t cap_live, uint32_t n_heavy, uint64_t L)
+{
+  return L < n_heavy ? (size_t)cap_live - 1 - (size_t)L : (size_t)(L - n_heavy);
+}
+
+// The header of a list kernel: the list lengths as published by the classification (RenderArgs::counts), wave-uniform
+// and never beyond the lists' capacity.  n_heavy (live_slot(): the heavy tiles come first) is read only by the
+// instantiations that can have any (HEAVY); the others get 0.
+template <bool HEAVY = true>
+__device__ __forceinline__ void list_counts(const RenderArgs& a, uint32_t& n_live, uint32_t& n_clear, uint32_t& n_heavy)
+{
+  n_live  = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)kCountLive)), a.cap_live);
+  n_clear = umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)kCountClear)), a.cap_clear);
+  n_heavy = HEAVY ? umin((uint32_t)__builtin_amdgcn_readfirstlane(ld1(a.counts, (size_t)kCountHeavy)), n_live) : 0u;
+}
+
+// Tile-list entries, packed as trt_kernels.hpp states (kTileXBits, kBatchTileXBits, ...): one frame per launch, or a
+// batch of frames (trt_render_batch_dev) whose entries carry the frame.
+template <bool BATCH> struct TileCode;
+template <> struct TileCode<false> {
+  static __device__ __forceinline__ uint32_t pack(uint32_t tx, uint32_t ty, uint32_t) { return tx | (ty << kTileXBits); }
+  static __device__ __forceinline__ uint32_t x(uint32_t p) { return p & field_max(kTileXBits); }
+  static __device__ __forceinline__ uint32_t y(uint32_t p) { return (p >> kTileXBits) & field_max(kTileYBits); }
+  static __device__ __forceinline__ uint32_t frame(uint32_t) { return 0u; }
+};
+template <> struct TileCode<true> {
+  static __device__ __forceinline__ uint32_t pack(uint32_t tx, uint32_t ty, uint32_t f) { return tx | (ty << kBatchTileXBits) | (f << kBatchFrameShift); }
+  static __device__ __forceinline__ uint32_t x(uint32_t p) { return p & field_max(kBatchTileXBits); }
+  static __device__ __forceinline__ uint32_t y(uint32_t p) { return (p >> kBatchTileXBits) & field_max(kTileYBits); }
+  static __device__ __forceinline__ uint32_t frame(uint32_t p) { return (p >> kBatchFrameShift) & field_max(kBatchFrameBits); }
+};
+__device__ __forceinline__ uint32_t tile_x(uint32_t packed) { return TileCode<false>::x(packed); }
+__device__ __forceinline__ uint32_t tile_y(uint32_t packed) { return TileCode<false>::y(packed); }
+
+// The launch arguments of the frame a wave works on: the kernel's own RenderArgs, or frame f of a batch (f wave-uniform).
+__device__ __forceinline__ const RenderArgs& frame_args(const RenderArgs& a, uint32_t) { return a; }
+__device__ __forceinline__ const RenderArgs& frame_args(const RenderBatch& b, uint32_t f) { return b.fr[f]; }
+template <bool BATCH> struct LaunchArgs { typedef RenderArgs type; };
+template <> struct LaunchArgs<true> { typedef RenderBatch type; };
+
+// Writes the constant miss record of one CLEAR macro tile (32×8 pixels) and returns the number
+// of image pixels this lane wrote.  Lane l = (row r = l >> 3, q = l & 7).  Each first-hit
+// stream is stored as ONE dwordx4 per lane (pixels 4q..4q+3 of row r): a wave instruction
+// writes 8 full 128-B lines.  rgba takes 4 dwordx4 per lane, instruction j writing pixels
+// 8j + q: again 8 full lines per instruction.  (Narrow stores are what bounds a streaming
+// writer on this chip: a dword store of 8×32-B row pieces is issue-limited to ≈3 B/clk/CU.)
+__device__ __forceinline__ uint32_t clear_macro(const RenderArgs& a, uint32_t tx, uint32_t ty, uint32_t lane)
+{
+  // The constants of the miss record are (re)materialised HERE on purpose: hoisted out of the
+  // caller's tile loop they stay live across the whole solve, get spilled to scratch, and every
+  // reload is a vector-memory load whose s_waitcnt drains the stream of output stores.
+  float inf, zero, one;
+  asm volatile("v_mov_b32 %0, 0x7f800000\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 1.0" : "=v"(inf), "=v"(zero), "=v"(one));
+  const float4 c = miss_rgba(a.pc, one);
+  const uint32_t x0 = tx * 8, ly = ty * 8 + (lane >> 3), q = lane & 7;
+  if(ly >= a.n_local_rows)
+    return 0;
+  const uint32_t y   = image_row(a, ly);
+  const size_t   row = (size_t)(a.compact ? ly : y) * a.W;
+  uint32_t n = 0;
+  // rgba: pixel 8j + q
+#pragma unroll
+  for(uint32_t j = 0; j < 4; ++j)
+  {
+    const uint32_t x = x0 + 8 * j + q;
+    if(x < a.W)
+    {
+      if(a.rgba) st4c(a.rgba + 4 * (row + x), c);
+      ++n;
+    }
+  }
+  // first-hit streams: pixels 4q .. 4q+3
+  const uint32_t xs = x0 + 4 * q;
+  if(a.vec4_ok && xs + 3 < a.W)
+  {
+    const float4 tv = make_float4(inf, inf, inf, inf), zv = make_float4(zero, zero, zero, zero);
+    const size_t i = row + xs;
+    if(a.hits.t) st4c(a.hits.t + i, tv);
+    if(a.hits.px) st4c(a.hits.px + i, zv);
+    if(a.hits.py) st4c(a.hits.py + i, zv);
+    if(a.hits.pz) st4c(a.hits.pz + i, zv);
+    if(a.hits.nx) st4c(a.hits.nx + i, zv);
+    if(a.hits.ny) st4c(a.hits.ny + i, zv);
+    if(a.hits.nz) st4c(a.hits.nz + i, zv);
+    if(a.hits.id)
+    {
+      const int m = miss_id();
+      st4c(a.hits.id + i, m, m, m, m);
+    }
+  }
+  else
+  {
+    for(uint32_t k = 0; k < 4; ++k)
+      if(xs + k < a.W)
+        store_first_miss(a, row + xs + k, inf, zero);
+  }
+  return n;
+}
+
+// ------------------------------------------------------------------------------------------
+// launch dispatch
+// ------------------------------------------------------------------------------------------
+// The one place that maps the scene's precision, solver family and orientation to <Real, ALT, ORIENT>: returns
+// f(Real{}, Alt<ALT>{}, Orient<ORIENT>{}).  The callers instantiate only the kernels they launch (if constexpr on the tags).
+// ORIENT: some torus of the scene turns about an axis other than +y (SceneK::oriented).  A template flag and not a
+// branch in the one kernel: the kernels of a scene without such a torus are then the code they were before oriented
+// tori existed (the plain FP32 listed kernel sits exactly on its 80-VGPR / 6-wave boundary), and inside
+// the ORIENT kernels a wave-uniform branch per test keeps the +y tori of a mixed scene on that same arithmetic.
+template <bool ALT> using Alt = std::integral_constant<bool, ALT>;
+template <bool ORIENT> using Orient = std::integral_constant<bool, ORIENT>;
+template <class F>
+hipError_t with_orient(const SceneK& scene, F&& f)
+{
+  if(scene.oriented != 0u) return f(Orient<true>{});
+  return f(Orient<false>{});
+}
+template <class F>
+hipError_t with_solver(const SceneK& scene, F&& f)
+{
+  const bool alt = scene.alt_solver != kSolverWalk;
+  return with_orient(scene, [&](auto ori) {
+    if(scene.f64 && alt) return f(double{}, Alt<true>{}, ori);
+    if(scene.f64) return f(double{}, Alt<false>{}, ori);
+    if(alt) return f(float{}, Alt<true>{}, ori);
+    return f(float{}, Alt<false>{}, ori);
+  });
+}
+
+}  // namespace trt
