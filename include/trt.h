@@ -15,6 +15,8 @@
  *                                  BEF/shaders/raytrace.rgen:10-17       trt_globals/trt_push/outputs
  *   traceRayEXT closest hit        REFL/shaders/raytrace.rgen:64-75      trt_trace*
  *   traceRayEXT any hit (shadow)   REFL/shaders/raytrace.rchit:114-131   trt_occluded*
+ *   every crossing of a ray, in    (none: build-defined, the reference
+ *   order, with entry / exit       has no counterpart)                   trt_crossings*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -216,6 +218,47 @@ int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, co
  * only, may be captured; it uses no scratch of the ctx). */
 int trt_occluded_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
                      float tmin, float tmax, uint8_t* flag_dev, uint64_t* mask_dev, void* stream);
+
+/* ---- crossings(rays_in -> every surface crossing, in order) ---------------------------- */
+/* What a line of sight crosses after its first surface: every shell wall, with each entry and exit, in order along
+ * the ray (chord lengths per shell, line integrals, thickness, CSG-style queries).  The reference has no counterpart.
+ * Crossings of ray i: for every torus j of the scene (with its axis from trt_set_torus_axes) the real roots of j's
+ * quartic inside the open interval (tmin, tmax); each root gets exactly what a trt_trace hit gets — the polish step,
+ * the rounding of t to FP32, then the open-interval test on the rounded value.  Every torus is solved over the FULL
+ * window (no shrinking interval, no enclosure cull), so the crossings whose id is j are, bit for bit and in order, the
+ * crossings of the scene that holds torus j alone; for a scene of one torus, slot 0 is trt_trace's (t, id).
+ * Order: all tori's crossings merged in ascending t; equal t keeps the torus tested first by trt_trace (descending
+ * R + r, ties by index) first, then the earlier root.
+ * Outputs are slot-major: crossing k of ray i lives at [k * n + i], k < max_per_ray, so that the slots of a ray
+ * stream are themselves ray streams.  count[i] is the number of crossings found (it may exceed max_per_ray); slots
+ * k < min(count[i], max_per_ray) hold the smallest ones — bit for bit the first slots of the untruncated answer — and
+ * the slots beyond are written as the miss record (t = +INFINITY, id = -1, entering = 0): the caller never clears.
+ * entering: 1 where the ray passes from outside torus id's tube to inside it (D·N < 0), 0 where it leaves.
+ * A grazing contact (double root) may report 0, 1 or 2 crossings: unspecified, as hit-or-miss is for trt_trace there.
+ * Zero, NaN and infinite ray components behave as in trt_trace; !(tmax > tmin) gives count = 0 and executes no test.
+ * Solvers: TRT_SOLVE_F32 and TRT_SOLVE_F64 only (the enumeration is a property of the walk); with any other solver set
+ * the call returns TRT_E_INVALID and the message says so.
+ * TRT_E_INVALID: NULL ctx, rays or out; a NULL ray stream with n > 0; count == NULL and t, id, entering all NULL;
+ * max_per_ray outside 1..TRT_MAX_CROSSINGS; n * max_per_ray overflowing uint64_t.  n == 0 is valid and launches nothing.
+ * Stats (trt_enable_stats): primary_tests = n x n_tori (rays with an empty window excepted), bounce_tests =
+ * shadow_tests = 0; traced_tests, solved_tests and evaluations as defined at trt_stats. */
+#define TRT_MAX_CROSSINGS (4 * TRT_MAX_TORI) /* a line meets a torus at most 4 times */
+
+/* Slot-major streams: crossing k of ray i lives at [k * n + i], k < max_per_ray.  Any of t / id / entering may be NULL. */
+typedef struct trt_crossing_streams {
+  float*    t;        /* ascending per ray; unused slots +INFINITY                          */
+  int32_t*  id;       /* torus crossed; unused slots -1                                     */
+  uint8_t*  entering; /* 1: the ray goes INTO that torus' tube here, 0: it leaves; unused 0 */
+  uint32_t* count;    /* n words: crossings found in the window (may exceed max_per_ray)    */
+} trt_crossing_streams;
+
+/* Host buffers: copies in, launches, copies out, synchronises. */
+int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin, float tmax,
+                  uint32_t max_per_ray, const trt_crossing_streams* out);
+/* Device-resident buffers, asynchronous on `stream`; launch contract of the *_dev entry points below (kernel nodes
+ * only, may be captured; it uses no scratch of the ctx). */
+int trt_crossings_dev(trt_ctx* ctx, const trt_rays* in_dev, const trt_scene* scene, float tmin, float tmax,
+                      uint32_t max_per_ray, const trt_crossing_streams* out_dev, void* stream);
 
 /* ---- render: the faithful equivalent of HelloVulkan::raytrace ---------------------- */
 /* rgba_out: W*H*4 floats, row-major, image[y][x] = (hitValue, 1)  (rgen:87); 16-byte aligned.

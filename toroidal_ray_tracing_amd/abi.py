@@ -16,6 +16,7 @@ TRT_OK, TRT_E_INVALID, TRT_E_NO_DEVICE, TRT_E_HIP, TRT_E_SCENE, TRT_E_NOMEM = 0,
 TRT_MAX_TORI = 8
 TRT_MAX_MATERIALS = 8
 TRT_MAX_BATCH = 8
+TRT_MAX_CROSSINGS = 4 * TRT_MAX_TORI   # a line meets a torus at most 4 times
 TRT_CAMERA_PINHOLE, TRT_CAMERA_TOROIDAL = 0, 1
 TRT_CLASSIFY_AUTO, TRT_CLASSIFY_MACRO, TRT_CLASSIFY_TILE = -1, 0, 1
 TRT_SOLVE_F32, TRT_SOLVE_F64, TRT_SOLVE_DK_F32, TRT_SOLVE_DK_F64 = 0, 1, 2, 3
@@ -75,6 +76,11 @@ class trt_rays(C.Structure):
 class trt_hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("px", C.c_void_p), ("py", C.c_void_p), ("pz", C.c_void_p),
                 ("nx", C.c_void_p), ("ny", C.c_void_p), ("nz", C.c_void_p), ("id", C.c_void_p)]
+
+
+class trt_crossing_streams(C.Structure):
+    """Outputs of trt_crossings, slot-major: crossing k of ray i at [k * n + i]; t, id and entering may each be null."""
+    _fields_ = [("t", C.c_void_p), ("id", C.c_void_p), ("entering", C.c_void_p), ("count", C.c_void_p)]
 
 
 class trt_point(C.Structure):
@@ -206,6 +212,26 @@ def hits_struct(arrays):
 def alloc_hits(n):
     d = {k: np.empty(n, np.float32) for k in HIT_FIELDS[:-1]}
     d["id"] = np.empty(n, np.int32)
+    return d
+
+
+CROSSING_FIELDS = ("t", "id", "entering", "count")
+CROSSING_DTYPES = {"t": np.float32, "id": np.int32, "entering": np.uint8, "count": np.uint32}
+
+
+def crossing_streams_struct(arrays):
+    """arrays: dict name -> numpy array | int address | None, over CROSSING_FIELDS."""
+    c = trt_crossing_streams()
+    for k in CROSSING_FIELDS:
+        a = arrays.get(k)
+        setattr(c, k, None if a is None else (a if isinstance(a, int) else a.ctypes.data))
+    return c
+
+
+def alloc_crossings(n, max_per_ray):
+    """Host arrays for trt_crossings: t, id, entering of shape (max_per_ray, n), count of shape (n,)."""
+    d = {k: np.empty((max_per_ray, n), CROSSING_DTYPES[k]) for k in CROSSING_FIELDS[:-1]}
+    d["count"] = np.empty(n, np.uint32)
     return d
 
 

@@ -37,8 +37,9 @@ struct DevBuf {
 // Before kBufGraphVisible: staging of the host-pointer entry points, which synchronise before they return and cannot be
 // captured.  From it on: scratch that a *_dev entry point hands to a kernel (DevBuf::graph_visible, grow()).
 enum Buf {
-  kBufIn,                       // [6] trt_trace, trt_occluded: the ray streams
-  kBufOut  = kBufIn + 6,        // [8] trt_trace, trt_render: the first-hit streams; trt_occluded: flag and mask in [0], [1]
+  kBufIn,                       // [6] trt_trace, trt_occluded, trt_crossings: the ray streams
+  kBufOut  = kBufIn + 6,        // [8] trt_trace, trt_render: the first-hit streams; trt_occluded: flag and mask in [0], [1];
+                                //     trt_crossings: t, id, entering, count in [0] .. [3]
   kBufRgba = kBufOut + 8,       // trt_render: the image
   kBufTmax,                     // trt_occluded: the per-ray bounds
   kBufGraphVisible,
@@ -245,7 +246,7 @@ int fetch_hits(trt_ctx* ctx, trt_hits& want, size_t bytes)
 }
 
 // stage_in(): one input stream uploaded through buf[which], with `*dev` pointed at the copy.  stage_rays(): the six
-// streams of `in` (trt_trace, trt_occluded) through buf[kBufIn ..], with `din` pointed at them; no rays, nothing staged.
+// streams of `in` (trt_trace, trt_occluded, trt_crossings) through buf[kBufIn ..], with `din` pointed at them; no rays, nothing staged.
 int stage_in(trt_ctx* ctx, int which, const float* host, size_t bytes, const float** dev)
 {
   DevBuf& b = ctx->buf[which];
@@ -741,7 +742,7 @@ extern "C" int trt_get_stats(trt_ctx* ctx, trt_stats* out)
 // ------------------------------------------------------------------------------------------
 // trace
 // ------------------------------------------------------------------------------------------
-// `in` and its six streams, for the entry point `who` (trt_trace, trt_occluded)
+// `in` and its six streams, for the entry point `who` (trt_trace, trt_occluded, trt_crossings)
 static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 {
   if(!ctx) return TRT_E_INVALID;
@@ -838,6 +839,66 @@ extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_
   if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, (uint8_t*)d_flag, (uint64_t*)d_mask, nullptr)) return rc;
   if(flag) TRT_HIP(ctx, hipMemcpyAsync(flag, d_flag, n, hipMemcpyDeviceToHost, nullptr));
   if(mask) TRT_HIP(ctx, hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, nullptr));
+  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
+  return TRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// crossings: every surface crossing of every ray, in order
+// ------------------------------------------------------------------------------------------
+static int check_crossings(trt_ctx* ctx, const trt_rays* in, uint32_t max_per_ray, const trt_crossing_streams* out)
+{
+  if(ctx && (!in || !out)) return fail(ctx, TRT_E_INVALID, "trt_crossings: NULL rays or output streams");
+  if(int rc = check_rays(ctx, in, "trt_crossings")) return rc;
+  if(!out->t && !out->id && !out->entering && !out->count) return fail(ctx, TRT_E_INVALID, "trt_crossings: no output (t, id, entering and count all NULL)");
+  if(max_per_ray < 1 || max_per_ray > TRT_MAX_CROSSINGS)
+    return fail(ctx, TRT_E_INVALID, "trt_crossings: max_per_ray = %u, must be 1..%d (TRT_MAX_CROSSINGS)", max_per_ray, TRT_MAX_CROSSINGS);
+  if(in->n > UINT64_MAX / max_per_ray) return fail(ctx, TRT_E_INVALID, "trt_crossings: n * max_per_ray overflows 64 bits");
+  if(solver_of(ctx->precision).alt != kSolverWalk)
+    return fail(ctx, TRT_E_INVALID, "trt_crossings: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
+                                    "set one of them with trt_set_solver");
+  return TRT_OK;
+}
+extern "C" int trt_crossings_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin, float tmax,
+                                 uint32_t max_per_ray, const trt_crossing_streams* out, void* stream)
+{
+  if(int rc = check_crossings(ctx, in, max_per_ray, out)) return rc;
+  const SceneK* Sp = nullptr;
+  if(int rc = build_scene(ctx, scene, Sp)) return rc;
+  const SceneK& S = *Sp;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t   st = (hipStream_t)stream;
+  CrossingsArgs a;
+  a.rays        = *in;
+  a.tmin        = tmin;
+  a.tmax        = tmax;
+  a.max_per_ray = max_per_ray;
+  a.out         = *out;
+  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
+  TRT_HIP(ctx, launch_crossings(S, a, ctx->tn, st));
+  return stats_end(ctx, st);
+}
+
+// Host buffers: the rays staged like trt_trace's, the four output streams through buf[kBufOut] .. [kBufOut + 3].
+extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin, float tmax,
+                             uint32_t max_per_ray, const trt_crossing_streams* out)
+{
+  if(int rc = check_crossings(ctx, in, max_per_ray, out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_crossings_dev(ctx, in, scene, tmin, tmax, max_per_ray, out, nullptr);   // validates, launches and writes nothing
+  if(in->n > SIZE_MAX / sizeof(float) / max_per_ray) return fail(ctx, TRT_E_NOMEM, "trt_crossings: n * max_per_ray floats do not fit the address space");
+  const size_t n = (size_t)in->n, slots = n * max_per_ray;
+  trt_rays din;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  void*        host[4]  = {out->t, out->id, out->entering, out->count};
+  const size_t bytes[4] = {slots * sizeof(float), slots * sizeof(int32_t), slots, n * sizeof(uint32_t)};
+  void*        dev[4];
+  for(int k = 0; k < 4; ++k)
+    if(int rc = stage_out(ctx, kBufOut + k, host[k], bytes[k], &dev[k])) return rc;
+  const trt_crossing_streams dout = {(float*)dev[0], (int32_t*)dev[1], (uint8_t*)dev[2], (uint32_t*)dev[3]};
+  if(int rc = trt_crossings_dev(ctx, &din, scene, tmin, tmax, max_per_ray, &dout, nullptr)) return rc;
+  for(int k = 0; k < 4; ++k)
+    if(host[k]) TRT_HIP(ctx, hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
   return TRT_OK;
 }

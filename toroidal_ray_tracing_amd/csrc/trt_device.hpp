@@ -438,6 +438,90 @@ struct TorusTest {
     }
   }
 
+  // EVERY root of the window, left to right (trt_crossings): walk()'s evaluation points and decisions up to and including
+  // the first root — u[0] is walk()'s `root` bit for bit — and then, instead of returning, the rest of the pieces.  A
+  // piece of constant sign f'' = sigma holds at most two roots: after a forward run has found one, f is evaluated at B
+  // (the next piece needs it anyway) and a second root exists exactly when sign f(B) = sigma; the backward run from B
+  // finds it, bounded on the left by the first.  A piece entered with sign f(A) = -sigma holds one root or none, as in
+  // walk().  A piece end that is itself a root (f = 0 exactly) is reported once, as the START of the next piece — at
+  // `hi`, which has no next piece, by whoever evaluated it — and the piece then continues with the sign f takes just
+  // right of it (that of f').  At most two runs per piece, each bounded by kNewtonCap; at most 4 roots are kept (a
+  // quartic has no more; rounding cannot be allowed to write past u[3]).  Returns their number.
+  // Call after a successful setup(); every root then goes through finish_root().
+  __device__ __forceinline__ int walk_all(uint32_t& evals, Real (&u)[4])
+  {
+    const Real A4x4 = Real(4) * A4, P2x2 = Real(2) * P2;
+    Real a = A, fa, da;          // setup() leaves the window start in A
+    eval(a, A4x4, P2x2, fa, da);
+    ++evals;
+    int  n    = 0;
+    auto push = [&](Real x) {    // (unrolled selects: u[] stays in registers)
+#pragma unroll
+      for(int k = 0; k < 4; ++k)
+        if(k == n) u[k] = x;
+      n = n < 4 ? n + 1 : n;
+    };
+    for(;;)
+    {
+      const bool c1 = split && a < -w, c2 = split && a < w;
+      const Real b  = c1 ? min_(-w, hi) : (c2 ? min_(w, hi) : hi);
+      const Real sg = (c2 && !c1) ? Real(-1) : Real(1);          // sign of f'' on the piece
+      const bool zero = fa == Real(0);                           // the piece end is itself a root
+      if(zero) push(a);
+      const bool apos = zero ? da > Real(0) : fa > Real(0);      // sign of f on entering the piece
+      const bool bwd  = apos != (sg > Real(0));                  // sign f(A) = -sigma: probe B
+      Real fb = Real(0), db = Real(0);                           // (f, f') at B, once evaluated
+      bool have_b = false;
+      Real x = a, fx = fa, dx = da, left = a;                    // `left`: where a backward run stops
+      bool pos  = apos;                                          // the sign the run must keep
+      bool back = bwd;
+      bool run  = !(zero && !bwd);   // leaving a root with sign f = sigma: f does not come back in this piece
+      if(bwd)
+      {
+        eval(b, A4x4, P2x2, fb, db);
+        ++evals;
+        have_b = true;
+        x = b; fx = fb; dx = db;
+        pos = fb > Real(0);
+        if(fb == Real(0)) { run = false; if(!(b < hi)) push(b); }
+        else if(pos != (sg > Real(0))) run = false;              // no sign change: no root in the piece
+      }
+      const Real ustop = (b - a) * kStepStop;
+      while(run)
+      {
+        const Real sd  = back ? -sg : sg;        // forward needs sigma·f' < 0, backward sigma·f' > 0
+        const Real lim = back ? -left : b;       // forward: xn < B; backward: xn > left  ⇔  -xn < -left
+        bool noroot = false;
+        for(int it = 0; it < kNewtonCap; ++it)
+        {
+          if(!(sd * dx < Real(0))) { noroot = !back; break; }
+          const Real st = fx / dx;
+          const Real xn = x - st;
+          if(!((back ? -xn : xn) < lim)) { noroot = !back; if(back) x = left; break; }
+          if(xn == x) break;
+          x = xn;
+          if(abs_(st) <= ustop) break;
+          eval(x, A4x4, P2x2, fx, dx);
+          ++evals;
+          if(fx == Real(0) || (fx > Real(0)) != pos) break;
+        }
+        if(noroot) break;                        // (forward runs only)
+        push(x);
+        if(back) break;                          // the last root of the piece
+        eval(b, A4x4, P2x2, fb, db);             // a forward run found a root: is there a second one?
+        ++evals;
+        have_b = true;
+        if(fb == Real(0)) { if(!(b < hi)) push(b); break; }
+        if((fb > Real(0)) != (sg > Real(0))) break;
+        back = true; left = x; x = b; fx = fb; dx = db; pos = fb > Real(0);
+      }
+      if(!(b < hi)) break;                       // that was the last piece
+      if(!have_b) { eval(b, A4x4, P2x2, fb, db); ++evals; }
+      a = b; fa = fb; da = db;
+    }
+    return n;
+  }
+
   // What the two alternative solvers share.  Prologue: the monic depressed quartic u⁴ + p·u² + q·u + s, the scale sc
   // of its roots (the bounding-sphere radius in u), the tolerance tol = kAltTol·sc and the window start lo.
   static constexpr Real kAltTol = sizeof(Real) == 4 ? Real(0.0009765625) : Real(2.384185791015625e-07);  // 2^-10 / 2^-22
@@ -576,15 +660,20 @@ struct TorusTest {
   __device__ __forceinline__ bool finish(Real dx_, Real dy_, Real dz_, Real tmin, Real tmax,
                                          const TorusK<Real>& T, Real& t_out) const
   {
-    if(!found)
-      return false;
-    Real r = root;
+    Real gh;
+    return found && finish_root(root, dx_, dy_, dz_, tmin, tmax, T, t_out, gh);
+  }
+  // The same for any root r of the walk (walk_all() returns several).  gh = ρ·g'/2 at the unpolished root, ρ > 0: the
+  // sign of g' — negative where the ray goes from outside the tube (g > 0) to inside it.
+  __device__ __forceinline__ bool finish_root(Real r, Real dx_, Real dy_, Real dz_, Real tmin, Real tmax,
+                                              const TorusK<Real>& T, Real& t_out, Real& gh) const
+  {
     const Real px  = fma_(r, dx_, qx), py = fma_(r, dy_, qy), pz = fma_(r, dz_, qz);
     const Real rho = sqrt_(fma_(pz, pz, px * px));
     const Real e   = rho - T.R;
     const Real g   = fma_(e, e, fma_(py, py, -T.r2));
     const Real s   = fma_(pz, dz_, px * dx_);
-    const Real gh  = fma_(e, s, (py * dy_) * rho);  // ρ·g'/2
+    gh             = fma_(e, s, (py * dy_) * rho);  // ρ·g'/2
     const Real du  = Real(0.5) * ((g * rho) / gh);
     if(abs_(du) <= T.rpol)
       r = r - du;
@@ -826,6 +915,39 @@ __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin,
       return true;
   }
   return false;
+}
+
+// Every crossing of one ray with torus i inside the open interval (r.tmin, r.tmax), left to right: emit(t, entering) per
+// crossing, t rounded to FP32.  The test is torus_hit()'s over the same window — the same setup(), the walk that
+// TorusTest::walk_all() continues past the first root, and for EVERY root the polish, round_t and the open-interval test
+// a closest hit gets — so the first crossing emitted is torus_hit()'s t bit for bit, unless that first root falls to the
+// interval test (torus_hit then reports a miss; the enumeration goes on to the next root).  Default solver only.
+template <class Real, bool ORIENT = false, class Emit>
+__device__ __forceinline__ void torus_crossings(const SceneK& S, int i, const RayK<Real>& r, WorkCount& wc, Emit&& emit)
+{
+  LocalRay<Real> l = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+  TorusK<Real>   T = torus_k<Real>(S, i);
+  if constexpr(ORIENT)
+    if(is_oriented(S, i))   // wave-uniform, as in torus_hit()
+    {
+      l.set(S, i, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+      T = centred(T);
+    }
+  TorusTest<Real> q;
+  ++wc.traced;
+  if(!q.setup(l.ox, l.oy, l.oz, l.dx, l.dy, l.dz, l.dd, l.inv_dd, (Real)r.tmin, (Real)r.tmax, T))
+    return;
+  ++wc.solved;
+  Real      u[4] = {};
+  const int n = q.walk_all(wc.evals, u);
+  for(int k = 0; k < n; ++k)
+  {
+    const Real uk = k == 0 ? u[0] : (k == 1 ? u[1] : (k == 2 ? u[2] : u[3]));
+    Real  tt, gh;
+    float t;
+    if(q.finish_root(uk, l.dx, l.dy, l.dz, (Real)r.tmin, (Real)r.tmax, T, tt, gh) && round_t(tt, r.tmin, r.tmax, t))
+      emit(t, gh < Real(0));
+  }
 }
 
 // T4: outward unit normal N = normalize(P - q), q = nearest point of the centre circle

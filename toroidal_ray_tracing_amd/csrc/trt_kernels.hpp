@@ -130,7 +130,7 @@ struct Tuning {
   uint64_t persist_blocks     = 0;    // TRT_PERSIST_BLOCKS   (0 = default)
   uint64_t listed_blocks      = 0;    // TRT_LISTED_BLOCKS
   int      static_tile        = 8;    // TRT_TILE
-  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel and occluded_kernel)
+  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel)
   int      occluded_walk      = kOccludedWalk;   // TRT_OCCLUDED_WALK: kWalkNested (0) | kWalkTable (1), occluded_kernel only
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
   uint64_t splat_blocks_per_cu = 0;   // TRT_SPLAT_BLOCKS_PER_CU
@@ -156,6 +156,16 @@ struct OccludedArgs {
   unsigned long long* stats;
 };
 
+// trt_crossings*: every crossing of every ray, slot-major (crossing k of ray i at [k * rays.n + i], k < max_per_ray);
+// t, id and entering are each optional, and so is count as long as one of them is there.
+struct CrossingsArgs {
+  trt_rays             rays;
+  float                tmin, tmax;
+  uint32_t             max_per_ray;   // 1 .. TRT_MAX_CROSSINGS
+  trt_crossing_streams out;
+  unsigned long long*  stats;
+};
+
 enum RenderVariant { kRenderStatic = 0, kRenderPersistent = 1, kRenderListed = 2 };
 constexpr int kPersistentBlocksPerCU = 16;  // 4× the resident 4 blocks/CU: the dispatcher evens out the tile costs
 
@@ -163,6 +173,7 @@ hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_
                        hipStream_t stream);
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

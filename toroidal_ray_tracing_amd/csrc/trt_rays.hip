@@ -1,8 +1,9 @@
-// trt_rays.hip — the ray-stream kernels of the toroidal ray tracer (trt_trace*, trt_occluded*), gfx950.
+// trt_rays.hip — the ray-stream kernels of the toroidal ray tracer (trt_trace*, trt_occluded*, trt_crossings*), gfx950.
 //
 //   trace_kernel       trace(rays_in → hits_out): SoA rays in, closest hit out.
 //   occluded_kernel    occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
-//   stream_grid, launch_trace, launch_occluded   their grid and launch wrappers.
+//   crossings_kernel   crossings(rays_in → slots_out): SoA rays in, every surface crossing out, in order, slot-major.
+//   stream_grid, launch_trace, launch_occluded, launch_crossings   their grid and launch wrappers.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
 //
 // One lane = one ray; the scene is staged into LDS once per block.  Compiled with -ffp-contract=off (see trt_device.hpp
@@ -89,10 +90,89 @@ __global__ __launch_bounds__(256) void occluded_kernel(const SceneK scene, const
 }
 
 // ------------------------------------------------------------------------------------------
+// crossings(rays_in → every surface crossing, in order)
+// ------------------------------------------------------------------------------------------
+// A lane enumerates its ray's crossings torus by torus (S.order, every torus over the full window: torus_crossings) and
+// inserts each into a sorted column of its own in LDS — slot k of lane `tid` at [k * 256 + tid], so a wave's access to
+// one slot is 64 consecutive words, and no indexed private array exists that could go to scratch
+// memory.  The column is dynamic shared memory sized by max_per_ray: 5 B per slot and lane (t, then a byte id << 1 |
+// entering), 1.25 KiB per slot and block — K = 4 keeps the block at 7 KiB with the scene, K = 32 at 42 KiB (3 blocks per
+// CU).  Insertion is stable: a crossing goes behind every kept one with t <= its own, which is the tie rule (torus
+// tested first, then earlier root); once the column is full only a crossing strictly below the last kept one gets in,
+// so the kept slots are the first slots of the untruncated answer.  Nobody but the lane reads its column: the only
+// barrier is stage_scene's, the only atomics the stats block add.  Stores are slot-major: one instruction, 64
+// consecutive elements of slot k.  The window test !(tmax > tmin) is kernel-uniform.
+constexpr uint32_t kCrossingSlotBytes = 256u * (sizeof(float) + sizeof(uint8_t));   // dynamic LDS per slot
+static_assert(TRT_MAX_TORI <= 128, "crossings_kernel packs id << 1 | entering into a byte");
+
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, const CrossingsArgs a)
+{
+  __shared__ SceneK S;
+  extern __shared__ float crossing_lds[];   // [K][256] t, then [K][256] bytes
+  stage_scene<ORIENT>(&S, scene);
+
+  const uint32_t K   = a.max_per_ray;
+  float*         ct  = crossing_lds + threadIdx.x;
+  uint8_t*       cw  = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
+  const bool     window = a.tmax > a.tmin;
+  const float    inf = __builtin_inff();
+
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
+  {
+    uint32_t count = 0;
+    if(window)
+    {
+      const v3 o = {a.rays.ox[i], a.rays.oy[i], a.rays.oz[i]};
+      const v3 d = {a.rays.dx[i], a.rays.dy[i], a.rays.dz[i]};
+      RayK<Real> r;
+      r.set(o, d, a.tmin, a.tmax);
+      for(int k = 0; k < S.n_tori; ++k)
+      {
+        const int j = S.order[k];
+        ++tests;
+        torus_crossings<Real, ORIENT>(S, j, r, wc, [&](float t, bool entering) {
+          uint32_t p = umin(count, K);   // slots kept so far
+          ++count;
+          if(p == K)
+          {
+            if(!(t < ct[(K - 1u) * 256u])) return;
+            p = K - 1u;
+          }
+          for(; p > 0u && ct[(p - 1u) * 256u] > t; --p)
+          {
+            ct[p * 256u] = ct[(p - 1u) * 256u];
+            cw[p * 256u] = cw[(p - 1u) * 256u];
+          }
+          ct[p * 256u] = t;
+          cw[p * 256u] = (uint8_t)(((uint32_t)j << 1) | (entering ? 1u : 0u));
+        });
+      }
+    }
+    const uint32_t kept = umin(count, K);
+    for(uint32_t k = 0; k < K; ++k)
+    {
+      const bool     used = k < kept;
+      const uint64_t at   = (uint64_t)k * a.rays.n + i;
+      const uint32_t w    = used ? cw[k * 256u] : 0u;
+      if(a.out.t) a.out.t[at] = used ? ct[k * 256u] : inf;
+      if(a.out.id) a.out.id[at] = used ? (int32_t)(w >> 1) : -1;
+      if(a.out.entering) a.out.entering[at] = (uint8_t)(w & 1u);
+    }
+    if(a.out.count) a.out.count[i] = count;
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 namespace {
-// The grid of the ray-stream kernels (trace_kernel, occluded_kernel; grid-stride loops): one block per 256 rays, at
+// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel; grid-stride loops): one block per 256 rays, at
 // most 4096 blocks (TRT_TRACE_BLOCKS).
 uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
@@ -130,6 +210,24 @@ hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tun
 #endif
     hipLaunchKernelGGL((occluded_kernel<Real, ALT, ORIENT>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();
+  });
+}
+
+// Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here).
+hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.rays.n, tn);
+  const uint32_t lds  = a.max_per_ray * kCrossingSlotBytes;
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;
+    else
+    {
+      hipLaunchKernelGGL((crossings_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, scene, a);
+      return hipGetLastError();
+    }
   });
 }
 

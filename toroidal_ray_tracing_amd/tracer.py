@@ -165,6 +165,29 @@ class Tracer:
         self._check(self._L.trt_occluded_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
                                              _vp(flag_ptr), _vp(mask_ptr), _vp(stream)))
 
+    # -- crossings(rays_in -> every surface crossing, in order) ---------------------------
+    def crossings(self, scene, o, d, tmin=0.001, tmax=10000.0, max_per_ray=abi.TRT_MAX_CROSSINGS):
+        """Every surface crossing of every ray, in order along it (trt_crossings), on host arrays: o, d of shape (n,3).
+        Returns (t, id, entering, count): t float32, id int32 and entering bool of shape (max_per_ray, n) — slot k of
+        ray i at [k, i], unused slots (inf, -1, False) — and count (n,), the crossings found (it may exceed max_per_ray)."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        out = abi.alloc_crossings(n, int(max_per_ray))
+        cs = abi.crossing_streams_struct(out)
+        self._check(self._L.trt_crossings(self._h, C.byref(rays), self._scene(scene), tmin, tmax, int(max_per_ray), C.byref(cs)))
+        return out["t"], out["id"], out["entering"].astype(bool), out["count"]
+
+    def crossings_dev(self, scene, ray_ptrs, n, out_ptrs, max_per_ray=abi.TRT_MAX_CROSSINGS, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses; out_ptrs: dict over abi.CROSSING_FIELDS -> address (0 / None /
+        absent: stream not wanted) — t float32, id int32, entering uint8 of max_per_ray * n elements each, slot-major, and
+        count uint32 of n.  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        cs = abi.crossing_streams_struct({k: (int(v) if v else None) for k, v in out_ptrs.items()})
+        self._check(self._L.trt_crossings_dev(self._h, C.byref(rays), self._scene(scene), tmin, tmax, int(max_per_ray),
+                                              C.byref(cs), _vp(stream)))
+
     # -- render -------------------------------------------------------------------------
     def render(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, want_hits=True):
         """Host buffers.  Returns (rgba (H,W,4), hits dict | None)."""
