@@ -15,6 +15,8 @@
  *                                  BEF/shaders/raytrace.rgen:10-17       trt_globals/trt_push/outputs
  *   traceRayEXT closest hit        REFL/shaders/raytrace.rgen:64-75      trt_trace*
  *   traceRayEXT any hit (shadow)   REFL/shaders/raytrace.rchit:114-131   trt_occluded*
+ *   payload loop on your own rays  REFL/shaders/raytrace.rgen:54-87 bounce
+ *                                  loop + rchit/rmiss                    trt_shade*
  *   every crossing of a ray, in    (none: build-defined, the reference
  *   order, with entry / exit       has no counterpart)                   trt_crossings*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
@@ -260,6 +262,38 @@ int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, floa
 int trt_crossings_dev(trt_ctx* ctx, const trt_rays* in_dev, const trt_scene* scene, float tmin, float tmax,
                       uint32_t max_per_ray, const trt_crossing_streams* out_dev, void* stream);
 
+/* ---- shade(rays_in -> one colour per output): radiance along caller-supplied rays --------- */
+/* The payload loop of REFL/shaders/raytrace.rgen:54-87 with the closest-hit, miss and shadow-miss shaders behind it
+ * (rchit:50-156, rmiss:37), on rays the caller brings instead of the two cameras of trt_render*: a third camera, jittered
+ * antialiasing, depth of field, re-lighting a stored ray set, rays another stage left on the device.
+ * Outputs and layout: in->n must be a multiple of `samples`, n_out = in->n / samples, and the rays are sample-major —
+ * sample s of output i is ray s * n_out + i, so that the samples of a stream are themselves ray streams (the idea of
+ * trt_crossings' slot-major outputs).  rgba_out holds n_out * 4 floats and is 16-byte aligned.
+ * Colour of one ray: exactly what trt_render* computes for a pixel whose primary ray is that ray — the same loop: the
+ * window (0.001, 10000) on every segment, pc->maxDepth (the loop body runs once even for maxDepth <= 0), clearColor * 0.8
+ * on a miss, the light of pc, the shadow query, the reflection of an illum == 3 material; the ctx's solver (every
+ * TRT_SOLVE_*) and torus axes apply; pc->rho is not read.  Bit for bit the colour trt_render* gives on the same device.
+ * Handed the primary rays trt_render_dev exports in RenderedData, the call gives back the frame's colours.
+ * Enclosure cull: a path starts with an empty mask (no camera has certified anything about its origin) and the mask grows
+ * by the two in-path rules of the render (the shadow ray; a reflection off a surface met from outside) — by the contract
+ * at trt_scene that changes no result and no query count.
+ * Directions may have any non-zero length, t in units of |d|, as in trt_trace.  Zero, NaN and infinite components behave
+ * as in trt_trace: a ray for which trt_trace (window 0.001, 10000) reports id = -1 gets the miss colour.
+ * Averaging: acc = c_0, then acc = acc + c_s for s = 1, 2, ... as plain FP32 adds in that order, rgb = acc / (float)samples
+ * with a correctly rounded division; samples == 1 is the ray's colour untouched.  Alpha is 1.  One lane owns
+ * one output and walks its samples in order: no atomics, nothing depends on the order of waves.
+ * TRT_E_INVALID: NULL ctx, rays, pc or rgba; a NULL ray stream with n > 0; samples == 0; n % samples != 0; a misaligned
+ * image.  A refused call leaves the ctx usable.  n == 0 is valid and launches nothing.
+ * Stats (trt_enable_stats): primary_tests = n x n_tori, bounce_tests and shadow_tests as the render counts them, pixels = n;
+ * traced_tests, solved_tests and evaluations as defined at trt_stats.
+ * Host buffers: copies in, launches, copies out, synchronises. */
+int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+              float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`; launch contract of the *_dev entry points below (kernel nodes
+ * only, may be captured; it uses no scratch of the ctx, allocates nothing and synchronises nothing). */
+int trt_shade_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                  float* rgba_dev, void* stream);
+
 /* ---- render: the faithful equivalent of HelloVulkan::raytrace ---------------------- */
 /* rgba_out: W*H*4 floats, row-major, image[y][x] = (hitValue, 1)  (rgen:87); 16-byte aligned.
  * first_hit_out: optional SoA record of the depth-0 hit per pixel, row-major y*W+x. */
@@ -398,7 +432,7 @@ enum { TRT_CLOUD_KEEP_ALL = 0, TRT_CLOUD_MARK_MISSES = 1, TRT_CLOUD_COMPACT = 2 
 int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t n_records, int mode, int append,
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
-/* Counters of the last render, trace or occluded call made with counting enabled. */
+/* Counters of the last render, trace, occluded, crossings or shade call made with counting enabled. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

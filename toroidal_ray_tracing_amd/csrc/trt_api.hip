@@ -37,10 +37,10 @@ struct DevBuf {
 // Before kBufGraphVisible: staging of the host-pointer entry points, which synchronise before they return and cannot be
 // captured.  From it on: scratch that a *_dev entry point hands to a kernel (DevBuf::graph_visible, grow()).
 enum Buf {
-  kBufIn,                       // [6] trt_trace, trt_occluded, trt_crossings: the ray streams
+  kBufIn,                       // [6] trt_trace, trt_occluded, trt_crossings, trt_shade: the ray streams
   kBufOut  = kBufIn + 6,        // [8] trt_trace, trt_render: the first-hit streams; trt_occluded: flag and mask in [0], [1];
                                 //     trt_crossings: t, id, entering, count in [0] .. [3]
-  kBufRgba = kBufOut + 8,       // trt_render: the image
+  kBufRgba = kBufOut + 8,       // trt_render, trt_shade: the image
   kBufTmax,                     // trt_occluded: the per-ray bounds
   kBufGraphVisible,
   kBufToro = kBufGraphVisible,  // the toroidal camera's trigonometry tables
@@ -246,7 +246,7 @@ int fetch_hits(trt_ctx* ctx, trt_hits& want, size_t bytes)
 }
 
 // stage_in(): one input stream uploaded through buf[which], with `*dev` pointed at the copy.  stage_rays(): the six
-// streams of `in` (trt_trace, trt_occluded, trt_crossings) through buf[kBufIn ..], with `din` pointed at them; no rays, nothing staged.
+// streams of `in` (trt_trace, trt_occluded, trt_crossings, trt_shade) through buf[kBufIn ..], with `din` pointed at them; no rays, nothing staged.
 int stage_in(trt_ctx* ctx, int which, const float* host, size_t bytes, const float** dev)
 {
   DevBuf& b = ctx->buf[which];
@@ -742,7 +742,7 @@ extern "C" int trt_get_stats(trt_ctx* ctx, trt_stats* out)
 // ------------------------------------------------------------------------------------------
 // trace
 // ------------------------------------------------------------------------------------------
-// `in` and its six streams, for the entry point `who` (trt_trace, trt_occluded, trt_crossings)
+// `in` and its six streams, for the entry point `who` (trt_trace, trt_occluded, trt_crossings, trt_shade)
 static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 {
   if(!ctx) return TRT_E_INVALID;
@@ -899,6 +899,57 @@ extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
   if(int rc = trt_crossings_dev(ctx, &din, scene, tmin, tmax, max_per_ray, &dout, nullptr)) return rc;
   for(int k = 0; k < 4; ++k)
     if(host[k]) TRT_HIP(ctx, hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, nullptr));
+  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
+  return TRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// shade: the render's bounce loop on caller-supplied rays, samples averaged
+// ------------------------------------------------------------------------------------------
+static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba)
+{
+  if(ctx && (!in || !pc || !rgba)) return fail(ctx, TRT_E_INVALID, "trt_shade: NULL rays, push constants or image");
+  if(int rc = check_rays(ctx, in, "trt_shade")) return rc;
+  if(samples == 0) return fail(ctx, TRT_E_INVALID, "trt_shade: samples = 0, must be at least 1");
+  if(in->n % samples)
+    return fail(ctx, TRT_E_INVALID, "trt_shade: n = %llu rays is not a multiple of samples = %u", (unsigned long long)in->n, samples);
+  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "trt_shade: the rgba image must be 16-byte aligned (it is written as float4)");
+  return TRT_OK;
+}
+extern "C" int trt_shade_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                             float* rgba, void* stream)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba)) return rc;
+  const SceneK* Sp = nullptr;
+  if(int rc = build_scene(ctx, scene, Sp)) return rc;
+  const SceneK& S = *Sp;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  ShadeArgs   a;
+  a.rays    = *in;
+  a.n_out   = in->n / samples;
+  a.samples = samples;
+  a.pc      = *pc;
+  a.rgba    = rgba;
+  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
+  TRT_HIP(ctx, launch_shade(S, a, ctx->tn, st));
+  return stats_end(ctx, st);
+}
+
+// Host buffers: the rays staged like trt_trace's, the image through buf[kBufRgba] like trt_render's.
+extern "C" int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                         float* rgba_out)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_shade_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
+  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
+  trt_rays din;
+  void*    d_rgba;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  if(int rc = stage_out(ctx, kBufRgba, rgba_out, bytes, &d_rgba)) return rc;
+  if(int rc = trt_shade_dev(ctx, &din, samples, pc, scene, (float*)d_rgba, nullptr)) return rc;
+  TRT_HIP(ctx, hipMemcpyAsync(rgba_out, d_rgba, bytes, hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
   return TRT_OK;
 }

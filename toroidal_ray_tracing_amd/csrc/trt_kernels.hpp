@@ -166,6 +166,18 @@ struct CrossingsArgs {
   unsigned long long*  stats;
 };
 
+// trt_shade*: the colour of every ray by the render's bounce loop, `samples` rays averaged per output.  The rays are
+// sample-major (sample s of output i is ray s * n_out + i, n_out = rays.n / samples: the samples of a stream are
+// themselves ray streams); rgba holds n_out * 4 floats, 16-byte aligned.  pc.rho is not read.
+struct ShadeArgs {
+  trt_rays            rays;
+  uint64_t            n_out;
+  uint32_t            samples;   // >= 1, divides rays.n
+  trt_push            pc;        // PushConstantRay, by value in the kernel-argument segment
+  float*              rgba;
+  unsigned long long* stats;
+};
+
 enum RenderVariant { kRenderStatic = 0, kRenderPersistent = 1, kRenderListed = 2 };
 constexpr int kPersistentBlocksPerCU = 16;  // 4× the resident 4 blocks/CU: the dispatcher evens out the tile costs
 
@@ -174,6 +186,7 @@ hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

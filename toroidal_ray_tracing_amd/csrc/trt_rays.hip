@@ -1,9 +1,10 @@
-// trt_rays.hip — the ray-stream kernels of the toroidal ray tracer (trt_trace*, trt_occluded*, trt_crossings*), gfx950.
+// trt_rays.hip — the ray-stream kernels of the toroidal ray tracer (trt_trace*, trt_occluded*, trt_crossings*, trt_shade*), gfx950.
 //
 //   trace_kernel       trace(rays_in → hits_out): SoA rays in, closest hit out.
 //   occluded_kernel    occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
 //   crossings_kernel   crossings(rays_in → slots_out): SoA rays in, every surface crossing out, in order, slot-major.
-//   stream_grid, launch_trace, launch_occluded, launch_crossings   their grid and launch wrappers.
+//   shade_ray, shade_kernel   shade(rays_in → colours_out): SoA rays in, the bounce loop's colour out, samples averaged.
+//   stream_grid, launch_trace, launch_occluded, launch_crossings, launch_shade   their grid and launch wrappers.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
 //
 // One lane = one ray; the scene is staged into LDS once per block.  Compiled with -ffp-contract=off (see trt_device.hpp
@@ -169,6 +170,96 @@ __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, cons
 }
 
 // ------------------------------------------------------------------------------------------
+// shade(rays_in → one colour per output): the payload loop on caller-supplied rays
+// ------------------------------------------------------------------------------------------
+// The colour of one ray: the raygen bounce loop (REFL/shaders/raytrace.rgen:54-87) with the closest-hit, miss and
+// shadow-miss shaders inlined — the loop trace_pixel (trt_kernels.hip) runs for a pixel, statement for statement, from
+// the same pieces (closest_hit with the render's walk, hit_begin, any_hit, hit_end, miss_colour), so that a ray gets bit
+// for bit the colour trt_render* gives the pixel whose primary ray it is.  What differs is where the ray comes from and
+// that nothing but the colour leaves: no first-hit record, no RenderedData.  The enclosure mask starts empty — nobody
+// has certified anything about a caller's origins — and grows by trace_pixel's two in-path rules.
+// It is a copy and not a helper shared with trace_pixel on purpose: the render kernels' register allocation is tuned to
+// the instruction, and moving their loop into a shared function would move it.
+template <class Real, bool ALT, bool ORIENT>
+__device__ __forceinline__ v3 shade_ray(const SceneK& S, const trt_push& pc, v3 origin, v3 direction,
+                                        uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
+{
+  int depth = 0, done = 1;                                                 // rgen:54,57
+  v3  attenuation = {1.0f, 1.0f, 1.0f};                                    // rgen:56
+  v3  hitValue    = {0.0f, 0.0f, 0.0f};                                    // rgen:61
+  uint32_t skip = 0u;
+  for(;;)                                                                  // rgen:62
+  {
+    v3    prdHit, nextO = origin, nextD = direction;
+    float t;
+    const int id = closest_hit<Real, ALT, kRenderWalk, ORIENT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
+    if(id < 0)
+      prdHit = miss_colour(pc);                                            // rmiss:37
+    else
+    {
+      HitState h;
+      hit_begin<ORIENT>(S, pc, id, t, origin, direction, h);
+      bool shadowed = false;
+      const uint32_t inside = S.inside[id];
+      if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
+        shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
+      if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
+        skip |= inside;
+      prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
+    }
+    hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
+    hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
+    hitValue.z = fma_(prdHit.z, attenuation.z, hitValue.z);
+    depth++;                                                               // rgen:78
+    if(done == 1 || depth >= pc.maxDepth)                                  // rgen:79
+      break;
+    origin    = nextO;                                                     // rgen:82
+    direction = nextD;                                                     // rgen:83
+    done      = 1;                                                         // rgen:84
+  }
+  return hitValue;
+}
+
+// One lane owns one OUTPUT and walks its samples in order (sample s of output i is ray s·n_out + i, so the six loads of
+// a sample are coalesced like trace_kernel's): acc = c_0, then acc += c_s as plain FP32 adds, then one correctly rounded
+// division by (float)samples — skipped, kernel-uniformly, for one sample, whose colour therefore leaves untouched.  No
+// atomics, nothing depends on the order of waves.  One dwordx4 store per output: a wave writes 1 KiB contiguous.
+// No wave-level compaction of finished paths: see DESIGN.md §5 (assumed from the render's measurement, not measured here).
+template <class Real, bool ALT, bool ORIENT = false>
+__global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const ShadeArgs a)
+{
+  __shared__ SceneK S;
+  stage_scene<ORIENT>(&S, scene);
+
+  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_out; i += stride)
+  {
+    v3 acc = {0.0f, 0.0f, 0.0f};
+    for(uint32_t s = 0; s < a.samples; ++s)
+    {
+      const uint64_t r = (uint64_t)s * a.n_out + i;
+      const v3 o = {ox[r], oy[r], oz[r]};
+      const v3 d = {dx[r], dy[r], dz[r]};
+      const v3 c = shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc);
+      if(s == 0u) acc = c;
+      else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
+    }
+    if(a.samples != 1u)
+    {
+      const float k = (float)a.samples;
+      acc = {acc.x / k, acc.y / k, acc.z / k};
+    }
+    st4(a.rgba + 4 * i, make_float4(acc.x, acc.y, acc.z, 1.0f));           // rgen:87
+  }
+  if(a.stats)
+    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+}
+
+// ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 namespace {
@@ -228,6 +319,18 @@ hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const T
       hipLaunchKernelGGL((crossings_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, scene, a);
       return hipGetLastError();
     }
+  });
+}
+
+// One lane per output (a.n_out = a.rays.n / a.samples); every solver, like launch_trace.
+hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.n_out == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.n_out, tn);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    hipLaunchKernelGGL((shade_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+    return hipGetLastError();
   });
 }
 

@@ -32,6 +32,10 @@ SYMBOLS = {
                                 C.c_uint32, C.POINTER(abi.trt_crossing_streams)]),
     "trt_crossings_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.POINTER(abi.trt_scene), C.c_float, C.c_float,
                                     C.c_uint32, C.POINTER(abi.trt_crossing_streams), C.c_void_p]),
+    "trt_shade": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
+                            C.c_void_p]),
+    "trt_shade_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
+                                C.c_void_p, C.c_void_p]),
     "trt_render": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push),
                              C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_int,
                              C.c_void_p, C.POINTER(abi.trt_hits)]),

@@ -188,6 +188,27 @@ class Tracer:
         self._check(self._L.trt_crossings_dev(self._h, C.byref(rays), self._scene(scene), tmin, tmax, int(max_per_ray),
                                               C.byref(cs), _vp(stream)))
 
+    # -- shade(rays_in -> one colour per output) -------------------------------------------
+    def shade(self, scene, o, d, pc, samples=1):
+        """Radiance along caller-supplied rays (trt_shade) on host arrays: o, d of shape (n,3), sample-major — sample s of
+        output i is ray s * n_out + i, n_out = n / samples.  Every ray gets the colour trt_render* gives a pixel with
+        that primary ray; the samples of an output are averaged.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        samples = int(samples)
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
+        self._check(self._L.trt_shade(self._h, C.byref(rays), samples, C.byref(pc), self._scene(scene), rgba.ctypes.data))
+        return rgba
+
+    def shade_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses of n floats each, sample-major; rgba_ptr: (n / samples) * 4
+        floats, 16-byte aligned.  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_shade_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
+                                          _vp(rgba_ptr), _vp(stream)))
+
     # -- render -------------------------------------------------------------------------
     def render(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, want_hits=True):
         """Host buffers.  Returns (rgba (H,W,4), hits dict | None)."""
