@@ -215,34 +215,43 @@ std::array<void**, 8> hit_streams(trt_hits& h)
 }
 
 // Host staging of the entry points that take host pointers; all of it runs on the default stream.
-// stage_out(): one output the caller wants (`host` non-NULL) gets buf[which], grown to `bytes`, as its device address
-// `*dev`; one it does not want, NULL.
-int stage_out(trt_ctx* ctx, int which, const void* host, size_t bytes, void** dev)
+// One output of such an entry point: stage_outs() gives each of `n` outputs the caller wants (`host` non-NULL) buf[which],
+// grown to `bytes`, as its device address `dev`, and NULL to one it does not want; fetch_outs() copies the wanted ones
+// back and waits for the default stream.
+struct StagedOut { void* host; size_t bytes; int which; void* dev; };
+
+int stage_outs(trt_ctx* ctx, StagedOut* outs, int n)
 {
-  *dev = nullptr;
-  if(!host || !bytes) return TRT_OK;
-  if(int rc = grow(ctx, ctx->buf[which], bytes)) return rc;
-  *dev = ctx->buf[which].p;
+  for(StagedOut* o = outs; o != outs + n; ++o)
+  {
+    o->dev = nullptr;
+    if(!o->host || !o->bytes) continue;
+    if(int rc = grow(ctx, ctx->buf[o->which], o->bytes)) return rc;
+    o->dev = ctx->buf[o->which].p;
+  }
   return TRT_OK;
 }
 
-// The hit streams (trt_trace, trt_render): stage_hits() stages every stream of `want` into the same stream of `dev`,
-// fetch_hits() copies those streams back and waits for the default stream.
-int stage_hits(trt_ctx* ctx, trt_hits& want, size_t bytes, trt_hits& dev)
+int fetch_outs(trt_ctx* ctx, const StagedOut* outs, int n)
 {
-  const auto dst = hit_streams(want), dptr = hit_streams(dev);
-  for(int k = 0; k < 8; ++k)
-    if(int rc = stage_out(ctx, kBufOut + k, *dst[k], bytes, dptr[k])) return rc;
-  return TRT_OK;
-}
-
-int fetch_hits(trt_ctx* ctx, trt_hits& want, size_t bytes)
-{
-  const auto dst = hit_streams(want);
-  for(int k = 0; k < 8 && bytes; ++k)
-    if(*dst[k]) TRT_HIP(ctx, hipMemcpyAsync(*dst[k], ctx->buf[kBufOut + k].p, bytes, hipMemcpyDeviceToHost, nullptr));
+  for(const StagedOut* o = outs; o != outs + n; ++o)
+    if(o->dev) TRT_HIP(ctx, hipMemcpyAsync(o->host, o->dev, o->bytes, hipMemcpyDeviceToHost, nullptr));
   TRT_HIP(ctx, hipStreamSynchronize(nullptr));
   return TRT_OK;
+}
+
+// The hit streams (trt_trace, trt_render): hit_outs() describes every stream of `want` as an output of `bytes` through
+// buf[kBufOut ..]; staged_hits() points the same streams of `dev` at where stage_outs() put them.
+void hit_outs(trt_hits& want, size_t bytes, StagedOut* outs)
+{
+  const auto src = hit_streams(want);
+  for(int k = 0; k < 8; ++k) outs[k] = {*src[k], bytes, kBufOut + k, nullptr};
+}
+
+void staged_hits(const StagedOut* outs, trt_hits& dev)
+{
+  const auto dptr = hit_streams(dev);
+  for(int k = 0; k < 8; ++k) *dptr[k] = outs[k].dev;
 }
 
 // stage_in(): one input stream uploaded through buf[which], with `*dev` pointed at the copy.  stage_rays(): the six
@@ -751,6 +760,22 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
     return fail(ctx, TRT_E_INVALID, "%s: NULL ray stream", who);
   return TRT_OK;
 }
+
+// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev), after the entry
+// point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
+template <class Args>
+static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
+                     hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t))
+{
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if(int rc = stats_begin(ctx, st, n, a.stats)) return rc;
+  TRT_HIP(ctx, launch(*S, a, ctx->tn, st));
+  return stats_end(ctx, st);
+}
+
 static int check_trace(trt_ctx* ctx, const trt_rays* in, const trt_hits* out)
 {
   if(ctx && (!in || !out)) return fail(ctx, TRT_E_INVALID, "trt_trace: NULL rays or hits");
@@ -760,19 +785,12 @@ extern "C" int trt_trace_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
                              float tmax, trt_hits* out, void* stream)
 {
   if(int rc = check_trace(ctx, in, out)) return rc;
-  const SceneK* Sp = nullptr;
-  if(int rc = build_scene(ctx, scene, Sp)) return rc;
-  const SceneK& S = *Sp;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  TraceArgs   a;
+  TraceArgs a;
   a.rays  = *in;
   a.hits  = *out;
   a.tmin  = tmin;
   a.tmax  = tmax;
-  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
-  TRT_HIP(ctx, launch_trace(S, a, ctx->tn, st));
-  return stats_end(ctx, st);
+  return ray_query(ctx, scene, stream, in->n, a, launch_trace);
 }
 
 extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin,
@@ -781,12 +799,15 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
   if(int rc = check_trace(ctx, in, out)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)in->n * sizeof(float);
-  trt_rays din;
-  trt_hits dout;
+  trt_rays  din;
+  trt_hits  dout;
+  StagedOut outs[8];
+  hit_outs(*out, bytes, outs);
   if(int rc = stage_rays(ctx, in, din)) return rc;
-  if(int rc = stage_hits(ctx, *out, bytes, dout)) return rc;
+  if(int rc = stage_outs(ctx, outs, 8)) return rc;
+  staged_hits(outs, dout);
   if(int rc = trt_trace_dev(ctx, &din, scene, tmin, tmax, &dout, nullptr)) return rc;
-  return fetch_hits(ctx, *out, bytes);
+  return fetch_outs(ctx, outs, 8);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -803,11 +824,6 @@ extern "C" int trt_occluded_dev(trt_ctx* ctx, const trt_rays* in, const float* t
                                 float tmax, uint8_t* flag, uint64_t* mask, void* stream)
 {
   if(int rc = check_occluded(ctx, in, flag, mask)) return rc;
-  const SceneK* Sp = nullptr;
-  if(int rc = build_scene(ctx, scene, Sp)) return rc;
-  const SceneK& S = *Sp;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t  st = (hipStream_t)stream;
   OccludedArgs a;
   a.rays         = *in;
   a.tmax_per_ray = tmax_per_ray;
@@ -815,9 +831,7 @@ extern "C" int trt_occluded_dev(trt_ctx* ctx, const trt_rays* in, const float* t
   a.tmax         = tmax;
   a.flag         = flag;
   a.mask         = (unsigned long long*)mask;
-  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
-  TRT_HIP(ctx, launch_occluded(S, a, ctx->tn, st));
-  return stats_end(ctx, st);
+  return ray_query(ctx, scene, stream, in->n, a, launch_occluded);
 }
 
 // Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], flag and mask through buf[kBufOut], [kBufOut + 1].
@@ -831,16 +845,12 @@ extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_
   trt_rays din;
   if(int rc = stage_rays(ctx, in, din)) return rc;
   const float* d_tmax = nullptr;
-  void *d_flag, *d_mask;
   if(tmax_per_ray)
     if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, &d_tmax)) return rc;
-  if(int rc = stage_out(ctx, kBufOut, flag, n, &d_flag)) return rc;
-  if(int rc = stage_out(ctx, kBufOut + 1, mask, mask_bytes, &d_mask)) return rc;
-  if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, (uint8_t*)d_flag, (uint64_t*)d_mask, nullptr)) return rc;
-  if(flag) TRT_HIP(ctx, hipMemcpyAsync(flag, d_flag, n, hipMemcpyDeviceToHost, nullptr));
-  if(mask) TRT_HIP(ctx, hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, nullptr));
-  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
-  return TRT_OK;
+  StagedOut outs[2] = {{flag, n, kBufOut, nullptr}, {mask, mask_bytes, kBufOut + 1, nullptr}};
+  if(int rc = stage_outs(ctx, outs, 2)) return rc;
+  if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, (uint8_t*)outs[0].dev, (uint64_t*)outs[1].dev, nullptr)) return rc;
+  return fetch_outs(ctx, outs, 2);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -863,20 +873,13 @@ extern "C" int trt_crossings_dev(trt_ctx* ctx, const trt_rays* in, const trt_sce
                                  uint32_t max_per_ray, const trt_crossing_streams* out, void* stream)
 {
   if(int rc = check_crossings(ctx, in, max_per_ray, out)) return rc;
-  const SceneK* Sp = nullptr;
-  if(int rc = build_scene(ctx, scene, Sp)) return rc;
-  const SceneK& S = *Sp;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t   st = (hipStream_t)stream;
   CrossingsArgs a;
   a.rays        = *in;
   a.tmin        = tmin;
   a.tmax        = tmax;
   a.max_per_ray = max_per_ray;
   a.out         = *out;
-  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
-  TRT_HIP(ctx, launch_crossings(S, a, ctx->tn, st));
-  return stats_end(ctx, st);
+  return ray_query(ctx, scene, stream, in->n, a, launch_crossings);
 }
 
 // Host buffers: the rays staged like trt_trace's, the four output streams through buf[kBufOut] .. [kBufOut + 3].
@@ -890,17 +893,12 @@ extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
   const size_t n = (size_t)in->n, slots = n * max_per_ray;
   trt_rays din;
   if(int rc = stage_rays(ctx, in, din)) return rc;
-  void*        host[4]  = {out->t, out->id, out->entering, out->count};
-  const size_t bytes[4] = {slots * sizeof(float), slots * sizeof(int32_t), slots, n * sizeof(uint32_t)};
-  void*        dev[4];
-  for(int k = 0; k < 4; ++k)
-    if(int rc = stage_out(ctx, kBufOut + k, host[k], bytes[k], &dev[k])) return rc;
-  const trt_crossing_streams dout = {(float*)dev[0], (int32_t*)dev[1], (uint8_t*)dev[2], (uint32_t*)dev[3]};
+  StagedOut outs[4] = {{out->t, slots * sizeof(float), kBufOut, nullptr}, {out->id, slots * sizeof(int32_t), kBufOut + 1, nullptr},
+                       {out->entering, slots, kBufOut + 2, nullptr}, {out->count, n * sizeof(uint32_t), kBufOut + 3, nullptr}};
+  if(int rc = stage_outs(ctx, outs, 4)) return rc;
+  const trt_crossing_streams dout = {(float*)outs[0].dev, (int32_t*)outs[1].dev, (uint8_t*)outs[2].dev, (uint32_t*)outs[3].dev};
   if(int rc = trt_crossings_dev(ctx, &din, scene, tmin, tmax, max_per_ray, &dout, nullptr)) return rc;
-  for(int k = 0; k < 4; ++k)
-    if(host[k]) TRT_HIP(ctx, hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, nullptr));
-  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
-  return TRT_OK;
+  return fetch_outs(ctx, outs, 4);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -920,20 +918,13 @@ extern "C" int trt_shade_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples,
                              float* rgba, void* stream)
 {
   if(int rc = check_shade(ctx, in, samples, pc, rgba)) return rc;
-  const SceneK* Sp = nullptr;
-  if(int rc = build_scene(ctx, scene, Sp)) return rc;
-  const SceneK& S = *Sp;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  ShadeArgs   a;
+  ShadeArgs a;
   a.rays    = *in;
   a.n_out   = in->n / samples;
   a.samples = samples;
   a.pc      = *pc;
   a.rgba    = rgba;
-  if(int rc = stats_begin(ctx, st, in->n, a.stats)) return rc;
-  TRT_HIP(ctx, launch_shade(S, a, ctx->tn, st));
-  return stats_end(ctx, st);
+  return ray_query(ctx, scene, stream, in->n, a, launch_shade);
 }
 
 // Host buffers: the rays staged like trt_trace's, the image through buf[kBufRgba] like trt_render's.
@@ -944,14 +935,12 @@ extern "C" int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, con
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   if(in->n == 0) return trt_shade_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
   const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
-  trt_rays din;
-  void*    d_rgba;
+  trt_rays  din;
+  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
   if(int rc = stage_rays(ctx, in, din)) return rc;
-  if(int rc = stage_out(ctx, kBufRgba, rgba_out, bytes, &d_rgba)) return rc;
-  if(int rc = trt_shade_dev(ctx, &din, samples, pc, scene, (float*)d_rgba, nullptr)) return rc;
-  TRT_HIP(ctx, hipMemcpyAsync(rgba_out, d_rgba, bytes, hipMemcpyDeviceToHost, nullptr));
-  TRT_HIP(ctx, hipStreamSynchronize(nullptr));
-  return TRT_OK;
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  if(int rc = trt_shade_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1247,16 +1236,16 @@ extern "C" int trt_render(trt_ctx* ctx, const trt_globals* g, const trt_push* pc
   if(!ctx) return TRT_E_INVALID;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t npx = (size_t)W * H;
-  void*        d_rgba;
-  if(int rc = stage_out(ctx, kBufRgba, rgba_out, npx * 16, &d_rgba)) return rc;
-  trt_hits dh, want{};
+  trt_hits     dh, want{};
   if(first_hit_out) want = *first_hit_out;
-  if(int rc = stage_hits(ctx, want, npx * 4, dh)) return rc;
-  if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, (float*)d_rgba, first_hit_out ? &dh : nullptr,
+  StagedOut outs[9] = {{rgba_out, npx * 16, kBufRgba, nullptr}};   // the image, then the eight first-hit streams
+  hit_outs(want, npx * 4, outs + 1);
+  if(int rc = stage_outs(ctx, outs, 9)) return rc;
+  staged_hits(outs + 1, dh);
+  if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, (float*)outs[0].dev, first_hit_out ? &dh : nullptr,
                              nullptr, nullptr))
     return rc;
-  if(rgba_out) TRT_HIP(ctx, hipMemcpyAsync(rgba_out, d_rgba, npx * 16, hipMemcpyDeviceToHost, nullptr));
-  return fetch_hits(ctx, want, npx * 4);
+  return fetch_outs(ctx, outs, 9);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // trt_kernels.hip — gfx950 (MI355X / CDNA4) tile render path of the toroidal ray tracer (trt_render*).
 //
 //   rd_unit, RdSink, rd_flush, rd_miss_tile   the RenderedData export, staged through LDS
-//   trace_pixel               one pixel, start to finish, on one lane
+//   trace_pixel               one pixel, start to finish, on one lane: raygen, bounce_loop() (trt_render.hpp), the stores
 //   render_static_kernel      one lane per pixel, 8×8 pixel tile per wavefront; each lane runs the
 //                             reference's raygen bounce loop (REFL/shaders/raytrace.rgen:62-85).
 //   render_listed_kernel      the DEFAULT render kernel: a wave takes its entries of both lists — CLEAR macro tiles as
@@ -33,11 +33,6 @@ __device__ unsigned long long* g_timeline = nullptr;
 #define TRT_STAMP(k, v) do { } while(0)
 #endif
 
-// ------------------------------------------------------------------------------------------
-// render, static mapping: lane ↔ pixel for the whole bounce loop
-// ------------------------------------------------------------------------------------------
-// One pixel, start to finish, on one lane: the reference's raygen main() with the closest-hit,
-// miss and shadow-miss shaders inlined (REFL/shaders/raytrace.rgen:40-88).
 // ------------------------------------------------------------------------------------------
 // RenderedData export (BEF/shaders/raytrace.rgen:72-73,111-112), staged through LDS
 // ------------------------------------------------------------------------------------------
@@ -104,6 +99,11 @@ __device__ __forceinline__ void rd_miss_tile(const RenderArgs& a, float4* tile, 
   rd_flush(a, tile, tx, ty, lane);
 }
 
+// ------------------------------------------------------------------------------------------
+// render, static mapping: lane ↔ pixel for the whole bounce loop
+// ------------------------------------------------------------------------------------------
+// One pixel, start to finish, on one lane: the reference's raygen main() (REFL/shaders/raytrace.rgen:40-88) — the
+// primary ray, bounce_loop() (trt_render.hpp) with the pixel's first-hit record and RenderedData pieces, the colour.
 template <class Real, bool ALT, bool ORIENT = false>
 __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a, uint32_t x, uint32_t y, uint32_t ly, const RdSink rd,
                                             uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
@@ -117,26 +117,13 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
     rd.put(3, make_float4(direction.x, direction.y, direction.z, 0.0f));   // BEF rgen:57,73
   }
 
-  int depth = 0, done = 1;                                                 // rgen:54,57
   // (the constant 1 is materialised per pixel: hoisted out of the tile loop hipcc keeps — and, at 80 VGPRs, spills — it)
   float one0;
   asm volatile("v_mov_b32 %0, 1.0" : "=v"(one0));
-  v3  attenuation = {one0, one0, one0};                                    // rgen:56
-  v3  hitValue    = {0.0f, 0.0f, 0.0f};                                    // rgen:61
-  // enclosure cull (trt_device.hpp closest_hit): the tori this path's rays cannot hit first — tubes strictly inside a tube
-  // the ray origin is outside of.  The camera's share is certified per frame on the host; a hit left OUTWARDS adds the
-  // tubes inside the torus hit (outside-ness persists along a path: a segment that ended on a surface crossed none).
-  uint32_t skip = a.skip_primary;
-  for(;;)                                                                  // rgen:62
-  {
-    v3    prdHit, nextO = origin, nextD = direction;
-    float t;
-    const int id = closest_hit<Real, ALT, kRenderWalk, ORIENT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
-    if(id < 0)
-    {
-      prdHit = miss_colour(a.pc);
-      if(depth == 0)
-      {
+  // the loop starts from the camera's share of the enclosure cull, certified per frame on the host (a.skip_primary)
+  const v3 hitValue = bounce_loop<Real, ALT, ORIENT>(
+      S, a.pc, origin, direction, a.skip_primary, {one0, one0, one0},
+      [&](float t) {
         store_first_miss(a, oi, t);   // (t = +inf: what closest_hit leaves without a hit)
         if(rd)
         {
@@ -145,35 +132,12 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
           asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 1.0" : "=v"(z), "=v"(o1));
           rd.put(0, make_float4(z, z, z, o1));
         }
-      }
-    }
-    else
-    {
-      HitState h;
-      hit_begin<ORIENT>(S, a.pc, id, t, origin, direction, h);
-      if(depth == 0)                                                       // BEF rgen:94-97
-      {
+      },
+      [&](float t, const HitState& h, int id) {
         store_first_hit(a, oi, t, h.P, h.N, id);
         if(rd) rd.put(0, make_float4(h.P.x, h.P.y, h.P.z, 1.0f));          // BEF rgen:112
-      }
-      bool shadowed = false;
-      const uint32_t inside = S.inside[id];
-      if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
-        shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
-      if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
-        skip |= inside;
-      prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
-    }
-    hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
-    hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
-    hitValue.z = fma_(prdHit.z, attenuation.z, hitValue.z);
-    depth++;                                                               // rgen:78
-    if(done == 1 || depth >= a.pc.maxDepth)                                // rgen:79
-      break;
-    origin    = nextO;                                                     // rgen:82
-    direction = nextD;                                                     // rgen:83
-    done      = 1;                                                         // rgen:84
-  }
+      },
+      n_primary, n_bounce, n_shadow, wc);
   // alpha 1, materialised here: as a plain constant it is kept live across the bounce loop and spilled when the
   // FP32 kernel is held to 80 VGPRs
   float one;

@@ -3,7 +3,7 @@
 //   trace_kernel       trace(rays_in → hits_out): SoA rays in, closest hit out.
 //   occluded_kernel    occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
 //   crossings_kernel   crossings(rays_in → slots_out): SoA rays in, every surface crossing out, in order, slot-major.
-//   shade_ray, shade_kernel   shade(rays_in → colours_out): SoA rays in, the bounce loop's colour out, samples averaged.
+//   shade_kernel       shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour (trt_render.hpp) out, samples averaged.
 //   stream_grid, launch_trace, launch_occluded, launch_crossings, launch_shade   their grid and launch wrappers.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
 //
@@ -172,54 +172,10 @@ __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, cons
 // ------------------------------------------------------------------------------------------
 // shade(rays_in → one colour per output): the payload loop on caller-supplied rays
 // ------------------------------------------------------------------------------------------
-// The colour of one ray: the raygen bounce loop (REFL/shaders/raytrace.rgen:54-87) with the closest-hit, miss and
-// shadow-miss shaders inlined — the loop trace_pixel (trt_kernels.hip) runs for a pixel, statement for statement, from
-// the same pieces (closest_hit with the render's walk, hit_begin, any_hit, hit_end, miss_colour), so that a ray gets bit
-// for bit the colour trt_render* gives the pixel whose primary ray it is.  What differs is where the ray comes from and
-// that nothing but the colour leaves: no first-hit record, no RenderedData.  The enclosure mask starts empty — nobody
-// has certified anything about a caller's origins — and grows by trace_pixel's two in-path rules.
-// It is a copy and not a helper shared with trace_pixel on purpose: the render kernels' register allocation is tuned to
-// the instruction, and moving their loop into a shared function would move it.
-template <class Real, bool ALT, bool ORIENT>
-__device__ __forceinline__ v3 shade_ray(const SceneK& S, const trt_push& pc, v3 origin, v3 direction,
-                                        uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
-{
-  int depth = 0, done = 1;                                                 // rgen:54,57
-  v3  attenuation = {1.0f, 1.0f, 1.0f};                                    // rgen:56
-  v3  hitValue    = {0.0f, 0.0f, 0.0f};                                    // rgen:61
-  uint32_t skip = 0u;
-  for(;;)                                                                  // rgen:62
-  {
-    v3    prdHit, nextO = origin, nextD = direction;
-    float t;
-    const int id = closest_hit<Real, ALT, kRenderWalk, ORIENT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
-    if(id < 0)
-      prdHit = miss_colour(pc);                                            // rmiss:37
-    else
-    {
-      HitState h;
-      hit_begin<ORIENT>(S, pc, id, t, origin, direction, h);
-      bool shadowed = false;
-      const uint32_t inside = S.inside[id];
-      if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
-        shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
-      if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
-        skip |= inside;
-      prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
-    }
-    hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
-    hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
-    hitValue.z = fma_(prdHit.z, attenuation.z, hitValue.z);
-    depth++;                                                               // rgen:78
-    if(done == 1 || depth >= pc.maxDepth)                                  // rgen:79
-      break;
-    origin    = nextO;                                                     // rgen:82
-    direction = nextD;                                                     // rgen:83
-    done      = 1;                                                         // rgen:84
-  }
-  return hitValue;
-}
-
+// The colour of one ray is the render's loop — bounce_loop() (trt_render.hpp), what trace_pixel runs for a pixel — on a
+// caller's ray: the enclosure mask starts empty (nobody has certified anything about a caller's origins), the
+// attenuation at 1, and nothing but the colour leaves (no first-hit record, no RenderedData: two empty callables).
+//
 // One lane owns one OUTPUT and walks its samples in order (sample s of output i is ray s·n_out + i, so the six loads of
 // a sample are coalesced like trace_kernel's): acc = c_0, then acc += c_s as plain FP32 adds, then one correctly rounded
 // division by (float)samples — skipped, kernel-uniformly, for one sample, whose colour therefore leaves untouched.  No
@@ -244,7 +200,8 @@ __global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const Sh
       const uint64_t r = (uint64_t)s * a.n_out + i;
       const v3 o = {ox[r], oy[r], oz[r]};
       const v3 d = {dx[r], dy[r], dz[r]};
-      const v3 c = shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc);
+      const v3 c = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
+                                                  n_primary, n_bounce, n_shadow, wc);
       if(s == 0u) acc = c;
       else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
     }
@@ -263,8 +220,8 @@ __global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const Sh
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 namespace {
-// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel; grid-stride loops): one block per 256 rays, at
-// most 4096 blocks (TRT_TRACE_BLOCKS).
+// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel; grid-stride loops):
+// one block per 256 rays (shade_kernel: outputs), at most 4096 blocks (TRT_TRACE_BLOCKS).
 uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
   const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;

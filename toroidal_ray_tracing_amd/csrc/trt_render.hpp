@@ -8,6 +8,7 @@
 //   block_add_stats                       the query counters of a block → the global totals
 //   settle_loads, stage_args, stage_block256   staging into LDS
 //   kTMin, kTMax                          the ray window of the render kernels
+//   bounce_loop                           the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (shade_kernel)
 //   live_slot, list_counts, TileCode, tile_x / tile_y, frame_args, LaunchArgs   the tile-list layout
 //   clear_macro                           the constant fill of one CLEAR macro tile
 //   with_orient, with_solver              launch dispatch: scene → <Real, ALT, ORIENT>
@@ -261,6 +262,63 @@ __device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const S
 
 constexpr float kTMin = 0.001f;    // rgen:51, rchit:114
 constexpr float kTMax = 10000.0f;  // rgen:52
+
+// ------------------------------------------------------------------------------------------
+// the bounce loop of one ray: a pixel's primary ray (trace_pixel) or a caller's (shade_kernel)
+// ------------------------------------------------------------------------------------------
+// The raygen payload loop (REFL/shaders/raytrace.rgen:54-87) with the closest-hit, miss and shadow-miss shaders inlined;
+// returns hitValue.  Stated once, so that trt_shade gives a ray bit for bit the colour trt_render* gives the pixel whose
+// primary ray it is.  What the caller owns of the FIRST ray's record goes through the two callables: first_miss(t) on a
+// miss at depth 0 (t = +inf: what closest_hit leaves without a hit), first_hit(t, h, id) right after hit_begin at depth 0.
+// `skip` is the enclosure cull (trt_device.hpp closest_hit): the tori this path's rays cannot hit first — tubes strictly
+// inside a tube the ray origin is outside of.  The caller passes what is certified of the origin (the camera's share,
+// per frame on the host; nothing for a caller's ray); a hit left OUTWARDS adds the tubes inside the torus hit
+// (outside-ness persists along a path: a segment that ended on a surface crossed none).
+template <class Real, bool ALT, bool ORIENT, class FirstMiss, class FirstHit>
+__device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v3 origin, v3 direction,
+                                          uint32_t skip, v3 attenuation,                   // rgen:56
+                                          FirstMiss&& first_miss, FirstHit&& first_hit,
+                                          uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
+{
+  int depth = 0, done = 1;                                                 // rgen:54,57
+  v3  hitValue = {0.0f, 0.0f, 0.0f};                                       // rgen:61
+  for(;;)                                                                  // rgen:62
+  {
+    v3    prdHit, nextO = origin, nextD = direction;
+    float t;
+    const int id = closest_hit<Real, ALT, kRenderWalk, ORIENT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
+    if(id < 0)
+    {
+      prdHit = miss_colour(pc);                                            // rmiss:37
+      if(depth == 0)
+        first_miss(t);
+    }
+    else
+    {
+      HitState h;
+      hit_begin<ORIENT>(S, pc, id, t, origin, direction, h);
+      if(depth == 0)                                                       // BEF rgen:94-97
+        first_hit(t, h, id);
+      bool shadowed = false;
+      const uint32_t inside = S.inside[id];
+      if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
+        shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
+      if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
+        skip |= inside;
+      prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
+    }
+    hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
+    hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
+    hitValue.z = fma_(prdHit.z, attenuation.z, hitValue.z);
+    depth++;                                                               // rgen:78
+    if(done == 1 || depth >= pc.maxDepth)                                  // rgen:79
+      break;
+    origin    = nextO;                                                     // rgen:82
+    direction = nextD;                                                     // rgen:83
+    done      = 1;                                                         // rgen:84
+  }
+  return hitValue;
+}
 
 // ------------------------------------------------------------------------------------------
 // tile lists: what the classification writes and the list kernels read
