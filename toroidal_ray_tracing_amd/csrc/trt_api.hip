@@ -636,6 +636,12 @@ extern "C" int trt_debug_reload_tuning(trt_ctx* ctx)
   ctx->lists.valid = false;         // (the knobs change what the classification is launched with)
   return TRT_OK;
 }
+// tests/test_gpu_splat_forms.py: the form (SplatMode) a trt_splat_dev call with these sizes takes under the knobs as last read
+extern "C" int trt_debug_splat_mode(trt_ctx* ctx, uint32_t W, uint32_t H, float point_size, uint64_t n_points)
+{
+  if(!ctx) return TRT_E_INVALID;
+  return splat_plan(W, H, point_size, n_points, ctx->tn).mode;
+}
 #endif
 
 #ifdef TRT_TIMELINE

@@ -3,15 +3,23 @@
 //
 //   splat_bin_kernel          paged (the default up to kSortBins bins): projects the points and scatters their 12-B
 //                             records by bin into pages, one sweep;
-//   splat_count_kernel        direct and sorted: projects the points and counts them per bin, then
-//   splat_scatter[_sorted]_kernel  writes the records of each bin into its range;
+//   splat_count_kernel        the two-pass forms: projects the points and counts them per bin, then
+//   splat_scatter[_sorted]_kernel  writes the records of each bin into its range — direct: images of more than kSortBins
+//                             bins; sorted: clouds the page scheme cannot address (splat_plan's fallback).  By splat_plan's
+//                             arithmetic (derived on the host, not measured) the release build first takes the sorted form
+//                             at 33.6 M points on a 4096² image (2,048 bins), 44.7 M at 4096x2048 (1,024), 67.1 M at 2048²
+//                             (512), 134 M at 1024² (128), never on an image of a dozen bins; from 153 M points (8 GiB of
+//                             scratch) every image takes the one-pass form;
 //   splat_resolve_bins_kernel one block per bin: the depth test in LDS, then every pixel of the bin written once;
 //   splat_clear/points/resolve_kernel  the one-pass form (global atomicMin on per-pixel keys): points wider than 32
 //                             pixels, images beyond 16,383 pixels a side or kSplatMaxBins bins, clouds whose records
 //                             would take more than 8 GiB.
 //
-// Every form produces the same image bit for bit.  Compiled with -ffp-contract=off (see trt_device.hpp for the
-// arithmetic contract).
+// The paged and the sorted scatter sort a chunk of points by bin in LDS, each in its own words: one set of helpers for both
+// compiled to other code in all four instantiations and measured slower (profiles/r12_splat_sort.txt), so only the
+// encoding of a staged record's bin (splat_stage_rec) is shared — a fix to one chunk sort belongs in the other too.
+// Every form produces the same image bit for bit (test_splat_bit_exact: paged, direct, one-pass;
+// tests/test_gpu_splat_forms.py: sorted).  Compiled with -ffp-contract=off (see trt_device.hpp for the arithmetic contract).
 #include "trt_splat.hpp"
 
 #include <cstdlib>
@@ -252,13 +260,23 @@ __global__ __launch_bounds__(M * 256) void splat_count_kernel(const trt_point* _
 // scatter, sorted: up to kSortBins bins (2048: images up to 4096² and beyond), 4,096 points per block of 512 threads,
 // 12-B records staged in LDS in bin order.  LDS: 3 words per bin + 12 B per staged record = 78 KB: two blocks per CU.
 constexpr uint32_t kSortBins = 2048, kSortChunk = 4096, kSortThreads = 512, kSortPer = kSortChunk / kSortThreads, kSortStage = 4608;
+// A staged record of the sorted and of the paged scatter carries its bin in its spare bits: z is a depth24 (splat_project: at
+// most 16777215) and rect ends with ry1 <= 64 at bit 21, below 2^28 — bits 31..24 of z take the bin's low byte, bits 30..28
+// of rect its three high bits.
+static_assert(kSortBins <= (1u << 11) && kBinW <= 128u && kBinH <= 64u, "8 + 3 spare bits for the bin; rect = 7 + 8 + 6 + 7 bits");
+__device__ __forceinline__ SplatRec splat_stage_rec(uint32_t idx, uint32_t z24, uint32_t rect, uint32_t bin)
+{
+  return SplatRec{idx, z24 | (bin << 24), rect | ((bin >> 8) << 28)};
+}
+__device__ __forceinline__ uint32_t splat_staged_bin(SplatRec r) { return (r.z >> 24) | ((r.rect >> 28) << 8); }
+__device__ __forceinline__ SplatRec splat_unstage_rec(SplatRec r) { return SplatRec{r.idx, r.z & 0xffffffu, r.rect & 0x0fffffffu}; }
 template <uint32_t NB>   // bins the block's LDS arrays hold: 512 (images up to 2048²: 61 KB of LDS) or kSortBins (79 KB)
 __global__ __launch_bounds__(kSortThreads) void splat_scatter_sorted_kernel(uint64_t n, const SplatBins b)
 {
   __shared__ uint32_t hist[NB];    // points of this block per bin, then the rank counter
   __shared__ uint32_t lbase[NB];   // first staged record of the bin
   __shared__ uint32_t gbase[NB];   // first global record of this block's range in the bin
-  __shared__ SplatRec stage[kSortStage];  // records in bin order; the bin rides in the spare bits (z: 31..24, rect: 30..28)
+  __shared__ SplatRec stage[kSortStage];  // records in bin order (splat_stage_rec)
   __shared__ uint32_t wsum[kSortThreads / 64];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   for(uint32_t k = tid; k < b.n_bins; k += kSortThreads) hist[k] = 0u;
@@ -329,7 +347,7 @@ __global__ __launch_bounds__(kSortThreads) void splat_scatter_sorted_kernel(uint
       splat_for_bins(b, x0, x1, y0, y1, [&](uint32_t bin, int rx0, int rx1, int ry0, int ry1) {
         const uint32_t rank = atomicAdd(&hist[bin], 1u), slot = lbase[bin] + rank, rect = splat_rect(rx0, rx1, ry0, ry1);
         if(slot < kSortStage)
-          stage[slot] = SplatRec{idx, z24 | (bin << 24), rect | ((bin >> 8) << 28)};
+          stage[slot] = splat_stage_rec(idx, z24, rect, bin);
         else
           b.records[gbase[bin] + rank] = SplatRec{idx, z24, rect};
       });
@@ -340,8 +358,8 @@ __global__ __launch_bounds__(kSortThreads) void splat_scatter_sorted_kernel(uint
   for(uint32_t j = tid; j < n_staged; j += kSortThreads)
   {
     const SplatRec r = stage[j];
-    const uint32_t bin = (r.z >> 24) | ((r.rect >> 28) << 8);
-    b.records[gbase[bin] + (j - lbase[bin])] = SplatRec{r.idx, r.z & 0xffffffu, r.rect & 0x0fffffffu};
+    const uint32_t bin = splat_staged_bin(r);
+    b.records[gbase[bin] + (j - lbase[bin])] = splat_unstage_rec(r);
   }
 }
 
@@ -591,7 +609,7 @@ __global__ __launch_bounds__(kSortThreads, 4) void splat_bin_kernel(const trt_po
       splat_for_bins(b, x0, x1, y0, y1, [&](uint32_t bin, int rx0, int rx1, int ry0, int ry1) {
         const uint32_t rank = atomicAdd(&hist[bin], 1u), slot = (lfirst[bin] & 0xffffu) + rank, rect = splat_rect(rx0, rx1, ry0, ry1);
         if(slot < kStage)
-          stage[slot] = SplatRec{idx, z24 | (bin << 24), rect | ((bin >> 8) << 28)};
+          stage[slot] = splat_stage_rec(idx, z24, rect, bin);
         else if(g0[bin] != ~0u)
           b.records[place(bin, rank)] = SplatRec{idx, z24, rect};
       });
@@ -602,9 +620,9 @@ __global__ __launch_bounds__(kSortThreads, 4) void splat_bin_kernel(const trt_po
   for(uint32_t j = tid; j < n_staged; j += kSortThreads)
   {
     const SplatRec r = stage[j];
-    const uint32_t bin = (r.z >> 24) | ((r.rect >> 28) << 8);
+    const uint32_t bin = splat_staged_bin(r);
     if(g0[bin] != ~0u)
-      b.records[place(bin, j - (lfirst[bin] & 0xffffu))] = SplatRec{r.idx, r.z & 0xffffffu, r.rect & 0x0fffffffu};
+      b.records[place(bin, j - (lfirst[bin] & 0xffffu))] = splat_unstage_rec(r);
   }
   }   // chunks
 }
@@ -675,6 +693,23 @@ __device__ __forceinline__ void splat_depth_test(unsigned long long* keys, const
   }
 }
 
+// the records of slots 0 .. n_slots-1 through the depth test: four records per lane and trip, their loads issued together
+// (eight: +2 %); rec_at(v) is the record of slot v, or the empty record SplatRec{0, 0, 0} (an empty rectangle)
+template <class RecAt>
+__device__ __forceinline__ void splat_gather_test(const SplatBins& b, unsigned long long* keys, uint32_t n_slots, RecAt rec_at)
+{
+  constexpr uint32_t kR = 4;
+  for(uint32_t rb = threadIdx.x; rb < n_slots; rb += kR * blockDim.x)
+  {
+    SplatRec rec[kR];
+#pragma unroll
+    for(uint32_t u = 0; u < kR; ++u)
+      rec[u] = TRT_SKIP(b, 64u) ? SplatRec{0u, 0u, 0u} : rec_at(rb + u * blockDim.x);
+    if(TRT_SKIP(b, 32u)) continue;
+    splat_depth_test<kR>(keys, rec);
+  }
+}
+
 template <bool PAGED>
 __global__ __launch_bounds__(kSplatResolveThreads) void splat_resolve_bins_kernel(const trt_point* __restrict__ pts, const SplatArgs a, const SplatBins b,
                                                                                   float4 clear, float4* rgba)
@@ -683,7 +718,6 @@ __global__ __launch_bounds__(kSplatResolveThreads) void splat_resolve_bins_kerne
   __shared__ uint32_t plist[PAGED ? kPageList : 1], n_list;
   for(uint32_t k = threadIdx.x; k < kBinW * kBinH; k += blockDim.x) keys[k] = kSplatClear;
   const uint32_t bin = blockIdx.x;
-  constexpr uint32_t kR = 4;   // four records per lane and trip, their loads issued together (eight: +2 %)
   if(PAGED)
   {
     // the bin's pages: its own two (abstract pages 0 and 1) and the pool pages whose notes name it; how many records a
@@ -709,21 +743,11 @@ __global__ __launch_bounds__(kSplatResolveThreads) void splat_resolve_bins_kerne
       }
     __syncthreads();
     const uint32_t slots = poisoned ? 0u : umin(n_list, kPageList) << b.page_shift;
-    for(uint32_t rb = threadIdx.x; rb < slots; rb += kR * blockDim.x)
-    {
-      SplatRec rec[kR];
-#pragma unroll
-      for(uint32_t u = 0; u < kR; ++u)
-      {
-        const uint32_t v = rb + u * blockDim.x, r = v & (S - 1u);
-        const uint32_t en = v < slots ? plist[v >> b.page_shift] : 0u, page = en & 0xffffu, P = en >> 16;
-        const uint32_t have = P < e ? S : (P == e ? umin(fill, S) : (P == e + 1u && fill > S ? umin(fill - S, S) : 0u));
-        const bool     in = v < slots && r < have && !TRT_SKIP(b, 64u);
-        rec[u] = in ? b.records[((size_t)page << b.page_shift) + r] : SplatRec{0u, 0u, 0u};   // an empty rectangle
-      }
-      if(TRT_SKIP(b, 32u)) continue;
-      splat_depth_test<kR>(keys, rec);
-    }
+    splat_gather_test(b, keys, slots, [&](uint32_t v) {
+      const uint32_t r = v & (S - 1u), en = v < slots ? plist[v >> b.page_shift] : 0u, page = en & 0xffffu, P = en >> 16;
+      const uint32_t have = P < e ? S : (P == e ? umin(fill, S) : (P == e + 1u && fill > S ? umin(fill - S, S) : 0u));
+      return v < slots && r < have ? b.records[((size_t)page << b.page_shift) + r] : SplatRec{0u, 0u, 0u};
+    });
     __syncthreads();
     if(threadIdx.x == 0)
     {
@@ -740,18 +764,7 @@ __global__ __launch_bounds__(kSplatResolveThreads) void splat_resolve_bins_kerne
   {
     __syncthreads();
     const uint32_t cnt = b.count[bin], off = b.offset[bin];
-    for(uint32_t rb = threadIdx.x; rb < cnt; rb += kR * blockDim.x)
-    {
-      SplatRec rec[kR];
-#pragma unroll
-      for(uint32_t u = 0; u < kR; ++u)
-      {
-        const uint32_t r = rb + u * blockDim.x;
-        rec[u] = r < cnt && !TRT_SKIP(b, 64u) ? b.records[off + r] : SplatRec{0u, 0u, 0u};   // an empty rectangle
-      }
-      if(TRT_SKIP(b, 32u)) continue;
-      splat_depth_test<kR>(keys, rec);
-    }
+    splat_gather_test(b, keys, cnt, [&](uint32_t r) { return r < cnt ? b.records[off + r] : SplatRec{0u, 0u, 0u}; });
     __syncthreads();
     if(threadIdx.x == 0) b.count[bin] = 0u;   // the next call counts from zero
   }
@@ -885,9 +898,9 @@ hipError_t launch_splat(const trt_point* pts, uint64_t n_points, const float* vp
     b.rticket = sc.bin_words + kSplatRTicketWord;
     char* base = static_cast<char*>(sc.records);
     b.records  = reinterpret_cast<SplatRec*>(base);
-    b.proj     = reinterpret_cast<uint2*>(base + pl.rec_bytes);
-    b.table    = pl.mode == kSplatSorted ? reinterpret_cast<uint32_t*>(base + pl.rec_bytes + pl.proj_bytes) : nullptr;
-    b.page_bin = reinterpret_cast<uint32_t*>(base + pl.rec_bytes + pl.proj_bytes + pl.table_bytes);
+    b.proj     = reinterpret_cast<uint2*>(base + pl.proj_at());
+    b.table    = pl.mode == kSplatSorted ? reinterpret_cast<uint32_t*>(base + pl.table_at()) : nullptr;
+    b.page_bin = reinterpret_cast<uint32_t*>(base + pl.pagebin_at());
     b.page_seq = b.page_bin + pl.pagebin_bytes / 2 / sizeof(uint32_t);
     b.page_shift = pl.page_shift; b.pool_pages = pl.pool_pages;
     b.debug_skip = tn.debug_skip;   // always 0 in the release build

@@ -33,7 +33,10 @@ struct SplatPlan {
   uint32_t page_shift;  // paged: a page holds 1 << page_shift records
   uint32_t pool_pages;  // paged: pages behind the bins' first pages
   size_t   rec_bytes, proj_bytes, table_bytes, pagebin_bytes;
-  size_t   total() const { return rec_bytes + proj_bytes + table_bytes + pagebin_bytes; }
+  size_t   proj_at() const { return rec_bytes; }   // byte offsets of the parts behind `records`, in the order above
+  size_t   table_at() const { return proj_at() + proj_bytes; }
+  size_t   pagebin_at() const { return table_at() + table_bytes; }   // page_bin, then page_seq: half of pagebin_bytes each
+  size_t   total() const { return pagebin_at() + pagebin_bytes; }
 };
 struct SplatScratch {
   SplatPlan           plan;
