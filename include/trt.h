@@ -13,6 +13,8 @@
  *                                  BEF/hello_vulkan.cpp:936-958          trt_render*
  *   raygen binding contract        REFL/shaders/raytrace.rgen:30-35,
  *                                  BEF/shaders/raytrace.rgen:10-17       trt_globals/trt_push/outputs
+ *   raygen, the cameras' rays      REFL/shaders/raytrace.rgen:42-48,
+ *   as streams / supersampled      BEF/shaders/raytrace.rgen:21-57       trt_camera_rays* / trt_shade_camera*
  *   traceRayEXT closest hit        REFL/shaders/raytrace.rgen:64-75      trt_trace*
  *   traceRayEXT any hit (shadow)   REFL/shaders/raytrace.rchit:114-131   trt_occluded*
  *   payload loop on your own rays  REFL/shaders/raytrace.rgen:54-87 bounce
@@ -294,6 +296,70 @@ int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push
 int trt_shade_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                   float* rgba_dev, void* stream);
 
+/* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
+/* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal
+ * BEF/shaders/raytrace.rgen:21-57), handed out: as SoA streams that feed trt_trace / trt_occluded / trt_crossings /
+ * trt_shade (trt_camera_rays*), or traced at once into a supersampled frame (trt_shade_camera*).
+ * Frame and band: rows [row_begin, row_end) of a W x H frame, n_px = (row_end - row_begin) * W pixels, `samples` rays per
+ * pixel.  Sample s has the sub-pixel offset (jx_s, jy_s) = (offsets[2s], offsets[2s + 1]), in pixels; offsets == NULL: all
+ * zero.  The 2 * samples host floats are copied before the call returns.
+ * The offset arithmetic, per camera (FP32, one rounding per operation, exactly as written):
+ *   pinhole    px = ((float)x + 0.5f) + jx,  py = ((float)y + 0.5f) + jy;  u = px / (float)W,  v = py / (float)H,  and on
+ *              as the render does (rgen:44-48).
+ *   toroidal   alfa = d_alfa * ((float)x + jx),  beta = d_beta * ((float)y + jy)  with d_alfa = 360 / (float)W and d_beta
+ *              = 360 / (float)H;  cos / sin of radians(alfa + omega) and radians(beta + theta) are evaluated on the host
+ *              (the C library's cosf / sinf, like the render's tables), origin and direction as BEF rgen:56-57.
+ * With jx = jy = 0 both cameras give, bit for bit, the ray trt_render* traces for that pixel (RenderedData.rayOrigin /
+ * rayDir).  Consequence: the regular 2 x 2 pattern on a W x H frame — pinhole offsets -0.25 / +0.25, toroidal offsets
+ * 0 / 0.5 — gives, bit for bit, the pixel-centre rays of the 2W x 2H frame (sample (kx, ky) of pixel (x, y) is pixel
+ * (2x + kx, 2y + ky) there).
+ * Layout (trt_camera_rays*): sample-major and compact — sample s of pixel (x, y) is ray s * n_px + (y - row_begin) * W + x:
+ * what trt_shade reads with the same `samples`, and each sample a ray stream of its own.  Any of the six streams may be
+ * NULL to skip it, not all; each holds samples * n_px floats.
+ * TRT_E_INVALID: NULL ctx, g, pc, out (rgba); all six streams NULL; W or H == 0; row_begin > row_end or row_end > H; an
+ * unknown camera; samples outside 1..TRT_MAX_CAMERA_SAMPLES; an offset that is NaN, infinite or larger than 1 in
+ * magnitude; samples * n_px overflowing uint64_t; a misaligned image.  row_begin == row_end is valid and launches nothing.
+ * A refused call leaves the ctx usable and the outputs unwritten.
+ * trt_camera_rays* executes no test: the counters of the last counted call stay as they are. */
+#define TRT_MAX_CAMERA_SAMPLES 64
+
+typedef struct trt_rays_out {
+  float* ox; float* oy; float* oz; /* origins                                                   */
+  float* dx; float* dy; float* dz; /* directions (pinhole: as the render traces them; toroidal: unit) */
+} trt_rays_out;
+
+/* Host buffers: launches, copies out, synchronises. */
+int trt_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H,
+                    uint32_t row_begin, uint32_t row_end, int camera,
+                    uint32_t samples, const float* offsets, const trt_rays_out* out);
+/* Device-resident streams, asynchronous on `stream`; launch contract of the *_dev entry points below (kernel nodes only,
+ * may be captured).  Toroidal camera: the per-sample trigonometry tables live in scratch of the ctx, keyed by everything
+ * they were built from (the camera's angles, W, H, samples and the offsets, compared as bits) and separate from the
+ * tables of trt_render*; a call whose tables are not on the device yet uploads them, and is refused with TRT_E_INVALID
+ * while `stream` is being captured (make the call eagerly once first).  The ctx holds ONE set of these tables, as it
+ * holds one set for trt_render*: a captured toroidal call replays with whatever the set holds at that time, so between the
+ * capture and its replays make no toroidal trt_camera_rays* / trt_shade_camera* call with another camera frame, frame
+ * shape, sample count or offsets. */
+int trt_camera_rays_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H,
+                        uint32_t row_begin, uint32_t row_end, int camera,
+                        uint32_t samples, const float* offsets, const trt_rays_out* out_dev, void* stream);
+
+/* The supersampled frame: the colour of pixel (x, y) is what trt_camera_rays followed by trt_shade(samples) gives for it,
+ * bit for bit, for every TRT_SOLVE_* and with the torus axes in force — the same loop per ray, the same averaging (acc =
+ * c_0, then acc = acc + c_s in order, one correctly rounded division by (float)samples; one sample: untouched), the
+ * enclosure mask empty at the start of every path — without the rays ever being stored.  With samples == 1 and offsets ==
+ * NULL these are trt_render*'s colours.  rgba is indexed relative to the FULL image as in trt_render_dev (pixel (x, y) at
+ * y * W + x; only the rows of the band are written) and 16-byte aligned.  Stats (trt_enable_stats): those of trt_shade
+ * on the same rays, pixels = samples * n_px.
+ * Host buffers: launches, copies the band out, synchronises. */
+int trt_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                     uint32_t row_begin, uint32_t row_end, int camera,
+                     uint32_t samples, const float* offsets, float* rgba_out);
+/* Device-resident image, asynchronous on `stream`; launch contract and toroidal tables as trt_camera_rays_dev. */
+int trt_shade_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                         uint32_t row_begin, uint32_t row_end, int camera,
+                         uint32_t samples, const float* offsets, float* rgba_dev, void* stream);
+
 /* ---- render: the faithful equivalent of HelloVulkan::raytrace ---------------------- */
 /* rgba_out: W*H*4 floats, row-major, image[y][x] = (hitValue, 1)  (rgen:87); 16-byte aligned.
  * first_hit_out: optional SoA record of the depth-0 hit per pixel, row-major y*W+x. */
@@ -432,7 +498,7 @@ enum { TRT_CLOUD_KEEP_ALL = 0, TRT_CLOUD_MARK_MISSES = 1, TRT_CLOUD_COMPACT = 2 
 int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t n_records, int mode, int append,
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
-/* Counters of the last render, trace, occluded, crossings or shade call made with counting enabled. */
+/* Counters of the last render, trace, occluded, crossings, shade or shade_camera call made with counting enabled. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

@@ -17,6 +17,7 @@ TRT_MAX_TORI = 8
 TRT_MAX_MATERIALS = 8
 TRT_MAX_BATCH = 8
 TRT_MAX_CROSSINGS = 4 * TRT_MAX_TORI   # a line meets a torus at most 4 times
+TRT_MAX_CAMERA_SAMPLES = 64             # samples per pixel of trt_camera_rays / trt_shade_camera
 TRT_CAMERA_PINHOLE, TRT_CAMERA_TOROIDAL = 0, 1
 TRT_CLASSIFY_AUTO, TRT_CLASSIFY_MACRO, TRT_CLASSIFY_TILE = -1, 0, 1
 TRT_SOLVE_F32, TRT_SOLVE_F64, TRT_SOLVE_DK_F32, TRT_SOLVE_DK_F64 = 0, 1, 2, 3
@@ -71,6 +72,12 @@ class trt_rays(C.Structure):
     _fields_ = [("ox", C.c_void_p), ("oy", C.c_void_p), ("oz", C.c_void_p),
                 ("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p),
                 ("n", C.c_uint64)]
+
+
+class trt_rays_out(C.Structure):
+    """Outputs of trt_camera_rays: six writable streams, any of them null to skip it (the ray count is implied by the call)."""
+    _fields_ = [("ox", C.c_void_p), ("oy", C.c_void_p), ("oz", C.c_void_p),
+                ("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p)]
 
 
 class trt_hits(C.Structure):
@@ -198,6 +205,25 @@ def rays_struct(arrays, n):
         setattr(r, k, a if isinstance(a, int) else a.ctypes.data)
     r.n = int(n)
     return r
+
+
+def rays_out_struct(arrays):
+    """arrays: six numpy arrays | int addresses | None (0: stream not wanted), in RAY_FIELDS order."""
+    r = trt_rays_out()
+    for k, a in zip(RAY_FIELDS, arrays):
+        setattr(r, k, None if a is None or (isinstance(a, int) and a == 0) else (a if isinstance(a, int) else a.ctypes.data))
+    return r
+
+
+def camera_offsets(offsets, samples):
+    """The sub-pixel offsets of trt_camera_rays / trt_shade_camera as the C ABI takes them: None (all zero) or a
+    contiguous float32 array of 2 * samples values (jx_0, jy_0, jx_1, ...) from anything shaped (samples, 2)."""
+    if offsets is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(offsets, np.float32).reshape(-1))
+    if a.size != 2 * int(samples):
+        raise ValueError(f"{a.size} offset values for {samples} samples (2 per sample)")
+    return a
 
 
 def hits_struct(arrays):

@@ -44,6 +44,7 @@ enum Buf {
   kBufTmax,                     // trt_occluded: the per-ray bounds
   kBufGraphVisible,
   kBufToro = kBufGraphVisible,  // the toroidal camera's trigonometry tables
+  kBufToroSamples,              // trt_camera_rays, trt_shade_camera: the toroidal camera's tables per sub-pixel sample
   kBufTiles,                    // LIVE + CLEAR tile lists of the listed and the persistent kernel
   kBufCost,                     // cost feedback: one word per macro tile (zero = no history)
   kBufKeys,                     // depth|index keys of trt_splat_dev (one-pass form)
@@ -96,7 +97,8 @@ struct trt_ctx {
   // Events instead of remembered stream handles (the caller may destroy a stream between calls):
   hipEvent_t    ev_toro  = nullptr;   // the last upload of the toroidal tables has read its host staging
   hipEvent_t    ev_stats = nullptr;   // the last counted launch is done
-  bool          ev_toro_set = false, ev_stats_set = false;
+  hipEvent_t    ev_toro_samples = nullptr;   // the same for the per-sample tables of trt_camera_rays / trt_shade_camera
+  bool          ev_toro_set = false, ev_stats_set = false, ev_toro_samples_set = false;
 
   Tuning        tn;                       // launch-shape knobs: defaults, or the environment ONCE in a -DTRT_TUNING build
   unsigned long long* d_stats = nullptr;  // [kStatWords]: the query counters of a counted launch (StatWord, trt_kernels.hpp)
@@ -107,6 +109,18 @@ struct trt_ctx {
   float* h_toro     = nullptr;
   size_t h_toro_cap = 0;
   struct { uint32_t W = 0, H = 0; float omega = 0, theta = 0; bool valid = false; } toro_key;
+
+  // per-sample toroidal tables (buf[kBufToroSamples]): a staging area and a key of their own, so that the render's
+  // tables and toro_key never see a trt_camera_rays / trt_shade_camera call.  Everything the tables are built from,
+  // compared as bits: the two angles, the frame shape, the sample count and the offsets.
+  float* h_toro_samples     = nullptr;
+  size_t h_toro_samples_cap = 0;
+  struct ToroSamplesKey {
+    uint32_t W, H, samples;
+    float    omega, theta;
+    float    offsets[2 * TRT_MAX_CAMERA_SAMPLES];
+  } toro_samples_key;
+  bool toro_samples_valid = false;
 
   DevBuf buf[kBufCount];        // grow-only device scratch (Buf), freed in trt_destroy
   trt_ctx() { for(int k = kBufGraphVisible; k < kBufCount; ++k) buf[k].graph_visible = true; }
@@ -490,10 +504,9 @@ constexpr float kRad2Deg = 57.29577951308232f;     // GLSL degrees()
 
 // Per-frame part of the toroidal camera (BEF/shaders/raytrace.rgen:36-53) and the
 // per-column / per-row trigonometry of :25-28,56-57, evaluated once on the host.
-int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t W, uint32_t H,
-               hipStream_t stream, ToroCam& out, bool must_match = false)
+// The per-frame part: the eye and the two angles (degrees) the tables add to alfa and beta.
+void toro_frame(const trt_globals& g, const trt_push& pc, float eye[3], float& omega_out, float& theta_out)
 {
-  float eye[3];
   mat4_origin(g.viewInverse, eye);                                           // :36
   float tx = g.center[0] - eye[0], ty, tz = g.center[2] - eye[2];            // :38
   float il    = 1.0f / std::sqrt(std::fma(tz, tz, tx * tx));                 // :39
@@ -510,6 +523,15 @@ int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t 
     theta = std::acos(tx * il) * kRad2Deg;                                   // :49
     if(ty < 0.0f) theta = 360.0f - theta;                                    // :50-52
   }
+  omega_out = omega;
+  theta_out = theta;
+}
+
+int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t W, uint32_t H,
+               hipStream_t stream, ToroCam& out, bool must_match = false)
+{
+  float eye[3], omega, theta;
+  toro_frame(g, pc, eye, omega, theta);
   const size_t n = 2 * ((size_t)W + H);
   if(int rc = grow(ctx, ctx->buf[kBufToro], n * sizeof(float), stream)) return rc;
   auto& key = ctx->toro_key;
@@ -565,6 +587,77 @@ int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t 
   return TRT_OK;
 }
 
+// The toroidal tables of trt_camera_rays* / trt_shade_camera*, one set per sample: sample s at s * 2 * (W + H) floats,
+// each set laid out like build_toro's (cos_a[W], sin_a[W], cos_b[H], sin_b[H]) from alfa = d_alfa·((float)x + jx_s) and
+// beta = d_beta·((float)y + jy_s) — with zero offsets build_toro's values bit for bit ((float)x + 0.0f is (float)x).
+// build_toro's discipline with a buffer, a pinned staging area, an event and a key of its own: the render's tables and
+// toro_key are not touched.  `offsets`: 2 * samples floats (jx_s, jy_s), validated.  Fills c.toro and c.toro_stride.
+int build_toro_samples(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, const float* offsets, hipStream_t stream, CameraArgs& c)
+{
+  const uint32_t W = c.W, H = c.H, samples = c.samples;
+  trt_ctx::ToroSamplesKey key;
+  std::memset(&key, 0, sizeof key);
+  float eye[3];
+  toro_frame(g, pc, eye, key.omega, key.theta);
+  key.W = W; key.H = H; key.samples = samples;
+  std::memcpy(key.offsets, offsets, 2 * samples * sizeof(float));
+  const size_t per = 2 * ((size_t)W + H), n = per * samples;
+  if(per > 0xffffffffull) return fail(ctx, TRT_E_INVALID, "toroidal camera: W + H = %zu does not fit the tables' 32-bit stride", per / 2);
+  if(int rc = grow(ctx, ctx->buf[kBufToroSamples], n * sizeof(float), stream)) return rc;
+  const bool same = ctx->toro_samples_valid && !std::memcmp(&ctx->toro_samples_key, &key, sizeof key);
+  if(!same && capturing(stream))
+    return fail(ctx, TRT_E_INVALID, "toroidal camera: the per-sample trigonometry tables of this (W, H, centre, rho, samples, offsets) "
+                "call are not on the device yet and cannot be uploaded while the stream is being captured into a hipGraph (a replay "
+                "would copy whatever the staging buffer holds later): make the call eagerly once before capturing it");
+  if(!same)
+  {
+    ctx->toro_samples_valid = false;
+    if(ctx->h_toro_samples_cap < n)
+    {
+      if(ctx->h_toro_samples) TRT_HIP(ctx, hipHostFree(ctx->h_toro_samples));
+      ctx->h_toro_samples = nullptr;
+      ctx->h_toro_samples_cap = 0;
+      TRT_HIP(ctx, hipHostMalloc((void**)&ctx->h_toro_samples, n * sizeof(float), hipHostMallocDefault));
+      ctx->h_toro_samples_cap = n;
+    }
+    else if(ctx->ev_toro_samples_set)
+      TRT_HIP(ctx, hipEventSynchronize(ctx->ev_toro_samples));  // an earlier upload may still be reading it
+    const float d_alfa = 360.0f / (float)W, d_beta = 360.0f / (float)H;      // :25-26
+    for(uint32_t s = 0; s < samples; ++s)
+    {
+      float* ca = ctx->h_toro_samples + s * per, *sa = ca + W, *cb = sa + W, *sb = cb + H;
+      const float jx = offsets[2 * s], jy = offsets[2 * s + 1];
+      for(uint32_t x = 0; x < W; ++x)
+      {
+        const float fx = (float)x + jx;
+        const float aw = (d_alfa * fx + key.omega) * kDeg2Rad;               // :27,56
+        ca[x] = std::cos(aw);
+        sa[x] = std::sin(aw);
+      }
+      for(uint32_t y = 0; y < H; ++y)
+      {
+        const float fy = (float)y + jy;
+        const float bt = (d_beta * fy + key.theta) * kDeg2Rad;               // :28,57
+        cb[y] = std::cos(bt);
+        sb[y] = std::sin(bt);
+      }
+    }
+    TRT_HIP(ctx, hipMemcpyAsync(ctx->buf[kBufToroSamples].p, ctx->h_toro_samples, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    TRT_HIP(ctx, hipEventRecord(ctx->ev_toro_samples, stream));
+    ctx->ev_toro_samples_set = true;
+    ctx->toro_samples_key = key;
+    ctx->toro_samples_valid = true;
+  }
+  c.toro.eye[0] = eye[0]; c.toro.eye[1] = eye[1]; c.toro.eye[2] = eye[2];
+  c.toro.rho   = pc.rho;
+  c.toro.cos_a = (const float*)ctx->buf[kBufToroSamples].p;
+  c.toro.sin_a = c.toro.cos_a + W;
+  c.toro.cos_b = c.toro.sin_a + W;
+  c.toro.sin_b = c.toro.cos_b + H;
+  c.toro_stride = (uint32_t)per;
+  return TRT_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -599,6 +692,7 @@ extern "C" int trt_create(int device, trt_ctx** out)
      || (e = hipMemset(ctx->d_stats, 0, kStatWords * sizeof(unsigned long long))) != hipSuccess
      || (e = hipMemset(ctx->d_queue, 0, kQueueWords * sizeof(unsigned int))) != hipSuccess
      || (e = hipEventCreateWithFlags(&ctx->ev_toro, hipEventDisableTiming)) != hipSuccess
+     || (e = hipEventCreateWithFlags(&ctx->ev_toro_samples, hipEventDisableTiming)) != hipSuccess
      || (e = hipEventCreateWithFlags(&ctx->ev_stats, hipEventDisableTiming)) != hipSuccess)
   {
     fail(nullptr, TRT_E_HIP, "trt_create: %s", hipGetErrorString(e));
@@ -616,10 +710,12 @@ extern "C" void trt_destroy(trt_ctx* ctx)
   if(!ctx) return;
   (void)hipSetDevice(ctx->device);
   if(ctx->ev_toro) (void)hipEventDestroy(ctx->ev_toro);
+  if(ctx->ev_toro_samples) (void)hipEventDestroy(ctx->ev_toro_samples);
   if(ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
   if(ctx->d_stats) (void)hipFree(ctx->d_stats);
   if(ctx->d_queue) (void)hipFree(ctx->d_queue);
   if(ctx->h_toro) (void)hipHostFree(ctx->h_toro);
+  if(ctx->h_toro_samples) (void)hipHostFree(ctx->h_toro_samples);
   for(DevBuf& b : ctx->buf)
     if(b.p) (void)hipFree(b.p);
   for(void* q : ctx->retired) (void)hipFree(q);
@@ -767,7 +863,7 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
   return TRT_OK;
 }
 
-// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev), after the entry
+// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev), after the entry
 // point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
@@ -946,6 +1042,129 @@ extern "C" int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, con
   if(int rc = stage_rays(ctx, in, din)) return rc;
   if(int rc = stage_outs(ctx, &image, 1)) return rc;
   if(int rc = trt_shade_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// camera rays: the two cameras as ray streams, and the supersampled frame
+// ------------------------------------------------------------------------------------------
+// What trt_camera_rays* and trt_shade_camera* (`who`) share: the checks of include/trt.h on the frame, the band, the
+// camera and the samples, and the CameraArgs they describe — all but the toroidal tables (camera_tables()).
+static int check_camera(trt_ctx* ctx, const char* who, const trt_globals* g, const trt_push* pc, const void* out, uint32_t W, uint32_t H,
+                        uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets, CameraArgs& c)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(!g || !pc || !out) return fail(ctx, TRT_E_INVALID, "%s: NULL globals, push constants or output", who);
+  if(W == 0 || H == 0 || row_begin > row_end || row_end > H)
+    return fail(ctx, TRT_E_INVALID, "%s: bad size/rows W=%u H=%u rows=[%u,%u)", who, W, H, row_begin, row_end);
+  if(camera != TRT_CAMERA_PINHOLE && camera != TRT_CAMERA_TOROIDAL) return fail(ctx, TRT_E_INVALID, "%s: unknown camera %d", who, camera);
+  if(samples < 1 || samples > TRT_MAX_CAMERA_SAMPLES)
+    return fail(ctx, TRT_E_INVALID, "%s: samples = %u, must be 1..%d (TRT_MAX_CAMERA_SAMPLES)", who, samples, TRT_MAX_CAMERA_SAMPLES);
+  std::memset(&c, 0, sizeof c);
+  for(uint32_t s = 0; s < samples && offsets; ++s)
+  {
+    c.jx[s] = offsets[2 * s];
+    c.jy[s] = offsets[2 * s + 1];
+    if(!(std::fabs(c.jx[s]) <= 1.0f) || !(std::fabs(c.jy[s]) <= 1.0f))   // (NaN fails the comparison)
+      return fail(ctx, TRT_E_INVALID, "%s: the offset of sample %u, (%g, %g), is not a finite number of at most 1 in magnitude", who, s,
+                  (double)c.jx[s], (double)c.jy[s]);
+  }
+  c.n_px = (uint64_t)(row_end - row_begin) * W;
+  if(c.n_px > UINT64_MAX / samples) return fail(ctx, TRT_E_INVALID, "%s: samples * pixels of the band overflows 64 bits", who);
+  c.g = *g;
+  c.W = W; c.H = H; c.row_begin = row_begin; c.row_end = row_end;
+  c.camera  = camera;
+  c.samples = samples;
+  return TRT_OK;
+}
+
+// The toroidal camera's share of a checked CameraArgs: the per-sample tables, on the device before the launch on `st`.
+static int camera_tables(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, hipStream_t st, CameraArgs& c)
+{
+  if(c.camera != TRT_CAMERA_TOROIDAL || c.n_px == 0) return TRT_OK;
+  float offsets[2 * TRT_MAX_CAMERA_SAMPLES];
+  for(uint32_t s = 0; s < c.samples; ++s) { offsets[2 * s] = c.jx[s]; offsets[2 * s + 1] = c.jy[s]; }
+  return build_toro_samples(ctx, *g, *pc, offsets, st, c);
+}
+
+static int check_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
+                             uint32_t row_end, int camera, uint32_t samples, const float* offsets, const trt_rays_out* out, CameraArgs& c)
+{
+  if(int rc = check_camera(ctx, "trt_camera_rays", g, pc, out, W, H, row_begin, row_end, camera, samples, offsets, c)) return rc;
+  if(!out->ox && !out->oy && !out->oz && !out->dx && !out->dy && !out->dz)
+    return fail(ctx, TRT_E_INVALID, "trt_camera_rays: no output (all six streams NULL)");
+  return TRT_OK;
+}
+extern "C" int trt_camera_rays_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
+                                   uint32_t row_end, int camera, uint32_t samples, const float* offsets, const trt_rays_out* out,
+                                   void* stream)
+{
+  CameraRaysArgs a;
+  if(int rc = check_camera_rays(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, out, a.cam)) return rc;
+  a.out = *out;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if(int rc = camera_tables(ctx, g, pc, st, a.cam)) return rc;
+  TRT_HIP(ctx, launch_camera_rays(a, ctx->tn, st));   // no test is executed: no counted bracket, the stats stay
+  return TRT_OK;
+}
+
+// Host buffers: the six streams through buf[kBufOut] .. [kBufOut + 5].
+extern "C" int trt_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
+                               uint32_t row_end, int camera, uint32_t samples, const float* offsets, const trt_rays_out* out)
+{
+  CameraArgs c;
+  if(int rc = check_camera_rays(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, out, c)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(c.n_px == 0) return TRT_OK;   // validated; nothing to launch or to write
+  if(c.n_px * samples > SIZE_MAX / sizeof(float)) return fail(ctx, TRT_E_NOMEM, "trt_camera_rays: samples * pixels floats do not fit the address space");
+  const size_t bytes = (size_t)(c.n_px * samples) * sizeof(float);
+  float* const host[6] = {out->ox, out->oy, out->oz, out->dx, out->dy, out->dz};
+  StagedOut outs[6];
+  for(int k = 0; k < 6; ++k) outs[k] = {host[k], bytes, kBufOut + k, nullptr};
+  if(int rc = stage_outs(ctx, outs, 6)) return rc;
+  const trt_rays_out dout = {(float*)outs[0].dev, (float*)outs[1].dev, (float*)outs[2].dev, (float*)outs[3].dev, (float*)outs[4].dev, (float*)outs[5].dev};
+  if(int rc = trt_camera_rays_dev(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, &dout, nullptr)) return rc;
+  return fetch_outs(ctx, outs, 6);
+}
+
+static int check_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
+                              uint32_t row_end, int camera, uint32_t samples, const float* offsets, const float* rgba, CameraArgs& c)
+{
+  if(int rc = check_camera(ctx, "trt_shade_camera", g, pc, rgba, W, H, row_begin, row_end, camera, samples, offsets, c)) return rc;
+  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "trt_shade_camera: the rgba image must be 16-byte aligned (it is written as float4)");
+  return TRT_OK;
+}
+extern "C" int trt_shade_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                                    uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                                    float* rgba, void* stream)
+{
+  ShadeCameraArgs a;
+  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba, a.cam)) return rc;
+  a.pc   = *pc;
+  a.rgba = rgba;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(int rc = camera_tables(ctx, g, pc, (hipStream_t)stream, a.cam)) return rc;
+  return ray_query(ctx, scene, stream, a.cam.n_px * samples, a, launch_shade_camera);
+}
+
+// Host buffers: the rows of the band through buf[kBufRgba]; the kernel indexes the full image, so it is handed the
+// staging block's address less the rows before the band (include/trt.h, trt_render_dev: "buffers offset by -row_begin*W").
+extern "C" int trt_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                                uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                                float* rgba_out)
+{
+  CameraArgs c;
+  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, c)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(c.n_px == 0)   // validates the scene, launches and writes nothing
+    return trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, nullptr);
+  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "trt_shade_camera: the band does not fit the address space");
+  const size_t before = (size_t)row_begin * W * 4;   // floats of the image in front of the band
+  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
+  if(int rc = trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
   return fetch_outs(ctx, &image, 1);
 }
 

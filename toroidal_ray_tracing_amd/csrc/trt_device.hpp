@@ -1024,8 +1024,10 @@ struct ToroCam {
   const float* sin_b;  // [H]
 };
 
-__device__ __forceinline__ void raygen(const trt_globals& g, const ToroCam& tc, uint32_t W, uint32_t H,
-                                       int camera, uint32_t x, uint32_t y, v3& origin, v3& dir)
+// The ray through film position (px, py) in pixels (pinhole) / of column x and row y of the tables (toroidal): the body
+// the two forms below share, so that a pixel centre and a sub-pixel sample run the same instructions.
+__device__ __forceinline__ void raygen_at(const trt_globals& g, const ToroCam& tc, uint32_t W, uint32_t H,
+                                          int camera, uint32_t x, uint32_t y, float px, float py, v3& origin, v3& dir)
 {
   if(camera == TRT_CAMERA_TOROIDAL)
   {
@@ -1038,13 +1040,29 @@ __device__ __forceinline__ void raygen(const trt_globals& g, const ToroCam& tc, 
     return;
   }
   // pinhole, REFL/shaders/raytrace.rgen:42-48
-  const float px = (float)x + 0.5f, py = (float)y + 0.5f;
   const float u = px / (float)W, v = py / (float)H;
   const float dx = u * 2.0f - 1.0f, dy = v * 2.0f - 1.0f;
   origin       = mat4_mul(g.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f);
   const v3 tgt = mat4_mul(g.projInverse, dx, dy, 1.0f, 1.0f);
   const v3 tn  = normalize3(tgt);
   dir          = mat4_mul(g.viewInverse, tn.x, tn.y, tn.z, 0.0f);
+}
+
+// The primary ray of pixel (x, y): through the pixel centre.
+__device__ __forceinline__ void raygen(const trt_globals& g, const ToroCam& tc, uint32_t W, uint32_t H,
+                                       int camera, uint32_t x, uint32_t y, v3& origin, v3& dir)
+{
+  raygen_at(g, tc, W, H, camera, x, y, (float)x + 0.5f, (float)y + 0.5f, origin, dir);
+}
+
+// The ray of a sub-pixel sample (trt_camera_rays*, trt_shade_camera*; include/trt.h states the arithmetic).  Pinhole: the
+// film position is the pixel centre plus (jx, jy).  Toroidal: the offset is in the tables — `tc` holds the tables of
+// THIS sample, built on the host from d_alfa·((float)x + jx) and d_beta·((float)y + jy) — and jx, jy are not read.
+// With jx = jy = 0 (and the render's tables) this is raygen(), bit for bit: t + 0.0f == t for every t that is not -0.
+__device__ __forceinline__ void raygen_offset(const trt_globals& g, const ToroCam& tc, uint32_t W, uint32_t H,
+                                              int camera, uint32_t x, uint32_t y, float jx, float jy, v3& origin, v3& dir)
+{
+  raygen_at(g, tc, W, H, camera, x, y, ((float)x + 0.5f) + jx, ((float)y + 0.5f) + jy, origin, dir);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -130,7 +130,7 @@ struct Tuning {
   uint64_t persist_blocks     = 0;    // TRT_PERSIST_BLOCKS   (0 = default)
   uint64_t listed_blocks      = 0;    // TRT_LISTED_BLOCKS
   int      static_tile        = 8;    // TRT_TILE
-  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel)
+  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, shade_camera_kernel)
   int      occluded_walk      = kOccludedWalk;   // TRT_OCCLUDED_WALK: kWalkNested (0) | kWalkTable (1), occluded_kernel only
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
   uint64_t splat_blocks_per_cu = 0;   // TRT_SPLAT_BLOCKS_PER_CU
@@ -178,6 +178,35 @@ struct ShadeArgs {
   unsigned long long* stats;
 };
 
+// trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
+// per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
+// sample-major layout ShadeArgs reads.  Pinhole: the offsets (jx[s], jy[s]) travel here, in the kernel-argument segment.
+// Toroidal: they are in the tables — toro points at the tables of sample 0 (cos_a[W], sin_a[W], cos_b[H], sin_b[H] behind
+// one another), those of sample s start toro_stride floats further on for each s; jx, jy are not read.
+struct CameraArgs {
+  trt_globals g;        // GlobalUniforms, by value in the kernel-argument segment
+  ToroCam     toro;
+  uint32_t    toro_stride;   // 2 * (W + H)
+  uint32_t    W, H, row_begin, row_end;
+  int         camera;
+  uint32_t    samples;       // 1 .. TRT_MAX_CAMERA_SAMPLES
+  uint64_t    n_px;          // (row_end - row_begin) * W
+  float       jx[TRT_MAX_CAMERA_SAMPLES], jy[TRT_MAX_CAMERA_SAMPLES];
+};
+struct CameraRaysArgs {
+  CameraArgs   cam;
+  trt_rays_out out;          // six streams of samples * n_px floats, each optional
+};
+// Tiles of shade_camera_kernel along one side of a band of n >= 0 pixels (no wrap-around up to n = 2^32 - 1, which tile_count has).
+__host__ __device__ constexpr uint32_t camera_tiles(uint32_t n) { return n ? (n - 1) / kTile + 1 : 0; }
+// trt_shade_camera*: ShadeArgs with the rays from CameraArgs; rgba is the FULL W x H image (pixel (x, y) at y * W + x).
+struct ShadeCameraArgs {
+  CameraArgs          cam;
+  trt_push            pc;
+  float*              rgba;
+  unsigned long long* stats;
+};
+
 enum RenderVariant { kRenderStatic = 0, kRenderPersistent = 1, kRenderListed = 2 };
 constexpr int kPersistentBlocksPerCU = 16;  // 4× the resident 4 blocks/CU: the dispatcher evens out the tile costs
 
@@ -187,6 +216,8 @@ hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& t
 hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

@@ -1,10 +1,14 @@
-// trt_rays.hip — the ray-stream kernels of the toroidal ray tracer (trt_trace*, trt_occluded*, trt_crossings*, trt_shade*), gfx950.
+// trt_rays.hip — the ray-stream kernels of the toroidal ray tracer (trt_trace*, trt_occluded*, trt_crossings*, trt_shade*,
+// trt_camera_rays*, trt_shade_camera*), gfx950.
 //
 //   trace_kernel       trace(rays_in → hits_out): SoA rays in, closest hit out.
 //   occluded_kernel    occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
 //   crossings_kernel   crossings(rays_in → slots_out): SoA rays in, every surface crossing out, in order, slot-major.
 //   shade_kernel       shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour (trt_render.hpp) out, samples averaged.
-//   stream_grid, launch_trace, launch_occluded, launch_crossings, launch_shade   their grid and launch wrappers.
+//   camera_rays_kernel   camera(frame → rays_out): the two cameras' rays with sub-pixel offsets, SoA and sample-major, out.
+//   shade_camera_kernel  shade_kernel with the rays made in registers by the camera: the supersampled frame.
+//   stream_grid, launch_trace, launch_occluded, launch_crossings, launch_shade, launch_camera_rays, launch_shade_camera
+//                        their grid and launch wrappers.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
 //
 // One lane = one ray; the scene is staged into LDS once per block.  Compiled with -ffp-contract=off (see trt_device.hpp
@@ -217,11 +221,146 @@ __global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const Sh
 }
 
 // ------------------------------------------------------------------------------------------
+// camera rays: the cameras of the render as ray streams, and shade_kernel fed by them
+// ------------------------------------------------------------------------------------------
+// Pixel i of the band → column x and image row y (camera_rays_kernel).  Linear rows, the simplest mapping: lane k of a
+// wave is pixel base + k, so every stream store is contiguous over the wave.
+// One division per pixel — by 32-bit arithmetic as long as the band has fewer than 2^32 pixels (kernel-uniform).
+__device__ __forceinline__ void camera_pixel(const CameraArgs& c, uint64_t i, uint32_t& x, uint32_t& y)
+{
+  if(c.n_px <= 0xffffffffull)
+  {
+    const uint32_t i32 = (uint32_t)i, ly = i32 / c.W;
+    x = i32 - ly * c.W;
+    y = c.row_begin + ly;
+  }
+  else
+  {
+    const uint64_t ly = i / c.W;
+    x = (uint32_t)(i - ly * c.W);
+    y = c.row_begin + (uint32_t)ly;
+  }
+}
+// The camera of sample s: the toroidal tables of that sample (CameraArgs::toro_stride floats per sample).
+__device__ __forceinline__ ToroCam camera_sample(const CameraArgs& c, uint32_t s)
+{
+  ToroCam t = c.toro;
+  const size_t off = (size_t)s * c.toro_stride;
+  t.cos_a += off; t.sin_a += off; t.cos_b += off; t.sin_b += off;
+  return t;
+}
+
+// One lane per (sample, pixel): blockIdx.y is the sample — block-uniform, so its offsets and table pointers are scalar
+// loads from the kernel arguments and the pinhole origin is computed from scalars alone — blockIdx.x and the grid-stride
+// loop run over the pixels of the band.  No loads but the four table entries of the toroidal camera (W + H floats per
+// sample: cache-resident), 24 B of stores per ray, each stream 256 B contiguous per wave.
+__global__ __launch_bounds__(256) void camera_rays_kernel(const CameraRaysArgs a)
+{
+  const CameraArgs& c = a.cam;
+  const uint32_t s  = blockIdx.y;
+  const ToroCam  tc = camera_sample(c, s);
+  const float    jx = c.jx[s], jy = c.jy[s];
+  const gptr<float> ox = (gptr<float>)a.out.ox, oy = (gptr<float>)a.out.oy, oz = (gptr<float>)a.out.oz;
+  const gptr<float> dx = (gptr<float>)a.out.dx, dy = (gptr<float>)a.out.dy, dz = (gptr<float>)a.out.dz;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < c.n_px; i += stride)
+  {
+    uint32_t x, y;
+    camera_pixel(c, i, x, y);
+    v3 o, d;
+    raygen_offset(c.g, tc, c.W, c.H, c.camera, x, y, jx, jy, o, d);
+    const uint64_t r = (uint64_t)s * c.n_px + i;
+    if(ox) ox[r] = o.x;
+    if(oy) oy[r] = o.y;
+    if(oz) oz[r] = o.z;
+    if(dx) dx[r] = d.x;
+    if(dy) dy[r] = d.y;
+    if(dz) dz[r] = d.z;
+  }
+}
+
+// shade_kernel's loop with the ray of (sample, pixel) produced in registers instead of loaded: one lane owns one pixel of
+// the band and walks its samples in order — the same bounce_loop() call, the same accumulation and division, so the
+// image is, bit for bit, camera_rays_kernel's rays put through shade_kernel.
+// Lane ↔ pixel: a wave owns one 8×8 tile of the band (kTile, the render's tile: lane = yl·8 + xl), not 64 pixels of a
+// row — the paths of a wave stay together where the image is coherent, and a silhouette cuts through far fewer waves
+// (DESIGN.md §5 has the measurement against linear rows).  The grid-stride loop runs on the wave's tile index, a scalar;
+// lanes beyond the right or lower edge of a ragged tile idle.  No output bit depends on the mapping.
+// The camera (CameraArgs) is staged into LDS beside the scene: left in the kernel-argument segment the matrices sit in
+// SGPRs across the bounce loop — the default-solver kernels then spill 70 of them to VGPR lanes and report an 84-byte
+// stack frame — and from LDS raygen reads them where it runs, as the render kernels read their RenderArgs (stage_args,
+// trt_render.hpp).  The sample index is wave-uniform: offsets and table pointers are broadcast reads.
+__device__ __forceinline__ void stage_camera(CameraArgs* lds, const CameraArgs& arg)   // no barrier: the caller's stage_scene has one
+{
+  static_assert(sizeof(CameraArgs) % 4 == 0 && sizeof(CameraArgs) / 4 <= 256, "one dword per thread of a 256-thread block");
+  if(threadIdx.x < sizeof(CameraArgs) / 4)
+    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&arg)[threadIdx.x];
+}
+
+template <class Real, bool ALT, bool ORIENT = false>
+__global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, const ShadeCameraArgs a)
+{
+  __shared__ SceneK     S;
+  __shared__ CameraArgs cam;
+  stage_camera(&cam, a.cam);
+  stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
+
+  const CameraArgs& c = cam;
+  const uint32_t rows = c.row_end - c.row_begin, tiles_x = camera_tiles(c.W);
+  const uint64_t n_tiles = (uint64_t)tiles_x * camera_tiles(rows);
+  const uint32_t lane = threadIdx.x & 63u, xl = lane % kTile, yl = lane / kTile;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  static_assert(kTile * kTile == 64, "one tile per wave");
+  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * 4u;
+  for(uint64_t t = (uint64_t)blockIdx.x * 4u + wave; t < n_tiles; t += stride)
+  {
+    uint32_t tx, ty;
+    if(n_tiles <= 0xffffffffull)   // (kernel-uniform) one 32-bit division per tile
+    {
+      ty = (uint32_t)t / tiles_x;
+      tx = (uint32_t)t - ty * tiles_x;
+    }
+    else
+    {
+      ty = (uint32_t)(t / tiles_x);
+      tx = (uint32_t)(t - (uint64_t)ty * tiles_x);
+    }
+    const uint32_t x = tx * kTile + xl, ly = ty * kTile + yl, y = c.row_begin + ly;
+    if(x >= c.W || ly >= rows)
+      continue;
+    v3 acc = {0.0f, 0.0f, 0.0f};
+    for(uint32_t s = 0; s < c.samples; ++s)
+    {
+      // The camera is read through a pointer hipcc cannot see through, once per sample: read through `cam` itself the
+      // matrices are loop-invariant, get hoisted and stay in ~50 VGPRs across the bounce loop.
+      const CameraArgs* cs = &cam;
+      asm volatile("" : "+v"(cs));
+      v3 o, d;
+      raygen_offset(cs->g, camera_sample(*cs, s), cs->W, cs->H, cs->camera, x, y, cs->jx[s], cs->jy[s], o, d);
+      const v3 col = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
+                                                    n_primary, n_bounce, n_shadow, wc);
+      if(s == 0u) acc = col;
+      else acc = {acc.x + col.x, acc.y + col.y, acc.z + col.z};
+    }
+    if(c.samples != 1u)
+    {
+      const float k = (float)c.samples;
+      acc = {acc.x / k, acc.y / k, acc.z / k};
+    }
+    st4(a.rgba + 4 * ((size_t)y * c.W + x), make_float4(acc.x, acc.y, acc.z, 1.0f));   // rgen:87
+  }
+  if(a.stats)
+    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+}
+
+// ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 namespace {
-// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel; grid-stride loops):
-// one block per 256 rays (shade_kernel: outputs), at most 4096 blocks (TRT_TRACE_BLOCKS).
+// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels;
+// grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels), at most 4096 blocks (TRT_TRACE_BLOCKS).
 uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
   const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;
@@ -287,6 +426,29 @@ hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& t
   const uint32_t grid = stream_grid(a.n_out, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     hipLaunchKernelGGL((shade_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+    return hipGetLastError();
+  });
+}
+
+// One block per 256 pixels of the band (at most 4096: grid-stride) times one grid row per sample; no scene, no solver.
+hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.cam.n_px == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.cam.n_px, tn);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(grid, a.cam.samples), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// One wave per 8×8 tile of the band, four to a block; every solver, like launch_shade.
+hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.cam.n_px == 0)
+    return hipSuccess;
+  const uint64_t n_tiles = (uint64_t)camera_tiles(a.cam.W) * camera_tiles(a.cam.row_end - a.cam.row_begin);
+  const uint32_t grid = stream_grid(n_tiles * 64u, tn);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    hipLaunchKernelGGL((shade_camera_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();
   });
 }

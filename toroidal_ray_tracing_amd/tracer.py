@@ -209,6 +209,55 @@ class Tracer:
         self._check(self._L.trt_shade_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
                                           _vp(rgba_ptr), _vp(stream)))
 
+    # -- camera rays: the two cameras as ray streams, and the supersampled frame ------------
+    @staticmethod
+    def _offsets(offsets, samples):
+        a = abi.camera_offsets(offsets, samples)
+        return a, (None if a is None else a.ctypes.data_as(abi.f32p))
+
+    def camera_rays(self, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None):
+        """The rays of a camera of trt_render* for the rows ``rows`` = (begin, end) of a W x H frame (None: all of it),
+        ``samples`` per pixel with the sub-pixel offsets ``offsets`` ((samples, 2) values (jx, jy) in pixels; None: the
+        pixel centres / table entries of the render), on host arrays (trt_camera_rays).  Returns (o, d) of shape (n, 3),
+        n = samples * rows * W, sample-major: sample s of pixel (x, y) is ray s * n_px + (y - begin) * W + x — what
+        ``shade(..., samples=samples)`` and the other ray queries take."""
+        r0, r1 = (0, H) if rows is None else rows
+        samples = int(samples)
+        n = max(samples, 0) * max(int(r1) - int(r0), 0) * int(W)
+        soa = np.empty((6, n), np.float32)
+        out = abi.rays_out_struct(list(soa))
+        keep, off = self._offsets(offsets, samples)
+        self._check(self._L.trt_camera_rays(self._h, C.byref(g), C.byref(pc), W, H, r0, r1, camera, samples, off, C.byref(out)))
+        return np.ascontiguousarray(soa[:3].T), np.ascontiguousarray(soa[3:].T)
+
+    def camera_rays_dev(self, g, pc, W, H, out_ptrs, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None, stream=0):
+        """Device pointers (ints): out_ptrs = 6 addresses (ox, oy, oz, dx, dy, dz; 0 = stream not wanted) of
+        samples * rows * W floats each, sample-major.  Asynchronous on ``stream``."""
+        r0, r1 = (0, H) if rows is None else rows
+        out = abi.rays_out_struct([int(p) for p in out_ptrs])
+        keep, off = self._offsets(offsets, samples)
+        self._check(self._L.trt_camera_rays_dev(self._h, C.byref(g), C.byref(pc), W, H, r0, r1, camera, int(samples), off,
+                                                C.byref(out), _vp(stream)))
+
+    def shade_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None):
+        """The supersampled frame (trt_shade_camera) on a host buffer: per pixel the colours of its ``samples`` camera rays
+        (offsets as in camera_rays) averaged as ``shade`` averages them.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
+        r0, r1 = (0, H) if rows is None else rows
+        rgba = np.zeros((H, W, 4), np.float32)
+        keep, off = self._offsets(offsets, samples)
+        self._check(self._L.trt_shade_camera(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
+                                             int(samples), off, rgba.ctypes.data))
+        return rgba
+
+    def shade_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None,
+                         stream=0):
+        """Device image (int address of the FULL W x H x 4 float image, 16-byte aligned; only the rows of ``rows`` are
+        written).  Asynchronous on ``stream``."""
+        r0, r1 = (0, H) if rows is None else rows
+        keep, off = self._offsets(offsets, samples)
+        self._check(self._L.trt_shade_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
+                                                 int(samples), off, _vp(rgba_ptr), _vp(stream)))
+
     # -- render -------------------------------------------------------------------------
     def render(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, want_hits=True):
         """Host buffers.  Returns (rgba (H,W,4), hits dict | None)."""
