@@ -17,6 +17,8 @@
  *   as streams / supersampled      BEF/shaders/raytrace.rgen:21-57       trt_camera_rays* / trt_shade_camera*
  *   traceRayEXT closest hit        REFL/shaders/raytrace.rgen:64-75      trt_trace*
  *   traceRayEXT any hit (shadow)   REFL/shaders/raytrace.rchit:114-131   trt_occluded*
+ *   K any-hit rays per hit point   (none: the ambient-occlusion chapter
+ *   in a fan about the normal      the tutorial family goes on to)       trt_fan_rays* / trt_fan_occluded*
  *   payload loop on your own rays  REFL/shaders/raytrace.rgen:54-87 bounce
  *                                  loop + rchit/rmiss                    trt_shade*
  *   every crossing of a ray, in    (none: build-defined, the reference
@@ -360,6 +362,58 @@ int trt_shade_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc,
                          uint32_t row_begin, uint32_t row_end, int camera,
                          uint32_t samples, const float* offsets, float* rgba_dev, void* stream);
 
+/* ---- ray fans: K rays from every surface point, as streams or as fused ambient occlusion ------------------------------ */
+/* The stage after the first hit, opened to caller data: from each of n surface points — the first-hit record of
+ * trt_render*, or the output of trt_trace*, passed as it stands — `samples` rays in a fan, handed out as SoA streams
+ * that feed trt_occluded / trt_trace / trt_shade (trt_fan_rays*), or put through the any-hit query at once and reduced
+ * to one word and one number per point (trt_fan_occluded*): ambient occlusion, sky visibility, area-light soft shadows.
+ * `at` is read, never written: px, py, pz are required; nx, ny, nz are required for TRT_FAN_LOCAL and not read for
+ * TRT_FAN_WORLD (they may be NULL there); id is optional, and where it is given a point with id < 0 is DEAD — no surface,
+ * the miss record; t is never read.
+ * dirs: samples x 3 host floats (lx, ly, lz) per sample, any length (t is in units of |d|); they are copied before the
+ * call returns and travel in the kernel arguments, so the _dev calls use no scratch of the ctx and allocate nothing.
+ * The ray of sample s at a live point (P, N) — FP32, one rounding per operation, exactly in the order written, no
+ * contraction, the division correctly rounded:
+ *   origin  o = P   (the shadow ray of REFL/shaders/raytrace.rchit:114; tmin keeps it off its own surface)
+ *   TRT_FAN_LOCAL   sg = copysignf(1, nz);  a = -1 / (sg + nz);  b = (nx * ny) * a
+ *                   T = (1 + ((sg * nx) * nx) * a,  sg * b,              (-sg) * nx)
+ *                   B = (b,                         sg + (ny * ny) * a,  -ny       )
+ *                   d.k = ((lx * T.k) + (ly * B.k)) + (lz * N.k)   for k = x, y, z
+ *   TRT_FAN_WORLD   d = (lx, ly, lz)
+ * (the branch-free orthonormal basis of Duff et al., "Building an Orthonormal Basis, Revisited", JCGT 2017: |sg + nz| >= 1,
+ * no pole).  N is used as given, never flipped and never renormalised.
+ * trt_fan_rays*: six streams of samples * n floats, any of them NULL to skip it, not all; sample-major like trt_camera_rays
+ * — sample s of point i is ray s * n + i, each sample a ray stream of its own.  A dead point gets o = P, d = (0, 0, 0).
+ * The call executes no test: the counters of the last counted call stay as they are.
+ * trt_fan_occluded*: bit s of bits[i] is set exactly when trt_occluded reports that ray occluded for the same scene,
+ * axes, solver and (tmin, tmax) — bit for bit, for every TRT_SOLVE_* and for oriented tori; bits at or above `samples` are
+ * zero.  open[i] = (float)(samples - popcount(bits[i])) / (float)samples, one correctly rounded division.  A dead point
+ * gets bits = 0, open = 1 and executes no test; !(tmax > tmin) gives that to every point.  Either output may be NULL,
+ * not both; bits must be 8-byte aligned.
+ * Stats (trt_enable_stats): shadow_tests = the tests executed — a sample stops counting at its first hit: trt_occluded's
+ * count on the live points' explicit rays — primary_tests = bounce_tests = 0, pixels = n; traced_tests, solved_tests and
+ * evaluations as defined at trt_stats.
+ * TRT_E_INVALID: NULL ctx, at, dirs or out; a required stream that is NULL with n > 0; an unknown frame; samples outside
+ * 1..TRT_MAX_FAN_SAMPLES; a dirs component that is NaN or infinite; all outputs NULL; a misaligned bits; samples * n
+ * overflowing uint64_t (trt_fan_rays*).  A refused call leaves the ctx usable and the outputs unwritten.  n == 0 is valid
+ * and launches nothing. */
+#define TRT_MAX_FAN_SAMPLES 64 /* one bit per sample in a 64-bit word; the table travels in the kernel arguments */
+enum { TRT_FAN_LOCAL = 0, TRT_FAN_WORLD = 1 };
+
+/* Host buffers: copies in, launches, copies out, synchronises. */
+int trt_fan_rays(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                 const trt_rays_out* out);
+/* Device-resident streams, asynchronous on `stream`; launch contract of the *_dev entry points below (kernel nodes only,
+ * may be captured; the table lives in the node's arguments). */
+int trt_fan_rays_dev(trt_ctx* ctx, const trt_hits* at_dev, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                     const trt_rays_out* out_dev, void* stream);
+/* Host buffers: copies in, launches, copies out, synchronises. */
+int trt_fan_occluded(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                     const trt_scene* scene, float tmin, float tmax, uint64_t* bits_out, float* open_out);
+/* Device-resident streams, asynchronous on `stream`; launch contract as trt_fan_rays_dev. */
+int trt_fan_occluded_dev(trt_ctx* ctx, const trt_hits* at_dev, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                         const trt_scene* scene, float tmin, float tmax, uint64_t* bits_dev, float* open_dev, void* stream);
+
 /* ---- render: the faithful equivalent of HelloVulkan::raytrace ---------------------- */
 /* rgba_out: W*H*4 floats, row-major, image[y][x] = (hitValue, 1)  (rgen:87); 16-byte aligned.
  * first_hit_out: optional SoA record of the depth-0 hit per pixel, row-major y*W+x. */
@@ -498,7 +552,7 @@ enum { TRT_CLOUD_KEEP_ALL = 0, TRT_CLOUD_MARK_MISSES = 1, TRT_CLOUD_COMPACT = 2 
 int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t n_records, int mode, int append,
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
-/* Counters of the last render, trace, occluded, crossings, shade or shade_camera call made with counting enabled. */
+/* Counters of the last render, trace, occluded, crossings, shade, shade_camera or fan_occluded call made with counting enabled. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

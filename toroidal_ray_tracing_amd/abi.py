@@ -18,6 +18,8 @@ TRT_MAX_MATERIALS = 8
 TRT_MAX_BATCH = 8
 TRT_MAX_CROSSINGS = 4 * TRT_MAX_TORI   # a line meets a torus at most 4 times
 TRT_MAX_CAMERA_SAMPLES = 64             # samples per pixel of trt_camera_rays / trt_shade_camera
+TRT_MAX_FAN_SAMPLES = 64                # samples per point of trt_fan_rays / trt_fan_occluded: one bit each in a 64-bit word
+TRT_FAN_LOCAL, TRT_FAN_WORLD = 0, 1     # the table's directions are about the point's normal | in world axes
 TRT_CAMERA_PINHOLE, TRT_CAMERA_TOROIDAL = 0, 1
 TRT_CLASSIFY_AUTO, TRT_CLASSIFY_MACRO, TRT_CLASSIFY_TILE = -1, 0, 1
 TRT_SOLVE_F32, TRT_SOLVE_F64, TRT_SOLVE_DK_F32, TRT_SOLVE_DK_F64 = 0, 1, 2, 3
@@ -224,6 +226,13 @@ def camera_offsets(offsets, samples):
     if a.size != 2 * int(samples):
         raise ValueError(f"{a.size} offset values for {samples} samples (2 per sample)")
     return a
+
+
+def fan_dirs(dirs):
+    """The direction table of trt_fan_rays / trt_fan_occluded as the C ABI takes it: a contiguous float32 array
+    (lx_0, ly_0, lz_0, lx_1, ...) from anything shaped (samples, 3).  Returns (array, samples)."""
+    a = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+    return a, len(a)
 
 
 def hits_struct(arrays):

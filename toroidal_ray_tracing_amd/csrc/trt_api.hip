@@ -37,11 +37,12 @@ struct DevBuf {
 // Before kBufGraphVisible: staging of the host-pointer entry points, which synchronise before they return and cannot be
 // captured.  From it on: scratch that a *_dev entry point hands to a kernel (DevBuf::graph_visible, grow()).
 enum Buf {
-  kBufIn,                       // [6] trt_trace, trt_occluded, trt_crossings, trt_shade: the ray streams
+  kBufIn,                       // [6] trt_trace, trt_occluded, trt_crossings, trt_shade: the ray streams; trt_fan_*: the points' P and N streams
   kBufOut  = kBufIn + 6,        // [8] trt_trace, trt_render: the first-hit streams; trt_occluded: flag and mask in [0], [1];
-                                //     trt_crossings: t, id, entering, count in [0] .. [3]
+                                //     trt_crossings: t, id, entering, count in [0] .. [3]; trt_camera_rays, trt_fan_rays: the ray streams
+                                //     in [0] .. [5]; trt_fan_occluded: bits and open in [0], [1]
   kBufRgba = kBufOut + 8,       // trt_render, trt_shade: the image
-  kBufTmax,                     // trt_occluded: the per-ray bounds
+  kBufTmax,                     // trt_occluded: the per-ray bounds; trt_fan_*: the points' id stream
   kBufGraphVisible,
   kBufToro = kBufGraphVisible,  // the toroidal camera's trigonometry tables
   kBufToroSamples,              // trt_camera_rays, trt_shade_camera: the toroidal camera's tables per sub-pixel sample
@@ -738,6 +739,12 @@ extern "C" int trt_debug_splat_mode(trt_ctx* ctx, uint32_t W, uint32_t H, float 
   if(!ctx) return TRT_E_INVALID;
   return splat_plan(W, H, point_size, n_points, ctx->tn).mode;
 }
+// tests/test_gpu_fan.py: the form (kFanLane | kFanBlock) a trt_fan_occluded* call takes under the knobs as last read
+extern "C" int trt_debug_fan_form(trt_ctx* ctx)
+{
+  if(!ctx) return TRT_E_INVALID;
+  return ctx->tn.fan_form == kFanLane || ctx->tn.fan_form == kFanBlock ? ctx->tn.fan_form : kFanForm;
+}
 #endif
 
 #ifdef TRT_TIMELINE
@@ -863,7 +870,7 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
   return TRT_OK;
 }
 
-// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev), after the entry
+// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev), after the entry
 // point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
@@ -1166,6 +1173,131 @@ extern "C" int trt_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_pu
   float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
   if(int rc = trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
   return fetch_outs(ctx, &image, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// ray fans: `samples` rays from every surface point, as streams or through the any-hit query at once
+// ------------------------------------------------------------------------------------------
+// What trt_fan_rays* and trt_fan_occluded* (`who`) share: the checks of include/trt.h on the points, the frame and the
+// table, and the FanArgs they describe.
+static int check_fan(trt_ctx* ctx, const char* who, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                     FanArgs& f)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(!at || !dirs) return fail(ctx, TRT_E_INVALID, "%s: NULL points or directions", who);
+  if(frame != TRT_FAN_LOCAL && frame != TRT_FAN_WORLD) return fail(ctx, TRT_E_INVALID, "%s: unknown frame %d", who, frame);
+  if(samples < 1 || samples > TRT_MAX_FAN_SAMPLES)
+    return fail(ctx, TRT_E_INVALID, "%s: samples = %u, must be 1..%d (TRT_MAX_FAN_SAMPLES)", who, samples, TRT_MAX_FAN_SAMPLES);
+  if(n && (!at->px || !at->py || !at->pz)) return fail(ctx, TRT_E_INVALID, "%s: NULL point stream (px, py, pz)", who);
+  if(n && frame == TRT_FAN_LOCAL && (!at->nx || !at->ny || !at->nz))
+    return fail(ctx, TRT_E_INVALID, "%s: NULL normal stream (nx, ny, nz are required for TRT_FAN_LOCAL)", who);
+  std::memset(&f, 0, sizeof f);
+  for(uint32_t s = 0; s < samples; ++s)
+  {
+    f.lx[s] = dirs[3 * s]; f.ly[s] = dirs[3 * s + 1]; f.lz[s] = dirs[3 * s + 2];
+    if(!std::isfinite(f.lx[s]) || !std::isfinite(f.ly[s]) || !std::isfinite(f.lz[s]))
+      return fail(ctx, TRT_E_INVALID, "%s: the direction of sample %u, (%g, %g, %g), is not finite", who, s, (double)f.lx[s], (double)f.ly[s],
+                  (double)f.lz[s]);
+  }
+  f.at      = *at;
+  f.n       = n;
+  f.frame   = frame;
+  f.samples = samples;
+  return TRT_OK;
+}
+
+// The points of a host-pointer call on the device: P and N through buf[kBufIn ..], id through buf[kBufTmax]; a stream the
+// caller left out (N for TRT_FAN_WORLD, id) stays NULL, and t is never read.
+static int stage_points(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, trt_hits& dat)
+{
+  dat = trt_hits{};
+  const size_t  bytes  = (size_t)n * sizeof(float);
+  const float*  src[6] = {at->px, at->py, at->pz, at->nx, at->ny, at->nz};
+  float**       dst[6] = {&dat.px, &dat.py, &dat.pz, &dat.nx, &dat.ny, &dat.nz};
+  for(int k = 0; k < (frame == TRT_FAN_LOCAL ? 6 : 3); ++k)
+    if(int rc = stage_in(ctx, kBufIn + k, src[k], bytes, const_cast<const float**>(dst[k]))) return rc;
+  if(at->id)
+    if(int rc = stage_in(ctx, kBufTmax, (const float*)at->id, bytes, (const float**)&dat.id)) return rc;
+  return TRT_OK;
+}
+
+static int check_fan_rays(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                          const trt_rays_out* out, FanArgs& f)
+{
+  if(ctx && !out) return fail(ctx, TRT_E_INVALID, "trt_fan_rays: NULL output streams");
+  if(int rc = check_fan(ctx, "trt_fan_rays", at, n, frame, samples, dirs, f)) return rc;
+  if(!out->ox && !out->oy && !out->oz && !out->dx && !out->dy && !out->dz)
+    return fail(ctx, TRT_E_INVALID, "trt_fan_rays: no output (all six streams NULL)");
+  if(n > UINT64_MAX / samples) return fail(ctx, TRT_E_INVALID, "trt_fan_rays: samples * n overflows 64 bits");
+  return TRT_OK;
+}
+extern "C" int trt_fan_rays_dev(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                                const trt_rays_out* out, void* stream)
+{
+  FanRaysArgs a;
+  if(int rc = check_fan_rays(ctx, at, n, frame, samples, dirs, out, a.fan)) return rc;
+  a.out = *out;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  TRT_HIP(ctx, launch_fan_rays(a, ctx->tn, (hipStream_t)stream));   // no test is executed: no counted bracket, the stats stay
+  return TRT_OK;
+}
+
+// Host buffers: the points staged by stage_points(), the six streams through buf[kBufOut] .. [kBufOut + 5].
+extern "C" int trt_fan_rays(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                            const trt_rays_out* out)
+{
+  FanArgs f;
+  if(int rc = check_fan_rays(ctx, at, n, frame, samples, dirs, out, f)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(n == 0) return TRT_OK;   // validated; nothing to launch or to write
+  if(n * samples > SIZE_MAX / sizeof(float)) return fail(ctx, TRT_E_NOMEM, "trt_fan_rays: samples * n floats do not fit the address space");
+  const size_t bytes = (size_t)(n * samples) * sizeof(float);
+  trt_hits dat;
+  if(int rc = stage_points(ctx, at, n, frame, dat)) return rc;
+  float* const host[6] = {out->ox, out->oy, out->oz, out->dx, out->dy, out->dz};
+  StagedOut outs[6];
+  for(int k = 0; k < 6; ++k) outs[k] = {host[k], bytes, kBufOut + k, nullptr};
+  if(int rc = stage_outs(ctx, outs, 6)) return rc;
+  const trt_rays_out dout = {(float*)outs[0].dev, (float*)outs[1].dev, (float*)outs[2].dev, (float*)outs[3].dev, (float*)outs[4].dev, (float*)outs[5].dev};
+  if(int rc = trt_fan_rays_dev(ctx, &dat, n, frame, samples, dirs, &dout, nullptr)) return rc;
+  return fetch_outs(ctx, outs, 6);
+}
+
+static int check_fan_occluded(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                              const uint64_t* bits, const float* open, FanArgs& f)
+{
+  if(int rc = check_fan(ctx, "trt_fan_occluded", at, n, frame, samples, dirs, f)) return rc;
+  if(!bits && !open) return fail(ctx, TRT_E_INVALID, "trt_fan_occluded: no output (bits and open both NULL)");
+  if((uintptr_t)bits & 7) return fail(ctx, TRT_E_INVALID, "trt_fan_occluded: bits must be 8-byte aligned (64-bit stores)");
+  return TRT_OK;
+}
+extern "C" int trt_fan_occluded_dev(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                                    const trt_scene* scene, float tmin, float tmax, uint64_t* bits, float* open, void* stream)
+{
+  FanOccludedArgs a;
+  if(int rc = check_fan_occluded(ctx, at, n, frame, samples, dirs, bits, open, a.fan)) return rc;
+  a.tmin = tmin;
+  a.tmax = tmax;
+  a.bits = (unsigned long long*)bits;
+  a.open = open;
+  return ray_query(ctx, scene, stream, n, a, launch_fan_occluded);
+}
+
+// Host buffers: the points staged by stage_points(), bits and open through buf[kBufOut], [kBufOut + 1].
+extern "C" int trt_fan_occluded(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
+                                const trt_scene* scene, float tmin, float tmax, uint64_t* bits, float* open)
+{
+  FanArgs f;
+  if(int rc = check_fan_occluded(ctx, at, n, frame, samples, dirs, bits, open, f)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(n == 0) return trt_fan_occluded_dev(ctx, at, n, frame, samples, dirs, scene, tmin, tmax, bits, open, nullptr);   // validates, launches and writes nothing
+  if(n > SIZE_MAX / sizeof(uint64_t)) return fail(ctx, TRT_E_NOMEM, "trt_fan_occluded: n words do not fit the address space");
+  trt_hits dat;
+  if(int rc = stage_points(ctx, at, n, frame, dat)) return rc;
+  StagedOut outs[2] = {{bits, (size_t)n * sizeof(uint64_t), kBufOut, nullptr}, {open, (size_t)n * sizeof(float), kBufOut + 1, nullptr}};
+  if(int rc = stage_outs(ctx, outs, 2)) return rc;
+  if(int rc = trt_fan_occluded_dev(ctx, &dat, n, frame, samples, dirs, scene, tmin, tmax, (uint64_t*)outs[0].dev, (float*)outs[1].dev, nullptr)) return rc;
+  return fetch_outs(ctx, outs, 2);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -366,6 +366,7 @@ Tuning tuning_from_env()
   i32("TRT_TILE", t.static_tile);
   u64("TRT_TRACE_BLOCKS", t.trace_blocks);
   i32("TRT_OCCLUDED_WALK", t.occluded_walk);
+  i32("TRT_FAN_FORM", t.fan_form);
   u64("TRT_POST_BLOCKS_PER_CU", t.post_blocks_per_cu);
   u64("TRT_SPLAT_BLOCKS_PER_CU", t.splat_blocks_per_cu);
   i32("TRT_SPLAT_VARIANT", t.splat_variant);

@@ -1,5 +1,5 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_rays.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// (trt_rays.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
 // trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
 // What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
@@ -130,8 +130,9 @@ struct Tuning {
   uint64_t persist_blocks     = 0;    // TRT_PERSIST_BLOCKS   (0 = default)
   uint64_t listed_blocks      = 0;    // TRT_LISTED_BLOCKS
   int      static_tile        = 8;    // TRT_TILE
-  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, shade_camera_kernel)
+  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, shade_camera_kernel, the fan kernels)
   int      occluded_walk      = kOccludedWalk;   // TRT_OCCLUDED_WALK: kWalkNested (0) | kWalkTable (1), occluded_kernel only
+  int      fan_form           = -1;   // TRT_FAN_FORM: kFanLane (0) | kFanBlock (1), trt_fan_occluded* only; -1 = kFanForm (below)
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
   uint64_t splat_blocks_per_cu = 0;   // TRT_SPLAT_BLOCKS_PER_CU
   int      splat_variant      = -1;   // TRT_SPLAT_VARIANT
@@ -155,6 +156,36 @@ struct OccludedArgs {
   unsigned long long* mask;
   unsigned long long* stats;
 };
+
+// trt_fan_rays*, trt_fan_occluded*: `samples` rays from each of n surface points (`at`: px, py, pz; nx, ny, nz for
+// TRT_FAN_LOCAL; id optional, id < 0 = a dead point; t never read).  The direction table (lx[s], ly[s], lz[s]) travels
+// here, in the kernel-argument segment, as CameraArgs::jx / jy do: the calls use no scratch of the ctx.  Sample s of
+// point i is ray s * n + i (the sample-major layout of CameraArgs).
+struct FanArgs {
+  trt_hits at;
+  uint64_t n;
+  int      frame;     // TRT_FAN_LOCAL | TRT_FAN_WORLD
+  uint32_t samples;   // 1 .. TRT_MAX_FAN_SAMPLES
+  float    lx[TRT_MAX_FAN_SAMPLES], ly[TRT_MAX_FAN_SAMPLES], lz[TRT_MAX_FAN_SAMPLES];
+};
+struct FanRaysArgs {
+  FanArgs      fan;
+  trt_rays_out out;   // six streams of samples * n floats, each optional
+};
+// trt_fan_occluded*: bit s of bits[i] = sample s of point i is occluded in (tmin, tmax); open[i] the share of clear samples.
+struct FanOccludedArgs {
+  FanArgs             fan;
+  float               tmin, tmax;
+  unsigned long long* bits;   // n words, optional
+  float*              open;   // n floats, optional
+  unsigned long long* stats;
+};
+// The two forms of fan_occluded (trt_fan.hip; bit-identical outputs and counts): kFanLane — one lane owns a point and
+// walks its samples; kFanBlock — a block compacts the live points of 256 and deals the (point, sample) pairs to its lanes.
+// kFanForm is the one the release library launches (DESIGN.md §5 has the measurement); TRT_FAN_FORM selects in a
+// -DTRT_TUNING build.
+enum : int { kFanLane = 0, kFanBlock = 1 };
+constexpr int kFanForm = kFanLane;
 
 // trt_crossings*: every crossing of every ray, slot-major (crossing k of ray i at [k * rays.n + i], k < max_per_ray);
 // t, id and entering are each optional, and so is count as long as one of them is there.
@@ -207,6 +238,15 @@ struct ShadeCameraArgs {
   unsigned long long* stats;
 };
 
+// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels,
+// the fan kernels; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
+// points), at most 4096 blocks (TRT_TRACE_BLOCKS).
+inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
+{
+  const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;
+  return (uint32_t)(want < cap ? want : cap);
+}
+
 enum RenderVariant { kRenderStatic = 0, kRenderPersistent = 1, kRenderListed = 2 };
 constexpr int kPersistentBlocksPerCU = 16;  // 4× the resident 4 blocks/CU: the dispatcher evens out the tile costs
 
@@ -215,6 +255,8 @@ hipError_t launch_post(const float* in, uint64_t n, float* f32_out, uint8_t* u8_
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_occluded(const SceneK& scene, const OccludedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_fan_rays(const FanRaysArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_fan_occluded(const SceneK& scene, const FanOccludedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);

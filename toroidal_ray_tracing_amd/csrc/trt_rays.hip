@@ -7,7 +7,7 @@
 //   shade_kernel       shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour (trt_render.hpp) out, samples averaged.
 //   camera_rays_kernel   camera(frame → rays_out): the two cameras' rays with sub-pixel offsets, SoA and sample-major, out.
 //   shade_camera_kernel  shade_kernel with the rays made in registers by the camera: the supersampled frame.
-//   stream_grid, launch_trace, launch_occluded, launch_crossings, launch_shade, launch_camera_rays, launch_shade_camera
+//   launch_trace, launch_occluded, launch_crossings, launch_shade, launch_camera_rays, launch_shade_camera
 //                        their grid and launch wrappers.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
 //
@@ -358,16 +358,7 @@ __global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, c
 // ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
-namespace {
-// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels;
-// grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels), at most 4096 blocks (TRT_TRACE_BLOCKS).
-uint32_t stream_grid(uint64_t n, const Tuning& tn)
-{
-  const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;
-  return (uint32_t)(want < cap ? want : cap);
-}
-}  // namespace
-
+// (stream_grid, the grid of these kernels: trt_kernels.hpp)
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream)
 {
   if(a.rays.n == 0)

@@ -183,6 +183,13 @@ void HelloHip::occluded(void* stream, const trt_rays& raysDev, const float* tmax
   check(trt_occluded_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, flagDev, maskDev, stream), "HelloHip::occluded");
 }
 
+void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
+                           float tmax, uint64_t* bitsDev, float* openDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_fan_occluded_dev(m_ctx, &atDev, n, frame, samples, dirs, &scene, tmin, tmax, bitsDev, openDev, stream), "HelloHip::fanOccluded");
+}
+
 void HelloHip::copyRenderedPosition(void* stream)
 {
   hipCheck(hipMemcpyAsync(m_hostRendered.data(), m_dRendered, m_hostRendered.size() * sizeof(trt_rendered_data),

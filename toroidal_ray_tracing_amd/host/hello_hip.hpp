@@ -59,6 +59,12 @@ public:
   void occluded(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax,
                 uint8_t* flagDev, uint64_t* maskDev);
 
+  // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
+  // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the
+  // point's normal) against the tori added so far; one word of bits and / or the share of clear samples per point out.
+  void fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
+                   float tmax, uint64_t* bitsDev, float* openDev);
+
   // --- readback + text dumps (ray_tracing__before/hello_vulkan.cpp:991-1259) ----------------
   void copyRenderedPosition(void* stream);  // RenderedData device → host
   void copyColorImage(void* stream);        // rgba32f image device → host

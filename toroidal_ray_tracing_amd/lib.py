@@ -46,6 +46,14 @@ SYMBOLS = {
     "trt_shade_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, abi.f32p, C.c_void_p,
                                        C.c_void_p]),
+    "trt_fan_rays": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,
+                               C.POINTER(abi.trt_rays_out)]),
+    "trt_fan_rays_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,
+                                   C.POINTER(abi.trt_rays_out), C.c_void_p]),
+    "trt_fan_occluded": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,
+                                   C.POINTER(abi.trt_scene), C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "trt_fan_occluded_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,
+                                       C.POINTER(abi.trt_scene), C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_render": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push),
                              C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_int,
                              C.c_void_p, C.POINTER(abi.trt_hits)]),

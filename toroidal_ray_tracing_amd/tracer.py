@@ -258,6 +258,58 @@ class Tracer:
         self._check(self._L.trt_shade_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
                                                  int(samples), off, _vp(rgba_ptr), _vp(stream)))
 
+    # -- ray fans: K rays from every surface point, as streams or as fused ambient occlusion --
+    @staticmethod
+    def _fan_points(at, frame):
+        """dict of host hit arrays (px, py, pz; nx, ny, nz for TRT_FAN_LOCAL; id optional) -> (kept arrays, trt_hits, n)."""
+        want = ("px", "py", "pz") + (("nx", "ny", "nz") if frame == abi.TRT_FAN_LOCAL else ())
+        keep = {k: np.ascontiguousarray(at[k], np.float32).reshape(-1) for k in want}
+        if at.get("id") is not None:
+            keep["id"] = np.ascontiguousarray(at["id"], np.int32).reshape(-1)
+        return keep, abi.hits_struct(keep), len(keep["px"])
+
+    def fan_rays(self, at, dirs, frame=abi.TRT_FAN_LOCAL):
+        """``samples`` rays from each of the n surface points ``at`` (a dict of host hit arrays as ``trace`` / ``render``
+        return them: px, py, pz; nx, ny, nz for TRT_FAN_LOCAL; id optional, id < 0 = no surface) with the direction table
+        ``dirs`` ((samples, 3), about the normal for TRT_FAN_LOCAL, in world axes for TRT_FAN_WORLD) (trt_fan_rays).
+        Returns (o, d) of shape (samples * n, 3), sample-major: sample s of point i is ray s * n + i."""
+        table, samples = abi.fan_dirs(dirs)
+        keep, hs, n = self._fan_points(at, frame)
+        soa = np.empty((6, samples * n), np.float32)
+        out = abi.rays_out_struct(list(soa))
+        self._check(self._L.trt_fan_rays(self._h, C.byref(hs), n, int(frame), samples, table.ctypes.data_as(abi.f32p), C.byref(out)))
+        return np.ascontiguousarray(soa[:3].T), np.ascontiguousarray(soa[3:].T)
+
+    def fan_rays_dev(self, at_ptrs, n, dirs, out_ptrs, frame=abi.TRT_FAN_LOCAL, stream=0):
+        """Device pointers (ints): at_ptrs = dict name -> address over abi.HIT_FIELDS (0 / None / absent: not given);
+        out_ptrs = 6 addresses (ox, oy, oz, dx, dy, dz; 0 = stream not wanted) of samples * n floats each, sample-major.
+        Asynchronous on ``stream``; the table is copied before the call returns."""
+        table, samples = abi.fan_dirs(dirs)
+        hs = _hits(at_ptrs) or abi.trt_hits()
+        out = abi.rays_out_struct([int(p) for p in out_ptrs])
+        self._check(self._L.trt_fan_rays_dev(self._h, C.byref(hs), int(n), int(frame), samples, table.ctypes.data_as(abi.f32p),
+                                             C.byref(out), _vp(stream)))
+
+    def fan_occluded(self, scene, at, dirs, frame=abi.TRT_FAN_LOCAL, tmin=0.001, tmax=10000.0):
+        """The fan of ``fan_rays`` put through the any-hit query at once (trt_fan_occluded) on host arrays.  Returns
+        (bits, open): bits uint64 (n,), bit s set where sample s of the point is occluded inside (tmin, tmax); open float32
+        (n,), the share of clear samples — the ambient-occlusion factor.  A point with id < 0 gets 0 and 1."""
+        table, samples = abi.fan_dirs(dirs)
+        keep, hs, n = self._fan_points(at, frame)
+        bits, opn = np.empty(n, np.uint64), np.empty(n, np.float32)
+        self._check(self._L.trt_fan_occluded(self._h, C.byref(hs), n, int(frame), samples, table.ctypes.data_as(abi.f32p),
+                                             self._scene(scene), tmin, tmax, abi.ptr(bits), abi.ptr(opn)))
+        return bits, opn
+
+    def fan_occluded_dev(self, scene, at_ptrs, n, dirs, bits_ptr=0, open_ptr=0, frame=abi.TRT_FAN_LOCAL, tmin=0.001, tmax=10000.0,
+                         stream=0):
+        """Device pointers (ints): at_ptrs as in fan_rays_dev — the hit_ptrs of ``render_dev`` / ``trace_dev`` as they stand;
+        bits_ptr: n uint64 and / or open_ptr: n float32.  Asynchronous on ``stream``."""
+        table, samples = abi.fan_dirs(dirs)
+        hs = _hits(at_ptrs) or abi.trt_hits()
+        self._check(self._L.trt_fan_occluded_dev(self._h, C.byref(hs), int(n), int(frame), samples, table.ctypes.data_as(abi.f32p),
+                                                 self._scene(scene), tmin, tmax, _vp(bits_ptr), _vp(open_ptr), _vp(stream)))
+
     # -- render -------------------------------------------------------------------------
     def render(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, want_hits=True):
         """Host buffers.  Returns (rgba (H,W,4), hits dict | None)."""
