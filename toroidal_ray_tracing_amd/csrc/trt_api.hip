@@ -2,8 +2,9 @@
 //
 // Host side of the drop-in boundary: validates arguments, derives the per-torus solver
 // constants and the toroidal camera frame, owns the grow-only device scratch (one table, Buf:
-// staging of the host-pointer entry points, and what the *_dev ones hand to kernels), and
-// launches the gfx950 kernels.  Replaces what
+// staging of the host-pointer entry points — stage_streams / stream_outs — and what the *_dev ones
+// hand to kernels, the two sets of toroidal tables of build_toro among it), and launches the
+// gfx950 kernels.  Replaces what
 // HelloVulkan::raytrace + the descriptor-set / push-constant plumbing do in the reference
 // (REFL/hello_vulkan.cpp:913-935, BEF/hello_vulkan.cpp:936-958).  Nothing in here computes
 // a ray on the CPU: without a HIP device trt_create fails.
@@ -37,15 +38,15 @@ struct DevBuf {
 // Before kBufGraphVisible: staging of the host-pointer entry points, which synchronise before they return and cannot be
 // captured.  From it on: scratch that a *_dev entry point hands to a kernel (DevBuf::graph_visible, grow()).
 enum Buf {
-  kBufIn,                       // [6] trt_trace, trt_occluded, trt_crossings, trt_shade: the ray streams; trt_fan_*: the points' P and N streams
-  kBufOut  = kBufIn + 6,        // [8] trt_trace, trt_render: the first-hit streams; trt_occluded: flag and mask in [0], [1];
-                                //     trt_crossings: t, id, entering, count in [0] .. [3]; trt_camera_rays, trt_fan_rays: the ray streams
-                                //     in [0] .. [5]; trt_fan_occluded: bits and open in [0], [1]
-  kBufRgba = kBufOut + 8,       // trt_render, trt_shade: the image
-  kBufTmax,                     // trt_occluded: the per-ray bounds; trt_fan_*: the points' id stream
+  kBufIn,                       // [6] stage_streams(): the ray streams of stage_rays, the points' P and N streams of stage_points
+  kBufOut  = kBufIn + 6,        // [8] stream_outs(): the first-hit streams (trt_trace, trt_render), the ray streams in [0] .. [5]
+                                //     (trt_camera_rays, trt_fan_rays); trt_occluded: flag and mask in [0], [1]; trt_crossings: t, id,
+                                //     entering, count in [0] .. [3]; trt_fan_occluded: bits and open in [0], [1]
+  kBufRgba = kBufOut + 8,       // trt_render, trt_shade, trt_shade_camera: the image
+  kBufTmax,                     // trt_occluded: the per-ray bounds; stage_points: the points' id stream
   kBufGraphVisible,
-  kBufToro = kBufGraphVisible,  // the toroidal camera's trigonometry tables
-  kBufToroSamples,              // trt_camera_rays, trt_shade_camera: the toroidal camera's tables per sub-pixel sample
+  kBufToro = kBufGraphVisible,  // trt_render*: the toroidal camera's trigonometry tables (ToroTables, trt_ctx::toro[kToroRender])
+  kBufToroSamples,              // trt_camera_rays, trt_shade_camera: the same per sub-pixel sample (trt_ctx::toro[kToroCamera])
   kBufTiles,                    // LIVE + CLEAR tile lists of the listed and the persistent kernel
   kBufCost,                     // cost feedback: one word per macro tile (zero = no history)
   kBufKeys,                     // depth|index keys of trt_splat_dev (one-pass form)
@@ -67,7 +68,7 @@ enum Buf {
 // Only 4- and 8-byte members, zeroed before they are filled, compared as bytes.
 struct ListKey {
   uint64_t    scene_gen;   // trt_ctx::scene_gen: the scene constants (tori, materials, solver, enclosure masks)
-  uint64_t    toro_gen;    // trt_ctx::toro_gen: the upload the toroidal tables come from (0: pinhole camera)
+  uint64_t    toro_gen;    // ToroTables::gen of the render's tables: the upload they come from (0: pinhole camera)
   const void* toro_tab;
   const void* tiles;       // where the lists, their counters and the cost words live
   const void* queue;
@@ -85,6 +86,28 @@ struct ListKey {
   } fr[kMaxBatch];
 };
 
+// One set of the toroidal camera's trigonometry tables on the device (build_toro), with a buffer, a pinned staging area,
+// an event and a key of its own.  The ctx holds two, and neither ever sees the other's calls: the render's (one sample,
+// zero offsets) and the one of trt_camera_rays* / trt_shade_camera*.
+struct ToroTables {
+  int         which;          // Buf
+  const char* cold;           // the refusal of an upload while the stream is being captured
+  bool        keeps_key;      // the key stays valid across an upload that fails half way: the render's set, as it always has
+  float*      host     = nullptr;   // pinned staging of host_cap floats
+  size_t      host_cap = 0;
+  hipEvent_t  ev       = nullptr;   // the last upload has read its staging (an event, not a remembered stream handle:
+  bool        ev_set   = false;     // the caller may destroy a stream between calls)
+  // what the tables are built from, compared as bits (a NaN angle, SURVEY §8a a2, still caches) up to the offsets in use
+  struct Key {
+    uint32_t W, H, samples;
+    float    omega, theta;
+    float    offsets[2 * TRT_MAX_CAMERA_SAMPLES];
+  } key = {};
+  bool        valid = false;
+  uint64_t    gen   = 0;      // bumped by every upload
+};
+enum { kToroRender, kToroCamera, kToroSets };
+
 }  // namespace
 
 struct trt_ctx {
@@ -95,33 +118,21 @@ struct trt_ctx {
   bool          stats_on  = false;
   int           classify  = TRT_CLASSIFY_AUTO;
   std::string   err;
-  // Events instead of remembered stream handles (the caller may destroy a stream between calls):
-  hipEvent_t    ev_toro  = nullptr;   // the last upload of the toroidal tables has read its host staging
-  hipEvent_t    ev_stats = nullptr;   // the last counted launch is done
-  hipEvent_t    ev_toro_samples = nullptr;   // the same for the per-sample tables of trt_camera_rays / trt_shade_camera
-  bool          ev_toro_set = false, ev_stats_set = false, ev_toro_samples_set = false;
+  hipEvent_t    ev_stats = nullptr;   // the last counted launch is done (an event, not a stream handle: ToroTables::ev)
+  bool          ev_stats_set = false;
 
   Tuning        tn;                       // launch-shape knobs: defaults, or the environment ONCE in a -DTRT_TUNING build
   unsigned long long* d_stats = nullptr;  // [kStatWords]: the query counters of a counted launch (StatWord, trt_kernels.hpp)
   unsigned int*       d_queue = nullptr;  // [kQueueWords]: the classification's accumulators and published counts (QueueWord)
   uint64_t            stats_pixels = 0;
 
-  // toroidal camera tables (buf[kBufToro]): pinned host staging + cache key
-  float* h_toro     = nullptr;
-  size_t h_toro_cap = 0;
-  struct { uint32_t W = 0, H = 0; float omega = 0, theta = 0; bool valid = false; } toro_key;
-
-  // per-sample toroidal tables (buf[kBufToroSamples]): a staging area and a key of their own, so that the render's
-  // tables and toro_key never see a trt_camera_rays / trt_shade_camera call.  Everything the tables are built from,
-  // compared as bits: the two angles, the frame shape, the sample count and the offsets.
-  float* h_toro_samples     = nullptr;
-  size_t h_toro_samples_cap = 0;
-  struct ToroSamplesKey {
-    uint32_t W, H, samples;
-    float    omega, theta;
-    float    offsets[2 * TRT_MAX_CAMERA_SAMPLES];
-  } toro_samples_key;
-  bool toro_samples_valid = false;
+  ToroTables toro[kToroSets] = {
+      {kBufToro, "toroidal camera: the trigonometry tables of this (W, H, centre, rho) frame are not on the device yet and cannot be "
+       "uploaded while the stream is being captured into a hipGraph (a replay would copy whatever the staging buffer holds "
+       "later): render the frame eagerly once before capturing it", true},
+      {kBufToroSamples, "toroidal camera: the per-sample trigonometry tables of this (W, H, centre, rho, samples, offsets) call are "
+       "not on the device yet and cannot be uploaded while the stream is being captured into a hipGraph (a replay would copy "
+       "whatever the staging buffer holds later): make the call eagerly once before capturing it", false}};
 
   DevBuf buf[kBufCount];        // grow-only device scratch (Buf), freed in trt_destroy
   trt_ctx() { for(int k = kBufGraphVisible; k < kBufCount; ++k) buf[k].graph_visible = true; }
@@ -143,13 +154,12 @@ struct trt_ctx {
   uint32_t n_axes = 0;
   double   axis[TRT_MAX_TORI][3];
   uint64_t scene_gen = 0;   // bumped whenever scene_cache is rebuilt
-  uint64_t toro_gen  = 0;   // bumped by every upload of the toroidal tables
 
   // The tile lists the last classification left in buf[kBufTiles] / d_queue, by what it read (ListKey): the third product a
   // frame loop recomputes for nothing, and the only one that costs GPU time (8 µs of a 116-µs frame at 4096²).
   // Cleared by: any error between a classification and the end of its call, trt_set_list_reuse, a reload of the tuning
   // knobs; everything else that changes a launch input (variant, classification level, solver and scene through
-  // scene_gen, growth of the tile lists / the cost words and a new upload of the toroidal tables through their addresses and toro_gen)
+  // scene_gen, growth of the tile lists / the cost words and a new upload of the render's toroidal tables through their addresses and gen)
   // is part of the key.  A ctx that has recorded a frame into a hipGraph stops reusing for good (`captured`): a replay
   // rewrites the lists at a time the host cannot see.
   struct ListCache {
@@ -228,6 +238,11 @@ std::array<void**, 8> hit_streams(trt_hits& h)
 {
   return {{(void**)&h.t, (void**)&h.px, (void**)&h.py, (void**)&h.pz, (void**)&h.nx, (void**)&h.ny, (void**)&h.nz, (void**)&h.id}};
 }
+// The six ray streams (ox, oy, oz, dx, dy, dz) of a trt_rays_out or a trt_rays likewise.
+template <class Rays> std::array<void**, 6> ray_streams(Rays& r)
+{
+  return {{(void**)&r.ox, (void**)&r.oy, (void**)&r.oz, (void**)&r.dx, (void**)&r.dy, (void**)&r.dz}};
+}
 
 // Host staging of the entry points that take host pointers; all of it runs on the default stream.
 // One output of such an entry point: stage_outs() gives each of `n` outputs the caller wants (`host` non-NULL) buf[which],
@@ -255,39 +270,53 @@ int fetch_outs(trt_ctx* ctx, const StagedOut* outs, int n)
   return TRT_OK;
 }
 
-// The hit streams (trt_trace, trt_render): hit_outs() describes every stream of `want` as an output of `bytes` through
-// buf[kBufOut ..]; staged_hits() points the same streams of `dev` at where stage_outs() put them.
-void hit_outs(trt_hits& want, size_t bytes, StagedOut* outs)
+// Output streams seen through hit_streams() / ray_streams() (the first hits of trt_trace and trt_render, the rays of
+// trt_camera_rays and trt_fan_rays): stream_outs() describes every stream of `want` as an output of `bytes` through
+// buf[kBufOut ..]; staged_streams() points the same streams of `dev` at where stage_outs() put them.
+template <size_t N> void stream_outs(const std::array<void**, N>& want, size_t bytes, StagedOut* outs)
 {
-  const auto src = hit_streams(want);
-  for(int k = 0; k < 8; ++k) outs[k] = {*src[k], bytes, kBufOut + k, nullptr};
+  for(size_t k = 0; k < N; ++k) outs[k] = {*want[k], bytes, kBufOut + (int)k, nullptr};
+}
+template <size_t N> void staged_streams(const StagedOut* outs, const std::array<void**, N>& dev)
+{
+  for(size_t k = 0; k < N; ++k) *dev[k] = outs[k].dev;
 }
 
-void staged_hits(const StagedOut* outs, trt_hits& dev)
-{
-  const auto dptr = hit_streams(dev);
-  for(int k = 0; k < 8; ++k) *dptr[k] = outs[k].dev;
-}
-
-// stage_in(): one input stream uploaded through buf[which], with `*dev` pointed at the copy.  stage_rays(): the six
-// streams of `in` (trt_trace, trt_occluded, trt_crossings, trt_shade) through buf[kBufIn ..], with `din` pointed at them; no rays, nothing staged.
-int stage_in(trt_ctx* ctx, int which, const float* host, size_t bytes, const float** dev)
+// stage_in(): one input stream uploaded through buf[which], with `*dev` pointed at the copy.  stage_streams(): `k`
+// streams of `bytes` each, given as their pointer fields, through buf[kBufIn ..]: each field is read as the host address
+// and pointed at the copy.
+int stage_in(trt_ctx* ctx, int which, const void* host, size_t bytes, void** dev)
 {
   DevBuf& b = ctx->buf[which];
   if(int rc = grow(ctx, b, bytes)) return rc;
   TRT_HIP(ctx, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, nullptr));
-  *dev = (const float*)b.p;
+  *dev = b.p;
+  return TRT_OK;
+}
+int stage_streams(trt_ctx* ctx, void** const* streams, int k, size_t bytes)
+{
+  for(int j = 0; j < k; ++j)
+    if(int rc = stage_in(ctx, kBufIn + j, *streams[j], bytes, streams[j])) return rc;
   return TRT_OK;
 }
 
+// The six streams of `in` (trt_trace, trt_occluded, trt_crossings, trt_shade), with `din` pointed at them; no rays, nothing staged.
 int stage_rays(trt_ctx* ctx, const trt_rays* in, trt_rays& din)
 {
   din = *in;
-  const float*  src[6] = {in->ox, in->oy, in->oz, in->dx, in->dy, in->dz};
-  const float** dst[6] = {&din.ox, &din.oy, &din.oz, &din.dx, &din.dy, &din.dz};
-  for(int k = 0; k < 6 && in->n; ++k)
-    if(int rc = stage_in(ctx, kBufIn + k, src[k], (size_t)in->n * sizeof(float), dst[k])) return rc;
-  return TRT_OK;
+  return stage_streams(ctx, ray_streams(din).data(), in->n ? 6 : 0, (size_t)in->n * sizeof(float));
+}
+
+// The points of a host-pointer trt_fan_* call, with `dat` pointed at them: P and, for TRT_FAN_LOCAL, N through
+// stage_streams(), id through buf[kBufTmax] when given; a stream left out or not read (N for TRT_FAN_WORLD, t) is NULL.
+int stage_points(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, trt_hits& dat)
+{
+  const size_t bytes = (size_t)n * sizeof(float);
+  dat   = *at;
+  dat.t = nullptr;
+  if(frame != TRT_FAN_LOCAL) dat.nx = dat.ny = dat.nz = nullptr;
+  if(int rc = stage_streams(ctx, hit_streams(dat).data() + 1, frame == TRT_FAN_LOCAL ? 6 : 3, bytes)) return rc;   // px .. nz
+  return at->id ? stage_in(ctx, kBufTmax, at->id, bytes, (void**)&dat.id) : TRT_OK;
 }
 
 // The bracket of a counted launch on `st`.  stats_begin() zeroes the query counters (a kernel node when captured) and
@@ -528,134 +557,75 @@ void toro_frame(const trt_globals& g, const trt_push& pc, float eye[3], float& o
   theta_out = theta;
 }
 
-int build_toro(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, uint32_t W, uint32_t H,
-               hipStream_t stream, ToroCam& out, bool must_match = false)
+// One sample's tables, 2 * (W + H) floats: cos_a[W] | sin_a[W] | cos_b[H] | sin_b[H] at `ca`, from
+// alfa = d_alfa·((float)x + jx) and beta = d_beta·((float)y + jy).  With zero offsets (the render) these are the values
+// of the plain column and row, bit for bit: (float)x + 0.0f is (float)x.
+void toro_fill(float* ca, uint32_t W, uint32_t H, float omega, float theta, float jx, float jy)
 {
-  float eye[3], omega, theta;
-  toro_frame(g, pc, eye, omega, theta);
-  const size_t n = 2 * ((size_t)W + H);
-  if(int rc = grow(ctx, ctx->buf[kBufToro], n * sizeof(float), stream)) return rc;
-  auto& key = ctx->toro_key;
-  // bit-compare the angles so that a NaN frame (eye above centre) still caches
-  const bool same = key.valid && key.W == W && key.H == H && !std::memcmp(&key.omega, &omega, 4)
-                    && !std::memcmp(&key.theta, &theta, 4);
+  float *sa = ca + W, *cb = sa + W, *sb = cb + H;
+  const float d_alfa = 360.0f / (float)W, d_beta = 360.0f / (float)H;      // :25-26
+  for(uint32_t x = 0; x < W; ++x)
+  {
+    const float aw = (d_alfa * ((float)x + jx) + omega) * kDeg2Rad;        // :27,56
+    ca[x] = std::cos(aw);
+    sa[x] = std::sin(aw);
+  }
+  for(uint32_t y = 0; y < H; ++y)
+  {
+    const float bt = (d_beta * ((float)y + jy) + theta) * kDeg2Rad;        // :28,57
+    cb[y] = std::cos(bt);
+    sb[y] = std::sin(bt);
+  }
+}
+
+// The tables `T` of this frame for `samples` sub-pixel offsets (`offsets`: 2 * samples floats (jx_s, jy_s), validated;
+// sample s at s * 2 * (W + H) floats), on the device before what `stream` runs next, and `out` pointed at sample 0
+// (out.eye is written before the checks: after an error `out` holds nothing to use).
+// Uploads only when T's key differs, from pinned staging that an earlier upload may still be reading (T.ev).
+// must_match: a frame of a batch behind the first, which has to find the first one's tables.
+int build_toro(trt_ctx* ctx, ToroTables& T, const trt_globals& g, const trt_push& pc, uint32_t W, uint32_t H, uint32_t samples,
+               const float* offsets, hipStream_t stream, ToroCam& out, bool must_match = false)
+{
+  ToroTables::Key key;
+  toro_frame(g, pc, out.eye, key.omega, key.theta);
+  key.W = W; key.H = H; key.samples = samples;
+  std::memcpy(key.offsets, offsets, 2 * samples * sizeof(float));
+  const size_t key_bytes = offsetof(ToroTables::Key, offsets) + 2 * samples * sizeof(float);
+  const size_t per = 2 * ((size_t)W + H), n = per * samples;
+  DevBuf& dev = ctx->buf[T.which];
+  if(int rc = grow(ctx, dev, n * sizeof(float), stream)) return rc;
+  const bool same = T.valid && !std::memcmp(&T.key, &key, key_bytes);
   if(!same && must_match)
     return fail(ctx, TRT_E_INVALID, "trt_render_batch: the frames of a batch must share the toroidal camera's trigonometry tables (same eye, centre and — with the eye off the centre's height — rho; the ctx holds "
                 "one set of trigonometry tables); render these frames one by one");
-  if(!same && capturing(stream))
-    return fail(ctx, TRT_E_INVALID, "toroidal camera: the trigonometry tables of this (W, H, centre, rho) frame are not on the "
-                "device yet and cannot be uploaded while the stream is being captured into a hipGraph (a replay would "
-                "copy whatever the staging buffer holds later): render the frame eagerly once before capturing it");
+  if(!same && capturing(stream)) return fail(ctx, TRT_E_INVALID, "%s", T.cold);
   if(!same)
   {
-    if(ctx->h_toro_cap < n)
+    if(!T.keeps_key) T.valid = false;
+    if(T.host_cap < n)
     {
-      if(ctx->h_toro) TRT_HIP(ctx, hipHostFree(ctx->h_toro));
-      ctx->h_toro = nullptr;
-      ctx->h_toro_cap = 0;
-      TRT_HIP(ctx, hipHostMalloc((void**)&ctx->h_toro, n * sizeof(float), hipHostMallocDefault));
-      ctx->h_toro_cap = n;
+      if(T.host) TRT_HIP(ctx, hipHostFree(T.host));
+      T.host = nullptr;
+      T.host_cap = 0;
+      TRT_HIP(ctx, hipHostMalloc((void**)&T.host, n * sizeof(float), hipHostMallocDefault));
+      T.host_cap = n;
     }
-    else if(ctx->ev_toro_set)
-      TRT_HIP(ctx, hipEventSynchronize(ctx->ev_toro));  // an earlier upload may still be reading it
-    float* ca = ctx->h_toro, *sa = ca + W, *cb = sa + W, *sb = cb + H;
-    const float d_alfa = 360.0f / (float)W, d_beta = 360.0f / (float)H;      // :25-26
-    for(uint32_t x = 0; x < W; ++x)
-    {
-      const float aw = (d_alfa * (float)x + omega) * kDeg2Rad;               // :27,56
-      ca[x] = std::cos(aw);
-      sa[x] = std::sin(aw);
-    }
-    for(uint32_t y = 0; y < H; ++y)
-    {
-      const float bt = (d_beta * (float)y + theta) * kDeg2Rad;               // :28,57
-      cb[y] = std::cos(bt);
-      sb[y] = std::sin(bt);
-    }
-    TRT_HIP(ctx, hipMemcpyAsync(ctx->buf[kBufToro].p, ctx->h_toro, n * sizeof(float), hipMemcpyHostToDevice,
-                                stream));
-    TRT_HIP(ctx, hipEventRecord(ctx->ev_toro, stream));
-    ctx->ev_toro_set = true;
-    ++ctx->toro_gen;
-    key.W = W; key.H = H; key.omega = omega; key.theta = theta; key.valid = true;
+    else if(T.ev_set)
+      TRT_HIP(ctx, hipEventSynchronize(T.ev));  // an earlier upload may still be reading it
+    for(uint32_t s = 0; s < samples; ++s)
+      toro_fill(T.host + s * per, W, H, key.omega, key.theta, offsets[2 * s], offsets[2 * s + 1]);
+    TRT_HIP(ctx, hipMemcpyAsync(dev.p, T.host, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    TRT_HIP(ctx, hipEventRecord(T.ev, stream));
+    T.ev_set = true;
+    std::memcpy(&T.key, &key, key_bytes);
+    T.valid = true;
+    ++T.gen;
   }
-  out.eye[0] = eye[0]; out.eye[1] = eye[1]; out.eye[2] = eye[2];
   out.rho   = pc.rho;
-  out.cos_a = (const float*)ctx->buf[kBufToro].p;
+  out.cos_a = (const float*)dev.p;
   out.sin_a = out.cos_a + W;
   out.cos_b = out.sin_a + W;
   out.sin_b = out.cos_b + H;
-  return TRT_OK;
-}
-
-// The toroidal tables of trt_camera_rays* / trt_shade_camera*, one set per sample: sample s at s * 2 * (W + H) floats,
-// each set laid out like build_toro's (cos_a[W], sin_a[W], cos_b[H], sin_b[H]) from alfa = d_alfa·((float)x + jx_s) and
-// beta = d_beta·((float)y + jy_s) — with zero offsets build_toro's values bit for bit ((float)x + 0.0f is (float)x).
-// build_toro's discipline with a buffer, a pinned staging area, an event and a key of its own: the render's tables and
-// toro_key are not touched.  `offsets`: 2 * samples floats (jx_s, jy_s), validated.  Fills c.toro and c.toro_stride.
-int build_toro_samples(trt_ctx* ctx, const trt_globals& g, const trt_push& pc, const float* offsets, hipStream_t stream, CameraArgs& c)
-{
-  const uint32_t W = c.W, H = c.H, samples = c.samples;
-  trt_ctx::ToroSamplesKey key;
-  std::memset(&key, 0, sizeof key);
-  float eye[3];
-  toro_frame(g, pc, eye, key.omega, key.theta);
-  key.W = W; key.H = H; key.samples = samples;
-  std::memcpy(key.offsets, offsets, 2 * samples * sizeof(float));
-  const size_t per = 2 * ((size_t)W + H), n = per * samples;
-  if(per > 0xffffffffull) return fail(ctx, TRT_E_INVALID, "toroidal camera: W + H = %zu does not fit the tables' 32-bit stride", per / 2);
-  if(int rc = grow(ctx, ctx->buf[kBufToroSamples], n * sizeof(float), stream)) return rc;
-  const bool same = ctx->toro_samples_valid && !std::memcmp(&ctx->toro_samples_key, &key, sizeof key);
-  if(!same && capturing(stream))
-    return fail(ctx, TRT_E_INVALID, "toroidal camera: the per-sample trigonometry tables of this (W, H, centre, rho, samples, offsets) "
-                "call are not on the device yet and cannot be uploaded while the stream is being captured into a hipGraph (a replay "
-                "would copy whatever the staging buffer holds later): make the call eagerly once before capturing it");
-  if(!same)
-  {
-    ctx->toro_samples_valid = false;
-    if(ctx->h_toro_samples_cap < n)
-    {
-      if(ctx->h_toro_samples) TRT_HIP(ctx, hipHostFree(ctx->h_toro_samples));
-      ctx->h_toro_samples = nullptr;
-      ctx->h_toro_samples_cap = 0;
-      TRT_HIP(ctx, hipHostMalloc((void**)&ctx->h_toro_samples, n * sizeof(float), hipHostMallocDefault));
-      ctx->h_toro_samples_cap = n;
-    }
-    else if(ctx->ev_toro_samples_set)
-      TRT_HIP(ctx, hipEventSynchronize(ctx->ev_toro_samples));  // an earlier upload may still be reading it
-    const float d_alfa = 360.0f / (float)W, d_beta = 360.0f / (float)H;      // :25-26
-    for(uint32_t s = 0; s < samples; ++s)
-    {
-      float* ca = ctx->h_toro_samples + s * per, *sa = ca + W, *cb = sa + W, *sb = cb + H;
-      const float jx = offsets[2 * s], jy = offsets[2 * s + 1];
-      for(uint32_t x = 0; x < W; ++x)
-      {
-        const float fx = (float)x + jx;
-        const float aw = (d_alfa * fx + key.omega) * kDeg2Rad;               // :27,56
-        ca[x] = std::cos(aw);
-        sa[x] = std::sin(aw);
-      }
-      for(uint32_t y = 0; y < H; ++y)
-      {
-        const float fy = (float)y + jy;
-        const float bt = (d_beta * fy + key.theta) * kDeg2Rad;               // :28,57
-        cb[y] = std::cos(bt);
-        sb[y] = std::sin(bt);
-      }
-    }
-    TRT_HIP(ctx, hipMemcpyAsync(ctx->buf[kBufToroSamples].p, ctx->h_toro_samples, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    TRT_HIP(ctx, hipEventRecord(ctx->ev_toro_samples, stream));
-    ctx->ev_toro_samples_set = true;
-    ctx->toro_samples_key = key;
-    ctx->toro_samples_valid = true;
-  }
-  c.toro.eye[0] = eye[0]; c.toro.eye[1] = eye[1]; c.toro.eye[2] = eye[2];
-  c.toro.rho   = pc.rho;
-  c.toro.cos_a = (const float*)ctx->buf[kBufToroSamples].p;
-  c.toro.sin_a = c.toro.cos_a + W;
-  c.toro.cos_b = c.toro.sin_a + W;
-  c.toro.sin_b = c.toro.cos_b + H;
-  c.toro_stride = (uint32_t)per;
   return TRT_OK;
 }
 
@@ -687,14 +657,14 @@ extern "C" int trt_create(int device, trt_ctx** out)
   if(!ctx) return fail(nullptr, TRT_E_NOMEM, "trt_create: out of host memory");
   ctx->device = device;
   hipDeviceProp_t prop;
-  if((e = hipSetDevice(device)) != hipSuccess || (e = hipGetDeviceProperties(&prop, device)) != hipSuccess
-     || (e = hipMalloc((void**)&ctx->d_stats, kStatWords * sizeof(unsigned long long))) != hipSuccess
-     || (e = hipMalloc((void**)&ctx->d_queue, kQueueWords * sizeof(unsigned int))) != hipSuccess
-     || (e = hipMemset(ctx->d_stats, 0, kStatWords * sizeof(unsigned long long))) != hipSuccess
-     || (e = hipMemset(ctx->d_queue, 0, kQueueWords * sizeof(unsigned int))) != hipSuccess
-     || (e = hipEventCreateWithFlags(&ctx->ev_toro, hipEventDisableTiming)) != hipSuccess
-     || (e = hipEventCreateWithFlags(&ctx->ev_toro_samples, hipEventDisableTiming)) != hipSuccess
-     || (e = hipEventCreateWithFlags(&ctx->ev_stats, hipEventDisableTiming)) != hipSuccess)
+  bool ok = (e = hipSetDevice(device)) == hipSuccess && (e = hipGetDeviceProperties(&prop, device)) == hipSuccess
+            && (e = hipMalloc((void**)&ctx->d_stats, kStatWords * sizeof(unsigned long long))) == hipSuccess
+            && (e = hipMalloc((void**)&ctx->d_queue, kQueueWords * sizeof(unsigned int))) == hipSuccess
+            && (e = hipMemset(ctx->d_stats, 0, kStatWords * sizeof(unsigned long long))) == hipSuccess
+            && (e = hipMemset(ctx->d_queue, 0, kQueueWords * sizeof(unsigned int))) == hipSuccess
+            && (e = hipEventCreateWithFlags(&ctx->ev_stats, hipEventDisableTiming)) == hipSuccess;
+  for(ToroTables& t : ctx->toro) ok = ok && (e = hipEventCreateWithFlags(&t.ev, hipEventDisableTiming)) == hipSuccess;
+  if(!ok)
   {
     fail(nullptr, TRT_E_HIP, "trt_create: %s", hipGetErrorString(e));
     trt_destroy(ctx);
@@ -710,13 +680,14 @@ extern "C" void trt_destroy(trt_ctx* ctx)
 {
   if(!ctx) return;
   (void)hipSetDevice(ctx->device);
-  if(ctx->ev_toro) (void)hipEventDestroy(ctx->ev_toro);
-  if(ctx->ev_toro_samples) (void)hipEventDestroy(ctx->ev_toro_samples);
+  for(ToroTables& t : ctx->toro)
+  {
+    if(t.ev) (void)hipEventDestroy(t.ev);
+    if(t.host) (void)hipHostFree(t.host);
+  }
   if(ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
   if(ctx->d_stats) (void)hipFree(ctx->d_stats);
   if(ctx->d_queue) (void)hipFree(ctx->d_queue);
-  if(ctx->h_toro) (void)hipHostFree(ctx->h_toro);
-  if(ctx->h_toro_samples) (void)hipHostFree(ctx->h_toro_samples);
   for(DevBuf& b : ctx->buf)
     if(b.p) (void)hipFree(b.p);
   for(void* q : ctx->retired) (void)hipFree(q);
@@ -911,10 +882,10 @@ extern "C" int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scen
   trt_rays  din;
   trt_hits  dout;
   StagedOut outs[8];
-  hit_outs(*out, bytes, outs);
+  stream_outs(hit_streams(*out), bytes, outs);
   if(int rc = stage_rays(ctx, in, din)) return rc;
   if(int rc = stage_outs(ctx, outs, 8)) return rc;
-  staged_hits(outs, dout);
+  staged_streams(outs, hit_streams(dout));
   if(int rc = trt_trace_dev(ctx, &din, scene, tmin, tmax, &dout, nullptr)) return rc;
   return fetch_outs(ctx, outs, 8);
 }
@@ -955,7 +926,7 @@ extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_
   if(int rc = stage_rays(ctx, in, din)) return rc;
   const float* d_tmax = nullptr;
   if(tmax_per_ray)
-    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, &d_tmax)) return rc;
+    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
   StagedOut outs[2] = {{flag, n, kBufOut, nullptr}, {mask, mask_bytes, kBufOut + 1, nullptr}};
   if(int rc = stage_outs(ctx, outs, 2)) return rc;
   if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, (uint8_t*)outs[0].dev, (uint64_t*)outs[1].dev, nullptr)) return rc;
@@ -1089,9 +1060,12 @@ static int check_camera(trt_ctx* ctx, const char* who, const trt_globals* g, con
 static int camera_tables(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, hipStream_t st, CameraArgs& c)
 {
   if(c.camera != TRT_CAMERA_TOROIDAL || c.n_px == 0) return TRT_OK;
+  const size_t per = 2 * ((size_t)c.W + c.H);
+  if(per > 0xffffffffull) return fail(ctx, TRT_E_INVALID, "toroidal camera: W + H = %zu does not fit the tables' 32-bit stride", per / 2);
+  c.toro_stride = (uint32_t)per;
   float offsets[2 * TRT_MAX_CAMERA_SAMPLES];
   for(uint32_t s = 0; s < c.samples; ++s) { offsets[2 * s] = c.jx[s]; offsets[2 * s + 1] = c.jy[s]; }
-  return build_toro_samples(ctx, *g, *pc, offsets, st, c);
+  return build_toro(ctx, ctx->toro[kToroCamera], *g, *pc, c.W, c.H, c.samples, offsets, st, c.toro);
 }
 
 static int check_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
@@ -1126,11 +1100,11 @@ extern "C" int trt_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_pus
   if(c.n_px == 0) return TRT_OK;   // validated; nothing to launch or to write
   if(c.n_px * samples > SIZE_MAX / sizeof(float)) return fail(ctx, TRT_E_NOMEM, "trt_camera_rays: samples * pixels floats do not fit the address space");
   const size_t bytes = (size_t)(c.n_px * samples) * sizeof(float);
-  float* const host[6] = {out->ox, out->oy, out->oz, out->dx, out->dy, out->dz};
-  StagedOut outs[6];
-  for(int k = 0; k < 6; ++k) outs[k] = {host[k], bytes, kBufOut + k, nullptr};
+  trt_rays_out want = *out, dout;
+  StagedOut    outs[6];
+  stream_outs(ray_streams(want), bytes, outs);
   if(int rc = stage_outs(ctx, outs, 6)) return rc;
-  const trt_rays_out dout = {(float*)outs[0].dev, (float*)outs[1].dev, (float*)outs[2].dev, (float*)outs[3].dev, (float*)outs[4].dev, (float*)outs[5].dev};
+  staged_streams(outs, ray_streams(dout));
   if(int rc = trt_camera_rays_dev(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, &dout, nullptr)) return rc;
   return fetch_outs(ctx, outs, 6);
 }
@@ -1206,21 +1180,6 @@ static int check_fan(trt_ctx* ctx, const char* who, const trt_hits* at, uint64_t
   return TRT_OK;
 }
 
-// The points of a host-pointer call on the device: P and N through buf[kBufIn ..], id through buf[kBufTmax]; a stream the
-// caller left out (N for TRT_FAN_WORLD, id) stays NULL, and t is never read.
-static int stage_points(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, trt_hits& dat)
-{
-  dat = trt_hits{};
-  const size_t  bytes  = (size_t)n * sizeof(float);
-  const float*  src[6] = {at->px, at->py, at->pz, at->nx, at->ny, at->nz};
-  float**       dst[6] = {&dat.px, &dat.py, &dat.pz, &dat.nx, &dat.ny, &dat.nz};
-  for(int k = 0; k < (frame == TRT_FAN_LOCAL ? 6 : 3); ++k)
-    if(int rc = stage_in(ctx, kBufIn + k, src[k], bytes, const_cast<const float**>(dst[k]))) return rc;
-  if(at->id)
-    if(int rc = stage_in(ctx, kBufTmax, (const float*)at->id, bytes, (const float**)&dat.id)) return rc;
-  return TRT_OK;
-}
-
 static int check_fan_rays(trt_ctx* ctx, const trt_hits* at, uint64_t n, int frame, uint32_t samples, const float* dirs,
                           const trt_rays_out* out, FanArgs& f)
 {
@@ -1254,11 +1213,11 @@ extern "C" int trt_fan_rays(trt_ctx* ctx, const trt_hits* at, uint64_t n, int fr
   const size_t bytes = (size_t)(n * samples) * sizeof(float);
   trt_hits dat;
   if(int rc = stage_points(ctx, at, n, frame, dat)) return rc;
-  float* const host[6] = {out->ox, out->oy, out->oz, out->dx, out->dy, out->dz};
-  StagedOut outs[6];
-  for(int k = 0; k < 6; ++k) outs[k] = {host[k], bytes, kBufOut + k, nullptr};
+  trt_rays_out want = *out, dout;
+  StagedOut    outs[6];
+  stream_outs(ray_streams(want), bytes, outs);
   if(int rc = stage_outs(ctx, outs, 6)) return rc;
-  const trt_rays_out dout = {(float*)outs[0].dev, (float*)outs[1].dev, (float*)outs[2].dev, (float*)outs[3].dev, (float*)outs[4].dev, (float*)outs[5].dev};
+  staged_streams(outs, ray_streams(dout));
   if(int rc = trt_fan_rays_dev(ctx, &dat, n, frame, samples, dirs, &dout, nullptr)) return rc;
   return fetch_outs(ctx, outs, 6);
 }
@@ -1346,11 +1305,9 @@ void list_commit(trt_ctx* ctx, const ListKey& key, bool same, bool reused)
   c.valid = c.on && !c.captured;
 }
 
-// One frame (the trt_render*_dev entry points) or a batch of them (trt_render_batch_dev): validates, fills one RenderArgs
-// per frame — the lists, their counters and capacities are shared by the frames of a batch — and launches.
-int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, const trt_scene* scene,
-                  uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, const trt_tiling* tiling,
-                  int camera, trt_rendered_data* rendered, void* stream)
+// The argument checks of render_frames(): everything that can be said before the scene is looked at.
+int check_render(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                 const trt_tiling* tiling, int camera, const trt_rendered_data* rendered)
 {
   if(!ctx) return TRT_E_INVALID;
   if(!frames || n_frames < 1 || n_frames > TRT_MAX_BATCH)
@@ -1378,12 +1335,103 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
           return fail(ctx, TRT_E_INVALID, "trt_render: first-hit streams must be 4-byte aligned");
     }
   }
-  const bool batch = n_frames > 1;
-  if(batch && (ctx->variant != kRenderListed || solver_of(ctx->precision).alt != kSolverWalk))
+  if(n_frames > 1 && (ctx->variant != kRenderListed || solver_of(ctx->precision).alt != kSolverWalk))
     return fail(ctx, TRT_E_INVALID, "trt_render_batch: batches run the listed variant with the default solver (TRT_SOLVE_F32 / _F64) only; "
                                     "render these frames one by one");
-  if(batch && W > kTile * field_max(kBatchTileXBits))
+  if(n_frames > 1 && W > kTile * field_max(kBatchTileXBits))
     return fail(ctx, TRT_E_INVALID, "trt_render_batch: W <= 65528 (a batch's tile lists pack the tile column in 13 bits)");
+  return TRT_OK;
+}
+
+// The classification level of a frame (RenderArgs::fine).  The finer, per-tile classification costs 8 µs more at 4096²
+// and pays when most macro tiles touch a bounding volume: the toroidal camera looks in every direction from among the
+// geometry (inside a torus: 0.30 → 0.21 ms); for a pinhole camera outside the scene the macro-level test already culls
+// 85 % of the frame and the extra pass is a net loss (+3…11 %).  trt_set_classification and, in a tuning build,
+// TRT_FINE_CLASSIFY overrule the choice.
+uint32_t classify_level(const trt_ctx* ctx, const trt_scene* scene, int camera, const float eye[3])
+{
+  uint32_t fine = camera == TRT_CAMERA_TOROIDAL ? 1u : 0u;
+  if(camera == TRT_CAMERA_PINHOLE)
+  {
+    // a pinhole camera INSIDE the scene (eye within two bounding radii of a torus) sees it the same way
+    for(uint32_t i = 0; i < scene->n_tori; ++i)
+    {
+      const trt_torus& t = scene->tori[i];
+      const float dx = eye[0] - t.center[0], dy = eye[1] - t.center[1], dz = eye[2] - t.center[2];
+      const float reach = 2.0f * (t.R + t.r);
+      if(dx * dx + dy * dy + dz * dz < reach * reach) fine = 1u;
+    }
+  }
+  if(ctx->classify != TRT_CLASSIFY_AUTO) fine = (uint32_t)ctx->classify;
+  if(ctx->tn.fine >= 0) fine = (uint32_t)ctx->tn.fine;
+  return fine;
+}
+
+// Frame f's own share of its RenderArgs; `a` comes holding what the frames of the call share (render_frames).  `lists`:
+// the variant has tile lists, and the fields only their kernels read are filled.
+int fill_frame(trt_ctx* ctx, const SceneK& S, const trt_scene* scene, const trt_frame& fr, uint32_t f, size_t n_macro, bool lists,
+               hipStream_t st, RenderArgs& a)
+{
+  a.g    = *fr.g;
+  a.pc   = *fr.pc;
+  a.rgba = fr.rgba_dev;
+  if(fr.first_hit_dev) a.hits = *fr.first_hit_dev;
+  static const float centred[2] = {0.0f, 0.0f};   // one sample on the pixel's corner, as raygen has it
+  if(a.camera == TRT_CAMERA_TOROIDAL)
+    if(int rc = build_toro(ctx, ctx->toro[kToroRender], *fr.g, *fr.pc, a.W, a.H, 1, centred, st, a.toro, f > 0)) return rc;
+  float eye[3];   // the frame's eye: the enclosure cull here, the choice of the classification below
+  mat4_origin(fr.g->viewInverse, eye);
+  a.skip_primary = primary_skip_mask(scene, S, eye, a.camera == TRT_CAMERA_TOROIDAL ? fr.pc->rho : 0.0f);
+  if(!lists) return TRT_OK;
+  if(a.tile_cost) a.tile_cost += (size_t)f * n_macro;
+  a.fine = classify_level(ctx, scene, a.camera, eye);
+  uintptr_t bits = 0;
+  for(void** q : hit_streams(a.hits)) bits |= (uintptr_t)*q;
+  a.vec4_ok = (a.W % 4 == 0 && (bits & 15) == 0) ? 1u : 0u;
+  return TRT_OK;
+}
+
+// The list key of a call from the RenderBatch it launches (so that it cannot drift from what is launched): ListKey.
+void list_key(const trt_ctx* ctx, const SceneK& S, const RenderBatch& B, ListKey& key)
+{
+  const RenderArgs& a = B.fr[0];
+  std::memset(&key, 0, sizeof key);
+  key.scene_gen = ctx->scene_gen;
+  if(a.camera == TRT_CAMERA_TOROIDAL)
+  {
+    key.toro_gen = ctx->toro[kToroRender].gen;
+    key.toro_tab = ctx->buf[kBufToro].p;
+  }
+  key.tiles = a.tiles_live;
+  key.queue = a.counters;
+  key.cost  = a.tile_cost;
+  key.cap_live = a.cap_live; key.cap_clear = a.cap_clear;
+  key.n_frames = B.n_frames; key.per_frame = B.per_frame; key.batch = B.n_frames > 1; key.variant = (uint32_t)ctx->variant;
+  key.W = a.W; key.H = a.H; key.row_begin = a.row_begin; key.row_end = a.row_end; key.n_local_rows = a.n_local_rows;
+  key.tile_group = a.tile_group; key.tile_parts = a.tile_parts; key.tile_part = a.tile_part; key.compact = a.compact;
+  key.camera = a.camera;
+  key.fb = render_feedback(S, a, ctx->variant);
+  key.heavy_x16 = a.heavy_x16;
+  key.stats = a.stats != nullptr;
+  key.rendered = a.rendered != nullptr;
+  for(uint32_t f = 0; f < B.n_frames; ++f)
+  {
+    const RenderArgs& af = B.fr[f];
+    ListKey::Frame&   k  = key.fr[f];
+    k.g = af.g; k.pc = af.pc;
+    k.fine = af.fine; k.tile_cull = af.tile_cull; k.skip_primary = af.skip_primary; k.debug_skip = af.debug_skip;
+  }
+}
+
+// One frame (the trt_render*_dev entry points) or a batch of them (trt_render_batch_dev): validates, sizes the scratch,
+// fills one RenderArgs per frame — the lists, their counters and capacities are shared by the frames of a batch — and
+// launches inside the stats bracket and, with tile lists, the list_begin() / list_commit() one.
+int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, const trt_scene* scene,
+                  uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, const trt_tiling* tiling,
+                  int camera, trt_rendered_data* rendered, void* stream)
+{
+  if(int rc = check_render(ctx, frames, n_frames, W, H, row_begin, row_end, tiling, camera, rendered)) return rc;
+  const bool batch = n_frames > 1;
   const SceneK* Sp = nullptr;
   if(int rc = build_scene(ctx, scene, Sp)) return rc;
   const SceneK& S = *Sp;
@@ -1392,11 +1440,7 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
   if(ctx->variant == kRenderPersistent && S.alt_solver != kSolverWalk)
     return fail(ctx, TRT_E_INVALID, "trt_render: the persistent variant implements the default solver only; "
                                     "use the listed or static variant with TRT_SOLVE_DK_* / TRT_SOLVE_FERRARI_*");
-  RenderBatch B;
-  std::memset(&B, 0, sizeof B);
-  B.n_frames = n_frames;
-  uint32_t n_local_rows = row_end - row_begin;
-  if(tiling) n_local_rows = tiling_rows(*tiling, H);
+  const uint32_t n_local_rows = tiling ? tiling_rows(*tiling, H) : row_end - row_begin;
   const size_t n_tiles = (size_t)tile_count(W) * tile_count(n_local_rows);                // per frame
   const size_t n_macro = (size_t)macro_count(tile_count(W)) * tile_count(n_local_rows);   // per frame
   const bool   lists   = ctx->variant != kRenderStatic;
@@ -1417,41 +1461,30 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     if(int rc = grow(ctx, ctx->buf[kBufCost], n_macro * n_frames * sizeof(uint32_t), st)) return rc;
     TRT_HIP(ctx, hipMemsetAsync(ctx->buf[kBufCost].p, 0, ctx->buf[kBufCost].cap, st));   // never inside a capture: grow() refuses there
   }
-  uint32_t fine_any = 0;
-  for(uint32_t f = 0; f < n_frames; ++f)
+  RenderArgs a;   // what the frames of the call share: the shape, the tiling, the counters and — with tile lists — the lists
+  std::memset(&a, 0, sizeof a);
+  a.W = W; a.H = H; a.row_begin = row_begin; a.row_end = row_end;
+  a.tile_group = 1; a.tile_parts = 1; a.tile_part = 0; a.compact = 0;
+  a.n_local_rows = n_local_rows;
+  if(tiling)
   {
-    const trt_frame& fr = frames[f];
-    RenderArgs& a = B.fr[f];
-    a.g = *fr.g;
-    a.pc = *fr.pc;
-    a.W = W; a.H = H; a.row_begin = row_begin; a.row_end = row_end;
-    a.tile_group = 1; a.tile_parts = 1; a.tile_part = 0; a.compact = 0;
-    a.n_local_rows = n_local_rows;
-    if(tiling)
-    {
-      a.row_begin = 0; a.row_end = H;
-      a.tile_group = tiling->group_rows; a.tile_parts = tiling->n_parts; a.tile_part = tiling->part;
-      a.compact = tiling->compact;
-    }
-    a.camera = camera;
-    a.rgba = fr.rgba_dev;
-    if(fr.first_hit_dev) a.hits = *fr.first_hit_dev;
-    a.rendered = rendered;
-    a.counters = ctx->d_queue;
-    a.counts   = ctx->d_queue + kQueueCounts;
-    if(camera == TRT_CAMERA_TOROIDAL)
-      if(int rc = build_toro(ctx, *fr.g, *fr.pc, W, H, st, a.toro, f > 0)) return rc;
-    float eye[3];   // the frame's eye: the enclosure cull here, the choice of the classification below
-    mat4_origin(fr.g->viewInverse, eye);
-    a.skip_primary = primary_skip_mask(scene, S, eye, camera == TRT_CAMERA_TOROIDAL ? fr.pc->rho : 0.0f);
-    if(!lists) continue;
+    a.row_begin = 0; a.row_end = H;
+    a.tile_group = tiling->group_rows; a.tile_parts = tiling->n_parts; a.tile_part = tiling->part;
+    a.compact = tiling->compact;
+  }
+  a.camera   = camera;
+  a.rendered = rendered;
+  a.counters = ctx->d_queue;
+  a.counts   = ctx->d_queue + kQueueCounts;
+  if(lists)
+  {
     a.tiles_live  = (uint32_t*)ctx->buf[kBufTiles].p;
     a.tiles_clear = a.tiles_live + n_tiles * n_frames;
     a.cap_live    = (uint32_t)(n_tiles * n_frames);
     a.cap_clear   = (uint32_t)(n_tiles * n_frames);
     if(cost_fb)
     {
-      a.tile_cost = (uint32_t*)ctx->buf[kBufCost].p + (size_t)f * n_macro;
+      a.tile_cost = (uint32_t*)ctx->buf[kBufCost].p;   // frame 0's words: fill_frame() moves on to frame f's
       a.heavy_x16 = ctx->tn.heavy_x16;
     }
     // tile culling needs tiles that are 8 contiguous image rows; with a RenderedData export the listed
@@ -1460,29 +1493,16 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     a.tile_cull = ((rendered == nullptr || ctx->variant == kRenderListed) && (a.tile_parts <= 1 || a.tile_group % 8 == 0)) ? 1u : 0u;
     a.min_batch = ctx->tn.min_batch;
     if(ctx->tn.no_tile_cull) a.tile_cull = 0;
-    // The finer, per-tile classification costs 8 µs more at 4096² and pays when most macro tiles
-    // touch a bounding volume: the toroidal camera looks in every direction from among the
-    // geometry (inside a torus: 0.30 → 0.21 ms); for a pinhole camera outside the scene the
-    // macro-level test already culls 85 % of the frame and the extra pass is a net loss (+3…11 %).
-    a.fine = camera == TRT_CAMERA_TOROIDAL ? 1u : 0u;
-    if(camera == TRT_CAMERA_PINHOLE)
-    {
-      // a pinhole camera INSIDE the scene (eye within two bounding radii of a torus) sees it the same way
-      for(uint32_t i = 0; i < scene->n_tori; ++i)
-      {
-        const trt_torus& t = scene->tori[i];
-        const float dx = eye[0] - t.center[0], dy = eye[1] - t.center[1], dz = eye[2] - t.center[2];
-        const float reach = 2.0f * (t.R + t.r);
-        if(dx * dx + dy * dy + dz * dz < reach * reach) a.fine = 1u;
-      }
-    }
-    if(ctx->classify != TRT_CLASSIFY_AUTO) a.fine = (uint32_t)ctx->classify;
-    if(ctx->tn.fine >= 0) a.fine = (uint32_t)ctx->tn.fine;
-    fine_any |= a.fine;
     a.debug_skip = ctx->tn.debug_skip;   // always 0 in the release build
-    uintptr_t bits = 0;
-    for(void** q : hit_streams(a.hits)) bits |= (uintptr_t)*q;
-    a.vec4_ok = (W % 4 == 0 && (bits & 15) == 0) ? 1u : 0u;
+  }
+  RenderBatch B;   // (frames beyond n_frames stay unwritten: nothing reads them)
+  B.n_frames = n_frames, B.per_frame = 0;
+  uint32_t fine_any = 0;
+  for(uint32_t f = 0; f < n_frames; ++f)
+  {
+    B.fr[f] = a;
+    if(int rc = fill_frame(ctx, S, scene, frames[f], f, n_macro, lists, st, B.fr[f])) return rc;
+    fine_any |= B.fr[f].fine;
   }
   if(int rc = stats_begin(ctx, st, (uint64_t)n_local_rows * W * n_frames, B.fr[0].stats)) return rc;
   for(uint32_t f = 1; f < n_frames; ++f) B.fr[f].stats = B.fr[0].stats;
@@ -1492,40 +1512,13 @@ int render_frames(trt_ctx* ctx, const trt_frame* frames, uint32_t n_frames, cons
     const uint64_t lanes = fine_any ? (uint64_t)n_macro * kMacroTiles : (uint64_t)n_macro;
     B.per_frame = (uint32_t)((lanes + 63) / 64 * 64);
   }
-  // The list key, from the RenderArgs just filled (so that it cannot drift from what is launched).  A launch without
-  // lists (static variant) or without rows touches nothing and leaves the key as it is.
+  // A launch without lists (static variant) or without rows touches nothing and leaves the key as it is.
   const bool keyed = lists && n_local_rows != 0;
   ListKey    key;
   bool       same = false, reuse = false;
   if(keyed)
   {
-    const RenderArgs& a = B.fr[0];
-    std::memset(&key, 0, sizeof key);
-    key.scene_gen = ctx->scene_gen;
-    if(camera == TRT_CAMERA_TOROIDAL)
-    {
-      key.toro_gen = ctx->toro_gen;
-      key.toro_tab = ctx->buf[kBufToro].p;
-    }
-    key.tiles = a.tiles_live;
-    key.queue = a.counters;
-    key.cost  = a.tile_cost;
-    key.cap_live = a.cap_live; key.cap_clear = a.cap_clear;
-    key.n_frames = n_frames; key.per_frame = B.per_frame; key.batch = batch; key.variant = (uint32_t)ctx->variant;
-    key.W = a.W; key.H = a.H; key.row_begin = a.row_begin; key.row_end = a.row_end; key.n_local_rows = a.n_local_rows;
-    key.tile_group = a.tile_group; key.tile_parts = a.tile_parts; key.tile_part = a.tile_part; key.compact = a.compact;
-    key.camera = a.camera;
-    key.fb = render_feedback(S, a, ctx->variant);
-    key.heavy_x16 = a.heavy_x16;
-    key.stats = a.stats != nullptr;
-    key.rendered = a.rendered != nullptr;
-    for(uint32_t f = 0; f < n_frames; ++f)
-    {
-      const RenderArgs& af = B.fr[f];
-      ListKey::Frame&   k  = key.fr[f];
-      k.g = af.g; k.pc = af.pc;
-      k.fine = af.fine; k.tile_cull = af.tile_cull; k.skip_primary = af.skip_primary; k.debug_skip = af.debug_skip;
-    }
+    list_key(ctx, S, B, key);
     reuse = list_begin(ctx, key, st, same);
   }
   if(batch)
@@ -1596,9 +1589,9 @@ extern "C" int trt_render(trt_ctx* ctx, const trt_globals* g, const trt_push* pc
   trt_hits     dh, want{};
   if(first_hit_out) want = *first_hit_out;
   StagedOut outs[9] = {{rgba_out, npx * 16, kBufRgba, nullptr}};   // the image, then the eight first-hit streams
-  hit_outs(want, npx * 4, outs + 1);
+  stream_outs(hit_streams(want), npx * 4, outs + 1);
   if(int rc = stage_outs(ctx, outs, 9)) return rc;
-  staged_hits(outs + 1, dh);
+  staged_streams(outs + 1, hit_streams(dh));
   if(int rc = trt_render_dev(ctx, g, pc, scene, W, H, 0, H, camera, (float*)outs[0].dev, first_hit_out ? &dh : nullptr,
                              nullptr, nullptr))
     return rc;

@@ -1,6 +1,7 @@
 // trt_fan.hip — the ray-fan kernels of the toroidal ray tracer (trt_fan_rays*, trt_fan_occluded*), gfx950.
 //
 //   fan_basis, fan_dir          the arithmetic contract of include/trt.h: Duff et al.'s basis about N, one sample's direction.
+//   fan_sample_dir              the choice between the table entry and fan_dir, for the two kernels with one lane per point.
 //   fan_rays_kernel             fan(points → rays_out): `samples` rays per surface point, SoA and sample-major, out.
 //   fan_occluded_kernel         form kFanLane of fan(points → bits, open): one lane owns a point and walks its samples.
 //   fan_occluded_block_kernel   form kFanBlock: a block compacts the live points of 256 and deals (point, sample) pairs out.
@@ -28,6 +29,12 @@ __device__ __forceinline__ FanBasis fan_basis(v3 N)
 __device__ __forceinline__ v3 fan_dir(const FanBasis& f, v3 N, float lx, float ly, float lz)
 {
   return {((lx * f.T.x) + (ly * f.B.x)) + (lz * N.x), ((lx * f.T.y) + (ly * f.B.y)) + (lz * N.y), ((lx * f.T.z) + (ly * f.B.z)) + (lz * N.z)};
+}
+// One sample's direction: the table entry as it is (TRT_FAN_WORLD) or about N (`local`).  fan_occluded_block_kernel keeps
+// its own text of this choice: it loads N and the basis from LDS inside it, and its machine code moves with the helper.
+__device__ __forceinline__ v3 fan_sample_dir(bool local, const FanBasis& f, v3 N, float lx, float ly, float lz)
+{
+  return local ? fan_dir(f, N, lx, ly, lz) : v3{lx, ly, lz};
 }
 
 // A point is dead when the caller gave an id stream and its id is negative (the miss record).
@@ -63,9 +70,7 @@ __global__ __launch_bounds__(256) void fan_rays_kernel(const FanRaysArgs a)
     const FanBasis tb = fan_basis(N);
     for(uint32_t s = 0; s < f.samples; ++s)
     {
-      const float lx = f.lx[s], ly = f.ly[s], lz = f.lz[s];
-      v3 d = {lx, ly, lz};
-      if(local) d = fan_dir(tb, N, lx, ly, lz);
+      v3 d = fan_sample_dir(local, tb, N, f.lx[s], f.ly[s], f.lz[s]);
       if(!live) d = {0.0f, 0.0f, 0.0f};
       const uint64_t r = (uint64_t)s * f.n + i;
       if(ox) ox[r] = P.x;
@@ -123,9 +128,7 @@ __global__ __launch_bounds__(256) void fan_occluded_kernel(const SceneK scene, c
       const FanBasis tb = fan_basis(N);
       for(uint32_t s = 0; s < f.samples; ++s)
       {
-        const float lx = f.lx[s], ly = f.ly[s], lz = f.lz[s];
-        v3 d = {lx, ly, lz};
-        if(local) d = fan_dir(tb, N, lx, ly, lz);
+        const v3 d = fan_sample_dir(local, tb, N, f.lx[s], f.ly[s], f.lz[s]);
         if(live && any_hit<Real, ALT, ORIENT, kOccludedWalk>(S, P, d, a.tmin, a.tmax, tests, wc))
           bits |= 1ull << s;
       }
