@@ -44,6 +44,10 @@ def lib():
         L.oracle_trace.argtypes = [C.POINTER(abi.trt_rays), C.POINTER(abi.trt_scene), C.c_float,
                                    C.c_float, C.c_int, C.c_int, C.POINTER(abi.trt_hits),
                                    C.POINTER(abi.trt_stats)]
+        L.oracle_shade.restype = C.c_int
+        L.oracle_shade.argtypes = [C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push),
+                                   C.POINTER(abi.trt_scene), C.c_int, C.c_int, C.c_void_p,
+                                   C.POINTER(abi.trt_stats)]
         L.oracle_raygen.restype = C.c_int
         L.oracle_raygen.argtypes = [C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push),
                                     C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
@@ -96,6 +100,20 @@ def trace(scene, o, d, tmin=0.001, tmax=10000.0, precision=abi.TRT_SOLVE_F32, nt
     _check(lib().oracle_trace(C.byref(rays), C.byref(scene.c), tmin, tmax, precision, nthreads,
                               C.byref(hs), C.byref(st)), "trace")
     return out, {k: int(getattr(st, k)) for k in abi.STAT_FIELDS}
+
+
+def shade(scene, o, d, pc, samples=1, precision=abi.TRT_SOLVE_F32, nthreads=1):
+    """trt_shade on the CPU: o, d of shape (n,3), sample-major (sample s of output i is ray s * n_out + i).  Returns
+    (rgba float32 of shape (n / samples, 4), stats dict)."""
+    o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+    d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+    n, samples = o.shape[1], int(samples)
+    rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+    rgba = np.zeros((n // samples if samples > 0 else 0, 4), np.float32)
+    st = abi.trt_stats()
+    _check(lib().oracle_shade(C.byref(rays), samples, C.byref(pc), C.byref(scene.c), precision, nthreads,
+                              abi.ptr(rgba), C.byref(st)), "shade")
+    return rgba, {k: int(getattr(st, k)) for k in abi.STAT_FIELDS}
 
 
 def render(scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, rows=None,

@@ -115,21 +115,69 @@ typedef struct {
   uint32_t     inside[TRT_MAX_TORI]; /* enclosure masks (T3, below): bit k = the torus at test-order position k */
 } scene_t;
 
-/* Enclosure cull (build-defined, like the rest of T3).  A ray whose origin lies OUTSIDE the tube of torus j
- * must cross j's surface before it can reach a tube that lies strictly inside j's: the closest hit is never the inner
- * torus, and an inner torus shadows nothing that j does not.  The queries therefore skip the tori named by a mask:
+/* Enclosure cull (build-defined, like the rest of T3).  A ray whose origin lies OUTSIDE the tube of torus j,
+ * by more than the tMin·|d| within which a crossing is dropped, must cross j's surface at t > tMin before it can reach a
+ * tube that lies strictly inside j's: the closest hit is never the inner torus, and an inner torus shadows nothing that j
+ * does not.  The queries therefore skip the tori named by a mask:
  *   - inside[j]: the tori whose tube lies strictly inside tube j (same axis line; centre circles everywhere
- *     sqrt(dR² + dy²) apart; that distance + r_k < r_j with 2^-10 of r_j to spare);
- *   - primary rays: the union of inside[j] over the tori j whose tube every ray origin of the frame lies outside of
- *     (the eye, or the circle of radius rho around it for the toroidal camera), with the same margin;
- *   - a hit on torus h that the path leaves OUTWARDS adds inside[h]: always for the shadow ray (it is cast only when
- *     N·L > 0), for the reflected ray when the incoming ray met the surface from outside (N·D < 0); the mask of a path
- *     only grows (a segment that ends on a surface has crossed none, so what the origin was outside of, the hit point is).
+ *     sqrt(dR² + dy²) apart; that distance + r_k < r_j with 2^-10 of r_j to spare) — and NOTHING unless every other
+ *     torus m keeps its surface clear of j's tube from outside by more than the margin of cull_keeps_clear() (tMin for
+ *     a unit direction, with spare): a path that starts outside j can start a segment only on such a surface, so no
+ *     segment starts within tMin of j and enters it unseen.  A torus that intersects j, touches it or wraps it with a
+ *     thinner gap switches j's share of the cull off for the whole scene;
+ *   - primary rays: the union of inside[j] over the tori j whose tube every ray origin of the frame lies outside of by
+ *     more than tMin (the eye, or the circle of radius rho around it for the toroidal camera; 2^-10 of each to spare);
+ *   - a hit on torus h that the path leaves OUTWARDS adds inside[h]: always for the shadow ray (unit length, cast only
+ *     when N·L > 0), for the reflected ray when the incoming ray met the surface from outside (N·D < 0) and the path's
+ *     directions are no longer than the unit length the margin was built for (|d|² <= 1 + 2^-9: render rays always, a
+ *     caller's ray of oracle_shade when it is; reflect keeps the length).  The mask of a path only grows.
  * A skipped torus still counts as a test of the query.  g_enclosure_cull = 0 (oracle_set_enclosure_cull, tests only)
- * tests every torus in every query: the images, records and query counts must come out the same — and do, on every
- * fixture and fuzz scene (tests/test_oracle.py::test_enclosure_cull_changes_nothing). */
+ * tests every torus in every query: the images, records and query counts must come out the same
+ * (tests/test_oracle.py::test_enclosure_cull_changes_nothing, eyes within tMin of a tube and seams of intersecting tori
+ * included).  Not covered by the rule: a reflected ray that re-enters the tube it left within tMin of its start. */
 static int g_enclosure_cull = 1;
 void oracle_set_enclosure_cull(int on) { g_enclosure_cull = on; }
+
+/* Whether torus M keeps its surface clear of torus J's tube from OUTSIDE: the tubes lie apart, or M's wraps J's, by more
+ * than tMin·(1 + 2^-10) — what a ray of at most that length per unit t covers before its crossings count — plus 2^-10 of
+ * both tube radii for the rounding of a hit point.  (Same text as trt_api.hip cull_keeps_clear; aJ, aM: the unit axes.)
+ * Bounding spheres first; two tori about one +y axis line in closed form; else the distance from J's centre circle to
+ * M's, sampled at 256 points of J's: the distance to a circle is 1-Lipschitz, so between two samples it moves by at most
+ * half their arc. */
+static int cull_keeps_clear(const trt_torus* J, const double aJ[3], const trt_torus* M, const double aM[3])
+{
+  const double margin = (double)0.001f * (1.0 + 0.0009765625) + ((double)J->r + (double)M->r) * 0.0009765625;
+  const double c[3] = {(double)M->center[0] - (double)J->center[0], (double)M->center[1] - (double)J->center[1], (double)M->center[2] - (double)J->center[2]};
+  if(sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) - ((double)J->R + (double)J->r) - ((double)M->R + (double)M->r) > margin) return 1;
+  /* two tori about one +y axis line: their centre circles are sqrt(dR² + dy²) apart everywhere — exact, no sampling */
+  if(c[0] == 0.0 && c[2] == 0.0 && aJ[0] == 0.0 && aJ[1] == 1.0 && aJ[2] == 0.0 && aM[0] == 0.0 && aM[1] == 1.0 && aM[2] == 0.0)
+  {
+    const double dR = (double)M->R - (double)J->R, D = sqrt(dR * dR + c[1] * c[1]);
+    return D - (double)J->r - (double)M->r > margin || D + (double)J->r + margin < (double)M->r;
+  }
+  /* (u, aJ, w): J's frame, by the rule of trt_api.hip torus_frame */
+  const int hi = fabs(aJ[0]) <= fabs(aJ[2]) ? 0 : 2;
+  double    u[3] = {-aJ[hi] * aJ[0], -aJ[hi] * aJ[1], -aJ[hi] * aJ[2]};
+  u[hi] += 1.0;
+  const double ul = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  for(int i = 0; i < 3; ++i) u[i] /= ul;
+  const double w[3] = {u[1] * aJ[2] - u[2] * aJ[1], u[2] * aJ[0] - u[0] * aJ[2], u[0] * aJ[1] - u[1] * aJ[0]};
+  enum { N = 256 };
+  double lo = INFINITY, hi_d = 0.0;
+  for(int i = 0; i < N; ++i)
+  {
+    const double phi = 6.283185307179586 * (double)i / (double)N, cs = (double)J->R * cos(phi), sn = (double)J->R * sin(phi);
+    const double v[3] = {cs * u[0] + sn * w[0] - c[0], cs * u[1] + sn * w[1] - c[1], cs * u[2] + sn * w[2] - c[2]};
+    const double h = v[0] * aM[0] + v[1] * aM[1] + v[2] * aM[2];
+    const double rho = sqrt(fmax(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] - h * h, 0.0)) - (double)M->R;
+    const double d = sqrt(rho * rho + h * h);
+    lo   = fmin(lo, d);
+    hi_d = fmax(hi_d, d);
+  }
+  const double slack = 3.141592653589793 * (double)J->R / (double)N;
+  return lo - slack - (double)J->r - (double)M->r > margin           /* apart */
+         || hi_d + slack + (double)J->r + margin < (double)M->r;      /* M's tube wraps J's */
+}
 
 static int scene_prepare(const trt_scene* s, int precision, scene_t* out)
 {
@@ -180,6 +228,14 @@ static int scene_prepare(const trt_scene* s, int precision, scene_t* out)
       if(D + (double)K->r < (double)J->r - (double)J->r * 0.0009765625) out->inside[j] |= 1u << p;
     }
   }
+  /* ... and none for a tube that another torus comes too close to from outside (cull_keeps_clear) */
+  const double up[3] = {0.0, 1.0, 0.0};
+  for(int j = 0; j < out->n; ++j)
+    for(int p = 0; p < out->n && out->inside[j]; ++p)
+    {
+      const int m = out->order[p];
+      if(m != j && !((out->inside[j] >> p) & 1u) && !cull_keeps_clear(&s->tori[j], up, &s->tori[m], up)) out->inside[j] = 0u;
+    }
   return TRT_OK;
 }
 
@@ -195,7 +251,8 @@ static uint32_t primary_skip_mask(const scene_t* S, v3 eye, float reach)
     const double rho = sqrt(ex * ex + ez * ez) - (double)T->R;
     const double d   = sqrt(rho * rho + ey * ey);
     const double rc  = fabs((double)reach);
-    if(d > ((double)T->r + (double)T->r * 0.0009765625) + (rc + rc * 0.0009765625)) mask |= S->inside[j];
+    const double tm  = (double)0.001f;   /* tMin: a distance along the render's unit directions */
+    if(d > ((double)T->r + (double)T->r * 0.0009765625) + (rc + rc * 0.0009765625) + (tm + tm * 0.0009765625)) mask |= S->inside[j];
   }
   return mask;
 }
@@ -395,12 +452,11 @@ typedef struct {
   v3    rayO, rayD;          /* primary ray (BEF rgen:72-73)                             */
 } pixel_out;
 
-static void shade_pixel(const scene_t* S, const trt_globals* g, const trt_push* pc,
-                        const toro_frame* F, uint32_t W, uint32_t H, int camera, uint32_t x,
-                        uint32_t y, uint32_t skip_primary, pixel_out* out, trt_stats* st)
+/* The payload loop on one ray: a pixel's primary ray (shade_pixel) or a caller's (oracle_shade).  `skip` is what is
+ * certified of the origin; `grow` whether hits may add to the path's mask (the enclosure cull, above). */
+static void shade_ray(const scene_t* S, const trt_push* pc, v3 origin, v3 direction, uint32_t skip, int grow,
+                      pixel_out* out, trt_stats* st)
 {
-  v3 origin, direction;
-  raygen(g, pc, F, W, H, camera, x, y, &origin, &direction);
   out->rayO = origin;
   out->rayD = direction;
 
@@ -411,7 +467,6 @@ static void shade_pixel(const scene_t* S, const trt_globals* g, const trt_push* 
   const v3 zero   = {0.0f, 0.0f, 0.0f};
   const v3 lp     = {pc->lightPosition[0], pc->lightPosition[1], pc->lightPosition[2]};
   out->t0 = INFINITY; out->P0 = zero; out->N0 = zero; out->id0 = -1;
-  uint32_t skip = skip_primary;                                                /* enclosure cull (above) */
 
   for(;;)                                                                      /* rgen:62 */
   {
@@ -462,7 +517,7 @@ static void shade_pixel(const scene_t* S, const trt_globals* g, const trt_push* 
         else
           specular = compute_specular(mat, direction, L, N);                   /* rchit:140 */
       }
-      if(dot3(N, direction) < 0.0f)   /* met from outside: whatever leaves this point by reflection leaves outwards */
+      if(grow && dot3(N, direction) < 0.0f)   /* met from outside: whatever leaves this point by reflection leaves outwards */
         skip |= S->inside[id];
       if(mat->illum == 3)                                                      /* rchit:145 */
       {
@@ -490,6 +545,15 @@ static void shade_pixel(const scene_t* S, const trt_globals* g, const trt_push* 
     done      = 1;                                                             /* rgen:84 */
   }
   out->color = hitValue;
+}
+
+static void shade_pixel(const scene_t* S, const trt_globals* g, const trt_push* pc,
+                        const toro_frame* F, uint32_t W, uint32_t H, int camera, uint32_t x,
+                        uint32_t y, uint32_t skip_primary, pixel_out* out, trt_stats* st)
+{
+  v3 origin, direction;
+  raygen(g, pc, F, W, H, camera, x, y, &origin, &direction);
+  shade_ray(S, pc, origin, direction, skip_primary, 1, out, st);   /* render directions are unit length */
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -635,6 +699,65 @@ int oracle_trace(const trt_rays* in, const trt_scene* scene, float tmin, float t
     stats->solved_tests = nsol;
     stats->evaluations  = nev;
     stats->reserved     = 0;
+  }
+  return TRT_OK;
+}
+
+/* Same contract as trt_shade (include/trt.h) on host buffers: one colour per output, sample s of output i is ray
+ * s·n_out + i (n_out = in->n / samples), the samples added in order as plain FP32 adds and divided once by
+ * (float)samples — not at all for one sample; alpha 1.  The mask of a caller's ray starts empty, and grows along the path
+ * only for a direction no longer than the unit length the cull's margin was built for (enclosure cull, above). */
+int oracle_shade(const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene, int precision,
+                 int nthreads, float* rgba, trt_stats* stats)
+{
+  scene_t S;
+  int     rc = scene_prepare(scene, precision, &S);
+  if(rc) return rc;
+  if(!in || !pc || !rgba || samples == 0 || in->n % samples != 0) return TRT_E_INVALID;
+  const int64_t n_out = (int64_t)(in->n / samples);
+  uint64_t np = 0, nb = 0, ns = 0, nsol = 0, nev = 0, ntr = 0;
+  (void)nthreads;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nthreads > 0 ? nthreads : 1) \
+    reduction(+ : np, nb, ns, nsol, nev, ntr)
+#endif
+  for(int64_t i = 0; i < n_out; ++i)
+  {
+    trt_stats st = {0, 0, 0, 0, 0, 0, 0, 0};
+    tl_solved = tl_evals = tl_traced = 0;
+    v3 acc = {0.0f, 0.0f, 0.0f};
+    for(uint32_t s = 0; s < samples; ++s)
+    {
+      const int64_t r = (int64_t)s * n_out + i;
+      const v3 o = {in->ox[r], in->oy[r], in->oz[r]}, d = {in->dx[r], in->dy[r], in->dz[r]};
+      pixel_out px;
+      shade_ray(&S, pc, o, d, 0u, dot3(d, d) <= 1.001953125f /* 1 + 2^-9 */, &px, &st);
+      if(s == 0) acc = px.color;
+      else { acc.x += px.color.x; acc.y += px.color.y; acc.z += px.color.z; }
+    }
+    if(samples != 1)
+    {
+      const float k = (float)samples;
+      acc.x /= k; acc.y /= k; acc.z /= k;
+    }
+    rgba[4 * i + 0] = acc.x; rgba[4 * i + 1] = acc.y; rgba[4 * i + 2] = acc.z; rgba[4 * i + 3] = 1.0f;
+    np += st.primary_tests;
+    nb += st.bounce_tests;
+    ns += st.shadow_tests;
+    nsol += tl_solved;
+    nev += tl_evals;
+    ntr += tl_traced;
+  }
+  if(stats)
+  {
+    stats->primary_tests = np;
+    stats->bounce_tests  = nb;
+    stats->shadow_tests  = ns;
+    stats->pixels        = in->n;
+    stats->traced_tests  = ntr;
+    stats->solved_tests  = nsol;
+    stats->evaluations   = nev;
+    stats->reserved      = 0;
   }
   return TRT_OK;
 }

@@ -4,7 +4,9 @@ The anchor is the frame itself: trt_render_dev exports every pixel's primary ray
 those rays — gathered in record order x*H + y, column-major, so that lanes and rays pair up differently from the render's
 tiles — must give back the frame's own colours bit for bit, for every solver, both cameras, nests seen from outside and
 from between two shells, and tori on axes of their own.  The oracle (same arithmetic on the same rays) bounds the colours
-and fixes the query counts.  The rest is what the call adds: independence of the rays, the averaging, misses and odd rays,
+and fixes the query counts.  The second anchor is oracle_shade — the oracle's bounce loop on caller rays (oracle.shade,
+checked on the CPU in tests/test_shade_oracle_cpu.py): with it rays that are no frame's primary rays have a reference,
+directions of any length included (tests/test_gpu_cull_independent.py::test_shade_dev_on_the_seam).  The rest is what the call adds: independence of the rays, the averaging, misses and odd rays,
 maxDepth <= 0, the layout, both forms, capture, errors, counters.
 
 Frames are 100x68 = 6800 rays: 106 waves and a ragged one.

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import cull_cases
 from conftest import GOLDEN, seeded_rays
 from oracle import truth
 from toroidal_ray_tracing_amd import abi, camera
@@ -220,13 +221,40 @@ def test_oracle_render_matches_golden(oracle, name, cam, prec):
     assert [stats[k] for k in ("primary_tests", "bounce_tests", "shadow_tests")] == z["stats"].tolist()
 
 
+def _cull_off_and_on(oracle, sc, g, pc, W, H, cam, prec, tag):
+    """One frame with every torus tested by every query and with the enclosure cull: images, first-hit records,
+    RenderedData and the query counts equal bit for bit.  Returns the tests the cull saved."""
+    try:
+        oracle.set_enclosure_cull(0)
+        a = oracle.render(sc, g, pc, W, H, cam, precision=prec, want_rendered=True, nthreads=4)
+    finally:
+        oracle.set_enclosure_cull(1)
+    b = oracle.render(sc, g, pc, W, H, cam, precision=prec, want_rendered=True, nthreads=4)
+    differ = int((a[0].view(np.uint32) != b[0].view(np.uint32)).any(axis=-1).sum())
+    assert differ == 0, (tag, f"{differ} pixels differ; bounce tests {a[3]['bounce_tests']} / {b[3]['bounce_tests']}")
+    for k in abi.HIT_FIELDS:
+        np.testing.assert_array_equal(a[1][k].view(np.uint32), b[1][k].view(np.uint32), err_msg=str(tag))
+    np.testing.assert_array_equal(a[2].view(np.uint32), b[2].view(np.uint32), err_msg=str(tag))
+    for k in ("primary_tests", "bounce_tests", "shadow_tests", "pixels"):
+        assert a[3][k] == b[3][k], (tag, k)
+    assert b[3]["traced_tests"] <= a[3]["traced_tests"] and b[3]["solved_tests"] <= a[3]["solved_tests"]
+    return a[3]["traced_tests"] - b[3]["traced_tests"]
+
+
 def test_enclosure_cull_changes_nothing(oracle):
     """T3's enclosure cull (trt_oracle.c: a query skips the tori whose tube lies strictly inside a tube its ray starts
     outside of) against the same oracle with the cull switched off — every torus tested by every query: images, first-hit
     records, RenderedData and the three query counts are identical bit for bit; only the tests a lane executes go down.
     The golden frames (rendered before the cull existed) pin the same thing from the other side
     (test_oracle_render_matches_golden).  Scenes: config 4's nest, nests beside and around other tori, a camera BETWEEN
-    two shells, shells that differ in R and in height, the toroidal camera inside and outside a nest, both precisions."""
+    two shells, shells that differ in R and in height, the toroidal camera inside and outside a nest, both precisions.
+
+    And the frames of tests/cull_cases.py, where the rule once changed the image (pixels that differed with the margins
+    of 2^-10·r alone and a path mask that grew after every outward hit, F32 / F64): an eye 0.0006 and 0.0008 outside the
+    enclosing tube, 2304 / 2304 and 2276 / 2272 of 2304 (0.0012 and 0.01: none); the toroidal camera whose origin circle
+    comes within 0.0009 of it, 7 / 7; a seam of intersecting tori at fov 0.5° and 8°, 169 and 16 of 4096, bounce tests
+    25734 without the cull and 27762 with it; a second layout with the intruder raised in y, 153.  The control — the
+    intruder moved away — must go on culling."""
     rng = np.random.default_rng(77)
     W = H = 48
     P, M = camera.PLASTIC, camera.MIRROR
@@ -251,21 +279,59 @@ def test_enclosure_cull_changes_nothing(oracle):
                 pc = abi.make_push(max_depth=4, rho=0.3 if cam == abi.TRT_CAMERA_TOROIDAL else 0.0,
                                    light_type=(si + ei) % 2)
                 prec = abi.TRT_SOLVE_F64 if (si + ei) % 3 == 0 else abi.TRT_SOLVE_F32
-                try:
-                    oracle.set_enclosure_cull(0)
-                    a = oracle.render(sc, g, pc, W, H, cam, precision=prec, want_rendered=True, nthreads=4)
-                finally:
-                    oracle.set_enclosure_cull(1)
-                b = oracle.render(sc, g, pc, W, H, cam, precision=prec, want_rendered=True, nthreads=4)
-                np.testing.assert_array_equal(a[0].view(np.uint32), b[0].view(np.uint32))
-                for k in abi.HIT_FIELDS:
-                    np.testing.assert_array_equal(a[1][k].view(np.uint32), b[1][k].view(np.uint32))
-                np.testing.assert_array_equal(a[2].view(np.uint32), b[2].view(np.uint32))
-                for k in ("primary_tests", "bounce_tests", "shadow_tests", "pixels"):
-                    assert a[3][k] == b[3][k], (si, ei, cam, k)
-                assert b[3]["traced_tests"] <= a[3]["traced_tests"] and b[3]["solved_tests"] <= a[3]["solved_tests"]
-                n_culled += a[3]["traced_tests"] - b[3]["traced_tests"]
+                n_culled += _cull_off_and_on(oracle, sc, g, pc, W, H, cam, prec, (si, ei, cam))
     assert n_culled > 0
+    # the frames that once differed, and the control that must keep its cull
+    for name, (sc, g, pc, Wf, Hf, cam) in cull_cases.frames().items():
+        for prec in (abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64):
+            saved = _cull_off_and_on(oracle, sc, g, pc, Wf, Hf, cam, prec, (name, prec))
+            if name in ("control", "near_2.51"):
+                assert saved > 0, name
+
+
+def nested_and_intersecting_case(seed):
+    """A fuzz scene that mixes what the enclosure cull works on with what switches it off: one or two nests of coaxial
+    shells, each with a ring that cuts through it, lies beside it less than tMin away, wraps it with a gap thinner than
+    tMin, or stays clear of it.  Returns (scene, eye, look-at): the look-at is a point where the first nest's outer tube
+    and its ring meet or all but meet, if there is one, else a point of that tube."""
+    rng = np.random.default_rng(seed)
+    tori, at = [], None
+    for c in [(0.0, 0.0, 0.0), (float(rng.uniform(4.5, 5.5)), float(rng.uniform(-0.3, 0.3)), 0.0)][:int(rng.integers(1, 3))]:
+        R, r = float(rng.uniform(1.2, 2.0)), float(rng.uniform(0.35, 0.55))
+        first = len(tori)
+        for k in range(int(rng.integers(2, 4))):
+            tori.append((c, R, r * (1.0 - 0.3 * k), int(rng.integers(0, 2))))
+        kind, aim = int(rng.integers(0, 4)), (c[0] + R, c[1] + r, 0.0)
+        if kind == 0:     # cuts through the outer tube
+            r2 = float(rng.uniform(0.2, 0.35))
+            tori.append(((c[0] + float(rng.uniform(r - r2 + 0.05, r + r2 - 0.05)), c[1] + float(rng.uniform(-0.1, 0.1)), c[2]), R, r2, 0))
+            aim = cull_cases.seam_point([tori[first], tori[-1]])
+        elif kind == 1:   # coaxial, beside the outer tube: apart by less than tMin
+            r2, gap = float(rng.uniform(0.1, 0.2)), float(rng.uniform(0.0002, 0.0009))
+            tori.append((c, R + r + r2 + gap, r2, 0))
+            aim = (c[0] + R + r, c[1] + 0.02, 0.0)
+        elif kind == 2:   # wraps the nest with a gap thinner than tMin
+            tori.append((c, R, r + float(rng.uniform(0.0006, 0.0015)), 0))
+        else:             # a ring above the nest, well clear of it
+            tori.append(((c[0], c[1] + r + 0.6, c[2]), R, 0.25, 0))
+        at = at or aim
+    order = rng.permutation(len(tori))
+    sc = abi.Scene([tori[i] for i in order], [camera.MIRROR, camera.PLASTIC])
+    eye = (at[0] + float(rng.uniform(0.4, 1.2)), at[1] + float(rng.uniform(0.8, 1.6)), float(rng.uniform(0.1, 0.5)))
+    return sc, eye, at
+
+
+@pytest.mark.parametrize("seed", [0, 3, 7, 12, 20, 31, 34, 39])
+def test_enclosure_cull_changes_nothing_on_mixed_scenes(oracle, seed):
+    """Fuzz scenes that mix nested and intersecting tori (nested_and_intersecting_case): a wide frame and a narrow one
+    aimed at the seam or the outer tube, cull off against cull on, bit for bit.  (Seeds 7, 20, 31 and 34 differed — 75, 1, 9
+    and 44 pixels of the narrow frame — while the path mask grew after every outward hit; of seeds 0..39 no other did.)"""
+    sc, eye, at = nested_and_intersecting_case(seed)
+    W = H = 48
+    for fov in (50.0, 0.5):
+        g = camera.globals_for(eye, at, W, H, fov_deg=fov)
+        prec = abi.TRT_SOLVE_F64 if seed % 2 else abi.TRT_SOLVE_F32
+        _cull_off_and_on(oracle, sc, g, abi.make_push(max_depth=6, light_type=seed % 2), W, H, abi.TRT_CAMERA_PINHOLE, prec, (seed, fov))
 
 
 def test_pinhole_raygen_vectors(oracle):
@@ -483,34 +549,47 @@ def test_shading_chain_vs_independent_fp64(name, cam):
     assert q["shadow"] - slack <= shadow <= (q["shadow"] + slack) * n_t
 
 
-@pytest.mark.parametrize("scene", [0, 1, 2])
+FP64_CULL_FRAMES = ["near_2.5006", "near_2.5008", "near_2.5012", "toroidal_near", "seam_0.5", "seam_8.0", "control"]
+
+
+@pytest.mark.parametrize("scene", [0, 1, 2] + FP64_CULL_FRAMES)
 def test_enclosure_cull_vs_independent_fp64(oracle, scene):
     """The oracle WITH its enclosure cull against oracle/truth.py::shade_frame — which tests every torus in every query and shares
     no arithmetic with the oracle — on nests seen from outside, from close by, from between two shells and from above the hole:
-    hit/miss and the torus hit agree on every robust pixel, colours to 1e-4 (what a wrongly skipped shell would break)."""
+    hit/miss and the torus hit agree on every robust pixel, colours to 1e-4 (what a wrongly skipped shell would break).
+
+    The named cases are frames of tests/cull_cases.py under the same bars: eyes within tMin of the enclosing tube, the
+    toroidal camera's origin circle within tMin of it, the seam of intersecting tori, the control.  With the margins of
+    2^-10·r alone, 2267, 1984, 5, 158 and 15 robust pixels of the first five were off by order 1.  (tilted_seam is left to
+    test_enclosure_cull_changes_nothing, which is bit-exact: at fov 0.5° and six mirror bounces the FP32 colour chain
+    alone puts 45 of its 4054 robust pixels between 1e-4 and 4.9e-4 of the FP64 colour, cull or no cull.)"""
     from oracle import truth
     P, M = camera.PLASTIC, camera.MIRROR
-    scenes = [camera.nested_tori_scene(),
-              abi.Scene([((0, 0, 0), 1.0, 0.4, 1), ((0, 0, 0), 1.05, 0.3, 0), ((0, 0.05, 0), 0.97, 0.2, 1), ((0, 0, 0), 1.0, 0.1, 0),
-                         ((2.5, 0, 0), 0.6, 0.2, 1), ((2.5, 0, 0), 0.6, 0.1, 0)], [P, M]),
-              abi.Scene([((0, 0, 0), 2.0, 1.2, 1), ((0, 0, 0), 2.0, 0.5, 1), ((0, 0, 0), 2.0, 0.2, 0)], [P, M])]
-    sc = scenes[scene]
-    W = H = 40
+    if isinstance(scene, str):
+        sc, g, pc, W, H, cam = cull_cases.frames()[scene]
+        views = [(g, pc, cam)]
+    else:
+        scenes = [camera.nested_tori_scene(),
+                  abi.Scene([((0, 0, 0), 1.0, 0.4, 1), ((0, 0, 0), 1.05, 0.3, 0), ((0, 0.05, 0), 0.97, 0.2, 1), ((0, 0, 0), 1.0, 0.1, 0),
+                             ((2.5, 0, 0), 0.6, 0.2, 1), ((2.5, 0, 0), 0.6, 0.1, 0)], [P, M]),
+                  abi.Scene([((0, 0, 0), 2.0, 1.2, 1), ((0, 0, 0), 2.0, 0.5, 1), ((0, 0, 0), 2.0, 0.2, 0)], [P, M])]
+        sc = scenes[scene]
+        W = H = 40
+        views = [(camera.globals_for(eye, (0.0, 0.0, 0.0), W, H), abi.make_push(max_depth=4), abi.TRT_CAMERA_PINHOLE)
+                 for eye in [(0.0, 1.5, -4.0), (0.0, 0.2, -2.9), (2.9, 0.0, 0.0) if scene == 2 else (1.1, 0.0, 0.0), (0.3, 2.5, 0.4)]]
     mats = [dict(ambient=tuple(m.ambient), diffuse=tuple(m.diffuse), specular=tuple(m.specular), shininess=m.shininess, illum=m.illum)
             for m in sc._mats]
     mat4 = lambda a: np.array(a[:], np.float64).reshape(4, 4).T
     checked = 0
-    for eye in [(0.0, 1.5, -4.0), (0.0, 0.2, -2.9), (2.9, 0.0, 0.0) if scene == 2 else (1.1, 0.0, 0.0), (0.3, 2.5, 0.4)]:
-        g = camera.globals_for(eye, (0.0, 0.0, 0.0), W, H)
-        pc = abi.make_push(max_depth=4)
+    for g, pc, cam in views:
         push = dict(clearColor=pc.clearColor[:], lightPosition=pc.lightPosition[:], lightIntensity=pc.lightIntensity,
                     lightType=pc.lightType, maxDepth=pc.maxDepth, rho=pc.rho)
-        want, robust, _ = truth.shade_frame(sc.tori_list(), mats, mat4(g.viewInverse), mat4(g.projInverse), g.center[:], push, W, H, 0)
-        got, hits, _, _ = oracle.render(sc, g, pc, W, H, abi.TRT_CAMERA_PINHOLE, precision=abi.TRT_SOLVE_F64, nthreads=4)
+        want, robust, _ = truth.shade_frame(sc.tori_list(), mats, mat4(g.viewInverse), mat4(g.projInverse), g.center[:], push, W, H, cam)
+        got, hits, _, _ = oracle.render(sc, g, pc, W, H, cam, precision=abi.TRT_SOLVE_F64, nthreads=4)
         got = got.astype(np.float64)
         rel = (np.abs(got - want) / (np.abs(want) + 1e-5)).max(axis=-1)[robust]
         assert robust.mean() > 0.8   # (an eye between two mirror shells sees grazing paths on more pixels than one outside)
         # (FP32 colour chain against FP64: a few pixels per frame sit between 1e-4 and 1e-3; a wrongly skipped shell is an error of order 1)
-        assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (scene, eye, rel.max(), int((rel > 1e-4).sum()))
+        assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (scene, rel.max(), int((rel > 1e-4).sum()))
         checked += int(robust.sum())
-    assert checked > 4 * W * H * 0.85
+    assert checked > len(views) * W * H * 0.85

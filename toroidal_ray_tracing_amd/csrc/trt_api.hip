@@ -427,6 +427,46 @@ int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
   return TRT_OK;
 }
 
+// Whether torus M keeps its surface clear of torus J's tube from OUTSIDE: the tubes lie apart, or M's wraps J's, by more
+// than tMin·(1 + 2^-10) — what a ray of at most that length per unit t covers before its crossings count — plus 2^-10 of
+// both tube radii for the rounding of a hit point.  aJ, aM: the unit axes.  Bounding spheres first; two tori about one +y
+// axis line in closed form; else the distance from J's centre circle to M's, sampled at 256 points of J's: the distance to
+// a circle is 1-Lipschitz, so between two samples it moves by at most half their arc.  (The oracle repeats these lines.)
+bool cull_keeps_clear(const trt_torus& J, const double aJ[3], const trt_torus& M, const double aM[3])
+{
+  const double margin = (double)0.001f * (1.0 + 0.0009765625) + ((double)J.r + (double)M.r) * 0.0009765625;
+  const double c[3] = {(double)M.center[0] - (double)J.center[0], (double)M.center[1] - (double)J.center[1], (double)M.center[2] - (double)J.center[2]};
+  if(std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) - ((double)J.R + (double)J.r) - ((double)M.R + (double)M.r) > margin) return true;
+  // two tori about one +y axis line: their centre circles are sqrt(dR² + dy²) apart everywhere — exact, no sampling
+  if(c[0] == 0.0 && c[2] == 0.0 && is_plus_y(aJ) && is_plus_y(aM))
+  {
+    const double dR = (double)M.R - (double)J.R, D = std::sqrt(dR * dR + c[1] * c[1]);
+    return D - (double)J.r - (double)M.r > margin || D + (double)J.r + margin < (double)M.r;
+  }
+  // (u, aJ, w): J's frame, by the rule of torus_frame
+  const int hi = std::fabs(aJ[0]) <= std::fabs(aJ[2]) ? 0 : 2;
+  double    u[3] = {-aJ[hi] * aJ[0], -aJ[hi] * aJ[1], -aJ[hi] * aJ[2]};
+  u[hi] += 1.0;
+  const double ul = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  for(double& x : u) x /= ul;
+  const double w[3] = {u[1] * aJ[2] - u[2] * aJ[1], u[2] * aJ[0] - u[0] * aJ[2], u[0] * aJ[1] - u[1] * aJ[0]};
+  constexpr int N = 256;
+  double lo = INFINITY, hi_d = 0.0;
+  for(int i = 0; i < N; ++i)
+  {
+    const double phi = 6.283185307179586 * (double)i / (double)N, cs = (double)J.R * std::cos(phi), sn = (double)J.R * std::sin(phi);
+    const double v[3] = {cs * u[0] + sn * w[0] - c[0], cs * u[1] + sn * w[1] - c[1], cs * u[2] + sn * w[2] - c[2]};
+    const double h = v[0] * aM[0] + v[1] * aM[1] + v[2] * aM[2];
+    const double rho = std::sqrt(std::fmax(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] - h * h, 0.0)) - (double)M.R;
+    const double d = std::sqrt(rho * rho + h * h);
+    lo   = std::fmin(lo, d);
+    hi_d = std::fmax(hi_d, d);
+  }
+  const double slack = 3.141592653589793 * (double)J.R / (double)N;
+  return lo - slack - (double)J.r - (double)M.r > margin           // apart
+         || hi_d + slack + (double)J.r + margin < (double)M.r;      // M's tube wraps J's
+}
+
 int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], SceneK& out)
 {
   std::memset(&out, 0, sizeof out);
@@ -486,6 +526,14 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[
       if(D + (double)K.r < (double)J.r - (double)J.r * 0.0009765625 && !ctx->tn.no_enclosure) out.inside[j] |= 1u << p;
     }
   }
+  // ... and none for a tube that another torus comes too close to from outside: a path that starts outside j starts its
+  // segments on the other tori's surfaces, and one that starts within tMin of j enters it unseen (cull_keeps_clear)
+  for(uint32_t j = 0; j < s->n_tori; ++j)
+    for(uint32_t p = 0; p < s->n_tori && out.inside[j]; ++p)
+    {
+      const uint32_t m = (uint32_t)out.order[p];
+      if(m != j && !((out.inside[j] >> p) & 1u) && !cull_keeps_clear(s->tori[j], axis[j], s->tori[m], axis[m])) out.inside[j] = 0u;
+    }
   for(uint32_t i = 0; i < s->n_materials; ++i)
   {
     const trt_material& m = s->materials[i];
@@ -510,8 +558,10 @@ void mat4_origin(const float* m, float out[3])
 }
 
 // Enclosure cull, the camera's share: the tori no primary ray of the frame can hit first — the tubes inside every tube j
-// that all ray origins lie outside of.  The origins are the eye (pinhole) or lie `reach` = |rho| from it (toroidal camera,
-// BEF rgen:56); certified when the eye's distance from j's centre circle exceeds r_j + reach with 2^-10 of each to spare.
+// that all ray origins lie outside of by more than tMin (a distance along the render's unit directions: a crossing of j
+// nearer than that is dropped, and the ray is then as good as inside j).  The origins are the eye (pinhole) or lie
+// `reach` = |rho| from it (toroidal camera, BEF rgen:56); certified when the eye's distance from j's centre circle exceeds
+// r_j + reach + tMin with 2^-10 of each to spare.
 // Double arithmetic on the same FP32 eye the kernels compute (mat4_origin); the oracle repeats it (shade setup).
 uint32_t primary_skip_mask(const trt_scene* s, const SceneK& K, const float eye[3], float reach)
 {
@@ -524,7 +574,8 @@ uint32_t primary_skip_mask(const trt_scene* s, const SceneK& K, const float eye[
     const double rho = std::sqrt(ex * ex + ez * ez) - (double)T.R;
     const double d   = std::sqrt(rho * rho + ey * ey);
     const double rc  = std::fabs((double)reach);
-    if(d > ((double)T.r + (double)T.r * 0.0009765625) + (rc + rc * 0.0009765625)) mask |= K.inside[j];
+    const double tm  = (double)0.001f;   // kTMin (trt_render.hpp)
+    if(d > ((double)T.r + (double)T.r * 0.0009765625) + (rc + rc * 0.0009765625) + (tm + tm * 0.0009765625)) mask |= K.inside[j];
   }
   return mask;
 }

@@ -109,7 +109,8 @@ struct SceneK {
   int            alt_solver;   // AltSolver: the Fourier–Newton walk, or an alternative root solver (kernels with ALT = true)
   int            order[TRT_MAX_TORI];  // test order: descending bounding radius R + r, ties by index
   uint32_t       inside[TRT_MAX_TORI]; // inside[i]: the tori whose tube lies strictly inside torus i's tube, as a mask over TEST-ORDER
-                                       // positions (bit k = order[k]) — what a ray that leaves i's surface outwards cannot hit first
+                                       // positions (bit k = order[k]) — what a ray that leaves i's surface outwards cannot hit first;
+                                       // empty when another torus cuts through i's tube or comes within tMin of it (trt_api.hip cull_keeps_clear)
   uint32_t       oriented;             // bit i: torus i turns about an axis other than +y (trt_set_torus_axes) and has a TorusRot record;
                                        // zero: the scene runs the kernels without ORIENT, which know nothing of all this
   uint32_t       reserved;

@@ -122,7 +122,7 @@ __device__ __forceinline__ void trace_pixel(const SceneK& S, const RenderArgs& a
   asm volatile("v_mov_b32 %0, 1.0" : "=v"(one0));
   // the loop starts from the camera's share of the enclosure cull, certified per frame on the host (a.skip_primary)
   const v3 hitValue = bounce_loop<Real, ALT, ORIENT>(
-      S, a.pc, origin, direction, a.skip_primary, {one0, one0, one0},
+      S, a.pc, origin, direction, a.skip_primary, /*grow: unit directions*/ true, {one0, one0, one0},
       [&](float t) {
         store_first_miss(a, oi, t);   // (t = +inf: what closest_hit leaves without a hit)
         if(rd)

@@ -177,8 +177,9 @@ __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, cons
 // shade(rays_in → one colour per output): the payload loop on caller-supplied rays
 // ------------------------------------------------------------------------------------------
 // The colour of one ray is the render's loop — bounce_loop() (trt_render.hpp), what trace_pixel runs for a pixel — on a
-// caller's ray: the enclosure mask starts empty (nobody has certified anything about a caller's origins), the
-// attenuation at 1, and nothing but the colour leaves (no first-hit record, no RenderedData: two empty callables).
+// caller's ray: the enclosure mask starts empty (nobody has certified anything about a caller's origins) and grows only
+// along a path of at most unit-length directions (kCullUnitDD, trt_render.hpp), the attenuation starts at 1, and nothing
+// but the colour leaves (no first-hit record, no RenderedData: two empty callables).
 //
 // One lane owns one OUTPUT and walks its samples in order (sample s of output i is ray s·n_out + i, so the six loads of
 // a sample are coalesced like trace_kernel's): acc = c_0, then acc += c_s as plain FP32 adds, then one correctly rounded
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const Sh
       const uint64_t r = (uint64_t)s * a.n_out + i;
       const v3 o = {ox[r], oy[r], oz[r]};
       const v3 d = {dx[r], dy[r], dz[r]};
-      const v3 c = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
+      const v3 c = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
                                                   n_primary, n_bounce, n_shadow, wc);
       if(s == 0u) acc = c;
       else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
@@ -339,7 +340,7 @@ __global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, c
       asm volatile("" : "+v"(cs));
       v3 o, d;
       raygen_offset(cs->g, camera_sample(*cs, s), cs->W, cs->H, cs->camera, x, y, cs->jx[s], cs->jy[s], o, d);
-      const v3 col = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
+      const v3 col = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
                                                     n_primary, n_bounce, n_shadow, wc);
       if(s == 0u) acc = col;
       else acc = {acc.x + col.x, acc.y + col.y, acc.z + col.z};

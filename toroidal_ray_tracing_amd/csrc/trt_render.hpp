@@ -271,12 +271,17 @@ constexpr float kTMax = 10000.0f;  // rgen:52
 // primary ray it is.  What the caller owns of the FIRST ray's record goes through the two callables: first_miss(t) on a
 // miss at depth 0 (t = +inf: what closest_hit leaves without a hit), first_hit(t, h, id) right after hit_begin at depth 0.
 // `skip` is the enclosure cull (trt_device.hpp closest_hit): the tori this path's rays cannot hit first — tubes strictly
-// inside a tube the ray origin is outside of.  The caller passes what is certified of the origin (the camera's share,
-// per frame on the host; nothing for a caller's ray); a hit left OUTWARDS adds the tubes inside the torus hit
-// (outside-ness persists along a path: a segment that ended on a surface crossed none).
+// inside a tube the ray origin is outside of by more than the tMin·|d| within which a crossing is dropped.  The caller
+// passes what is certified of the origin (the camera's share, per frame on the host; nothing for a caller's ray); a hit
+// left OUTWARDS adds the tubes inside the torus hit: always for the shadow ray, which is unit length; for the rest of the
+// path when `grow` is set.  The host leaves inside[j] empty unless every other torus keeps its surface more than tMin
+// (unit directions) clear of tube j (trt_api.hip cull_keeps_clear), so no segment of a path that began outside j starts
+// close enough to enter it unseen — and `grow` says that the path's directions are no longer than that: the render's
+// cameras always; a caller's ray when |d|² <= kCullUnitDD (reflect keeps the length).
+constexpr float kCullUnitDD = 1.001953125f;   // 1 + 2^-9: |d| <= 1 + 2^-10, the length the host's margin allows for
 template <class Real, bool ALT, bool ORIENT, class FirstMiss, class FirstHit>
 __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v3 origin, v3 direction,
-                                          uint32_t skip, v3 attenuation,                   // rgen:56
+                                          uint32_t skip, bool grow, v3 attenuation,        // rgen:56
                                           FirstMiss&& first_miss, FirstHit&& first_hit,
                                           uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
 {
@@ -303,7 +308,7 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
       const uint32_t inside = S.inside[id];
       if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
         shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
-      if(dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
+      if(grow && dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
         skip |= inside;
       prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
     }
