@@ -23,6 +23,10 @@
  *                                  loop + rchit/rmiss                    trt_shade*
  *   every crossing of a ray, in    (none: build-defined, the reference
  *   order, with entry / exit       has no counterpart)                   trt_crossings*
+ *   shadow ray through translucent (none: the expectation of the any-hit
+ *   walls: a fraction, not a bit   chapter's stochastic `dissolve` test)  trt_transmittance*
+ *   payload loop with translucent  (none: the same expectation, "over"
+ *   walls composited front to back compositing of trt_crossings' list)   trt_shade_through*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -106,7 +110,7 @@ typedef struct trt_material {
   float   emission[3];
   float   shininess;
   float   ior;
-  float   dissolve;
+  float   dissolve;  /* MTL `d`, the opacity.  Read by trt_transmittance* and trt_shade_through* ONLY; see there */
   int32_t illum;
   int32_t textureId; /* must be -1: tori are untextured (REFL rchit:100)                */
 } trt_material;      /* 80 bytes                                                        */
@@ -299,6 +303,67 @@ int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push
  * only, may be captured; it uses no scratch of the ctx, allocates nothing and synchronises nothing). */
 int trt_shade_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                   float* rgba_dev, void* stream);
+
+/* ---- translucent surfaces: transmittance(rays_in -> one fraction per ray), shade_through(rays_in -> colours) -------- */
+/* Every other call treats every surface as opaque.  These four read the `dissolve` of the materials (MTL `d`) as an
+ * opacity and give the deterministic expectation of the tutorial family's any-hit chapter, where `dissolve` decides at
+ * random whether a hit is accepted: front-to-back "over" compositing with weights `dissolve`, and a shadow ray that
+ * returns the fraction of light that gets through instead of a bit.  No random numbers, no accumulation over frames.
+ *
+ * !!  A ZERO-INITIALISED trt_material HAS dissolve == 0: ITS TORI ARE INVISIBLE TO THESE FOUR CALLS.  Set dissolve = 1  !!
+ * !!  for an opaque surface.  (Every other call ignores the field, whatever it holds.)                                   !!
+ *
+ * Opacity: torus j has a_j = min(max(dissolve of its material, 0), 1) and the pass factor p_j = 1.0f - a_j (FP32).  A NaN
+ * dissolve on a material some torus uses is refused by these four calls alone with TRT_E_SCENE, and the message names the material.
+ * Crossings of a segment: exactly trt_crossings' list for that ray — the same scene, axes and solver, the same window,
+ * all 4 * n_tori slots, the same order and tie rule; every torus is solved over the full window, with no enclosure cull.
+ * Solvers: TRT_SOLVE_F32 and TRT_SOLVE_F64 only; with any other solver set the calls return TRT_E_INVALID and the message
+ * says so, as trt_crossings does.
+ *
+ * trt_transmittance — the soft counterpart of trt_occluded.  Ray i has the window (tmin, tmax_i), tmax_i = tmax_per_ray[i]
+ * or, with tmax_per_ray == NULL, tmax.  T = 1; then torus by torus in trt_trace's test order (descending R + r, ties by
+ * index), that torus' roots left to right, T = T * p_id per crossing; the query stops after the torus at which T becomes 0.
+ * !(tmax_i > tmin) — a NaN bound included — gives T = 1 and executes no test.  With every a in {0, 1}, (T == 0) is
+ * trt_occluded's flag wherever no first root falls to the open-interval test after rounding (see trt_crossings).
+ * T_out: n floats.  TRT_E_INVALID: NULL ctx, rays or T_out; a NULL ray stream with n > 0.  n == 0 is valid and launches nothing.
+ * Stats (trt_enable_stats): shadow_tests = the tori started, primary_tests = bounce_tests = 0, pixels = n; traced_tests,
+ * solved_tests and evaluations as defined at trt_stats.
+ *
+ * trt_shade_through — trt_shade with translucent surfaces.  Rays, the `samples` layout, the averaging rule, the alignment
+ * of the image, the refusals and n == 0 are exactly trt_shade's.  The colour of one ray comes from trt_shade's loop (the
+ * window (0.001, 10000) on every segment, pc->maxDepth, the body runs once even for maxDepth <= 0) carrying a path
+ * throughput A (rgb, 1 at the start) and acc = 0.  Per segment, walk its crossings in order:
+ *   a == 0: the crossing is skipped — no shading, no shadow query.
+ *   otherwise: P, the normal N (never flipped: a wall met from inside is shaded with its outward normal), L, the diffuse
+ *     term and wantShadow = N.L > 0 as the closest-hit shader forms them (rchit:50-112); T = the transmittance of the
+ *     shadow ray (P, L) over (0.001, lightDistance) by the rule above if wantShadow, else 1;
+ *     att = fma(0.3f, 1.0f - T, T); spec = (T > 0 && wantShadow) ? compute_specular(...) * T : 0;
+ *     c = (att * lightIntensity) * (diffuse + spec); acc = fma(c, A * a, acc) per channel.
+ *     a < 1: A = A * p and the walk goes on — a translucent surface never reflects, whatever its illum.
+ *     a == 1 and illum == 3: the next segment is (P, reflect(d, N)) with A * Ks, and this segment ends.  As in the
+ *       reference, where rchit:149 scales the attenuation before rgen:76 adds, Ks weighs the mirror's own colour too:
+ *       A = A * Ks comes before the fma above.
+ *     a == 1 otherwise: the path ends.
+ *   out of crossings: acc = fma(clearColor * 0.8, A, acc) and the path ends.
+ * With every a in {0, 1} these expressions are, bit for bit, trt_shade's — on a scene of one torus the colours are
+ * trt_shade's wherever the first root does not fall to the interval test; with several tori the two calls may round t
+ * differently (trt_shade shrinks the window of later tori, this call never does).
+ * Stats (trt_enable_stats): primary_tests = n x n_tori, bounce_tests = n_tori per later segment, shadow_tests as in
+ * trt_transmittance (a shadow ray counts whatever its window), pixels = n; traced_tests, solved_tests and evaluations as
+ * defined at trt_stats.
+ * Not here: a fused camera variant, refraction / ior, coloured transmittance[3], transparency inside trt_render*.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+int trt_transmittance(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                      float tmin, float tmax, float* T_out);
+int trt_shade_through(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                      float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  The opacities are resolved on the host and travel in the kernel
+ * arguments: the calls use no scratch of the ctx, allocate nothing, synchronise nothing, put only kernel nodes on the
+ * stream and may be captured. */
+int trt_transmittance_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                          float tmin, float tmax, float* T_dev, void* stream);
+int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                          float* rgba_dev, void* stream);
 
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal
@@ -554,7 +619,8 @@ enum { TRT_CLOUD_KEEP_ALL = 0, TRT_CLOUD_MARK_MISSES = 1, TRT_CLOUD_COMPACT = 2 
 int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t n_records, int mode, int append,
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
-/* Counters of the last render, trace, occluded, crossings, shade, shade_camera or fan_occluded call made with counting enabled. */
+/* Counters of the last render, trace, occluded, crossings, shade, shade_camera, fan_occluded, transmittance or shade_through
+ * call made with counting enabled. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

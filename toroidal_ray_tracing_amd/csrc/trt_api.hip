@@ -892,7 +892,8 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
   return TRT_OK;
 }
 
-// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev), after the entry
+// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev,
+// trt_transmittance_dev, trt_shade_through_dev), after the entry
 // point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
@@ -1035,14 +1036,15 @@ extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
 // ------------------------------------------------------------------------------------------
 // shade: the render's bounce loop on caller-supplied rays, samples averaged
 // ------------------------------------------------------------------------------------------
-static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba)
+// (`who`: trt_shade or trt_shade_through, which takes the same rays, samples and image)
+static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba, const char* who = "trt_shade")
 {
-  if(ctx && (!in || !pc || !rgba)) return fail(ctx, TRT_E_INVALID, "trt_shade: NULL rays, push constants or image");
-  if(int rc = check_rays(ctx, in, "trt_shade")) return rc;
-  if(samples == 0) return fail(ctx, TRT_E_INVALID, "trt_shade: samples = 0, must be at least 1");
+  if(ctx && (!in || !pc || !rgba)) return fail(ctx, TRT_E_INVALID, "%s: NULL rays, push constants or image", who);
+  if(int rc = check_rays(ctx, in, who)) return rc;
+  if(samples == 0) return fail(ctx, TRT_E_INVALID, "%s: samples = 0, must be at least 1", who);
   if(in->n % samples)
-    return fail(ctx, TRT_E_INVALID, "trt_shade: n = %llu rays is not a multiple of samples = %u", (unsigned long long)in->n, samples);
-  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "trt_shade: the rgba image must be 16-byte aligned (it is written as float4)");
+    return fail(ctx, TRT_E_INVALID, "%s: n = %llu rays is not a multiple of samples = %u", who, (unsigned long long)in->n, samples);
+  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "%s: the rgba image must be 16-byte aligned (it is written as float4)", who);
   return TRT_OK;
 }
 extern "C" int trt_shade_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
@@ -1071,6 +1073,101 @@ extern "C" int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, con
   if(int rc = stage_rays(ctx, in, din)) return rc;
   if(int rc = stage_outs(ctx, &image, 1)) return rc;
   if(int rc = trt_shade_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// translucent surfaces: the soft shadow query, and trt_shade with "over" compositing of the crossings
+// ------------------------------------------------------------------------------------------
+// What trt_transmittance* and trt_shade_through* (`who`) share behind their own checks: the solver the enumeration runs,
+// the scene (validated here, so that a matId can be trusted), and the opacity of every torus from its material's
+// `dissolve` — the only readers of that field.  No scratch of the ctx: the table travels in the kernel arguments.
+static int through_opacity(trt_ctx* ctx, const char* who, const trt_scene* scene, Opacity& op)
+{
+  if(solver_of(ctx->precision).alt != kSolverWalk)
+    return fail(ctx, TRT_E_INVALID, "%s: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
+                                    "set one of them with trt_set_solver", who);
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  std::memset(&op, 0, sizeof op);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    const int   m = scene->tori[j].matId;
+    const float d = scene->materials[m].dissolve;
+    if(std::isnan(d))
+      return fail(ctx, TRT_E_SCENE, "%s: material %d (of torus %u) has a NaN dissolve; the opacity must be a number", who, m, j);
+    op.a[j] = std::fmin(std::fmax(d, 0.0f), 1.0f);
+    op.p[j] = 1.0f - op.a[j];
+  }
+  return TRT_OK;
+}
+
+static int check_transmittance(trt_ctx* ctx, const trt_rays* in, const float* T)
+{
+  if(int rc = check_rays(ctx, in, "trt_transmittance")) return rc;
+  if(!T) return fail(ctx, TRT_E_INVALID, "trt_transmittance: NULL output");
+  return TRT_OK;
+}
+extern "C" int trt_transmittance_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
+                                     float tmax, float* T, void* stream)
+{
+  if(int rc = check_transmittance(ctx, in, T)) return rc;
+  TransmittanceArgs a;
+  if(int rc = through_opacity(ctx, "trt_transmittance", scene, a.op)) return rc;
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.T            = T;
+  return ray_query(ctx, scene, stream, in->n, a, launch_transmittance);
+}
+
+// Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], T through buf[kBufOut].
+extern "C" int trt_transmittance(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
+                                 float tmax, float* T_out)
+{
+  if(int rc = check_transmittance(ctx, in, T_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_transmittance_dev(ctx, in, nullptr, scene, tmin, tmax, T_out, nullptr);   // validates, launches and writes nothing
+  const size_t bytes = (size_t)in->n * sizeof(float);
+  trt_rays din;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  const float* d_tmax = nullptr;
+  if(tmax_per_ray)
+    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
+  StagedOut out = {T_out, bytes, kBufOut, nullptr};
+  if(int rc = stage_outs(ctx, &out, 1)) return rc;
+  if(int rc = trt_transmittance_dev(ctx, &din, d_tmax, scene, tmin, tmax, (float*)out.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &out, 1);
+}
+
+extern "C" int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                                     float* rgba, void* stream)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba, "trt_shade_through")) return rc;
+  ShadeThroughArgs a;
+  if(int rc = through_opacity(ctx, "trt_shade_through", scene, a.op)) return rc;
+  a.rays    = *in;
+  a.n_out   = in->n / samples;
+  a.samples = samples;
+  a.pc      = *pc;
+  a.rgba    = rgba;
+  return ray_query(ctx, scene, stream, in->n, a, launch_shade_through);
+}
+
+// Host buffers: as trt_shade's.
+extern "C" int trt_shade_through(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                                 float* rgba_out)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, "trt_shade_through")) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_shade_through_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
+  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
+  trt_rays  din;
+  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  if(int rc = trt_shade_through_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
   return fetch_outs(ctx, &image, 1);
 }
 

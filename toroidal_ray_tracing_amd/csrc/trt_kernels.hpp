@@ -1,5 +1,5 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_rays.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// (trt_rays.hip, trt_through.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
 // trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
 // What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
@@ -209,6 +209,32 @@ struct ShadeArgs {
   unsigned long long* stats;
 };
 
+// trt_transmittance*, trt_shade_through*: the opacity a_j = clamp(dissolve, 0, 1) of torus j's material and its pass factor
+// p_j = 1.0f - a_j, resolved on the host and indexed by TORUS id (not by material).  They travel here, in the
+// kernel-argument segment, as FanArgs' table does: the calls use no scratch of the ctx, and SceneK stays what it was.
+struct Opacity {
+  float a[TRT_MAX_TORI], p[TRT_MAX_TORI];
+};
+// trt_transmittance*: OccludedArgs with a float per ray out — the product of p_id over the crossings of (tmin, tmax_i).
+struct TransmittanceArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  Opacity             op;
+  float*              T;
+  unsigned long long* stats;
+};
+// trt_shade_through*: ShadeArgs with the opacities; the kernel's dynamic LDS holds 4 * n_tori crossing slots per lane.
+struct ShadeThroughArgs {
+  trt_rays            rays;
+  uint64_t            n_out;
+  uint32_t            samples;   // >= 1, divides rays.n
+  trt_push            pc;
+  Opacity             op;
+  float*              rgba;
+  unsigned long long* stats;
+};
+
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
 // sample-major layout ShadeArgs reads.  Pinhole: the offsets (jx[s], jy[s]) travel here, in the kernel-argument segment.
@@ -239,7 +265,7 @@ struct ShadeCameraArgs {
 };
 
 // The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels,
-// the fan kernels; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
+// the fan kernels, transmittance_kernel, shade_through_kernel; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
 // points), at most 4096 blocks (TRT_TRACE_BLOCKS).
 inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
@@ -258,6 +284,8 @@ hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const T
 hipError_t launch_fan_rays(const FanRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_fan_occluded(const SceneK& scene, const FanOccludedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_transmittance(const SceneK& scene, const TransmittanceArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_shade_through(const SceneK& scene, const ShadeThroughArgs& a, const Tuning& tn, hipStream_t stream);    // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);

@@ -107,9 +107,7 @@ __global__ __launch_bounds__(256) void occluded_kernel(const SceneK scene, const
 // so the kept slots are the first slots of the untruncated answer.  Nobody but the lane reads its column: the only
 // barrier is stage_scene's, the only atomics the stats block add.  Stores are slot-major: one instruction, 64
 // consecutive elements of slot k.  The window test !(tmax > tmin) is kernel-uniform.
-constexpr uint32_t kCrossingSlotBytes = 256u * (sizeof(float) + sizeof(uint8_t));   // dynamic LDS per slot
-static_assert(TRT_MAX_TORI <= 128, "crossings_kernel packs id << 1 | entering into a byte");
-
+// (kCrossingSlotBytes, column_insert: trt_render.hpp — shade_through_kernel fills the same column)
 template <class Real, bool ORIENT = false>
 __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, const CrossingsArgs a)
 {
@@ -139,22 +137,7 @@ __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, cons
       {
         const int j = S.order[k];
         ++tests;
-        torus_crossings<Real, ORIENT>(S, j, r, wc, [&](float t, bool entering) {
-          uint32_t p = umin(count, K);   // slots kept so far
-          ++count;
-          if(p == K)
-          {
-            if(!(t < ct[(K - 1u) * 256u])) return;
-            p = K - 1u;
-          }
-          for(; p > 0u && ct[(p - 1u) * 256u] > t; --p)
-          {
-            ct[p * 256u] = ct[(p - 1u) * 256u];
-            cw[p * 256u] = cw[(p - 1u) * 256u];
-          }
-          ct[p * 256u] = t;
-          cw[p * 256u] = (uint8_t)(((uint32_t)j << 1) | (entering ? 1u : 0u));
-        });
+        torus_crossings<Real, ORIENT>(S, j, r, wc, [&](float t, bool entering) { column_insert(ct, cw, K, count, t, j, entering); });
       }
     }
     const uint32_t kept = umin(count, K);

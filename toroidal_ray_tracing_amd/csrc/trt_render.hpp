@@ -1,5 +1,5 @@
 // trt_render.hpp — what more than one kernel family of the render path uses.  Device side: included only by
-// trt_rays.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
+// trt_rays.hip, trt_through.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
 //
 //   gptr, st1 / st4 / st4c, ld1           global-memory accessors
 //   HitState, hit_begin, hit_end          the closest-hit shader body, split at the shadow query
@@ -9,6 +9,7 @@
 //   settle_loads, stage_args, stage_block256   staging into LDS
 //   kTMin, kTMax                          the ray window of the render kernels
 //   bounce_loop                           the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (shade_kernel)
+//   kCrossingSlotBytes, column_insert     the sorted crossing column of a lane in LDS
 //   live_slot, list_counts, TileCode, tile_x / tile_y, frame_args, LaunchArgs   the tile-list layout
 //   clear_macro                           the constant fill of one CLEAR macro tile
 //   with_orient, with_solver              launch dispatch: scene → <Real, ALT, ORIENT>
@@ -323,6 +324,34 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
     done      = 1;                                                         // rgen:84
   }
   return hitValue;
+}
+
+// ------------------------------------------------------------------------------------------
+// the sorted crossing column of a lane (crossings_kernel, shade_through_kernel)
+// ------------------------------------------------------------------------------------------
+// Slot k of lane `tid` at [k * 256 + tid] of dynamic LDS: K floats t, then K bytes id << 1 | entering (the layout and
+// its reasons: crossings_kernel, trt_rays.hip).  ct / cw point at the lane's slot 0; `count` is the number of crossings
+// met so far (it may exceed K).  Insertion is stable — a crossing goes behind every kept one with t <= its own — and
+// once the column is full only a crossing strictly below the last kept one gets in.  (Parameters by reference, as the
+// lambda this was captured them: passed by value, crossings_kernel comes out two VGPRs larger.)
+constexpr uint32_t kCrossingSlotBytes = 256u * (sizeof(float) + sizeof(uint8_t));   // dynamic LDS per slot
+static_assert(TRT_MAX_TORI <= 128, "the column packs id << 1 | entering into a byte");
+__device__ __forceinline__ void column_insert(float* const& ct, uint8_t* const& cw, const uint32_t& K, uint32_t& count, float t, const int& j, bool entering)
+{
+  uint32_t p = umin(count, K);   // slots kept so far
+  ++count;
+  if(p == K)
+  {
+    if(!(t < ct[(K - 1u) * 256u])) return;
+    p = K - 1u;
+  }
+  for(; p > 0u && ct[(p - 1u) * 256u] > t; --p)
+  {
+    ct[p * 256u] = ct[(p - 1u) * 256u];
+    cw[p * 256u] = cw[(p - 1u) * 256u];
+  }
+  ct[p * 256u] = t;
+  cw[p * 256u] = (uint8_t)(((uint32_t)j << 1) | (entering ? 1u : 0u));
 }
 
 // ------------------------------------------------------------------------------------------

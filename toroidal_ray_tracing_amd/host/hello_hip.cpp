@@ -183,6 +183,16 @@ void HelloHip::occluded(void* stream, const trt_rays& raysDev, const float* tmax
   check(trt_occluded_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, flagDev, maskDev, stream), "HelloHip::occluded");
 }
 
+void HelloHip::shadeThrough(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev)
+{
+  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
+  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
+  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
+  m_pcRay.lightType      = m_pcRaster.lightType;
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_shade_through_dev(m_ctx, &raysDev, samples, &m_pcRay, &scene, rgbaDev, stream), "HelloHip::shadeThrough");
+}
+
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {

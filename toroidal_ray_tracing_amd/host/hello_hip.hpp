@@ -59,6 +59,12 @@ public:
   void occluded(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax,
                 uint8_t* flagDev, uint64_t* maskDev);
 
+  // The payload loop on caller-supplied rays with translucent surfaces (trt_shade_through_dev): the push constants are
+  // refreshed as raytrace() refreshes them, then every ray of raysDev (sample-major, `samples` per output) is composited
+  // front to back through the tori added so far, a material's `dissolve` being its opacity — a material added with
+  // dissolve 0 is invisible here.  rgbaDev: (raysDev.n / samples) * 4 floats, 16-byte aligned.
+  void shadeThrough(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
+
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the
   // point's normal) against the tori added so far; one word of bits and / or the share of clear samples per point out.

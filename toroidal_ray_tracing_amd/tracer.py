@@ -209,6 +209,46 @@ class Tracer:
         self._check(self._L.trt_shade_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
                                           _vp(rgba_ptr), _vp(stream)))
 
+    # -- translucent surfaces: the soft shadow query, and shade with "over" compositing ---------
+    def transmittance(self, scene, o, d, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """The fraction of light that gets along each ray (trt_transmittance) on host arrays: o, d of shape (n,3),
+        tmax_per_ray as in ``occluded``.  The product over the walls crossed of 1 - clamp(dissolve, 0, 1) of their
+        material — a material with dissolve 0 (a zero-initialised one!) is invisible.  Returns float32 (n,)."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        T = np.empty(n, np.float32)
+        self._check(self._L.trt_transmittance(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), tmin, tmax, T.ctypes.data))
+        return T
+
+    def transmittance_dev(self, scene, ray_ptrs, n, T_ptr, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses; T_ptr: n floats; tmax_ptr: n per-ray bounds or 0.
+        Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_transmittance_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
+                                                  _vp(T_ptr), _vp(stream)))
+
+    def shade_through(self, scene, o, d, pc, samples=1):
+        """``shade`` with translucent surfaces (trt_shade_through) on host arrays: the crossings of every segment composited
+        front to back with the materials' ``dissolve`` as opacity, the shadow ray a transmittance.  Layout and averaging as
+        in ``shade``.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        samples = int(samples)
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
+        self._check(self._L.trt_shade_through(self._h, C.byref(rays), samples, C.byref(pc), self._scene(scene), rgba.ctypes.data))
+        return rgba
+
+    def shade_through_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
+        """Device pointers (ints): as ``shade_dev``.  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_shade_through_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
+                                                  _vp(rgba_ptr), _vp(stream)))
+
     # -- camera rays: the two cameras as ray streams, and the supersampled frame ------------
     @staticmethod
     def _offsets(offsets, samples):
