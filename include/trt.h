@@ -27,6 +27,10 @@
  *   walls: a fraction, not a bit   chapter's stochastic `dissolve` test)  trt_transmittance*
  *   payload loop with translucent  (none: the same expectation, "over"
  *   walls composited front to back compositing of trt_crossings' list)   trt_shade_through*
+ *   length of a ray inside every   (none: build-defined, the pairing of
+ *   torus' tube                    trt_crossings' entries and exits)     trt_chords*
+ *   emission and absorption of     (none: build-defined, the line integral
+ *   media that fill the tubes      of a synthetic diagnostic)            trt_glow*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -365,6 +369,81 @@ int trt_transmittance_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tma
 int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                           float* rgba_dev, void* stream);
 
+/* ---- media inside the tubes: chords(rays_in -> a length per ray and torus), glow(rays_in -> radiance, transmittance) -- */
+/* Every other call sees a torus as a surface.  These four see its tube as a volume: trt_chords returns how long every ray
+ * runs inside every torus' tube, trt_glow integrates emission and absorption of homogeneous media that fill the tubes
+ * (line-integrated emission: the picture a synthetic diagnostic of nested plasma shells gives).  Neither stores a
+ * crossing, both own the pairing of entries and exits, and both handle a ray that starts or ends inside a tube — also
+ * one that lies inside as a whole and meets no wall.  Materials are not read: a zero-initialised material is fine.
+ *
+ * Window.  Ray i has the window (tmin, tmax_i); with b = tmax_per_ray[i]: tmax_i = b > tmax ? tmax : b — the bound is
+ * clipped by the scalar, a NaN bound stays NaN, a NaN scalar clips nothing — and tmax_i = tmax with tmax_per_ray == NULL.
+ * (So trt_trace's t stream, +INFINITY on a miss, can be passed as it stands: "what lies in front of the first opaque
+ * wall".)  !(tmax_i > tmin) gives every length 0 and rgba = (0, 0, 0, 1) and executes no test.
+ * Crossings.  For torus j exactly trt_crossings' for that ray, window, axes and solver: every torus over the full window,
+ * no enclosure cull.  Solvers: TRT_SOLVE_F32 and TRT_SOLVE_F64 only; with any other solver set the calls return
+ * TRT_E_INVALID and the message says so, as trt_crossings does.
+ * Intervals of torus j (the pairing rule).  in0 and in1 are inside tests at the two end points of the window, t = tmin and
+ * t = tmax_i, in the solver's precision (Real = float or double) and in the frame the solver works in: (o, d) is the world
+ * ray and c the torus' centre, or, for a torus with an axis of its own (trt_set_torus_axes), (o, d) is the ray in the
+ * torus' frame as trt_trace forms it (o - C and d rotated) and c = 0.  P = fma(t, d, o) - c per component;
+ * q = sqrt(fma(Pz, Pz, Px * Px)) - R; inside iff fma(q, q, Py * Py) < r * r.  A non-finite point is outside.
+ * Walk j's crossings left to right — in trt_crossings' order: ascending t, and among equal t the root found first —
+ * carrying `open`, which starts at tmin if in0 and is none otherwise: an entering
+ * crossing opens an interval if none is open and is ignored otherwise; a leaving crossing closes the open interval and
+ * emits it, and is ignored if none is open; what is open after the last crossing is emitted up to tmax_i only if in1 and
+ * is dropped otherwise.  In exact arithmetic that is at most two intervals per torus.  A grazing contact or an unpaired
+ * root never produces a chord that runs to tmax = 10000; a window wholly inside a tube, with no crossing, is one interval.
+ * Length.  len = sqrtf((dx * dx + dy * dy) + dz * dz): lengths and coefficients are per unit of WORLD length, not of t.
+ *
+ * trt_chords.  length[j * n + i] is the length of ray i inside torus j (torus-major: each torus' lengths are a stream;
+ * the buffer holds n_tori * n floats): acc = 0, then acc = acc + (b - a) * len per interval (a, b) in order, plain FP32
+ * operations as written.  The lengths of torus j are, bit for bit, those of the scene that holds j alone.
+ *
+ * trt_glow.  media[j] = emission (rgb, radiance per unit length) and sigma (absorption per unit length) of the medium in
+ * torus j's tube: scene->n_tori host structs, copied before the call returns.  Where tubes overlap, the media add.
+ * A torus whose medium is all zero (the three emissions and sigma == 0) is not tested at all: it is absent, bit for bit,
+ * and counts no test.  The interval ends of the remaining tori are merged in ascending t into break points
+ * tmin = t_0 <= t_1 <= ... <= tmax_i; a torus is active on a piece (u, v) between consecutive break points if one of its
+ * intervals covers it.  L = 0, T = 1; then for every piece with v > u and at least one active torus, front to back:
+ *   l = (v - u) * len;  e_c and s = the FP32 sums of emission[c] and sigma over the active tori in ascending id, from 0;
+ *   tau = s * l;  E = 1 if s == 0, else exp2p(-tau * 1.44269504f), where exp2p(y) is the fixed polynomial of the post
+ *   pass: y clamped to [-126, 127], n = floor(y), z = (y - n) * 0.693147181f, the Taylor polynomial of exp(z) to z^9 by
+ *   Horner with fma, n added to the exponent bits — no math library, the same bits everywhere (E never underflows to 0:
+ *   the smallest E is 2^-126);
+ *   w = l if s == 0;  else, if tau < 0.25, w = l * P(tau), P(tau) = sum over k = 0..6 of (-tau)^k / (k + 1)! by Horner
+ *   with fma, so that small optical depths do not cancel (truncation below 1.6e-9 relative);  else w = (1 - E) / s;
+ *   L_c = fma(e_c * w, T, L_c) per channel, then T = T * E.
+ * rgba[4 i ..] = (L_r, L_g, L_b, T), 16-byte aligned: the radiance that reaches the ray's origin and the transmittance
+ * left; the caller composites L + T * behind over a background or a trt_shade colour.  With s == 0 and one torus,
+ * L_c = emission[c] * (trt_chords' length) to the last bit when emission[c] is a power of two.
+ *
+ * TRT_E_INVALID: NULL ctx, rays, scene, output or (trt_glow) media; a NULL ray stream with n > 0; an rgba that is not
+ * 16-byte aligned; a medium component that is negative, NaN or infinite (the message names the torus); the solver, as
+ * above; n_tori * n overflowing 64 bits (trt_chords).  n == 0 is valid and launches nothing.  A refused call leaves the
+ * ctx usable and the outputs unwritten.
+ * Stats (trt_enable_stats): primary_tests = the tori started, bounce_tests = shadow_tests = 0, pixels = n; traced_tests,
+ * solved_tests and evaluations as defined at trt_stats.
+ * Not here: a fused camera variant, media inside trt_render* / trt_shade*, scattering, a sigma per channel, density that
+ * varies inside a tube.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+typedef struct trt_medium {
+  float emission[3]; /* radiance emitted per unit world length, rgb; >= 0 and finite */
+  float sigma;       /* absorption per unit world length; >= 0 and finite            */
+} trt_medium;        /* 16 bytes                                                     */
+
+int trt_chords(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+               float tmin, float tmax, float* length_out);
+int trt_glow(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, const trt_medium* media,
+             float tmin, float tmax, float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  `media` stays a host pointer: the media travel in the kernel
+ * arguments.  The calls use no scratch of the ctx, allocate nothing, synchronise nothing, put only kernel nodes on the
+ * stream and may be captured. */
+int trt_chords_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                   float tmin, float tmax, float* length_dev, void* stream);
+int trt_glow_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene, const trt_medium* media,
+                 float tmin, float tmax, float* rgba_dev, void* stream);
+
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal
  * BEF/shaders/raytrace.rgen:21-57), handed out: as SoA streams that feed trt_trace / trt_occluded / trt_crossings /
@@ -620,7 +699,7 @@ int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t 
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
 /* Counters of the last render, trace, occluded, crossings, shade, shade_camera, fan_occluded, transmittance or shade_through
- * call made with counting enabled. */
+ * call made with counting enabled.  trt_chords and trt_glow count as well. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

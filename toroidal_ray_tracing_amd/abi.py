@@ -70,6 +70,27 @@ class trt_rendered_data(C.Structure):
                 ("rayOrigin", C.c_float * 4), ("rayDir", C.c_float * 4)]
 
 
+class trt_medium(C.Structure):
+    """The homogeneous medium that fills a torus' tube (trt_glow): per unit world length."""
+    _fields_ = [("emission", C.c_float * 3), ("sigma", C.c_float)]
+
+
+def media(items):
+    """A ``trt_medium`` array for trt_glow, one entry per torus: each item is ((er, eg, eb), sigma), a dict with
+    ``emission`` and / or ``sigma`` (missing: 0), or None for no medium.  An array made here is passed through."""
+    if isinstance(items, C.Array) and items._type_ is trt_medium:
+        return items
+    items = list(items)
+    arr = (trt_medium * max(len(items), 1))()
+    for m, it in zip(arr, items):
+        if it is None:
+            continue
+        e, s = (it.get("emission", (0.0, 0.0, 0.0)), it.get("sigma", 0.0)) if isinstance(it, dict) else it
+        m.emission[:] = [float(v) for v in e]
+        m.sigma = float(s)
+    return arr
+
+
 class trt_rays(C.Structure):
     _fields_ = [("ox", C.c_void_p), ("oy", C.c_void_p), ("oz", C.c_void_p),
                 ("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p),

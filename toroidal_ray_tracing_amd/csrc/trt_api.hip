@@ -893,7 +893,7 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 }
 
 // The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev,
-// trt_transmittance_dev, trt_shade_through_dev), after the entry
+// trt_transmittance_dev, trt_shade_through_dev, trt_chords_dev, trt_glow_dev), after the entry
 // point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
@@ -1168,6 +1168,121 @@ extern "C" int trt_shade_through(trt_ctx* ctx, const trt_rays* in, uint32_t samp
   if(int rc = stage_rays(ctx, in, din)) return rc;
   if(int rc = stage_outs(ctx, &image, 1)) return rc;
   if(int rc = trt_shade_through_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// media inside the tubes: the length of every ray in every tube, and the emission-absorption integral
+// ------------------------------------------------------------------------------------------
+// What trt_chords* and trt_glow* (`who`) share: the rays, the output, and the solver the enumeration runs.
+static int check_media(trt_ctx* ctx, const trt_rays* in, const void* out, const char* who)
+{
+  if(int rc = check_rays(ctx, in, who)) return rc;
+  if(!out) return fail(ctx, TRT_E_INVALID, "%s: NULL output", who);
+  if(solver_of(ctx->precision).alt != kSolverWalk)
+    return fail(ctx, TRT_E_INVALID, "%s: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
+                                    "set one of them with trt_set_solver", who);
+  return TRT_OK;
+}
+
+static int check_chords(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, const float* length)
+{
+  if(int rc = check_media(ctx, in, length, "trt_chords")) return rc;
+  if(scene && scene->n_tori && in->n > UINT64_MAX / scene->n_tori)
+    return fail(ctx, TRT_E_INVALID, "trt_chords: n_tori * n overflows 64 bits");
+  return TRT_OK;
+}
+extern "C" int trt_chords_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
+                              float tmax, float* length, void* stream)
+{
+  if(int rc = check_chords(ctx, in, scene, length)) return rc;
+  ChordsArgs a;
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.length       = length;
+  return ray_query(ctx, scene, stream, in->n, a, launch_chords);
+}
+
+// Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], the n_tori streams through buf[kBufOut].
+extern "C" int trt_chords(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
+                          float tmax, float* length_out)
+{
+  if(int rc = check_chords(ctx, in, scene, length_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0 || !scene) return trt_chords_dev(ctx, in, nullptr, scene, tmin, tmax, length_out, nullptr);   // validates, launches and writes nothing
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
+  if(in->n > SIZE_MAX / sizeof(float) / scene->n_tori) return fail(ctx, TRT_E_NOMEM, "trt_chords: n_tori * n floats do not fit the address space");
+  const size_t bytes = (size_t)in->n * sizeof(float);
+  trt_rays din;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  const float* d_tmax = nullptr;
+  if(tmax_per_ray)
+    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
+  StagedOut out = {length_out, bytes * scene->n_tori, kBufOut, nullptr};
+  if(int rc = stage_outs(ctx, &out, 1)) return rc;
+  if(int rc = trt_chords_dev(ctx, &din, d_tmax, scene, tmin, tmax, (float*)out.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &out, 1);
+}
+
+// The media of trt_glow*, validated (the scene first, so that n_tori can be trusted) and copied into the kernel arguments.
+static int glow_media(trt_ctx* ctx, const trt_scene* scene, const trt_medium* media, Media& out)
+{
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  std::memset(&out, 0, sizeof out);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    const float v[4] = {media[j].emission[0], media[j].emission[1], media[j].emission[2], media[j].sigma};
+    for(int c = 0; c < 4; ++c)
+      if(!(v[c] >= 0.0f) || std::isinf(v[c]))
+        return fail(ctx, TRT_E_INVALID, "trt_glow: the medium of torus %u has %s = %g; emission and sigma must be finite and not negative",
+                    j, c < 3 ? "an emission" : "sigma", (double)v[c]);
+    out.m[j] = media[j];
+    if(v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f || v[3] != 0.0f)
+      out.present |= 1u << j;
+  }
+  return TRT_OK;
+}
+static int check_glow(trt_ctx* ctx, const trt_rays* in, const trt_medium* media, const float* rgba)
+{
+  if(int rc = check_media(ctx, in, rgba, "trt_glow")) return rc;
+  if(!media) return fail(ctx, TRT_E_INVALID, "trt_glow: NULL media");
+  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "trt_glow: the rgba output must be 16-byte aligned (it is written as float4)");
+  return TRT_OK;
+}
+extern "C" int trt_glow_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, const trt_medium* media,
+                            float tmin, float tmax, float* rgba, void* stream)
+{
+  if(int rc = check_glow(ctx, in, media, rgba)) return rc;
+  GlowArgs a;
+  if(int rc = glow_media(ctx, scene, media, a.media)) return rc;
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.rgba         = rgba;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow);
+}
+
+// Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], the float4 per ray through buf[kBufRgba].
+extern "C" int trt_glow(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, const trt_medium* media,
+                        float tmin, float tmax, float* rgba_out)
+{
+  if(int rc = check_glow(ctx, in, media, rgba_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_glow_dev(ctx, in, nullptr, scene, media, tmin, tmax, rgba_out, nullptr);   // validates, launches and writes nothing
+  const size_t bytes = (size_t)in->n * sizeof(float);
+  trt_rays din;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  const float* d_tmax = nullptr;
+  if(tmax_per_ray)
+    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
+  StagedOut image = {rgba_out, bytes * 4, kBufRgba, nullptr};
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  if(int rc = trt_glow_dev(ctx, &din, d_tmax, scene, media, tmin, tmax, (float*)image.dev, nullptr)) return rc;
   return fetch_outs(ctx, &image, 1);
 }
 

@@ -1,5 +1,5 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_rays.hip, trt_through.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// (trt_rays.hip, trt_through.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
 // trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
 // What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
@@ -235,6 +235,32 @@ struct ShadeThroughArgs {
   unsigned long long* stats;
 };
 
+// trt_chords*, trt_glow*: ray i has the window (tmin, min(tmax_per_ray[i], tmax)); tmax_per_ray == nullptr: every ray ends at tmax.
+// trt_chords*: the length of ray i inside torus j's tube at length[j * rays.n + i] (torus-major: n_tori streams).
+struct ChordsArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  float*              length;
+  unsigned long long* stats;
+};
+// The media of trt_glow*, indexed by TORUS id, validated and copied on the host; bit j of `present`: medium j is not all
+// zero (a torus without that bit is never tested).  They travel here, in the kernel-argument segment, as Opacity does
+// (128 B for eight tori): the calls use no scratch of the ctx, and the kernel reads them with scalar loads.
+struct Media {
+  trt_medium m[TRT_MAX_TORI];
+  uint32_t   present;
+};
+// trt_glow*: (L_r, L_g, L_b, T) of ray i at rgba[4 i], 16-byte aligned; the kernel's dynamic LDS holds 4 * n_tori slots per lane.
+struct GlowArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  Media               media;
+  float*              rgba;
+  unsigned long long* stats;
+};
+
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
 // sample-major layout ShadeArgs reads.  Pinhole: the offsets (jx[s], jy[s]) travel here, in the kernel-argument segment.
@@ -265,7 +291,7 @@ struct ShadeCameraArgs {
 };
 
 // The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels,
-// the fan kernels, transmittance_kernel, shade_through_kernel; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
+// the fan kernels, transmittance_kernel, shade_through_kernel, chords_kernel, glow_kernel; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
 // points), at most 4096 blocks (TRT_TRACE_BLOCKS).
 inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
@@ -286,6 +312,8 @@ hipError_t launch_fan_occluded(const SceneK& scene, const FanOccludedArgs& a, co
 hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_transmittance(const SceneK& scene, const TransmittanceArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_shade_through(const SceneK& scene, const ShadeThroughArgs& a, const Tuning& tn, hipStream_t stream);    // default solver only
+hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream);       // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);

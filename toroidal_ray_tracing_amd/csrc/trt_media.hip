@@ -1,0 +1,288 @@
+// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*), gfx950.
+//
+//   tube_inside      whether the point of a ray at parameter t lies inside torus j's tube
+//   tube_intervals   the pairing rule: torus j's crossings and the two inside tests → at most two intervals
+//   chords_kernel    chords(rays_in → the length of every ray inside every tube): n_tori coalesced streams out.
+//   glow_kernel      glow(rays_in → radiance and the transmittance left): the emission–absorption integral over the
+//                    pieces between the merged interval ends, one float4 per ray out.
+//   launch_chords, launch_glow   their grid and launch wrappers.
+//
+// The crossings of torus j are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
+// window, no enclosure cull); include/trt.h states the arithmetic of everything on top of them, expression by expression.
+// The media come in the kernel arguments (Media, trt_kernels.hpp); SceneK knows nothing of them and no material is read.
+// Default solver only: instantiated for <float | double> × ORIENT.  Compiled with -ffp-contract=off like every unit.
+#include "trt_render.hpp"
+
+namespace trt {
+
+// ------------------------------------------------------------------------------------------
+// the pairing rule
+// ------------------------------------------------------------------------------------------
+// P = fma(t, d, o) per component in the solver precision, (o, d) being the ray torus_crossings() hands the solver: the
+// world ray and torus_k()'s centre, or — wave-uniform — the ray in the frame of an oriented torus and a centre of zero.
+// q = sqrt(fma(pz, pz, px·px)) − R; inside iff fma(q, q, py·py) < r².  A non-finite point compares false: outside.
+template <class Real, bool ORIENT>
+__device__ __forceinline__ bool tube_inside(const SceneK& S, int i, const RayK<Real>& r, float t)
+{
+  LocalRay<Real> l = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+  TorusK<Real>   T = torus_k<Real>(S, i);
+  if constexpr(ORIENT)
+    if(is_oriented(S, i))
+    {
+      l.set(S, i, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+      T = centred(T);
+    }
+  const Real px = fma_((Real)t, l.dx, l.ox) - T.cx, py = fma_((Real)t, l.dy, l.oy) - T.cy, pz = fma_((Real)t, l.dz, l.oz) - T.cz;
+  const Real q  = sqrt_(fma_(pz, pz, px * px)) - T.R;
+  return fma_(q, q, py * py) < T.r2;
+}
+
+// emit(a, b, from_start, to_end) per interval of torus j inside the window (r.tmin, r.tmax) of ray r, left to right:
+// from_start — a is r.tmin because the window starts inside the tube; to_end — b is r.tmax because it ends inside.
+// The torus' at most four crossings are first put in trt_crossings' order — ascending t, a crossing behind every earlier
+// one with t <= its own (column_insert's stable rule): the two roots of a grazing contact can come out of the solver's
+// polish in descending order, and walked as found they would close an interval before it opens — in four registers and
+// four flags, by select chains (nothing is indexed: no private array that could go to scratch).  Then the walk carries
+// one open interval: an entering crossing opens one if none is open, a leaving one closes and emits it, both are ignored
+// otherwise; what is still open behind the last crossing is emitted only if the window's end point lies inside, and
+// dropped if not.  At most two intervals in exact arithmetic.
+template <class Real, bool ORIENT, class Emit>
+__device__ __forceinline__ void tube_intervals(const SceneK& S, int j, const RayK<Real>& r, WorkCount& wc, Emit&& emit)
+{
+  const bool  in0 = tube_inside<Real, ORIENT>(S, j, r, r.tmin), in1 = tube_inside<Real, ORIENT>(S, j, r, r.tmax);
+  const float inf = __builtin_inff();
+  float t0 = inf, t1 = inf, t2 = inf, t3 = inf;   // (a crossing has t < tmax: an unused slot never compares <= t)
+  bool  e0 = false, e1 = false, e2 = false, e3 = false;
+  int   n  = 0;
+  torus_crossings<Real, ORIENT>(S, j, r, wc, [&](float t, bool entering) {
+    const bool c0 = t0 <= t, c1 = t1 <= t, c2 = t2 <= t;   // sorted: c2 implies c1 implies c0
+    t3 = c2 ? t : t2;   e3 = c2 ? entering : e2;
+    t2 = c2 ? t2 : (c1 ? t : t1);   e2 = c2 ? e2 : (c1 ? entering : e1);
+    t1 = c1 ? t1 : (c0 ? t : t0);   e1 = c1 ? e1 : (c0 ? entering : e0);
+    t0 = c0 ? t0 : t;   e0 = c0 ? e0 : entering;
+    ++n;
+  });
+  float open = r.tmin;
+  bool  has = in0, first = in0;
+  for(int k = 0; k < n && k < 4; ++k)
+  {
+    const float t        = k == 0 ? t0 : (k == 1 ? t1 : (k == 2 ? t2 : t3));
+    const bool  entering = k == 0 ? e0 : (k == 1 ? e1 : (k == 2 ? e2 : e3));
+    if(entering)
+    {
+      if(!has)
+      {
+        open = t;
+        has  = true;
+      }
+    }
+    else if(has)
+    {
+      emit(open, t, first, false);
+      has   = false;
+      first = false;
+    }
+  }
+  if(has && in1)
+    emit(open, r.tmax, first, true);
+}
+
+// The window of ray i: the per-ray bound clipped by the scalar (a NaN bound stays NaN and empties the window).
+__device__ __forceinline__ float window_end(const float* tmax_per_ray, uint64_t i, float tmax)
+{
+  const float b = tmax_per_ray ? ((gptr<const float>)tmax_per_ray)[i] : tmax;
+  return b > tmax ? tmax : b;
+}
+// World length per unit of t.
+__device__ __forceinline__ float ray_length(v3 d) { return sqrt_((d.x * d.x + d.y * d.y) + d.z * d.z); }
+
+// ------------------------------------------------------------------------------------------
+// chords(rays_in → n_tori streams of lengths)
+// ------------------------------------------------------------------------------------------
+// One lane per ray, no LDS beyond the scene.  The torus loop is wave-uniform, so the store of torus j is one
+// instruction of 64 consecutive floats of stream j.  A ray whose window is empty executes no test and stores zeros.
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256) void chords_kernel(const SceneK scene, const ChordsArgs a)
+{
+  __shared__ SceneK S;
+  stage_scene<ORIENT>(&S, scene);
+
+  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
+  {
+    const float tmax   = window_end(a.tmax_per_ray, i, a.tmax);
+    const bool  window = tmax > a.tmin;
+    RayK<Real>  r;
+    float       len = 0.0f;
+    if(window)
+    {
+      const v3 o = {ox[i], oy[i], oz[i]};
+      const v3 d = {dx[i], dy[i], dz[i]};
+      r.set(o, d, a.tmin, tmax);
+      len = ray_length(d);
+    }
+    for(int k = 0; k < S.n_tori; ++k)
+    {
+      const int j   = S.order[k];
+      float     acc = 0.0f;
+      if(window)
+      {
+        ++tests;
+        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool, bool) { acc = acc + (v - u) * len; });
+      }
+      st1(a.length, (uint64_t)j * a.rays.n + i, acc);
+    }
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
+// glow(rays_in → radiance and transmittance)
+// ------------------------------------------------------------------------------------------
+// (1 − exp(−τ)) / τ for τ < kGlowSeries, where the quotient would cancel: its series Σ (−τ)^k / (k + 1)! to τ⁶ (the
+// first term left out is below 1.6e-9 there), Horner with fma.
+constexpr float kGlowSeries = 0.25f;
+__device__ __forceinline__ float one_minus_exp_over(float tau)
+{
+  float p = fma_(tau, 1.98412698e-4f, -1.38888889e-3f);   // 1/7!, -1/6!
+  p = fma_(tau, p, 8.33333333e-3f);                       // 1/5!
+  p = fma_(tau, p, -4.16666667e-2f);                      // -1/4!
+  p = fma_(tau, p, 1.66666667e-1f);                       // 1/3!
+  p = fma_(tau, p, -0.5f);
+  return fma_(tau, p, 1.0f);
+}
+
+// One lane owns one ray.  A torus with a medium (bit j of media.present) goes through the pairing rule; the ends of its
+// intervals go into the lane's sorted column in dynamic LDS (column_insert: crossings_kernel's layout, K = 4 · n_tori
+// slots — two intervals per torus at most, so nothing is ever truncated) with the byte id << 1 | 1 for a start and
+// id << 1 for an end.  An interval that starts with the window is a bit of the initial active mask instead of a slot,
+// and one that ends with the window has no end slot: the last piece closes it.  Then the pieces between consecutive
+// break points are walked front to back.  The sums over the active tori are a loop over the torus id that is uniform
+// for the wave (its bound and the media come from the kernel arguments: scalar loads), predicated by the lane's mask.
+// Equal break points give an empty piece, which is skipped: their order in the column does not matter.
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256) void glow_kernel(const SceneK scene, const GlowArgs a)
+{
+  __shared__ SceneK S;
+  extern __shared__ float crossing_lds[];   // [K][256] t, then [K][256] bytes
+  stage_scene<ORIENT>(&S, scene);
+
+  const uint32_t K  = 4u * (uint32_t)S.n_tori;
+  float*         ct = crossing_lds + threadIdx.x;
+  uint8_t*       cw = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
+
+  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
+  {
+    const float tmax = window_end(a.tmax_per_ray, i, a.tmax);
+    float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f;
+    if(tmax > a.tmin)
+    {
+      const v3 o = {ox[i], oy[i], oz[i]};
+      const v3 d = {dx[i], dy[i], dz[i]};
+      RayK<Real> r;
+      r.set(o, d, a.tmin, tmax);
+      const float len = ray_length(d);
+      uint32_t active = 0u, count = 0u;
+      for(int k = 0; k < S.n_tori; ++k)
+      {
+        const int j = S.order[k];
+        if(!((a.media.present >> j) & 1u))
+          continue;
+        ++tests;
+        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
+          if(from_start) active |= 1u << j;
+          else column_insert(ct, cw, K, count, u, j, true);
+          if(!to_end) column_insert(ct, cw, K, count, v, j, false);
+        });
+      }
+      float u = a.tmin;
+      for(uint32_t k = 0; k <= count; ++k)
+      {
+        const bool     last = k == count;
+        const float    v    = last ? tmax : ct[k * 256u];
+        const uint32_t w    = last ? 0u : cw[k * 256u];
+        if(active != 0u && v > u)
+        {
+          float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f, sg = 0.0f;
+          for(int j = 0; j < scene.n_tori; ++j)
+            if((active >> j) & 1u)
+            {
+              e0 = e0 + a.media.m[j].emission[0];
+              e1 = e1 + a.media.m[j].emission[1];
+              e2 = e2 + a.media.m[j].emission[2];
+              sg = sg + a.media.m[j].sigma;
+            }
+          const float l   = (v - u) * len;
+          const float tau = sg * l;
+          float E = 1.0f, wgt = l;
+          if(sg != 0.0f)
+          {
+            E   = exp2_poly(-tau * 1.44269504f);
+            wgt = tau < kGlowSeries ? l * one_minus_exp_over(tau) : (1.0f - E) / sg;
+          }
+          Lr = fma_(e0 * wgt, T, Lr);
+          Lg = fma_(e1 * wgt, T, Lg);
+          Lb = fma_(e2 * wgt, T, Lb);
+          T  = T * E;
+        }
+        const uint32_t bit = 1u << (w >> 1);
+        if(!last)
+          active = (w & 1u) ? (active | bit) : (active & ~bit);
+        u = v;
+      }
+    }
+    st4(a.rgba + 4 * i, make_float4(Lr, Lg, Lb, T));
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
+// launch wrappers
+// ------------------------------------------------------------------------------------------
+// Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here).
+hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.rays.n, tn);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;
+    else
+    {
+      hipLaunchKernelGGL((chords_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+      return hipGetLastError();
+    }
+  });
+}
+
+// 4 · n_tori slots per lane: 5 KiB of columns for one torus, 40 KiB for eight (shade_through_kernel's).
+hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.rays.n, tn);
+  const uint32_t lds  = 4u * (uint32_t)scene.n_tori * kCrossingSlotBytes;
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;
+    else
+    {
+      hipLaunchKernelGGL((glow_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, scene, a);
+      return hipGetLastError();
+    }
+  });
+}
+
+}  // namespace trt

@@ -193,6 +193,19 @@ void HelloHip::shadeThrough(void* stream, const std::array<float, 4>& clearColor
   check(trt_shade_through_dev(m_ctx, &raysDev, samples, &m_pcRay, &scene, rgbaDev, stream), "HelloHip::shadeThrough");
 }
 
+void HelloHip::chords(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_chords_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, lengthDev, stream), "HelloHip::chords");
+}
+
+void HelloHip::glow(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_medium* media, float tmin, float tmax,
+                    float* rgbaDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, media, tmin, tmax, rgbaDev, stream), "HelloHip::glow");
+}
+
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {

@@ -65,6 +65,15 @@ public:
   // dissolve 0 is invisible here.  rgbaDev: (raysDev.n / samples) * 4 floats, 16-byte aligned.
   void shadeThrough(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
 
+  // Media inside the tubes of the tori added so far (trt_chords_dev, trt_glow_dev; materials are not read).  chords: the
+  // length of every ray of raysDev inside every tube, lengthDev[j * raysDev.n + i] for torus j (the order of the
+  // addTorus calls).  glow: emission and absorption of media (one trt_medium per torus, host memory) integrated along
+  // every ray; rgbaDev: raysDev.n * 4 floats, 16-byte aligned, (radiance rgb, transmittance left) per ray — composite
+  // L + T * behind.  Ray i ends at min(tmaxPerRayDev[i], tmax), or at tmax if tmaxPerRayDev is null.
+  void chords(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev);
+  void glow(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_medium* media, float tmin, float tmax,
+            float* rgbaDev);
+
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the
   // point's normal) against the tori added so far; one word of bits and / or the share of clear samples per point out.

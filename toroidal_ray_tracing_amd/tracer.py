@@ -249,6 +249,57 @@ class Tracer:
         self._check(self._L.trt_shade_through_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
                                                   _vp(rgba_ptr), _vp(stream)))
 
+    # -- media inside the tubes: chord lengths, and the emission-absorption integral ---------
+    def chords(self, scene, o, d, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """The length of each ray inside each torus' tube (trt_chords) on host arrays: o, d of shape (n,3), tmax_per_ray
+        as in ``occluded`` (here clipped by ``tmax``).  World units, not units of t; a ray that starts or ends inside a
+        tube counts from / to its window's end.  Returns float32 (n_tori, n)."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        length = np.empty((scene.n_tori, n), np.float32)
+        self._check(self._L.trt_chords(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), tmin, tmax, length.ctypes.data))
+        return length
+
+    def chords_dev(self, scene, ray_ptrs, n, length_ptr, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses; length_ptr: n_tori * n floats, torus-major; tmax_ptr: n per-ray
+        bounds or 0.  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_chords_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
+                                           _vp(length_ptr), _vp(stream)))
+
+    def glow(self, scene, o, d, media, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """Emission and absorption of the media that fill the tubes, integrated along each ray (trt_glow) on host arrays:
+        media as ``abi.media`` takes them, one per torus — ((er, eg, eb), sigma) per unit world length.  Returns float32
+        (n, 4): the radiance that reaches the origin and the transmittance left; composite ``L + T * behind``."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        rgba = np.empty((n, 4), np.float32)
+        self._check(self._L.trt_glow(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), self._media(scene, media),
+                                     tmin, tmax, rgba.ctypes.data))
+        return rgba
+
+    def glow_dev(self, scene, ray_ptrs, n, media, rgba_ptr, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses; rgba_ptr: n * 4 floats, 16-byte aligned; tmax_ptr: n per-ray
+        bounds or 0; ``media`` stays on the host (it travels in the launch's arguments).  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_glow_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), self._media(scene, media),
+                                         tmin, tmax, _vp(rgba_ptr), _vp(stream)))
+
+    @staticmethod
+    def _media(scene, media):
+        if media is None:
+            return None
+        arr = abi.media(media)
+        if len(arr) < scene.n_tori:
+            raise ValueError(f"{len(arr)} media for {scene.n_tori} tori: trt_glow reads one per torus")
+        return arr
+
     # -- camera rays: the two cameras as ray streams, and the supersampled frame ------------
     @staticmethod
     def _offsets(offsets, samples):
