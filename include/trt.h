@@ -27,6 +27,8 @@
  *   walls: a fraction, not a bit   chapter's stochastic `dissolve` test)  trt_transmittance*
  *   payload loop with translucent  (none: the same expectation, "over"
  *   walls composited front to back compositing of trt_crossings' list)   trt_shade_through*
+ *   payload loop with glass tori:  (none: MTL illum 6 / 7, GLSL refract()    trt_shade_refract* /
+ *   refraction, total reflection   with the materials' ior)              trt_shade_refract_camera*
  *   length of a ray inside every   (none: build-defined, the pairing of
  *   torus' tube                    trt_crossings' entries and exits)     trt_chords*
  *   emission and absorption of     (none: build-defined, the line integral
@@ -110,10 +112,10 @@ typedef struct trt_material {
   float   ambient[3];
   float   diffuse[3];
   float   specular[3];
-  float   transmittance[3];
+  float   transmittance[3];  /* MTL `Tf`, the filter of a glass wall.  Read by trt_shade_refract* ONLY; see there */
   float   emission[3];
   float   shininess;
-  float   ior;
+  float   ior;       /* MTL `Ni`.  Read by trt_shade_refract* ONLY, for the materials of illum 6 / 7; see there */
   float   dissolve;  /* MTL `d`, the opacity.  Read by trt_transmittance* and trt_shade_through* ONLY; see there */
   int32_t illum;
   int32_t textureId; /* must be -1: tori are untextured (REFL rchit:100)                */
@@ -355,7 +357,8 @@ int trt_shade_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const 
  * Stats (trt_enable_stats): primary_tests = n x n_tori, bounce_tests = n_tori per later segment, shadow_tests as in
  * trt_transmittance (a shadow ray counts whatever its window), pixels = n; traced_tests, solved_tests and evaluations as
  * defined at trt_stats.
- * Not here: a fused camera variant, refraction / ior, coloured transmittance[3], transparency inside trt_render*.
+ * Not here: a fused camera variant, transparency inside trt_render*; refraction / ior and the coloured transmittance[3]
+ * are trt_shade_refract*'s (below), which in turn knows nothing of `dissolve`.
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_transmittance(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                       float tmin, float tmax, float* T_out);
@@ -368,6 +371,72 @@ int trt_transmittance_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tma
                           float tmin, float tmax, float* T_dev, void* stream);
 int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                           float* rgba_dev, void* stream);
+
+/* ---- glass tori: shade_refract(rays_in -> colours), shade_refract_camera(camera -> the band of an image) ------------ */
+/* Every other path the library follows is straight between mirror bounces.  These four bend it: a torus whose material
+ * has illum 6 or 7 — MTL's two "refraction on" models; Fresnel is not modelled, so the two are the same here — is a
+ * dielectric, and the path goes on through its wall along the refracted ray.  They are the only readers of `ior` and
+ * `transmittance[3]`.
+ *
+ * !!  A ZERO-INITIALISED trt_material HAS ior == 0.  These four calls REFUSE a glass material with such an ior when a   !!
+ * !!  torus uses it; they never bend light by 1/0.  (Every other call ignores both fields, whatever they hold.)         !!
+ *
+ * Glass data of torus j: n_j = ior and Tf_j = transmittance[3] of its material, inv_j = 1.0f / n_j (one FP32 division on
+ * the host).  TRT_E_SCENE, with a message naming the material, from these four calls alone: a glass material that some
+ * torus uses whose ior is NaN, infinite or <= 0, or whose transmittance has a NaN, infinite or negative component.  The
+ * same values on a material no torus uses, or on a material of any other illum, are accepted.  `dissolve` is not read.
+ * Every other illum behaves as in trt_shade; illum == 3 is still the mirror.
+ *
+ * trt_shade_refract — trt_shade with glass.  Rays, the `samples` layout, the averaging rule, the alignment of the image,
+ * the refusals and n == 0 are exactly trt_shade's; the ctx's solver (every TRT_SOLVE_*) and torus axes apply, as only the
+ * closest hit of a segment is needed.  The loop is trt_shade's: the window (0.001, 10000) on every segment, pc->maxDepth
+ * (the body runs once even for maxDepth <= 0), clearColor * 0.8 on a miss, the light of pc, the OPAQUE any-hit shadow
+ * query, hitValue = fma(prdHit, attenuation, hitValue).  Every segment, glass or not, counts towards maxDepth.
+ * A glass hit is shaded exactly as a non-mirror hit: P, the outward normal N (never flipped), L, the shadow bit, diffuse
+ * plus specular.  Then, before that fma — as the mirror scales the attenuation by Ks before its own colour is added
+ * (rchit:149 before rgen:76) — in FP32, every operation rounded once, in this order (fma where written, no other
+ * contraction; d the segment's direction):
+ *     I    = d * (1.0f / sqrt(fma(d.z, d.z, fma(d.y, d.y, d.x * d.x))))              (normalize)
+ *     c    = fma(N.z, I.z, fma(N.y, I.y, N.x * I.x));   entering = c < 0
+ *     Nf   = entering ? N : -N;   eta = entering ? inv_j : n_j;   cosi = -(Nf . I)   (the same fma chain, negated)
+ *     k    = 1.0f - (eta * eta) * (1.0f - cosi * cosi)
+ *     k < 0 (total internal reflection):  nextD = reflect(I, Nf) = fma(-(2.0f * (Nf . I)), Nf, I); the attenuation is untouched
+ *     otherwise:  m = eta * cosi - sqrt(k);   nextD = fma(m, Nf, eta * I) per component      (GLSL refract)
+ *                 and, if entering, attenuation = attenuation * Tf_j per channel
+ *     nextO = P, and the path goes on.
+ * The filter is applied once per passage, on the way in, so it tints the wall's own colour as Ks tints the mirror's.
+ * Stateless: only the sign of N.I at the hit decides between entering and leaving; the path carries no "inside" flag, and
+ * the other side of a wall is always vacuum (eta is 1/n or n, never n_a/n_b).  A chord shorter than tMin, on which the
+ * exit is dropped, or overlapping glass tubes therefore give a consistent answer, if an unphysical one.
+ * With no glass material in use the colours and the counters are, bit for bit, trt_shade's.
+ * Enclosure cull: as in trt_shade until the first glass hit of a path; from there on the path's mask is cleared and no
+ * longer grows (the refracted segment starts inside a tube, and the shells nested in it are what it hits); the shadow
+ * ray of a hit still skips the tubes inside the torus it leaves outwards.  By the contract at trt_scene no colour and no
+ * query count depends on it.
+ * Stats (trt_enable_stats): primary_tests = n x n_tori, bounce_tests = n_tori per later segment, shadow_tests as trt_shade
+ * counts them, pixels = n; traced_tests, solved_tests and evaluations as defined at trt_stats.
+ *
+ * trt_shade_refract_camera — trt_shade_camera with glass: arguments, band addressing, offsets, the toroidal-table contract,
+ * refusals and row_begin == row_end exactly as there.  Bit for bit trt_camera_rays put through trt_shade_refract;
+ * pixels = samples x the pixels of the band.
+ *
+ * Not here: a Fresnel split or a reflected branch (a path has one successor); light through glass in the shadow query —
+ * glass casts an opaque shadow — and caustics; Beer-Lambert absorption along the inside chord; nested or overlapping
+ * dielectrics with a medium stack; glass inside trt_render*.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+int trt_shade_refract(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                      float* rgba_out);
+int trt_shade_refract_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W,
+                             uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
+                             const float* offsets, float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  The glass data is resolved on the host and travels in the kernel
+ * arguments: the calls use no scratch of the ctx beyond the toroidal tables of the camera form, allocate nothing,
+ * synchronise nothing, put only kernel nodes on the stream and may be captured (the toroidal camera: as trt_shade_camera_dev). */
+int trt_shade_refract_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                          float* rgba_dev, void* stream);
+int trt_shade_refract_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W,
+                                 uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
+                                 const float* offsets, float* rgba_dev, void* stream);
 
 /* ---- media inside the tubes: chords(rays_in -> a length per ray and torus), glow(rays_in -> radiance, transmittance) -- */
 /* Every other call sees a torus as a surface.  These four see its tube as a volume: trt_chords returns how long every ray

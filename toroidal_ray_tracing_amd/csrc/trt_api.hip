@@ -893,7 +893,7 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 }
 
 // The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev,
-// trt_transmittance_dev, trt_shade_through_dev, trt_chords_dev, trt_glow_dev), after the entry
+// trt_transmittance_dev, trt_shade_through_dev, trt_chords_dev, trt_glow_dev, trt_shade_refract_dev, trt_shade_refract_camera_dev), after the entry
 // point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
@@ -1036,7 +1036,7 @@ extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
 // ------------------------------------------------------------------------------------------
 // shade: the render's bounce loop on caller-supplied rays, samples averaged
 // ------------------------------------------------------------------------------------------
-// (`who`: trt_shade or trt_shade_through, which takes the same rays, samples and image)
+// (`who`: trt_shade, or trt_shade_through / trt_shade_refract, which take the same rays, samples and image)
 static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba, const char* who = "trt_shade")
 {
   if(ctx && (!in || !pc || !rgba)) return fail(ctx, TRT_E_INVALID, "%s: NULL rays, push constants or image", who);
@@ -1373,10 +1373,11 @@ extern "C" int trt_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_pus
 }
 
 static int check_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
-                              uint32_t row_end, int camera, uint32_t samples, const float* offsets, const float* rgba, CameraArgs& c)
+                              uint32_t row_end, int camera, uint32_t samples, const float* offsets, const float* rgba, CameraArgs& c,
+                              const char* who = "trt_shade_camera")
 {
-  if(int rc = check_camera(ctx, "trt_shade_camera", g, pc, rgba, W, H, row_begin, row_end, camera, samples, offsets, c)) return rc;
-  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "trt_shade_camera: the rgba image must be 16-byte aligned (it is written as float4)");
+  if(int rc = check_camera(ctx, who, g, pc, rgba, W, H, row_begin, row_end, camera, samples, offsets, c)) return rc;
+  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "%s: the rgba image must be 16-byte aligned (it is written as float4)", who);
   return TRT_OK;
 }
 extern "C" int trt_shade_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
@@ -1409,6 +1410,103 @@ extern "C" int trt_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_pu
   if(int rc = stage_outs(ctx, &image, 1)) return rc;
   float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
   if(int rc = trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// glass tori: trt_shade and trt_shade_camera with refraction at the dielectrics of the scene
+// ------------------------------------------------------------------------------------------
+// What the four trt_shade_refract* calls (`who`) share behind their own checks: the scene (validated here, so that a matId
+// can be trusted) and the dielectric of every torus whose material has illum 6 or 7 — the only readers of `ior` and
+// `transmittance`.  Only a glass material that some torus uses is checked.  No scratch of the ctx: the table travels in
+// the kernel arguments.
+static int refract_glass(trt_ctx* ctx, const char* who, const trt_scene* scene, Glass& gl)
+{
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  std::memset(&gl, 0, sizeof gl);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    const int           m   = scene->tori[j].matId;
+    const trt_material& mat = scene->materials[m];
+    if(mat.illum != 6 && mat.illum != 7)
+      continue;
+    if(!std::isfinite(mat.ior) || !(mat.ior > 0.0f))
+      return fail(ctx, TRT_E_SCENE, "%s: glass material %d (illum %d, of torus %u) has ior = %g; it must be finite and > 0 "
+                                    "(a zero-initialised material has ior == 0)", who, m, (int)mat.illum, j, (double)mat.ior);
+    for(int k = 0; k < 3; ++k)
+      if(!std::isfinite(mat.transmittance[k]) || !(mat.transmittance[k] >= 0.0f))
+        return fail(ctx, TRT_E_SCENE, "%s: glass material %d (illum %d, of torus %u) has transmittance[%d] = %g; it must be finite and >= 0",
+                    who, m, (int)mat.illum, j, k, (double)mat.transmittance[k]);
+    gl.mask |= 1u << j;
+    gl.n[j]     = mat.ior;
+    gl.inv_n[j] = 1.0f / mat.ior;
+    for(int k = 0; k < 3; ++k) gl.tf[j][k] = mat.transmittance[k];
+  }
+  return TRT_OK;
+}
+
+extern "C" int trt_shade_refract_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                                     float* rgba, void* stream)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba, "trt_shade_refract")) return rc;
+  ShadeRefractArgs a;
+  if(int rc = refract_glass(ctx, "trt_shade_refract", scene, a.glass)) return rc;
+  a.rays    = *in;
+  a.n_out   = in->n / samples;
+  a.samples = samples;
+  a.pc      = *pc;
+  a.rgba    = rgba;
+  return ray_query(ctx, scene, stream, in->n, a, launch_shade_refract);
+}
+
+// Host buffers: as trt_shade's.
+extern "C" int trt_shade_refract(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                                 float* rgba_out)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, "trt_shade_refract")) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_shade_refract_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
+  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
+  trt_rays  din;
+  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  if(int rc = trt_shade_refract_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// The scene is checked before the toroidal tables are touched: a refused call leaves them as they were.
+extern "C" int trt_shade_refract_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                                            uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                                            float* rgba, void* stream)
+{
+  ShadeRefractCameraArgs a;
+  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba, a.cam, "trt_shade_refract_camera")) return rc;
+  if(int rc = refract_glass(ctx, "trt_shade_refract_camera", scene, a.glass)) return rc;
+  a.pc   = *pc;
+  a.rgba = rgba;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(int rc = camera_tables(ctx, g, pc, (hipStream_t)stream, a.cam)) return rc;
+  return ray_query(ctx, scene, stream, a.cam.n_px * samples, a, launch_shade_refract_camera);
+}
+
+// Host buffers: as trt_shade_camera's.
+extern "C" int trt_shade_refract_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                                        uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                                        float* rgba_out)
+{
+  CameraArgs c;
+  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, c, "trt_shade_refract_camera")) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(c.n_px == 0)   // validates the scene, launches and writes nothing
+    return trt_shade_refract_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, nullptr);
+  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "trt_shade_refract_camera: the band does not fit the address space");
+  const size_t before = (size_t)row_begin * W * 4;   // floats of the image in front of the band
+  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
+  if(int rc = trt_shade_refract_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
   return fetch_outs(ctx, &image, 1);
 }
 

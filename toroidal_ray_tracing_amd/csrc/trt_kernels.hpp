@@ -1,5 +1,5 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_rays.hip, trt_through.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// (trt_rays.hip, trt_through.hip, trt_glass.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
 // trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
 // What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
@@ -290,8 +290,36 @@ struct ShadeCameraArgs {
   unsigned long long* stats;
 };
 
+// trt_shade_refract*, trt_shade_refract_camera*: the dielectrics of the scene, indexed by TORUS id (not by material),
+// validated and resolved on the host.  Bit j of `mask`: torus j's material has illum 6 or 7; n[j] its ior, inv_n[j] =
+// 1.0f / n[j] (one correctly rounded FP32 division on the host), tf[j] its transmittance[3].  They travel here, in the
+// kernel-argument segment, as Opacity does (164 B): the calls use no scratch of the ctx, and SceneK stays what it was.
+struct Glass {
+  uint32_t mask;
+  float    n[TRT_MAX_TORI], inv_n[TRT_MAX_TORI];
+  float    tf[TRT_MAX_TORI][3];
+};
+// trt_shade_refract*: ShadeArgs with the dielectrics.
+struct ShadeRefractArgs {
+  trt_rays            rays;
+  uint64_t            n_out;
+  uint32_t            samples;   // >= 1, divides rays.n
+  trt_push            pc;
+  Glass               glass;
+  float*              rgba;
+  unsigned long long* stats;
+};
+// trt_shade_refract_camera*: ShadeCameraArgs with the dielectrics.
+struct ShadeRefractCameraArgs {
+  CameraArgs          cam;
+  trt_push            pc;
+  Glass               glass;
+  float*              rgba;
+  unsigned long long* stats;
+};
+
 // The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels,
-// the fan kernels, transmittance_kernel, shade_through_kernel, chords_kernel, glow_kernel; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
+// the fan kernels, transmittance_kernel, shade_through_kernel, chords_kernel, glow_kernel, the two shade_refract kernels; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
 // points), at most 4096 blocks (TRT_TRACE_BLOCKS).
 inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
@@ -316,6 +344,8 @@ hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning&
 hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream);       // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_refract_camera(const SceneK& scene, const ShadeRefractCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

@@ -225,15 +225,6 @@ __device__ __forceinline__ void camera_pixel(const CameraArgs& c, uint64_t i, ui
     y = c.row_begin + (uint32_t)ly;
   }
 }
-// The camera of sample s: the toroidal tables of that sample (CameraArgs::toro_stride floats per sample).
-__device__ __forceinline__ ToroCam camera_sample(const CameraArgs& c, uint32_t s)
-{
-  ToroCam t = c.toro;
-  const size_t off = (size_t)s * c.toro_stride;
-  t.cos_a += off; t.sin_a += off; t.cos_b += off; t.sin_b += off;
-  return t;
-}
-
 // One lane per (sample, pixel): blockIdx.y is the sample — block-uniform, so its offsets and table pointers are scalar
 // loads from the kernel arguments and the pinhole origin is computed from scalars alone — blockIdx.x and the grid-stride
 // loop run over the pixels of the band.  No loads but the four table entries of the toroidal camera (W + H floats per
@@ -270,17 +261,8 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const CameraRaysArgs a
 // row — the paths of a wave stay together where the image is coherent, and a silhouette cuts through far fewer waves
 // (DESIGN.md §5 has the measurement against linear rows).  The grid-stride loop runs on the wave's tile index, a scalar;
 // lanes beyond the right or lower edge of a ragged tile idle.  No output bit depends on the mapping.
-// The camera (CameraArgs) is staged into LDS beside the scene: left in the kernel-argument segment the matrices sit in
-// SGPRs across the bounce loop — the default-solver kernels then spill 70 of them to VGPR lanes and report an 84-byte
-// stack frame — and from LDS raygen reads them where it runs, as the render kernels read their RenderArgs (stage_args,
-// trt_render.hpp).  The sample index is wave-uniform: offsets and table pointers are broadcast reads.
-__device__ __forceinline__ void stage_camera(CameraArgs* lds, const CameraArgs& arg)   // no barrier: the caller's stage_scene has one
-{
-  static_assert(sizeof(CameraArgs) % 4 == 0 && sizeof(CameraArgs) / 4 <= 256, "one dword per thread of a 256-thread block");
-  if(threadIdx.x < sizeof(CameraArgs) / 4)
-    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&arg)[threadIdx.x];
-}
-
+// The camera (CameraArgs) is staged into LDS beside the scene (stage_camera, trt_render.hpp, has the reason); the sample
+// index is wave-uniform: offsets and table pointers are broadcast reads.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, const ShadeCameraArgs a)
 {

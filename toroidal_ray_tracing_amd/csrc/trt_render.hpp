@@ -1,5 +1,5 @@
 // trt_render.hpp — what more than one kernel family of the render path uses.  Device side: included only by
-// trt_rays.hip, trt_through.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
+// trt_rays.hip, trt_through.hip, trt_glass.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
 //
 //   gptr, st1 / st4 / st4c, ld1           global-memory accessors
 //   HitState, hit_begin, hit_end          the closest-hit shader body, split at the shadow query
@@ -8,7 +8,9 @@
 //   block_add_stats                       the query counters of a block → the global totals
 //   settle_loads, stage_args, stage_block256   staging into LDS
 //   kTMin, kTMax                          the ray window of the render kernels
-//   bounce_loop                           the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (shade_kernel)
+//   bounce_loop, NoGlass                  the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (shade_kernel,
+//                                         shade_refract_kernel: the same loop with a dielectric asked at every hit)
+//   camera_sample, stage_camera           the camera of the fused kernels: a sample's tables, the CameraArgs in LDS
 //   kCrossingSlotBytes, column_insert     the sorted crossing column of a lane in LDS
 //   live_slot, list_counts, TileCode, tile_x / tile_y, frame_args, LaunchArgs   the tile-list layout
 //   clear_macro                           the constant fill of one CLEAR macro tile
@@ -280,11 +282,18 @@ constexpr float kTMax = 10000.0f;  // rgen:52
 // close enough to enter it unseen — and `grow` says that the path's directions are no longer than that: the render's
 // cameras always; a caller's ray when |d|² <= kCullUnitDD (reflect keeps the length).
 constexpr float kCullUnitDD = 1.001953125f;   // 1 + 2^-9: |d| <= 1 + 2^-10, the length the host's margin allows for
-template <class Real, bool ALT, bool ORIENT, class FirstMiss, class FirstHit>
+// `glass` (trt_shade_refract*, trt_glass.hip): asked after hit_end() and before the fma of rgen:76 — where the mirror has
+// just chosen its successor — whether the torus hit is a dielectric; it then sets the refracted successor ray, filters the
+// attenuation and clears `done`.  From the first glass hit on the path runs without the enclosure mask: the mask was
+// collected OUTSIDE the tubes it names, and the refracted segment starts inside one.  With NoGlass, the
+// default, nothing of this is instantiated: the loop of every other kernel is the code it was.
+struct NoGlass {};
+template <class Real, bool ALT, bool ORIENT, class FirstMiss, class FirstHit, class GlassT = NoGlass>
 __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v3 origin, v3 direction,
                                           uint32_t skip, bool grow, v3 attenuation,        // rgen:56
                                           FirstMiss&& first_miss, FirstHit&& first_hit,
-                                          uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
+                                          uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc,
+                                          GlassT glass = GlassT{})
 {
   int depth = 0, done = 1;                                                 // rgen:54,57
   v3  hitValue = {0.0f, 0.0f, 0.0f};                                       // rgen:61
@@ -312,6 +321,12 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
       if(grow && dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
         skip |= inside;
       prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
+      if constexpr(!std::is_same<GlassT, NoGlass>::value)
+        if(glass.hit(id, h, direction, attenuation, done, nextO, nextD))
+        {
+          skip = 0u;
+          grow = false;
+        }
     }
     hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
     hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
@@ -324,6 +339,27 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
     done      = 1;                                                         // rgen:84
   }
   return hitValue;
+}
+
+// ------------------------------------------------------------------------------------------
+// the camera of a fused kernel (shade_camera_kernel, shade_refract_camera_kernel)
+// ------------------------------------------------------------------------------------------
+// The camera of sample s: the toroidal tables of that sample (CameraArgs::toro_stride floats per sample).
+__device__ __forceinline__ ToroCam camera_sample(const CameraArgs& c, uint32_t s)
+{
+  ToroCam t = c.toro;
+  const size_t off = (size_t)s * c.toro_stride;
+  t.cos_a += off; t.sin_a += off; t.cos_b += off; t.sin_b += off;
+  return t;
+}
+// The camera (CameraArgs) is staged into LDS beside the scene: left in the kernel-argument segment the matrices sit in
+// SGPRs across the bounce loop — the default-solver kernels then spill 70 of them to VGPR lanes and report an 84-byte
+// stack frame — and from LDS raygen reads them where it runs, as the render kernels read their RenderArgs (stage_args).
+__device__ __forceinline__ void stage_camera(CameraArgs* lds, const CameraArgs& arg)   // no barrier: the caller's stage_scene has one
+{
+  static_assert(sizeof(CameraArgs) % 4 == 0 && sizeof(CameraArgs) / 4 <= 256, "one dword per thread of a 256-thread block");
+  if(threadIdx.x < sizeof(CameraArgs) / 4)
+    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&arg)[threadIdx.x];
 }
 
 // ------------------------------------------------------------------------------------------

@@ -193,7 +193,29 @@ void HelloHip::shadeThrough(void* stream, const std::array<float, 4>& clearColor
   check(trt_shade_through_dev(m_ctx, &raysDev, samples, &m_pcRay, &scene, rgbaDev, stream), "HelloHip::shadeThrough");
 }
 
-void HelloHip::chords(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
+void HelloHip::shadeRefract(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev)
+{
+  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
+  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
+  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
+  m_pcRay.lightType      = m_pcRaster.lightType;
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_shade_refract_dev(m_ctx, &raysDev, samples, &m_pcRay, &scene, rgbaDev, stream), "HelloHip::shadeRefract");
+}
+
+void HelloHip::raytraceRefract(void* stream, const std::array<float, 4>& clearColor, uint32_t samples, const float* offsets)
+{
+  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
+  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
+  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
+  m_pcRay.lightType      = m_pcRaster.lightType;
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_shade_refract_camera_dev(m_ctx, &m_globals, &m_pcRay, &scene, m_size.width, m_size.height, 0, m_size.height, m_camera,
+                                     samples, offsets, m_dColor, stream),
+        "HelloHip::raytraceRefract");
+}
+
+void HelloHip::chords(void* stream,const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
 {
   const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
   check(trt_chords_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, lengthDev, stream), "HelloHip::chords");

@@ -65,6 +65,15 @@ public:
   // dissolve 0 is invisible here.  rgbaDev: (raysDev.n / samples) * 4 floats, 16-byte aligned.
   void shadeThrough(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
 
+  // Glass tori (trt_shade_refract_dev, trt_shade_refract_camera_dev): a material added with illum 6 or 7 refracts by its
+  // `ior` and filters by its `transmittance` — give it an ior > 0, a zero-initialised glass material is refused.  The push
+  // constants are refreshed as raytrace() refreshes them.  shadeRefract: every ray of raysDev (sample-major, `samples` per
+  // output) into rgbaDev ((raysDev.n / samples) * 4 floats, 16-byte aligned).  raytraceRefract: the frame of m_camera into
+  // the colour image raytrace() writes, `samples` rays per pixel at the sub-pixel offsets (2 floats per sample; nullptr:
+  // the pixel centres); no RenderedData is written.
+  void shadeRefract(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
+  void raytraceRefract(void* stream, const std::array<float, 4>& clearColor, uint32_t samples = 1, const float* offsets = nullptr);
+
   // Media inside the tubes of the tori added so far (trt_chords_dev, trt_glow_dev; materials are not read).  chords: the
   // length of every ray of raysDev inside every tube, lengthDev[j * raysDev.n + i] for torus j (the order of the
   // addTorus calls).  glow: emission and absorption of media (one trt_medium per torus, host memory) integrated along

@@ -349,6 +349,45 @@ class Tracer:
         self._check(self._L.trt_shade_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
                                                  int(samples), off, _vp(rgba_ptr), _vp(stream)))
 
+    # -- glass tori: shade and shade_camera with refraction at the materials of illum 6 / 7 -------
+    def shade_refract(self, scene, o, d, pc, samples=1):
+        """``shade`` with glass tori (trt_shade_refract) on host arrays: a torus whose material has illum 6 or 7 bends the
+        path by Snell's law with the material's ``ior`` (total internal reflection where there is no refracted ray) and
+        filters it by ``transmittance`` once per passage.  A glass material in use needs ior > 0 — a zero-initialised one
+        is refused.  Layout and averaging as in ``shade``.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        samples = int(samples)
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
+        self._check(self._L.trt_shade_refract(self._h, C.byref(rays), samples, C.byref(pc), self._scene(scene), rgba.ctypes.data))
+        return rgba
+
+    def shade_refract_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
+        """Device pointers (ints): as ``shade_dev``.  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_shade_refract_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
+                                                  _vp(rgba_ptr), _vp(stream)))
+
+    def shade_refract_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None):
+        """``shade_camera`` with glass tori (trt_shade_refract_camera) on a host buffer: bit for bit ``camera_rays`` put
+        through ``shade_refract``.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
+        r0, r1 = (0, H) if rows is None else rows
+        rgba = np.zeros((H, W, 4), np.float32)
+        keep, off = self._offsets(offsets, samples)
+        self._check(self._L.trt_shade_refract_camera(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
+                                                     int(samples), off, rgba.ctypes.data))
+        return rgba
+
+    def shade_refract_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None,
+                                 rows=None, stream=0):
+        """Device image: as ``shade_camera_dev``.  Asynchronous on ``stream``."""
+        r0, r1 = (0, H) if rows is None else rows
+        keep, off = self._offsets(offsets, samples)
+        self._check(self._L.trt_shade_refract_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1,
+                                                         camera, int(samples), off, _vp(rgba_ptr), _vp(stream)))
+
     # -- ray fans: K rays from every surface point, as streams or as fused ambient occlusion --
     @staticmethod
     def _fan_points(at, frame):
