@@ -29,6 +29,8 @@
  *   walls composited front to back compositing of trt_crossings' list)   trt_shade_through*
  *   payload loop with glass tori:  (none: MTL illum 6 / 7, GLSL refract()    trt_shade_refract* /
  *   refraction, total reflection   with the materials' ior)              trt_shade_refract_camera*
+ *   payload loop with a table of   (none: rchit:79-155 once per light, the   trt_shade_lit* /
+ *   lights, area lights among them shadow bit a fraction of K any-hit rays)  trt_shade_lit_camera*
  *   length of a ray inside every   (none: build-defined, the pairing of
  *   torus' tube                    trt_crossings' entries and exits)     trt_chords*
  *   emission and absorption of     (none: build-defined, the line integral
@@ -437,6 +439,98 @@ int trt_shade_refract_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples
 int trt_shade_refract_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W,
                                  uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
                                  const float* offsets, float* rgba_dev, void* stream);
+
+/* ---- several lights, area lights: shade_lit(rays_in -> colours), shade_lit_camera(camera -> the band of an image) ---- */
+/* Every other shading call takes exactly one light, the one inside trt_push, and answers its shadow ray with one bit.
+ * These four take a table of up to TRT_MAX_LIGHTS lights, each with a colour and, if its radius is > 0, an extent: the
+ * shadow of such a light is the share of K any-hit rays towards a disc about its centre that get through.
+ * pc->lightPosition, lightIntensity and lightType are not read (nor is rho, but by the toroidal camera of the camera form);
+ * `dissolve`, `ior` and `transmittance` are not read: the families do not mix.  Everything that is not about lights is trt_shade's (trt_shade_lit*) or trt_shade_camera's
+ * (trt_shade_lit_camera*): rays, the `samples` layout, the averaging rule, the alignment of the image, the window
+ * (0.001, 10000) on every segment, pc->maxDepth (the body runs once even for maxDepth <= 0), clearColor * 0.8 on a miss,
+ * the mirror of illum == 3, every TRT_SOLVE_*, the torus axes, band addressing, offsets, the toroidal-table contract, the
+ * refusals, and n == 0 / row_begin == row_end, which launch nothing.
+ *
+ * lights: n_lights host structs, copied before the call returns; disc: shadow_samples x 2 host floats (u_s, v_s), positions
+ * on the unit disc (any finite values are taken as they are), copied too; it may be NULL when no light has radius > 0.
+ *
+ * The colour of one hit.  P, N and the material as the closest-hit shader forms them (rchit:50-75, BEF rchit:134), d the
+ * segment's direction; FP32, one rounding per operation, in the order written, fma only where written.  With
+ * dot3(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)), for light l = 0, 1, ... in table order (lp = its position[3]):
+ *   1. type 0:  lDir = lp - P;  dist = sqrt(dot3(lDir, lDir));  I = intensity / (dist * dist);  L = lDir * (1.0f / dist)
+ *      type 1:  L = lp * (1.0f / sqrt(dot3(lp, lp)));  dist = 100000;  I = intensity;  lDir = L           (rchit:79-92)
+ *   2. diffuse = computeDiffuse(mat, L, N) (wavefront.glsl:22-30);  want = dot3(N, L) > 0                  (rchit:100,112)
+ *   3. the visibility v:
+ *      !want:               no shadow ray; att = 1 and spec = 0 in step 4 (rchit:133-142).
+ *      want, radius == 0:   the any-hit query (P, L) over (0.001, dist); v = 0 if it hits, else 1.
+ *      want, radius > 0:    (T, B) = the basis of the fan section (TRT_FAN_LOCAL, with L in the place of N: sg, a, b, T, B
+ *                           exactly as written there).  For s = 0 .. K - 1, K = shadow_samples:
+ *                             a = radius * u_s;  b = radius * v_s;  e.k = lDir.k + ((a * T.k) + (b * B.k))  for k = x, y, z
+ *                             len = sqrt(dot3(e, e));  Ls = e * (1.0f / len)
+ *                             the any-hit query (P, Ls) over (0.001, type == 0 ? len : 100000).
+ *                           occ = the number of occluded samples;  v = (float)(K - occ) / (float)K, one correctly rounded
+ *                           division (trt_fan_occluded's `open`).  No sample is special-cased: one that points below the
+ *                           horizon of P starts into its own tube and finds it.
+ *   4. att = fma(0.3f, 1.0f - v, v);  spec = v > 0 ? computeSpecular(mat, d, L, N) * v : 0;  c = (att * I) * (diffuse + spec)
+ *      — the expressions trt_shade_through uses for its transmittance T.
+ *   5. per channel:  prd = c * color  for l == 0,  prd = fma(c, color, prd)  for every later light.  n_lights == 0: prd = 0.
+ * Then the mirror step (rchit:145-153: attenuation * Ks, the next segment (P, reflect(d, N))) and
+ * hitValue = fma(prd, attenuation, hitValue) follow as in trt_shade.
+ * Consequences:
+ *   - With one light of radius 0 and colour (1, 1, 1) the colours and the three query counters are trt_shade's with that
+ *     light in pc, bit for bit.  The same light with radius > 0, K = 1 and the table (0, 0) is that light again, bit for
+ *     bit: e = lDir and len = dist.  (A directional light: whenever sqrt(dot3(L, L)) rounds to 1; otherwise Ls is L scaled
+ *     by one rounding — the same ray — and a shadow bit can differ only where a root sits on the edge of its window.)
+ *   - The specular lobe and the inverse-square law use the light's centre; only the shadow knows the extent.
+ *   - The material's ambient term is part of every light's diffuse term (wavefront.glsl:27): it counts once per light.
+ *   - v is a count: the order of the disc table changes no bit and no counter.
+ * Enclosure cull: the path's mask starts empty and grows as in trt_shade.  The shadow ray of a light of radius 0 skips
+ * the path's mask and the tubes inside the torus hit, as trt_shade's does; a sample of an area light skips the tubes inside
+ * the torus hit only where dot3(N, Ls) > 0 — a sample below the horizon enters that tube — and the path's mask always.  By
+ * the contract at trt_scene no colour and no query count depends on it.
+ * Stats (trt_enable_stats): primary_tests and bounce_tests as trt_shade counts them; shadow_tests = the sum over all shadow
+ * rays, every sample of an area light one of them, of the tests each executes up to its first hit; pixels = n
+ * (trt_shade_lit*) or samples x the pixels of the band (trt_shade_lit_camera*); traced_tests, solved_tests and evaluations
+ * as defined at trt_stats.
+ * trt_shade_lit_camera is, bit for bit and counter for counter, trt_camera_rays put through trt_shade_lit.
+ * TRT_E_INVALID, with a message that begins "trt_shade_lit:" or "trt_shade_lit_camera:" and names what was wrong: NULL
+ * lights; n_lights > TRT_MAX_LIGHTS; a NULL table with n_lights > 0; a type other than 0 or 1; a radius that is NaN,
+ * infinite or negative; a position, intensity or colour that is NaN or infinite; shadow_samples outside
+ * 1..TRT_MAX_LIGHT_SAMPLES; a NULL disc while some light has radius > 0; a disc entry that is NaN or infinite; and
+ * everything trt_shade / trt_shade_camera refuse.  A refused call leaves the ctx usable and the outputs unwritten.
+ * Not here: lights inside trt_render*, or in the translucent and glass families; textured or spot lights; importance
+ * sampling; a rotation of the disc table per pixel (every hit uses the same K positions: the penumbra is banded, not noisy).
+ * Host buffers: copy in, launch, copy out, synchronise. */
+#define TRT_MAX_LIGHTS        8
+#define TRT_MAX_LIGHT_SAMPLES 64
+typedef struct trt_light {
+  float   position[3]; /* type 0: the centre; type 1: the direction TOWARDS the light, any length (pc->lightPosition's meaning) */
+  float   intensity;
+  float   color[3];    /* per-channel scale of this light's contribution; (1,1,1) is pc's light */
+  int32_t type;        /* 0 point, 1 directional: pc->lightType's values */
+  float   radius;      /* 0: one shadow ray, the reference's light.  > 0: an area light (above) */
+} trt_light;           /* 36 bytes */
+typedef struct trt_lights {
+  const trt_light* lights;         /* HOST memory in every form; copied before the call returns */
+  uint32_t         n_lights;       /* 0 .. TRT_MAX_LIGHTS */
+  uint32_t         shadow_samples; /* K, 1 .. TRT_MAX_LIGHT_SAMPLES: shadow rays per area light per hit */
+  const float*     disc;           /* K x 2 host floats (u, v): positions on the unit disc, any finite values; may be NULL when no light has radius > 0 */
+} trt_lights;
+
+int trt_shade_lit(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                  const trt_scene* scene, float* rgba_out);
+int trt_shade_lit_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, const trt_scene* scene,
+                         uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
+                         const float* offsets, float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  `lights` and what it points at stay in host memory: the light table
+ * and the disc table travel in the kernel arguments.  The calls use no scratch of the ctx beyond the toroidal tables of
+ * the camera form, allocate nothing, synchronise nothing, put only kernel nodes on the stream and may be captured (the
+ * toroidal camera: as trt_shade_camera_dev). */
+int trt_shade_lit_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                      const trt_scene* scene, float* rgba_dev, void* stream);
+int trt_shade_lit_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights,
+                             const trt_scene* scene, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera,
+                             uint32_t samples, const float* offsets, float* rgba_dev, void* stream);
 
 /* ---- media inside the tubes: chords(rays_in -> a length per ray and torus), glow(rays_in -> radiance, transmittance) -- */
 /* Every other call sees a torus as a surface.  These four see its tube as a volume: trt_chords returns how long every ray

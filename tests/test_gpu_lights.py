@@ -1,0 +1,555 @@
+"""trt_shade_lit[_dev] / trt_shade_lit_camera[_dev]: several lights and area lights along caller and camera rays (include/trt.h).
+
+Anchors, from the strictest down:
+  1. trt_shade_dev — one hard white light is its light: the colours bit for bit on every ray, the three ray-class counters
+     too; and the same light as an area light of one sample at the centre is that light again;
+  2. the fused camera form is trt_camera_rays_dev followed by trt_shade_lit_dev, bit for bit, stats included;
+  3. superposition in bits: two hard lights with power-of-two colours are the FP32 sum of trt_shade_dev's two colours;
+  4. the FP64 truth of tests/lights_truth.py at the bars of tests/test_oracle.py's FP64 comparison;
+  5. v is a count: a permuted disc table gives the same bits and the same counters;
+  6. no light at all: black hits, the miss colour elsewhere.
+Then the layout, the paths (host, device, captured) and the refusals.  Sets are crossings_truth's 4096 rays, frames 64x64.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import camera_truth
+import crossings_truth as ct
+import lights_truth as lt
+from camera_support import image as frame_image, n_rays, ray_buffers, read_image, stream_handle
+from toroidal_ray_tracing_amd import abi, camera
+
+pytestmark = pytest.mark.gpu
+
+SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64]
+SOLVER_IDS = ["f32", "f64"]
+ALL_SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64, abi.TRT_SOLVE_DK_F32, abi.TRT_SOLVE_DK_F64, abi.TRT_SOLVE_FERRARI_F32,
+               abi.TRT_SOLVE_FERRARI_F64]
+ALL_SOLVER_IDS = ["f32", "f64", "dk32", "dk64", "ferrari32", "ferrari64"]
+SENTINEL = -7.25
+PAD = 8
+W = H = 64
+BAND = (5, 59)
+QUERY_KEYS = ("primary_tests", "bounce_tests", "shadow_tests")
+f32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def tr():
+    from toroidal_ray_tracing_amd.tracer import Tracer
+    t = Tracer(0)
+    yield t
+    t.close()
+
+
+def u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def upload(o, d):
+    import torch
+    dev = torch.device("cuda:0")
+    soa = [torch.from_numpy(np.array(a[:, k], np.float32)).to(dev) for a in (o, d) for k in range(3)]   # (a writable copy)
+    return soa, [a.data_ptr() for a in soa]
+
+
+def image(n_floats):
+    import torch
+    return torch.full((n_floats + PAD,), SENTINEL, dtype=torch.float32, device="cuda:0")
+
+
+def read(buf, n_floats):
+    raw = buf.cpu().numpy()
+    assert (raw[n_floats:] == f32(SENTINEL)).all(), "written beyond the output"
+    return raw[:n_floats].copy()
+
+
+def _rays_call(tr, which, sc, o, d, pc, samples, solver, stats, **kw):
+    """One trt_shade_dev / trt_shade_lit_dev call into a sentinel-padded image: (n_out, 4) [, stats]."""
+    import torch
+    n_out = len(o) // samples
+    keep, ptrs = upload(o, d) if len(o) else (None, [0] * 6)
+    buf = image(n_out * 4)
+    tr.set_solver(solver)
+    tr.enable_stats(stats)
+    try:
+        getattr(tr, which)(sc, ptrs, len(o), pc, buf.data_ptr(), samples=samples, stream=stream_handle(), **kw)
+        st = tr.stats() if stats else None
+    finally:
+        tr.enable_stats(False)
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    torch.cuda.synchronize()
+    out = read(buf, n_out * 4).reshape(n_out, 4)
+    return (out, st) if stats else out
+
+
+def lit_dev(tr, sc, o, d, pc, lights, K=1, disc=None, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
+    return _rays_call(tr, "shade_lit_dev", sc, o, d, pc, samples, solver, stats, lights=lights, shadow_samples=K, disc=disc)
+
+
+def shade_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
+    return _rays_call(tr, "shade_dev", sc, o, d, pc, samples, solver, stats)
+
+
+def lit_camera_dev(tr, sc, g, pc, cam, lights, K=1, disc=None, samples=1, offsets=None, rows=None, solver=abi.TRT_SOLVE_F32, stats=False):
+    """One trt_shade_lit_camera_dev call into a sentinel-filled full-frame image: (H, W, 4) [, stats]."""
+    import torch
+    buf = frame_image(W, H)
+    tr.set_solver(solver)
+    tr.enable_stats(stats)
+    try:
+        tr.shade_lit_camera_dev(sc, g, pc, W, H, buf.data_ptr(), camera=cam, samples=samples, offsets=offsets, rows=rows,
+                                stream=stream_handle(), lights=lights, shadow_samples=K, disc=disc)
+        st = tr.stats() if stats else None
+    finally:
+        tr.enable_stats(False)
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    torch.cuda.synchronize()
+    out = read_image(buf, W, H, rows)
+    return (out, st) if stats else out
+
+
+def case_dev(tr, c, **kw):
+    return lit_dev(tr, c["sc"], c["o"], c["d"], c["pc"], c["lights"], c["K"], c["disc"], **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. one hard white light: trt_shade_dev, bit for bit
+# ---------------------------------------------------------------------------------------------------------------------
+# illum 0, 2 and 3; "rings2" has the oriented tori, "nest3" the enclosure masks (the mirror is the outer shell)
+ONE_LIGHT = {
+    "nest3": ("nest3", [camera.FLAT, camera.PLASTIC, camera.MIRROR]),
+    "rings2": ("rings2", [camera.MIRROR, camera.PLASTIC]),
+    "single_flat": ("single", [camera.FLAT]),
+}
+
+
+@pytest.mark.parametrize("solver", ALL_SOLVERS, ids=ALL_SOLVER_IDS)
+def test_one_hard_white_light_is_shade_bit_for_bit(tr, solver):
+    """Point and directional, 1 and 3 samples (4095 of the 4096 rays), depth 5 — and the same light with a radius, K = 1
+    and the table (0, 0).  The light inside the push constants handed to trt_shade_lit_dev is NaN: it is not read."""
+    for name, (set_name, mats) in ONE_LIGHT.items():
+        geo, axes = ct.SCENES[set_name]
+        sc = abi.Scene([(C_, R, r, j) for j, (C_, R, r) in enumerate(geo)], mats, axes=axes)
+        s = ct.ray_set(set_name)
+        o, d = s["o"][:4095], s["d"][:4095]
+        for light_type in (0, 1):
+            pc = abi.make_push(max_depth=5, light_type=light_type, light_pos=(3.0, 5.0, 2.0) if light_type else lt.BASELINE_LIGHT,
+                               light_intensity=1.0 if light_type else 100.0)
+            blind = abi.make_push(max_depth=5, light_type=7, light_pos=(float("nan"),) * 3, light_intensity=float("nan"), rho=float("nan"))
+            hard = abi.light_from_push(pc)
+            area = abi.make_light(pc.lightPosition[:], pc.lightIntensity, type=light_type, radius=0.75)
+            for samples in (1, 3):
+                want, wst = shade_dev(tr, sc, o, d, pc, samples, solver, stats=True)
+                for what, lights, disc in (("hard", [hard], None), ("area K=1", [area], [[0.0, 0.0]])):
+                    got, st = lit_dev(tr, sc, o, d, blind, lights, 1, disc, samples, solver, stats=True)
+                    key = (name, light_type, samples, what)
+                    assert np.array_equal(u32(got), u32(want)), (key, int((u32(got) != u32(want)).any(axis=1).sum()))
+                    assert {k: st[k] for k in QUERY_KEYS} == {k: wst[k] for k in QUERY_KEYS}, key
+                    assert st["pixels"] == len(o) and st["primary_tests"] == len(o) * len(geo)
+            assert len(np.unique(u32(want), axis=0)) > 20 and wst["shadow_tests"] > 0, (name, light_type)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. the fused camera form is camera_rays_dev -> shade_lit_dev
+# ---------------------------------------------------------------------------------------------------------------------
+def lit_frame(cam_name):
+    """A plastic ring over a matte one in front of the pinhole camera, or a plastic shell around a mirror core about the
+    toroidal one's line of sight; an area light, a coloured hard one and a directional fill, K = 8."""
+    if cam_name == "pinhole":
+        tori = [((0.0, 0.6, 0.0), 0.5, 0.12, 0), ((0.0, 0.0, 0.0), 1.0, 0.3, 1)]
+        mats = [camera.PLASTIC, camera.MATTE]
+        g, pc, cam = camera.baseline_camera(W, H), camera.baseline_push(4), abi.TRT_CAMERA_PINHOLE
+        lights = [abi.make_light(lt.BASELINE_LIGHT, radius=2.0), abi.make_light((-3.0, 4.0, -2.0), 20.0, (1.0, 0.8, 0.5)),
+                  abi.make_light((0.0, 1.0, -1.0), 0.2, (0.4, 0.5, 1.0), type=1, radius=0.2)]
+    else:
+        tori = [((0.0, 0.0, 0.0), 6.0, 1.5, 0), ((0.0, 0.0, 0.0), 6.0, 0.6, 1)]
+        mats = [camera.PLASTIC, camera.MIRROR]
+        g, pc, cam = (camera.toroidal_camera(W, H, eye=(0.5, 0.4, -0.3), center=(4.0, -1.0, 7.0)),
+                      abi.make_push(max_depth=4, rho=3.0), abi.TRT_CAMERA_TOROIDAL)
+        lights = [abi.make_light((0.0, 5.0, 0.0), 60.0, radius=1.5), abi.make_light((1.0, -2.0, 0.5), 8.0, (1.0, 0.8, 0.5)),
+                  abi.make_light((0.0, 1.0, 0.3), 0.2, (0.4, 0.5, 1.0), type=1, radius=0.2)]
+    return abi.Scene(tori, mats), g, pc, cam, lights
+
+
+def chain(tr, sc, g, pc, cam, lights, samples, offsets, rows, solver):
+    """trt_camera_rays_dev into device streams, then trt_shade_lit_dev on them: the band's image and the stats."""
+    import torch
+    r0, r1 = (0, H) if rows is None else rows
+    n = n_rays(W, H, samples, rows)
+    bufs = ray_buffers(n)
+    ptrs = [b.data_ptr() for b in bufs]
+    out = torch.full(((r1 - r0) * W * 4,), SENTINEL, dtype=torch.float32, device="cuda:0")
+    tr.set_solver(solver)
+    tr.enable_stats(True)
+    try:
+        tr.camera_rays_dev(g, pc, W, H, ptrs, camera=cam, samples=samples, offsets=offsets, rows=rows, stream=stream_handle())
+        tr.shade_lit_dev(sc, ptrs, n, pc, out.data_ptr(), samples=samples, stream=stream_handle(), lights=lights, shadow_samples=8)
+        st = tr.stats()
+    finally:
+        tr.enable_stats(False)
+        tr.set_solver(abi.TRT_SOLVE_F32)
+    torch.cuda.synchronize()
+    return out.cpu().numpy().reshape(r1 - r0, W, 4), st
+
+
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("samples", [1, 4])
+@pytest.mark.parametrize("cam_name", ["pinhole", "toroidal"])
+def test_the_fused_camera_is_camera_rays_then_shade_lit(tr, cam_name, samples, solver):
+    sc, g, pc, cam, lights = lit_frame(cam_name)
+    off = None if samples == 1 else camera_truth.grid_2x2(cam)
+    for rows in (None, BAND):
+        got, st = lit_camera_dev(tr, sc, g, pc, cam, lights, 8, samples=samples, offsets=off, rows=rows, solver=solver, stats=True)
+        want, wst = chain(tr, sc, g, pc, cam, lights, samples, off, rows, solver)
+        r0, r1 = (0, H) if rows is None else rows
+        n_px = (r1 - r0) * W
+        assert np.array_equal(u32(got[r0:r1]), u32(want)), (rows, int((u32(got[r0:r1]) != u32(want)).any(axis=2).sum()))
+        assert st == wst and st["pixels"] == samples * n_px and st["primary_tests"] == samples * n_px * sc.n_tori
+        assert st["shadow_tests"] > 0 and (u32(got[r0:r1, :, 3]) == u32(f32(1.0))).all()
+    full = lit_camera_dev(tr, sc, g, pc, cam, lights, 8, solver=solver)
+    hard = lit_camera_dev(tr, sc, g, pc, cam, [abi.make_light(q.position[:], q.intensity, q.color[:], q.type, 0.0) for q in lights], 8, solver=solver)
+    assert (u32(full) != u32(hard)).any(axis=2).sum() >= 8   # the penumbrae are in the picture
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. superposition in bits
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("set_name", ["single", "rings2"])
+def test_two_hard_lights_are_the_fp32_sum_of_two_shade_calls(tr, set_name, solver):
+    """Depth 1; colours (1, 0.5, 0.25) and (0.5, 1, 2): the products with a power of two are exact, so prd = c0 * col0 and
+    fma(c1, col1, prd) is the plain FP32 sum of the two products, and hitValue = fma(prd, 1, 0) is prd."""
+    geo, axes = ct.SCENES[set_name]
+    sc = abi.Scene([(C_, R, r, j) for j, (C_, R, r) in enumerate(geo)], [camera.PLASTIC, camera.MATTE][:len(geo)], axes=axes)
+    s = ct.ray_set(set_name)
+    o, d = s["o"], s["d"]
+    spots = [(lt.BASELINE_LIGHT, 100.0, 0), ((-3.0, 2.0, -4.0), 0.75, 1)]
+    cols = [f32([1.0, 0.5, 0.25]), f32([0.5, 1.0, 2.0])]
+    one = [shade_dev(tr, sc, o, d, abi.make_push(max_depth=1, light_pos=p, light_intensity=i, light_type=t), solver=solver) for p, i, t in spots]
+    lights = [abi.make_light(p, i, c, t) for (p, i, t), c in zip(spots, cols)]
+    got = lit_dev(tr, sc, o, d, abi.make_push(max_depth=1), lights, solver=solver)
+    tr.set_solver(solver)
+    try:
+        hit = tr.trace(sc, o, d)["id"] >= 0
+    finally:
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    want = one[0][:, :3] * cols[0] + one[1][:, :3] * cols[1]
+    assert want.dtype == np.float32 and 0.5 < hit.mean() < 0.95
+    assert np.array_equal(u32(got[hit, :3]), u32(want[hit])), int((u32(got[hit, :3]) != u32(want[hit])).any(axis=1).sum())
+    assert np.array_equal(u32(got[~hit]), u32(one[0][~hit])) and (got[~hit, :3] == f32(0.8)).all()   # a miss: the miss colour
+    assert (np.abs(one[0][hit, :3] - one[1][hit, :3]).max(1) > 1e-3).mean() > 0.5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. the FP64 truth
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("name", list(lt.cases()))
+def test_against_the_fp64_truth(tr, name, solver):
+    """The bars of tests/test_oracle.py's FP64 comparison: rel = |got - want| / (|want| + 1e-5), rel <= 1e-4 on at least
+    99.5 % of the robust rays and max <= 2e-3."""
+    c = lt.case(name)
+    assert c["robust"].mean() > 0.9
+    if lt.has_area(name):
+        assert c["first"]["fractional"].mean() >= 0.02
+    got = case_dev(tr, c, solver=solver)[:, :3].astype(np.float64)
+    rel = (np.abs(got - c["rgb"]) / (np.abs(c["rgb"]) + 1e-5)).max(axis=-1)[c["robust"]]
+    print(f"{name} {SOLVER_IDS[SOLVERS.index(solver)]}: robust {c['robust'].mean():.4f}, rel max {rel.max():.3e}, "
+          f"over 1e-4: {int((rel > 1e-4).sum())} of {len(rel)}; fractional v at the first hit {c['first']['fractional'].mean():.4f} "
+          f"({int((c['first']['fractional'] & c['robust']).sum())} of them robust)")
+    assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (name, rel.max(), int((rel > 1e-4).sum()))
+    miss = np.asarray(c["pc"].clearColor[:3]) * 0.8
+    assert (np.abs(c["rgb"] - miss).max(1) > 1e-3).mean() > 0.5   # (most rays of a set see a surface)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. v is a count; 6. no light at all
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+def test_a_permuted_disc_table_changes_no_bit_and_no_counter(tr, solver):
+    for name in ("nest3_area_point", "rings2_area_dir_and_hard"):
+        c = lt.case(name)
+        a, sa = case_dev(tr, c, solver=solver, stats=True)
+        perm = np.random.default_rng(5).permutation(c["K"])
+        assert (perm != np.arange(c["K"])).sum() >= 4
+        b, sb = lit_dev(tr, c["sc"], c["o"], c["d"], c["pc"], c["lights"], c["K"], c["disc"][perm], solver=solver, stats=True)
+        assert np.array_equal(u32(a), u32(b)), name
+        assert {k: sa[k] for k in QUERY_KEYS} == {k: sb[k] for k in QUERY_KEYS} and sa["shadow_tests"] > 0, name
+        # (and the table matters: another table, another picture)
+        other = lit_dev(tr, c["sc"], c["o"], c["d"], c["pc"], c["lights"], c["K"], c["disc"] * f32(0.25), solver=solver)
+        assert (u32(other) != u32(a)).any(axis=1).sum() >= 8, name
+
+
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+def test_without_a_light_hits_are_black(tr, solver):
+    """n_lights == 0, depth 1, no mirror: rgb is exactly 0 on every ray trt_trace (the same solver) reports hit, the miss
+    colour elsewhere, alpha 1 everywhere — with an empty table, and with a NULL one."""
+    s = ct.ray_set("rings2")
+    geo, axes = ct.SCENES["rings2"]
+    sc = abi.Scene([(C_, R, r, j) for j, (C_, R, r) in enumerate(geo)], [camera.PLASTIC, camera.MATTE], axes=axes)
+    pc = abi.make_push(clear=(0.1, 0.2, 0.4, 1.0), max_depth=1)
+    tr.set_solver(solver)
+    try:
+        hit = tr.trace(sc, s["o"], s["d"])["id"] >= 0
+    finally:
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    for lights in ((), None):
+        got, st = lit_dev(tr, sc, s["o"], s["d"], pc, lights, solver=solver, stats=True)
+        assert 0.5 < hit.mean() < 0.95 and (got[hit, :3] == 0.0).all()
+        assert np.array_equal(u32(got[~hit, :3]), u32(np.tile(f32([0.1, 0.2, 0.4]) * f32(0.8), ((~hit).sum(), 1))))
+        assert (u32(got[:, 3]) == u32(f32(1.0))).all()
+        assert st["shadow_tests"] == 0 and st["bounce_tests"] == 0 and st["primary_tests"] == len(hit) * 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. layout and paths
+# ---------------------------------------------------------------------------------------------------------------------
+def test_layout_and_both_forms(tr):
+    import torch
+    c = lt.case("rings2_area_dir_and_hard")
+    sc, pc, o, d, lights, K, disc = c["sc"], c["pc"], c["o"], c["d"], c["lights"], c["K"], c["disc"]
+    n = len(o)
+    dev = case_dev(tr, c)
+    host = tr.shade_lit(sc, o, d, pc, lights=lights, shadow_samples=K, disc=disc)
+    tr.set_torus_axes(None)
+    assert host.shape == (n, 4) and host.dtype == np.float32 and np.array_equal(u32(host), u32(dev))
+    assert (u32(dev[:, 3]) == u32(f32(1.0))).all()
+    assert np.array_equal(u32(lit_dev(tr, sc, o, d, pc, lights, K)), u32(dev))   # disc=None: abi.disc_samples(K), the case's table
+    # samples: trt_shade's rule — acc = c_0, then plain FP32 adds in order, one correctly rounded division
+    for samples in (2, 4):
+        got = case_dev(tr, c, samples=samples)
+        parts = dev[:, :3].reshape(samples, n // samples, 3)
+        acc = parts[0].copy()
+        for k in range(1, samples):
+            acc = acc + parts[k]
+        want = acc / f32(samples)
+        assert want.dtype == np.float32 and got.shape == (n // samples, 4)
+        assert np.array_equal(u32(got[:, :3]), u32(want))
+        assert np.array_equal(u32(got), u32(tr.shade_lit(sc, o, d, pc, samples=samples, lights=lights, shadow_samples=K, disc=disc)))
+        tr.set_torus_axes(None)
+    # rays are independent: a permutation of the inputs permutes the outputs (cut ragged: 15 full blocks and 219 rays)
+    perm = np.random.default_rng(11).permutation(n)[:n - 37]
+    assert np.array_equal(u32(lit_dev(tr, sc, o[perm], d[perm], pc, lights, K, disc)), u32(dev[perm]))
+    for m in (1, 63, 65, 257):
+        assert np.array_equal(u32(lit_dev(tr, sc, o[100:100 + m], d[100:100 + m], pc, lights, K, disc)), u32(dev[100:100 + m])), m
+    # the camera form: host == device, in the band and for the frame; rows outside the band of the host image are 0
+    gsc, g, gpc, cam, glights = lit_frame("toroidal")
+    off = camera_truth.grid_2x2(cam)
+    for rows in (None, BAND):
+        devi = lit_camera_dev(tr, gsc, g, gpc, cam, glights, 8, samples=4, offsets=off, rows=rows)
+        hosti = tr.shade_lit_camera(gsc, g, gpc, W, H, camera=cam, samples=4, offsets=off, rows=rows, lights=glights, shadow_samples=8)
+        r0, r1 = (0, H) if rows is None else rows
+        assert np.array_equal(u32(hosti[r0:r1]), u32(devi[r0:r1])) and not hosti[:r0].any() and not hosti[r1:].any()
+    # n == 0 and row_begin == row_end: nothing launched, nothing written
+    z = np.zeros((0, 3), f32)
+    assert tr.shade_lit(sc, z, z, pc, lights=lights, shadow_samples=K).shape == (0, 4)
+    assert not tr.shade_lit_camera(gsc, g, gpc, W, H, camera=cam, rows=(7, 7), lights=glights, shadow_samples=8).any()
+    buf = image(16)
+    tr.enable_stats(True)
+    try:
+        tr.shade_lit_dev(sc, [0] * 6, 0, pc, buf.data_ptr(), lights=lights, shadow_samples=K)
+        st0 = tr.stats()
+        tr.shade_lit_camera_dev(gsc, g, gpc, W, H, buf.data_ptr(), camera=cam, rows=(7, 7), lights=glights, shadow_samples=8)
+        st1 = tr.stats()
+    finally:
+        tr.enable_stats(False)
+        tr.set_torus_axes(None)
+    torch.cuda.synchronize()
+    assert (buf.cpu().numpy() == f32(SENTINEL)).all()
+    for st in (st0, st1):
+        assert st["pixels"] == 0 and all(st[k] == 0 for k in QUERY_KEYS)
+
+
+def test_the_full_tables_are_read_to_their_end(tr):
+    """n_lights == 8 and K == 64 on 257 rays: host and device forms agree, the counters count 64 rays per lit hit and
+    light at the most, and both the last light and the last disc position are in the picture."""
+    c = lt.case("nest3_area_point")
+    sc, pc = c["sc"], c["pc"]
+    o, d = c["o"][1000:1257], c["d"][1000:1257]
+    rng = np.random.default_rng(3)
+    lights = [abi.make_light(rng.uniform(-3.0, 3.0, 3) + (0.0, 4.0, 0.0), 5.0, rng.uniform(0.2, 1.0, 3), radius=0.5) for _ in range(8)]
+    disc = abi.disc_samples(64)
+    dev, st = lit_dev(tr, sc, o, d, pc, lights, 64, disc, stats=True)
+    host = tr.shade_lit(sc, o, d, pc, lights=lights, shadow_samples=64, disc=disc)
+    assert np.array_equal(u32(host), u32(dev)) and np.isfinite(dev).all() and len(np.unique(u32(dev), axis=0)) > 20
+    assert 0 < st["shadow_tests"] <= (st["primary_tests"] + st["bounce_tests"]) * 8 * 64
+    dark = lights[:7] + [abi.make_light(lights[7].position[:], 5.0, (0.0, 0.0, 0.0), radius=0.5)]
+    assert (u32(lit_dev(tr, sc, o, d, pc, dark, 64, disc)) != u32(dev)).any()
+    moved = disc.copy()
+    moved[63] = (0.0, 0.0)
+    assert (u32(lit_dev(tr, sc, o, d, pc, lights, 64, moved)) != u32(dev)).any()
+
+
+def test_capture_and_replay(tr):
+    """Both _dev calls captured on one stream into a graph and replayed twice give the eager bits (kernel nodes only, no ctx
+    scratch but the toroidal tables: the toroidal call is made eagerly once first); an eager call with another scene and
+    other lights between the replays changes nothing — the tables are in the nodes' arguments."""
+    import torch
+    c = lt.case("nest3_area_point")
+    sc, pc, lights, K, disc = c["sc"], c["pc"], c["lights"], c["K"], c["disc"]
+    n = 256 * 5 + 33
+    o, d = c["o"][:2 * n], c["d"][:2 * n]
+    eager = lit_dev(tr, sc, o, d, pc, lights, K, disc, samples=2)
+    gsc, g, gpc, cam, glights = lit_frame("toroidal")
+    off = camera_truth.grid_2x2(cam)
+    eager_img = lit_camera_dev(tr, gsc, g, gpc, cam, glights, 8, samples=4, offsets=off, rows=BAND)   # (uploads the tables)
+    keep, ptrs = upload(o, d)
+    buf, img = image(n * 4), frame_image(W, H)
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=side):
+            tr.shade_lit_dev(sc, ptrs, 2 * n, pc, buf.data_ptr(), samples=2, stream=side.cuda_stream, lights=lights, shadow_samples=K, disc=disc)
+            tr.shade_lit_camera_dev(gsc, g, gpc, W, H, img.data_ptr(), camera=cam, samples=4, offsets=off, rows=BAND,
+                                    stream=side.cuda_stream, lights=glights, shadow_samples=8)
+    cur.wait_stream(side)
+    other = lt.case("single_three")
+    for k in range(2):
+        buf.fill_(SENTINEL)
+        img.fill_(SENTINEL)
+        gr.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(u32(read(buf, n * 4).reshape(n, 4)), u32(eager)), k
+        assert np.array_equal(u32(read_image(img, W, H, BAND)), u32(eager_img)), k
+        lit_dev(tr, other["sc"], other["o"][:500], other["d"][:500], other["pc"], other["lights"], other["K"], other["disc"])   # an eager call in between
+    assert len(np.unique(u32(eager), axis=0)) > 50
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. refusals
+# ---------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_ctx_usable_and_the_outputs_unwritten(tr):
+    import torch
+    from toroidal_ray_tracing_amd.tracer import TrtError
+    c = lt.case("single_three")
+    sc, pc, lights, K, disc = c["sc"], c["pc"], c["lights"], c["K"], c["disc"]
+    n = 300
+    o, d = c["o"][:n], c["d"][:n]
+    want = lit_dev(tr, sc, o, d, pc, lights, K, disc)
+    gsc, g, gpc, cam, glights = lit_frame("pinhole")
+    want_img = lit_camera_dev(tr, gsc, g, gpc, cam, glights, 8)
+    keep, ptrs = upload(o, d)
+    out = image(n * 4)
+    img = frame_image(W, H)
+    host_out = np.full((n + 1, 4), SENTINEL, f32)
+    L = tr._L
+    rays = abi.rays_struct(ptrs, n)
+    host_rays = abi.rays_struct([np.ascontiguousarray(a[:, k]) for a in (o, d) for k in range(3)], n)
+
+    def good():
+        assert np.array_equal(u32(lit_dev(tr, sc, o, d, pc, lights, K, disc)), u32(want))
+        assert np.array_equal(u32(lit_camera_dev(tr, gsc, g, gpc, cam, glights, 8)), u32(want_img))
+
+    def refused(call, who, *needles):
+        with pytest.raises(TrtError) as e:
+            call()
+        assert e.value.code == abi.TRT_E_INVALID, str(e.value)
+        for needle in (who + ":",) + needles:
+            assert needle in str(e.value), str(e.value)
+        good()
+
+    def refused_raw(rc, *needles):
+        assert rc == abi.TRT_E_INVALID
+        for needle in needles:
+            assert needle in L.trt_last_error(tr._h), L.trt_last_error(tr._h)
+        good()
+
+    good()
+    sl, slc = "trt_shade_lit", "trt_shade_lit_camera"
+    lk = dict(lights=lights, shadow_samples=K, disc=disc)
+    # everything trt_shade* refuses, with this call's name
+    refused(lambda: tr.shade_lit_dev(sc, ptrs, n, pc, out.data_ptr(), samples=0, **lk), sl, "samples")
+    refused(lambda: tr.shade_lit_dev(sc, ptrs, n, pc, out.data_ptr(), samples=7, **lk), sl, "multiple")        # 300 % 7 != 0
+    refused(lambda: tr.shade_lit_dev(sc, ptrs, n, pc, out.data_ptr() + 4, **lk), sl, "aligned")
+    refused(lambda: tr.shade_lit_dev(sc, ptrs, n, pc, 0, **lk), sl, "NULL")
+    refused(lambda: tr.shade_lit_dev(sc, ptrs[:2] + [0] + ptrs[3:], n, pc, out.data_ptr(), **lk), sl, "NULL ray stream")
+    refused(lambda: tr.shade_lit(sc, o, d, pc, samples=0, **lk), sl, "samples")
+    refused(lambda: tr.shade_lit(sc, o, d, pc, samples=7, **lk), sl, "multiple")
+    table, keep_t = abi.lights_struct(lights, K, disc)
+    tp, scp, pcp, outp = C.byref(table), C.byref(sc.c), C.byref(pc), C.c_void_p(out.data_ptr())
+    refused_raw(L.trt_shade_lit_dev(tr._h, None, 1, pcp, tp, scp, outp, None), b"trt_shade_lit:")
+    refused_raw(L.trt_shade_lit_dev(tr._h, C.byref(rays), 1, None, tp, scp, outp, None), b"trt_shade_lit:")
+    refused_raw(L.trt_shade_lit_dev(tr._h, C.byref(rays), 1, pcp, tp, None, outp, None), b"scene")
+    refused_raw(L.trt_shade_lit(tr._h, C.byref(host_rays), 1, pcp, tp, scp, None), b"trt_shade_lit:")
+    refused_raw(L.trt_shade_lit(tr._h, C.byref(host_rays), 1, pcp, tp, scp, host_out.ctypes.data + 4), b"trt_shade_lit:")
+    # everything trt_shade_camera* refuses, with this call's name
+    glk = dict(lights=glights, shadow_samples=8)
+    cam_dev = lambda **kw: tr.shade_lit_camera_dev(gsc, g, gpc, kw.pop("W", W), kw.pop("H", H), kw.pop("ptr", img.data_ptr()),
+                                                   camera=kw.pop("camera", cam), **dict(glk, **kw))
+    refused(lambda: cam_dev(W=0), slc, "bad size")
+    refused(lambda: cam_dev(rows=(9, 5)), slc, "bad size")
+    refused(lambda: cam_dev(rows=(0, H + 1)), slc, "bad size")
+    refused(lambda: cam_dev(camera=5), slc, "unknown camera")
+    refused(lambda: cam_dev(samples=0), slc, "samples")
+    refused(lambda: cam_dev(samples=abi.TRT_MAX_CAMERA_SAMPLES + 1, offsets=np.zeros((abi.TRT_MAX_CAMERA_SAMPLES + 1, 2), f32)), slc, "samples")
+    refused(lambda: cam_dev(samples=2, offsets=f32([[0.0, 0.0], [1.5, 0.0]])), slc, "offset")
+    refused(lambda: cam_dev(samples=2, offsets=f32([[0.0, np.nan], [0.0, 0.0]])), slc, "offset")
+    refused(lambda: cam_dev(ptr=img.data_ptr() + 4), slc, "aligned")
+    refused(lambda: cam_dev(ptr=0), slc, "NULL")
+    refused(lambda: tr.shade_lit_camera(gsc, g, gpc, W, H, camera=5, **glk), slc, "unknown camera")
+    gtable, keep_g = abi.lights_struct(glights, 8)
+    gtp, gp, gpcp, gscp, imgp = C.byref(gtable), C.byref(g), C.byref(gpc), C.byref(gsc.c), C.c_void_p(img.data_ptr())
+    refused_raw(L.trt_shade_lit_camera_dev(tr._h, None, gpcp, gtp, gscp, W, H, 0, H, cam, 1, None, imgp, None), b"trt_shade_lit_camera:")
+    refused_raw(L.trt_shade_lit_camera_dev(tr._h, gp, None, gtp, gscp, W, H, 0, H, cam, 1, None, imgp, None), b"trt_shade_lit_camera:")
+    refused_raw(L.trt_shade_lit_camera_dev(tr._h, gp, gpcp, gtp, None, W, H, 0, H, cam, 1, None, imgp, None), b"scene")
+
+    # the light table, through all four calls
+    def every_form(lights_, K_, disc_, *needles):
+        kw = dict(lights=lights_, shadow_samples=K_, disc=disc_)
+        refused(lambda: tr.shade_lit_dev(sc, ptrs, n, pc, out.data_ptr(), **kw), sl, *needles)
+        refused(lambda: tr.shade_lit(sc, o, d, pc, **kw), sl, *needles)
+        refused(lambda: tr.shade_lit_camera_dev(gsc, g, gpc, W, H, img.data_ptr(), camera=cam, **kw), slc, *needles)
+        refused(lambda: tr.shade_lit_camera(gsc, g, gpc, W, H, camera=cam, **kw), slc, *needles)
+
+    nan, inf = float("nan"), float("inf")
+    base = dict(position=(1.0, 5.0, 2.0), intensity=50.0, color=(1.0, 1.0, 1.0), type=0, radius=0.5)
+    mk = lambda **f: abi.make_light(**dict(base, **f))
+    every_form([mk()] * 9, 8, None, "n_lights", "TRT_MAX_LIGHTS")
+    every_form([mk(type=2)], 8, None, "light 0", "type")
+    every_form([mk(), mk(type=-1)], 8, None, "light 1", "type")
+    for r in (nan, inf, -0.5):
+        every_form([mk(), mk(radius=r)], 8, None, "light 1", "radius")
+    for k, bad in enumerate((nan, inf, -inf)):
+        every_form([mk(position=tuple(bad if j == k else 1.0 for j in range(3)))], 8, None, "light 0", "position")
+        every_form([mk(color=tuple(bad if j == k else 1.0 for j in range(3)))], 8, None, "light 0", "color")
+    for bad in (nan, inf):
+        every_form([mk(intensity=bad)], 8, None, "light 0", "intensity")
+    every_form([mk()], 0, None, "shadow_samples")
+    every_form([mk()], abi.TRT_MAX_LIGHT_SAMPLES + 1, np.zeros((abi.TRT_MAX_LIGHT_SAMPLES + 1, 2), f32), "shadow_samples", "TRT_MAX_LIGHT_SAMPLES")
+    every_form([mk(radius=0.0)], 0, None, "shadow_samples")                     # K is checked whatever the radii
+    for bad in (nan, inf):
+        table8 = abi.disc_samples(8)
+        table8[5, 1] = bad
+        every_form([mk()], 8, table8, "disc", "sample 5")
+    # what the binding cannot express: NULL lights, a NULL table with n_lights > 0, a NULL disc with an area light
+    one, keep_1 = abi.lights_struct([mk()], 8)
+    for form in ("rays", "camera"):
+        def raw(tp_):
+            if form == "rays":
+                return L.trt_shade_lit_dev(tr._h, C.byref(rays), 1, pcp, tp_, scp, outp, None)
+            return L.trt_shade_lit_camera_dev(tr._h, gp, gpcp, tp_, gscp, W, H, 0, H, cam, 1, None, imgp, None)
+        who = (sl if form == "rays" else slc).encode() + b":"
+        refused_raw(raw(None), who, b"NULL lights")
+        refused_raw(raw(C.byref(abi.trt_lights(None, 2, 8, one.disc))), who, b"NULL light table")
+        refused_raw(raw(C.byref(abi.trt_lights(one.lights, 1, 8, None))), who, b"NULL disc")
+    assert L.trt_shade_lit(tr._h, C.byref(host_rays), 1, pcp, None, scp, host_out.ctypes.data) == abi.TRT_E_INVALID
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == f32(SENTINEL)).all() and (host_out == f32(SENTINEL)).all()   # a refused call writes nothing
+    assert (img.cpu().numpy() == f32(SENTINEL)).all()
+    # accepted: a hard light needs no disc, and a table with n_lights == 0 no lights
+    hard, keep_h = abi.lights_struct([mk(radius=0.0)], 8)
+    assert not hard.disc and L.trt_shade_lit_dev(tr._h, C.byref(rays), 1, pcp, C.byref(hard), scp, outp, None) == abi.TRT_OK
+    assert L.trt_shade_lit_dev(tr._h, C.byref(rays), 1, pcp, C.byref(abi.trt_lights(None, 0, 1, None)), scp, outp, None) == abi.TRT_OK
+    torch.cuda.synchronize()
+    assert L.trt_shade_lit_dev(None, C.byref(rays), 1, pcp, tp, scp, outp, None) == abi.TRT_E_INVALID
+    assert L.trt_shade_lit_camera_dev(None, gp, gpcp, gtp, gscp, W, H, 0, H, cam, 1, None, imgp, None) == abi.TRT_E_INVALID
+    good()

@@ -91,6 +91,66 @@ def media(items):
     return arr
 
 
+TRT_MAX_LIGHTS = 8                      # lights per trt_shade_lit* call
+TRT_MAX_LIGHT_SAMPLES = 64              # shadow rays per area light per hit
+
+
+class trt_light(C.Structure):
+    """One light of trt_shade_lit*: pc's light (position / direction towards it, intensity, type) with a colour and a
+    radius; radius 0 is the reference's light, radius > 0 an area light."""
+    _fields_ = [("position", C.c_float * 3), ("intensity", C.c_float), ("color", C.c_float * 3),
+                ("type", C.c_int32), ("radius", C.c_float)]
+
+
+class trt_lights(C.Structure):
+    """The light table of trt_shade_lit*: host pointers in every form of the call."""
+    _fields_ = [("lights", C.POINTER(trt_light)), ("n_lights", C.c_uint32), ("shadow_samples", C.c_uint32),
+                ("disc", f32p)]
+
+
+assert C.sizeof(trt_light) == 36
+
+
+def make_light(position, intensity=100.0, color=(1.0, 1.0, 1.0), type=0, radius=0.0):
+    """A ``trt_light``: type 0 a point light at ``position``, type 1 a directional one whose ``position`` points towards
+    it; ``radius`` > 0 makes it an area light (a disc across the direction to it)."""
+    q = trt_light()
+    q.position[:] = [float(v) for v in position]
+    q.intensity = float(intensity)
+    q.color[:] = [float(v) for v in color]
+    q.type = int(type)
+    q.radius = float(radius)
+    return q
+
+
+def light_from_push(pc):
+    """The light inside a ``trt_push`` as a ``trt_light``: white, radius 0 — trt_shade_lit with it alone is trt_shade."""
+    return make_light(pc.lightPosition[:], pc.lightIntensity, (1.0, 1.0, 1.0), pc.lightType, 0.0)
+
+
+def disc_samples(K):
+    """K positions on the unit disc, a Vogel spiral: r = sqrt((s + 0.5) / K) at the angle s times the golden angle.
+    (K, 2) float32, what ``trt_lights.disc`` takes.  Caller data: the library reads whatever table it is given."""
+    s = np.arange(int(K), dtype=np.float64)
+    r, phi = np.sqrt((s + 0.5) / max(int(K), 1)), s * 2.399963229728653
+    return np.ascontiguousarray(np.stack([r * np.cos(phi), r * np.sin(phi)], axis=1), np.float32)
+
+
+def lights_struct(lights, shadow_samples=1, disc=None):
+    """(trt_lights, keep): the table of trt_shade_lit* from an iterable of ``trt_light`` (None: a NULL table), K and a
+    (K, 2) disc table (None: ``disc_samples(K)`` when a light has a radius, else NULL).  ``keep`` owns the memory."""
+    K = int(shadow_samples)
+    items = None if lights is None else list(lights)
+    arr = None if items is None else (trt_light * max(len(items), 1))(*items)
+    if disc is None and items and any(q.radius > 0 for q in items) and 1 <= K <= TRT_MAX_LIGHT_SAMPLES:
+        disc = disc_samples(K)
+    d = None if disc is None else np.ascontiguousarray(np.asarray(disc, np.float32).reshape(-1))
+    if d is not None and d.size != 2 * K:
+        raise ValueError(f"{d.size} disc values for {K} shadow samples (2 per sample)")
+    st = trt_lights(arr, 0 if items is None else len(items), K, None if d is None else d.ctypes.data_as(f32p))
+    return st, (arr, d)
+
+
 class trt_rays(C.Structure):
     _fields_ = [("ox", C.c_void_p), ("oy", C.c_void_p), ("oz", C.c_void_p),
                 ("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p),

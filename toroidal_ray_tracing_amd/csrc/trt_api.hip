@@ -893,7 +893,7 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 }
 
 // The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev,
-// trt_transmittance_dev, trt_shade_through_dev, trt_chords_dev, trt_glow_dev, trt_shade_refract_dev, trt_shade_refract_camera_dev), after the entry
+// trt_transmittance_dev, trt_shade_through_dev, trt_chords_dev, trt_glow_dev, trt_shade_refract_dev, trt_shade_refract_camera_dev, trt_shade_lit_dev, trt_shade_lit_camera_dev), after the entry
 // point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
@@ -1036,7 +1036,7 @@ extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
 // ------------------------------------------------------------------------------------------
 // shade: the render's bounce loop on caller-supplied rays, samples averaged
 // ------------------------------------------------------------------------------------------
-// (`who`: trt_shade, or trt_shade_through / trt_shade_refract, which take the same rays, samples and image)
+// (`who`: trt_shade, or trt_shade_through / trt_shade_refract / trt_shade_lit, which take the same rays, samples and image)
 static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba, const char* who = "trt_shade")
 {
   if(ctx && (!in || !pc || !rgba)) return fail(ctx, TRT_E_INVALID, "%s: NULL rays, push constants or image", who);
@@ -1507,6 +1507,115 @@ extern "C" int trt_shade_refract_camera(trt_ctx* ctx, const trt_globals* g, cons
   if(int rc = stage_outs(ctx, &image, 1)) return rc;
   float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
   if(int rc = trt_shade_refract_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// several lights, area lights: trt_shade and trt_shade_camera with a light table in the place of pc's light
+// ------------------------------------------------------------------------------------------
+// What the four trt_shade_lit* calls (`who`) share behind their own checks: the checks of include/trt.h on the light table
+// and the disc table, the Lights they describe, and the scene (validated here, so that a refused call has touched nothing
+// of the ctx — the toroidal tables of the camera form come after it).  No scratch of the ctx: both tables travel in the
+// kernel arguments.
+static int lit_lights(trt_ctx* ctx, const char* who, const trt_lights* in, const trt_scene* scene, Lights& lt)
+{
+  if(!in) return fail(ctx, TRT_E_INVALID, "%s: NULL lights", who);
+  if(in->n_lights > TRT_MAX_LIGHTS)
+    return fail(ctx, TRT_E_INVALID, "%s: n_lights = %u, must be 0..%d (TRT_MAX_LIGHTS)", who, in->n_lights, TRT_MAX_LIGHTS);
+  if(in->n_lights && !in->lights) return fail(ctx, TRT_E_INVALID, "%s: NULL light table with n_lights = %u", who, in->n_lights);
+  if(in->shadow_samples < 1 || in->shadow_samples > TRT_MAX_LIGHT_SAMPLES)
+    return fail(ctx, TRT_E_INVALID, "%s: shadow_samples = %u, must be 1..%d (TRT_MAX_LIGHT_SAMPLES)", who, in->shadow_samples, TRT_MAX_LIGHT_SAMPLES);
+  std::memset(&lt, 0, sizeof lt);
+  lt.n = in->n_lights;
+  lt.K = in->shadow_samples;
+  bool area = false;
+  for(uint32_t l = 0; l < lt.n; ++l)
+  {
+    const trt_light& q = lt.l[l] = in->lights[l];
+    if(q.type != 0 && q.type != 1) return fail(ctx, TRT_E_INVALID, "%s: light %u has the unknown type %d (0 point, 1 directional)", who, l, (int)q.type);
+    if(!std::isfinite(q.radius) || q.radius < 0.0f)
+      return fail(ctx, TRT_E_INVALID, "%s: light %u has radius = %g; it must be finite and >= 0", who, l, (double)q.radius);
+    for(int k = 0; k < 3; ++k)
+    {
+      if(!std::isfinite(q.position[k])) return fail(ctx, TRT_E_INVALID, "%s: light %u has position[%d] = %g; it must be finite", who, l, k, (double)q.position[k]);
+      if(!std::isfinite(q.color[k])) return fail(ctx, TRT_E_INVALID, "%s: light %u has color[%d] = %g; it must be finite", who, l, k, (double)q.color[k]);
+    }
+    if(!std::isfinite(q.intensity)) return fail(ctx, TRT_E_INVALID, "%s: light %u has intensity = %g; it must be finite", who, l, (double)q.intensity);
+    area = area || q.radius > 0.0f;
+  }
+  if(area && !in->disc) return fail(ctx, TRT_E_INVALID, "%s: NULL disc table while a light has radius > 0", who);
+  for(uint32_t s = 0; s < lt.K && in->disc; ++s)
+  {
+    lt.u[s] = in->disc[2 * s];
+    lt.v[s] = in->disc[2 * s + 1];
+    if(!std::isfinite(lt.u[s]) || !std::isfinite(lt.v[s]))
+      return fail(ctx, TRT_E_INVALID, "%s: the disc position of sample %u, (%g, %g), is not finite", who, s, (double)lt.u[s], (double)lt.v[s]);
+  }
+  const SceneK* S = nullptr;
+  return build_scene(ctx, scene, S);
+}
+
+extern "C" int trt_shade_lit_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                                 const trt_scene* scene, float* rgba, void* stream)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba, "trt_shade_lit")) return rc;
+  ShadeLitArgs a;
+  if(int rc = lit_lights(ctx, "trt_shade_lit", lights, scene, a.lights)) return rc;
+  a.rays    = *in;
+  a.n_out   = in->n / samples;
+  a.samples = samples;
+  a.pc      = *pc;
+  a.rgba    = rgba;
+  return ray_query(ctx, scene, stream, in->n, a, launch_shade_lit);
+}
+
+// Host buffers: as trt_shade's.
+extern "C" int trt_shade_lit(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                             const trt_scene* scene, float* rgba_out)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, "trt_shade_lit")) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_shade_lit_dev(ctx, in, samples, pc, lights, scene, rgba_out, nullptr);   // validates, launches and writes nothing
+  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
+  trt_rays  din;
+  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  if(int rc = trt_shade_lit_dev(ctx, &din, samples, pc, lights, scene, (float*)image.dev, nullptr)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+// The lights and the scene are checked before the toroidal tables are touched: a refused call leaves them as they were.
+extern "C" int trt_shade_lit_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, const trt_scene* scene,
+                                        uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
+                                        const float* offsets, float* rgba, void* stream)
+{
+  ShadeLitCameraArgs a;
+  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba, a.cam, "trt_shade_lit_camera")) return rc;
+  if(int rc = lit_lights(ctx, "trt_shade_lit_camera", lights, scene, a.lights)) return rc;
+  a.pc   = *pc;
+  a.rgba = rgba;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(int rc = camera_tables(ctx, g, pc, (hipStream_t)stream, a.cam)) return rc;
+  return ray_query(ctx, scene, stream, a.cam.n_px * samples, a, launch_shade_lit_camera);
+}
+
+// Host buffers: as trt_shade_camera's.
+extern "C" int trt_shade_lit_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, const trt_scene* scene,
+                                    uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
+                                    const float* offsets, float* rgba_out)
+{
+  CameraArgs c;
+  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, c, "trt_shade_lit_camera")) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(c.n_px == 0)   // validates the lights and the scene, launches and writes nothing
+    return trt_shade_lit_camera_dev(ctx, g, pc, lights, scene, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, nullptr);
+  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "trt_shade_lit_camera: the band does not fit the address space");
+  const size_t before = (size_t)row_begin * W * 4;   // floats of the image in front of the band
+  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
+  if(int rc = trt_shade_lit_camera_dev(ctx, g, pc, lights, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
   return fetch_outs(ctx, &image, 1);
 }
 

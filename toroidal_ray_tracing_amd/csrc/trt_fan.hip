@@ -1,6 +1,6 @@
 // trt_fan.hip — the ray-fan kernels of the toroidal ray tracer (trt_fan_rays*, trt_fan_occluded*), gfx950.
 //
-//   fan_basis, fan_dir          the arithmetic contract of include/trt.h: Duff et al.'s basis about N, one sample's direction.
+//   fan_dir                     the arithmetic contract of include/trt.h: one sample's direction in Duff et al.'s basis about N (fan_basis, trt_render.hpp).
 //   fan_sample_dir              the choice between the table entry and fan_dir, for the two kernels with one lane per point.
 //   fan_rays_kernel             fan(points → rays_out): `samples` rays per surface point, SoA and sample-major, out.
 //   fan_occluded_kernel         form kFanLane of fan(points → bits, open): one lane owns a point and walks its samples.
@@ -13,18 +13,7 @@
 
 namespace trt {
 
-// The basis about N (TRT_FAN_LOCAL): T and B of include/trt.h, operation for operation.  |sg + nz| >= 1: no pole.
-struct FanBasis { v3 T, B; };
-__device__ __forceinline__ FanBasis fan_basis(v3 N)
-{
-  const float sg = copysignf(1.0f, N.z);
-  const float a  = -1.0f / (sg + N.z);
-  const float b  = (N.x * N.y) * a;
-  FanBasis f;
-  f.T = {1.0f + ((sg * N.x) * N.x) * a, sg * b, (-sg) * N.x};
-  f.B = {b, sg + (N.y * N.y) * a, -N.y};
-  return f;
-}
+// (FanBasis, fan_basis: trt_render.hpp — the area lights of trt_lights.hip build the same basis about L.)
 // d.k = ((lx * T.k) + (ly * B.k)) + (lz * N.k)
 __device__ __forceinline__ v3 fan_dir(const FanBasis& f, v3 N, float lx, float ly, float lz)
 {

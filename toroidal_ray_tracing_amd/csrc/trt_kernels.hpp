@@ -1,5 +1,5 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_rays.hip, trt_through.hip, trt_glass.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// (trt_rays.hip, trt_through.hip, trt_glass.hip, trt_lights.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
 // trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
 // What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
@@ -318,8 +318,36 @@ struct ShadeRefractCameraArgs {
   unsigned long long* stats;
 };
 
+// trt_shade_lit*, trt_shade_lit_camera*: the light table and the disc table (u[s], v[s]) of the area lights, validated and
+// copied on the host.  They travel here, in the kernel-argument segment, as FanArgs' table and Glass do (808 B): the calls
+// use no scratch of the ctx, and the kernels read them with scalar loads — every index is kernel-uniform.
+struct Lights {
+  trt_light l[TRT_MAX_LIGHTS];
+  uint32_t  n;   // 0 .. TRT_MAX_LIGHTS
+  uint32_t  K;   // 1 .. TRT_MAX_LIGHT_SAMPLES: shadow rays per area light per hit
+  float     u[TRT_MAX_LIGHT_SAMPLES], v[TRT_MAX_LIGHT_SAMPLES];
+};
+// trt_shade_lit*: ShadeArgs with the lights (pc's own light is not read).
+struct ShadeLitArgs {
+  trt_rays            rays;
+  uint64_t            n_out;
+  uint32_t            samples;   // >= 1, divides rays.n
+  trt_push            pc;
+  Lights              lights;
+  float*              rgba;
+  unsigned long long* stats;
+};
+// trt_shade_lit_camera*: ShadeCameraArgs with the lights.
+struct ShadeLitCameraArgs {
+  CameraArgs          cam;
+  trt_push            pc;
+  Lights              lights;
+  float*              rgba;
+  unsigned long long* stats;
+};
+
 // The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels,
-// the fan kernels, transmittance_kernel, shade_through_kernel, chords_kernel, glow_kernel, the two shade_refract kernels; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
+// the fan kernels, transmittance_kernel, shade_through_kernel, chords_kernel, glow_kernel, the two shade_refract kernels, the two shade_lit kernels; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
 // points), at most 4096 blocks (TRT_TRACE_BLOCKS).
 inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
@@ -346,6 +374,8 @@ hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStre
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract_camera(const SceneK& scene, const ShadeRefractCameraArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_lit(const SceneK& scene, const ShadeLitArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_lit_camera(const SceneK& scene, const ShadeLitCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

@@ -1,8 +1,10 @@
 // trt_render.hpp — what more than one kernel family of the render path uses.  Device side: included only by
-// trt_rays.hip, trt_through.hip, trt_glass.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
+// trt_rays.hip, trt_through.hip, trt_glass.hip, trt_lights.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
 //
 //   gptr, st1 / st4 / st4c, ld1           global-memory accessors
 //   HitState, hit_begin, hit_end          the closest-hit shader body, split at the shadow query
+//   hit_point, hit_mirror                 its two halves that know no light: the geometry of the hit, the mirror step
+//   FanBasis, fan_basis                   Duff et al.'s basis about a unit vector (the fans about N, the area lights about L)
 //   image_row, out_index, rendered_record pixel addressing
 //   miss_id, miss_colour, miss_rgba, store_first_hit, store_first_miss   the first-hit record and the miss record
 //   block_add_stats                       the query counters of a block → the global totals
@@ -64,13 +66,21 @@ struct HitState {
   bool  wantShadow;  // dot(N,L) > 0  (rchit:112)
 };
 
+// The geometry half of hit_begin: the material, P and N of the hit — what does not depend on the light (lit_loop,
+// trt_lights.hip, forms the light half once per light of its table).
 template <bool ORIENT = false>
-__device__ __forceinline__ void hit_begin(const SceneK& S, const trt_push& pc, int id, float t, v3 o,
-                                          v3 d, HitState& h)
+__device__ __forceinline__ void hit_point(const SceneK& S, int id, float t, v3 o, v3 d, HitState& h)
 {
   h.matId = S.shade[id].matId;                                               // rchit:95-96
   h.P     = {fma_(t, d.x, o.x), fma_(t, d.y, o.y), fma_(t, d.z, o.z)};       // BEF rchit:134
   h.N     = torus_normal<ORIENT>(S, id, h.P);
+}
+
+template <bool ORIENT = false>
+__device__ __forceinline__ void hit_begin(const SceneK& S, const trt_push& pc, int id, float t, v3 o,
+                                          v3 d, HitState& h)
+{
+  hit_point<ORIENT>(S, id, t, o, d, h);
   const v3 lp = {pc.lightPosition[0], pc.lightPosition[1], pc.lightPosition[2]};
   h.lightIntensity = pc.lightIntensity;                                      // rchit:79
   h.lightDistance  = 100000.0f;                                              // rchit:80
@@ -87,6 +97,21 @@ __device__ __forceinline__ void hit_begin(const SceneK& S, const trt_push& pc, i
   h.wantShadow = dot3(h.N, h.L) > 0.0f;                                      // rchit:112
 }
 
+// The mirror step of the closest-hit shader (rchit:145-153), stated once for hit_end and lit_loop (trt_lights.hip): an
+// illum == 3 material scales the payload's attenuation by Ks and sets the next segment.
+__device__ __forceinline__ void hit_mirror(const MaterialK& mat, const HitState& h, v3 d, v3& attenuation, int& done, v3& nextO, v3& nextD)
+{
+  if(mat.illum == 3)                                                         // rchit:145
+  {
+    attenuation.x *= mat.specular[0];
+    attenuation.y *= mat.specular[1];
+    attenuation.z *= mat.specular[2];
+    done  = 0;
+    nextO = h.P;
+    nextD = reflect3(d, h.N);
+  }
+}
+
 // Finishes the closest-hit shader once the shadow query is answered; returns prd.hitValue and
 // updates the payload (attenuation, done, next ray) exactly as rchit:133-155.
 __device__ __forceinline__ v3 hit_end(const SceneK& S, const HitState& h, v3 d, bool shadowed,
@@ -100,15 +125,7 @@ __device__ __forceinline__ v3 hit_end(const SceneK& S, const HitState& h, v3 d, 
     if(shadowed) attenuation1 = 0.3f;                                        // rchit:135
     else specular = compute_specular(mat, d, h.L, h.N);                      // rchit:140
   }
-  if(mat.illum == 3)                                                         // rchit:145
-  {
-    attenuation.x *= mat.specular[0];
-    attenuation.y *= mat.specular[1];
-    attenuation.z *= mat.specular[2];
-    done  = 0;
-    nextO = h.P;
-    nextD = reflect3(d, h.N);
-  }
+  hit_mirror(mat, h, d, attenuation, done, nextO, nextD);
   const float k = attenuation1 * h.lightIntensity;                           // rchit:155
   return {k * (h.diffuse.x + specular.x), k * (h.diffuse.y + specular.y),
           k * (h.diffuse.z + specular.z)};
@@ -261,6 +278,22 @@ __device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const S
     }
   }
   __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------
+// the orthonormal basis about a unit vector (trt_fan.hip: about N; trt_lights.hip: about L)
+// ------------------------------------------------------------------------------------------
+// The basis about N (TRT_FAN_LOCAL): T and B of include/trt.h, operation for operation.  |sg + nz| >= 1: no pole.
+struct FanBasis { v3 T, B; };
+__device__ __forceinline__ FanBasis fan_basis(v3 N)
+{
+  const float sg = copysignf(1.0f, N.z);
+  const float a  = -1.0f / (sg + N.z);
+  const float b  = (N.x * N.y) * a;
+  FanBasis f;
+  f.T = {1.0f + ((sg * N.x) * N.x) * a, sg * b, (-sg) * N.x};
+  f.B = {b, sg + (N.y * N.y) * a, -N.y};
+  return f;
 }
 
 constexpr float kTMin = 0.001f;    // rgen:51, rchit:114

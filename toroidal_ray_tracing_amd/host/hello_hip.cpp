@@ -215,6 +215,24 @@ void HelloHip::raytraceRefract(void* stream, const std::array<float, 4>& clearCo
         "HelloHip::raytraceRefract");
 }
 
+void HelloHip::shadeLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, const trt_rays& raysDev,
+                        uint32_t samples, float* rgbaDev)
+{
+  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_shade_lit_dev(m_ctx, &raysDev, samples, &m_pcRay, &lights, &scene, rgbaDev, stream), "HelloHip::shadeLit");
+}
+
+void HelloHip::raytraceLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, uint32_t samples,
+                           const float* offsets)
+{
+  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_shade_lit_camera_dev(m_ctx, &m_globals, &m_pcRay, &lights, &scene, m_size.width, m_size.height, 0, m_size.height, m_camera,
+                                 samples, offsets, m_dColor, stream),
+        "HelloHip::raytraceLit");
+}
+
 void HelloHip::chords(void* stream,const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
 {
   const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};

@@ -74,6 +74,17 @@ public:
   void shadeRefract(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
   void raytraceRefract(void* stream, const std::array<float, 4>& clearColor, uint32_t samples = 1, const float* offsets = nullptr);
 
+  // Several lights and area lights (trt_shade_lit_dev, trt_shade_lit_camera_dev): the light of the push constants is
+  // replaced by `lights` (host memory: the table, K = shadow_samples and the K x 2 disc positions of the area lights; see
+  // include/trt.h).  Only the clear colour of the push constants is refreshed.  shadeLit: every ray of raysDev
+  // (sample-major, `samples` per output) into rgbaDev ((raysDev.n / samples) * 4 floats, 16-byte aligned).  raytraceLit:
+  // the frame of m_camera into the colour image raytrace() writes, `samples` rays per pixel at the sub-pixel offsets
+  // (2 floats per sample; nullptr: the pixel centres); no RenderedData is written.
+  void shadeLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, const trt_rays& raysDev, uint32_t samples,
+                float* rgbaDev);
+  void raytraceLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, uint32_t samples = 1,
+                   const float* offsets = nullptr);
+
   // Media inside the tubes of the tori added so far (trt_chords_dev, trt_glow_dev; materials are not read).  chords: the
   // length of every ray of raysDev inside every tube, lengthDev[j * raysDev.n + i] for torus j (the order of the
   // addTorus calls).  glow: emission and absorption of media (one trt_medium per torus, host memory) integrated along

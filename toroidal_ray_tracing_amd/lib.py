@@ -71,6 +71,16 @@ SYMBOLS = {
     "trt_shade_refract_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, abi.f32p,
                                                C.c_void_p, C.c_void_p]),
+    "trt_shade_lit": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                C.POINTER(abi.trt_scene), C.c_void_p]),
+    "trt_shade_lit_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                    C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p]),
+    "trt_shade_lit_camera": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                       C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                       abi.f32p, C.c_void_p]),
+    "trt_shade_lit_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                           C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                           abi.f32p, C.c_void_p, C.c_void_p]),
     "trt_fan_rays": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,
                                C.POINTER(abi.trt_rays_out)]),
     "trt_fan_rays_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,

@@ -388,6 +388,52 @@ class Tracer:
         self._check(self._L.trt_shade_refract_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1,
                                                          camera, int(samples), off, _vp(rgba_ptr), _vp(stream)))
 
+    # -- several lights, area lights: shade and shade_camera with a light table -------------------
+    def shade_lit(self, scene, o, d, pc, samples=1, lights=(), shadow_samples=1, disc=None):
+        """``shade`` under a table of lights (trt_shade_lit) on host arrays: ``lights`` an iterable of ``abi.trt_light``
+        (``abi.make_light``, ``abi.light_from_push``), at most abi.TRT_MAX_LIGHTS; the light inside ``pc`` is not read.  A
+        light with radius > 0 casts a soft shadow: ``shadow_samples`` any-hit rays per hit towards the positions ``disc``
+        ((K, 2) on the unit disc; None: ``abi.disc_samples(K)``) of its disc.  Layout and averaging as in ``shade``.
+        Returns rgba float32 of shape (n_out, 4), alpha 1."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        samples = int(samples)
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
+        lt, keep = abi.lights_struct(lights, shadow_samples, disc)
+        self._check(self._L.trt_shade_lit(self._h, C.byref(rays), samples, C.byref(pc), C.byref(lt), self._scene(scene), rgba.ctypes.data))
+        return rgba
+
+    def shade_lit_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0, lights=(), shadow_samples=1, disc=None):
+        """Device pointers (ints): as ``shade_dev``; the lights stay on the host (they travel in the launch's arguments).
+        Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        lt, keep = abi.lights_struct(lights, shadow_samples, disc)
+        self._check(self._L.trt_shade_lit_dev(self._h, C.byref(rays), int(samples), C.byref(pc), C.byref(lt), self._scene(scene),
+                                              _vp(rgba_ptr), _vp(stream)))
+
+    def shade_lit_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None,
+                         lights=(), shadow_samples=1, disc=None):
+        """``shade_camera`` under a table of lights (trt_shade_lit_camera) on a host buffer: bit for bit ``camera_rays`` put
+        through ``shade_lit``.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
+        r0, r1 = (0, H) if rows is None else rows
+        rgba = np.zeros((H, W, 4), np.float32)
+        keep, off = self._offsets(offsets, samples)
+        lt, keep_l = abi.lights_struct(lights, shadow_samples, disc)
+        self._check(self._L.trt_shade_lit_camera(self._h, C.byref(g), C.byref(pc), C.byref(lt), self._scene(scene), W, H, r0, r1,
+                                                 camera, int(samples), off, rgba.ctypes.data))
+        return rgba
+
+    def shade_lit_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None,
+                             rows=None, stream=0, lights=(), shadow_samples=1, disc=None):
+        """Device image: as ``shade_camera_dev``; the lights stay on the host.  Asynchronous on ``stream``."""
+        r0, r1 = (0, H) if rows is None else rows
+        keep, off = self._offsets(offsets, samples)
+        lt, keep_l = abi.lights_struct(lights, shadow_samples, disc)
+        self._check(self._L.trt_shade_lit_camera_dev(self._h, C.byref(g), C.byref(pc), C.byref(lt), self._scene(scene), W, H, r0, r1,
+                                                     camera, int(samples), off, _vp(rgba_ptr), _vp(stream)))
+
     # -- ray fans: K rays from every surface point, as streams or as fused ambient occlusion --
     @staticmethod
     def _fan_points(at, frame):
