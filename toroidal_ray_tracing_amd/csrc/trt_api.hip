@@ -882,7 +882,7 @@ extern "C" int trt_get_stats(trt_ctx* ctx, trt_stats* out)
 // ------------------------------------------------------------------------------------------
 // trace
 // ------------------------------------------------------------------------------------------
-// `in` and its six streams, for the entry point `who` (trt_trace, trt_occluded, trt_crossings, trt_shade)
+// `in` and its six streams, for the entry point `who` (any that takes a trt_rays)
 static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 {
   if(!ctx) return TRT_E_INVALID;
@@ -892,9 +892,9 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
   return TRT_OK;
 }
 
-// The device half of a ray query (trt_trace_dev, trt_occluded_dev, trt_crossings_dev, trt_shade_dev, trt_shade_camera_dev, trt_fan_occluded_dev,
-// trt_transmittance_dev, trt_shade_through_dev, trt_chords_dev, trt_glow_dev, trt_shade_refract_dev, trt_shade_refract_camera_dev, trt_shade_lit_dev, trt_shade_lit_camera_dev), after the entry
-// point's own check_*: the scene's kernel constants, then the counted bracket around `launch` of the filled `a` on `stream`.
+// The device half of a ray query — every *_dev entry point whose kernel reads the scene and counts its tests (Args has a
+// `stats` field) — after the entry point's own check_*: the scene's kernel constants, then the counted bracket around
+// `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
                      hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t))
@@ -906,6 +906,31 @@ static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_
   if(int rc = stats_begin(ctx, st, n, a.stats)) return rc;
   TRT_HIP(ctx, launch(*S, a, ctx->tn, st));
   return stats_end(ctx, st);
+}
+
+// The queries that enumerate crossings (`who`) run the default solver only: the enumeration is the walk's.
+static int check_walk_solver(trt_ctx* ctx, const char* who)
+{
+  if(solver_of(ctx->precision).alt == kSolverWalk) return TRT_OK;
+  return fail(ctx, TRT_E_INVALID, "%s: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
+                                  "set one of them with trt_set_solver", who);
+}
+
+// The host staging of a bounded ray query (a host-pointer entry point that takes rays and an optional bound per ray),
+// behind the entry point's own checks and its n == 0 pass-through: the rays staged like trt_trace's, the bounds through
+// buf[kBufTmax], the `n_outs` outputs as `outs` describes them; then dev(rays, bounds) — the *_dev form, which reads
+// outs[k].dev — and the copy back.  Refusals in that order: staging (TRT_E_NOMEM / TRT_E_HIP), then whatever dev refuses.
+template <class Dev>
+static int bounded_query_host(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, StagedOut* outs, int n_outs, Dev&& dev)
+{
+  trt_rays din;
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  const float* d_tmax = nullptr;
+  if(tmax_per_ray)
+    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, (size_t)in->n * sizeof(float), (void**)&d_tmax)) return rc;
+  if(int rc = stage_outs(ctx, outs, n_outs)) return rc;
+  if(int rc = dev(&din, d_tmax)) return rc;
+  return fetch_outs(ctx, outs, n_outs);
 }
 
 static int check_trace(trt_ctx* ctx, const trt_rays* in, const trt_hits* out)
@@ -972,17 +997,12 @@ extern "C" int trt_occluded(trt_ctx* ctx, const trt_rays* in, const float* tmax_
 {
   if(int rc = check_occluded(ctx, in, flag, mask)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t n = (size_t)in->n, bytes = n * sizeof(float), mask_bytes = (n + 63) / 64 * sizeof(uint64_t);
+  const size_t n = (size_t)in->n, mask_bytes = (n + 63) / 64 * sizeof(uint64_t);
   if(n == 0) return trt_occluded_dev(ctx, in, nullptr, scene, tmin, tmax, flag, mask, nullptr);   // validates, launches and writes nothing
-  trt_rays din;
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  const float* d_tmax = nullptr;
-  if(tmax_per_ray)
-    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
   StagedOut outs[2] = {{flag, n, kBufOut, nullptr}, {mask, mask_bytes, kBufOut + 1, nullptr}};
-  if(int rc = stage_outs(ctx, outs, 2)) return rc;
-  if(int rc = trt_occluded_dev(ctx, &din, d_tmax, scene, tmin, tmax, (uint8_t*)outs[0].dev, (uint64_t*)outs[1].dev, nullptr)) return rc;
-  return fetch_outs(ctx, outs, 2);
+  return bounded_query_host(ctx, in, tmax_per_ray, outs, 2, [&](const trt_rays* rays, const float* bounds) {
+    return trt_occluded_dev(ctx, rays, bounds, scene, tmin, tmax, (uint8_t*)outs[0].dev, (uint64_t*)outs[1].dev, nullptr);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -996,10 +1016,7 @@ static int check_crossings(trt_ctx* ctx, const trt_rays* in, uint32_t max_per_ra
   if(max_per_ray < 1 || max_per_ray > TRT_MAX_CROSSINGS)
     return fail(ctx, TRT_E_INVALID, "trt_crossings: max_per_ray = %u, must be 1..%d (TRT_MAX_CROSSINGS)", max_per_ray, TRT_MAX_CROSSINGS);
   if(in->n > UINT64_MAX / max_per_ray) return fail(ctx, TRT_E_INVALID, "trt_crossings: n * max_per_ray overflows 64 bits");
-  if(solver_of(ctx->precision).alt != kSolverWalk)
-    return fail(ctx, TRT_E_INVALID, "trt_crossings: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
-                                    "set one of them with trt_set_solver");
-  return TRT_OK;
+  return check_walk_solver(ctx, "trt_crossings");
 }
 extern "C" int trt_crossings_dev(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, float tmin, float tmax,
                                  uint32_t max_per_ray, const trt_crossing_streams* out, void* stream)
@@ -1036,8 +1053,8 @@ extern "C" int trt_crossings(trt_ctx* ctx, const trt_rays* in, const trt_scene* 
 // ------------------------------------------------------------------------------------------
 // shade: the render's bounce loop on caller-supplied rays, samples averaged
 // ------------------------------------------------------------------------------------------
-// (`who`: trt_shade, or trt_shade_through / trt_shade_refract / trt_shade_lit, which take the same rays, samples and image)
-static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba, const char* who = "trt_shade")
+// (`who`: the four stream forms take the same rays, samples and image)
+static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const float* rgba, const char* who)
 {
   if(ctx && (!in || !pc || !rgba)) return fail(ctx, TRT_E_INVALID, "%s: NULL rays, push constants or image", who);
   if(int rc = check_rays(ctx, in, who)) return rc;
@@ -1047,33 +1064,55 @@ static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const
   if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "%s: the rgba image must be 16-byte aligned (it is written as float4)", who);
   return TRT_OK;
 }
-extern "C" int trt_shade_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
-                             float* rgba, void* stream)
+
+// The device half of the four stream forms (`who`), which differ in the kernel and in the table that travels with its
+// arguments: `table(a)` validates and fills it (through_opacity, refract_glass, lit_lights; nothing for trt_shade).
+// Refusals in this order: check_shade; the table's own checks, the scene's among them; the scene (trt_shade, whose table
+// checks nothing); HIP errors of the launch.
+template <class Args, class Table>
+static int shade_stream_dev(trt_ctx* ctx, const char* who, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                            float* rgba, void* stream, hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), Table&& table)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba)) return rc;
-  ShadeArgs a;
+  if(int rc = check_shade(ctx, in, samples, pc, rgba, who)) return rc;
+  Args a;
+  if(int rc = table(a)) return rc;
   a.rays    = *in;
   a.n_out   = in->n / samples;
   a.samples = samples;
   a.pc      = *pc;
   a.rgba    = rgba;
-  return ray_query(ctx, scene, stream, in->n, a, launch_shade);
+  return ray_query(ctx, scene, stream, in->n, a, launch);
 }
 
-// Host buffers: the rays staged like trt_trace's, the image through buf[kBufRgba] like trt_render's.
+// The host-pointer half of the same four: the rays staged like trt_trace's, the image through buf[kBufRgba] like
+// trt_render's, around dev(rays, image) — the form's own *_dev call on the default stream.  Refusals in this order:
+// check_shade; without rays whatever dev refuses (it validates, launches and writes nothing); staging (TRT_E_NOMEM /
+// TRT_E_HIP); whatever dev refuses.
+template <class Dev>
+static int shade_stream_host(trt_ctx* ctx, const char* who, const trt_rays* in, uint32_t samples, const trt_push* pc, float* rgba_out, Dev&& dev)
+{
+  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, who)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return dev(in, rgba_out);
+  trt_rays  din;
+  StagedOut image = {rgba_out, (size_t)(in->n / samples) * 4 * sizeof(float), kBufRgba, nullptr};
+  if(int rc = stage_rays(ctx, in, din)) return rc;
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  if(int rc = dev(&din, (float*)image.dev)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
+extern "C" int trt_shade_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                             float* rgba, void* stream)
+{
+  return shade_stream_dev(ctx, "trt_shade", in, samples, pc, scene, rgba, stream, launch_shade, [](ShadeArgs&) { return TRT_OK; });
+}
+
 extern "C" int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                          float* rgba_out)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba_out)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0) return trt_shade_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
-  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
-  trt_rays  din;
-  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  if(int rc = trt_shade_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_stream_host(ctx, "trt_shade", in, samples, pc, rgba_out,
+                           [&](const trt_rays* rays, float* image) { return trt_shade_dev(ctx, rays, samples, pc, scene, image, nullptr); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1084,9 +1123,7 @@ extern "C" int trt_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, con
 // `dissolve` — the only readers of that field.  No scratch of the ctx: the table travels in the kernel arguments.
 static int through_opacity(trt_ctx* ctx, const char* who, const trt_scene* scene, Opacity& op)
 {
-  if(solver_of(ctx->precision).alt != kSolverWalk)
-    return fail(ctx, TRT_E_INVALID, "%s: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
-                                    "set one of them with trt_set_solver", who);
+  if(int rc = check_walk_solver(ctx, who)) return rc;
   const SceneK* S = nullptr;
   if(int rc = build_scene(ctx, scene, S)) return rc;
   std::memset(&op, 0, sizeof op);
@@ -1129,46 +1166,24 @@ extern "C" int trt_transmittance(trt_ctx* ctx, const trt_rays* in, const float* 
   if(int rc = check_transmittance(ctx, in, T_out)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   if(in->n == 0) return trt_transmittance_dev(ctx, in, nullptr, scene, tmin, tmax, T_out, nullptr);   // validates, launches and writes nothing
-  const size_t bytes = (size_t)in->n * sizeof(float);
-  trt_rays din;
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  const float* d_tmax = nullptr;
-  if(tmax_per_ray)
-    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
-  StagedOut out = {T_out, bytes, kBufOut, nullptr};
-  if(int rc = stage_outs(ctx, &out, 1)) return rc;
-  if(int rc = trt_transmittance_dev(ctx, &din, d_tmax, scene, tmin, tmax, (float*)out.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &out, 1);
+  StagedOut out = {T_out, (size_t)in->n * sizeof(float), kBufOut, nullptr};
+  return bounded_query_host(ctx, in, tmax_per_ray, &out, 1, [&](const trt_rays* rays, const float* bounds) {
+    return trt_transmittance_dev(ctx, rays, bounds, scene, tmin, tmax, (float*)out.dev, nullptr);
+  });
 }
 
 extern "C" int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                                      float* rgba, void* stream)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba, "trt_shade_through")) return rc;
-  ShadeThroughArgs a;
-  if(int rc = through_opacity(ctx, "trt_shade_through", scene, a.op)) return rc;
-  a.rays    = *in;
-  a.n_out   = in->n / samples;
-  a.samples = samples;
-  a.pc      = *pc;
-  a.rgba    = rgba;
-  return ray_query(ctx, scene, stream, in->n, a, launch_shade_through);
+  return shade_stream_dev(ctx, "trt_shade_through", in, samples, pc, scene, rgba, stream, launch_shade_through,
+                          [&](ShadeThroughArgs& a) { return through_opacity(ctx, "trt_shade_through", scene, a.op); });
 }
 
-// Host buffers: as trt_shade's.
 extern "C" int trt_shade_through(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                                  float* rgba_out)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, "trt_shade_through")) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0) return trt_shade_through_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
-  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
-  trt_rays  din;
-  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  if(int rc = trt_shade_through_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_stream_host(ctx, "trt_shade_through", in, samples, pc, rgba_out,
+                           [&](const trt_rays* rays, float* image) { return trt_shade_through_dev(ctx, rays, samples, pc, scene, image, nullptr); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1179,10 +1194,7 @@ static int check_media(trt_ctx* ctx, const trt_rays* in, const void* out, const 
 {
   if(int rc = check_rays(ctx, in, who)) return rc;
   if(!out) return fail(ctx, TRT_E_INVALID, "%s: NULL output", who);
-  if(solver_of(ctx->precision).alt != kSolverWalk)
-    return fail(ctx, TRT_E_INVALID, "%s: the enumeration runs the default solver (TRT_SOLVE_F32 / _F64) only; "
-                                    "set one of them with trt_set_solver", who);
-  return TRT_OK;
+  return check_walk_solver(ctx, who);
 }
 
 static int check_chords(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, const float* length)
@@ -1215,16 +1227,10 @@ extern "C" int trt_chords(trt_ctx* ctx, const trt_rays* in, const float* tmax_pe
   const SceneK* S = nullptr;
   if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
   if(in->n > SIZE_MAX / sizeof(float) / scene->n_tori) return fail(ctx, TRT_E_NOMEM, "trt_chords: n_tori * n floats do not fit the address space");
-  const size_t bytes = (size_t)in->n * sizeof(float);
-  trt_rays din;
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  const float* d_tmax = nullptr;
-  if(tmax_per_ray)
-    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
-  StagedOut out = {length_out, bytes * scene->n_tori, kBufOut, nullptr};
-  if(int rc = stage_outs(ctx, &out, 1)) return rc;
-  if(int rc = trt_chords_dev(ctx, &din, d_tmax, scene, tmin, tmax, (float*)out.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &out, 1);
+  StagedOut out = {length_out, (size_t)in->n * sizeof(float) * scene->n_tori, kBufOut, nullptr};
+  return bounded_query_host(ctx, in, tmax_per_ray, &out, 1, [&](const trt_rays* rays, const float* bounds) {
+    return trt_chords_dev(ctx, rays, bounds, scene, tmin, tmax, (float*)out.dev, nullptr);
+  });
 }
 
 // The media of trt_glow*, validated (the scene first, so that n_tori can be trusted) and copied into the kernel arguments.
@@ -1274,16 +1280,10 @@ extern "C" int trt_glow(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_
   if(int rc = check_glow(ctx, in, media, rgba_out)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   if(in->n == 0) return trt_glow_dev(ctx, in, nullptr, scene, media, tmin, tmax, rgba_out, nullptr);   // validates, launches and writes nothing
-  const size_t bytes = (size_t)in->n * sizeof(float);
-  trt_rays din;
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  const float* d_tmax = nullptr;
-  if(tmax_per_ray)
-    if(int rc = stage_in(ctx, kBufTmax, tmax_per_ray, bytes, (void**)&d_tmax)) return rc;
-  StagedOut image = {rgba_out, bytes * 4, kBufRgba, nullptr};
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  if(int rc = trt_glow_dev(ctx, &din, d_tmax, scene, media, tmin, tmax, (float*)image.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  StagedOut image = {rgba_out, (size_t)in->n * 4 * sizeof(float), kBufRgba, nullptr};
+  return bounded_query_host(ctx, in, tmax_per_ray, &image, 1, [&](const trt_rays* rays, const float* bounds) {
+    return trt_glow_dev(ctx, rays, bounds, scene, media, tmin, tmax, (float*)image.dev, nullptr);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1372,45 +1372,77 @@ extern "C" int trt_camera_rays(trt_ctx* ctx, const trt_globals* g, const trt_pus
   return fetch_outs(ctx, outs, 6);
 }
 
-static int check_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, uint32_t W, uint32_t H, uint32_t row_begin,
-                              uint32_t row_end, int camera, uint32_t samples, const float* offsets, const float* rgba, CameraArgs& c,
-                              const char* who = "trt_shade_camera")
+// The frame of a trt_shade*_camera* call (`who`), as the entry point received it.
+struct CameraFrame {
+  const trt_globals* g;
+  const trt_push*    pc;
+  uint32_t           W, H, row_begin, row_end;
+  int                camera;
+  uint32_t           samples;
+  const float*       offsets;
+};
+static int check_shade_camera(trt_ctx* ctx, const char* who, const CameraFrame& f, const float* rgba, CameraArgs& c)
 {
-  if(int rc = check_camera(ctx, who, g, pc, rgba, W, H, row_begin, row_end, camera, samples, offsets, c)) return rc;
+  if(int rc = check_camera(ctx, who, f.g, f.pc, rgba, f.W, f.H, f.row_begin, f.row_end, f.camera, f.samples, f.offsets, c)) return rc;
   if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "%s: the rgba image must be 16-byte aligned (it is written as float4)", who);
   return TRT_OK;
 }
+
+// The device half of the three camera forms, which differ as the stream forms do: `table(a)` validates and fills the table
+// that travels with the kernel's arguments (refract_glass, lit_lights; nothing for trt_shade_camera).  Refusals in this
+// order: check_shade_camera; the table's own checks, the scene's among them — BEFORE the toroidal tables are touched, so
+// that a call refused for its table or its scene leaves them as they were; the toroidal tables (camera_tables); the scene
+// (trt_shade_camera, whose table checks nothing); HIP errors of the launch.
+template <class Args, class Table>
+static int shade_camera_dev(trt_ctx* ctx, const char* who, const CameraFrame& f, const trt_scene* scene, float* rgba, void* stream,
+                            hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), Table&& table)
+{
+  Args a;
+  if(int rc = check_shade_camera(ctx, who, f, rgba, a.cam)) return rc;
+  if(int rc = table(a)) return rc;
+  a.pc   = *f.pc;
+  a.rgba = rgba;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(int rc = camera_tables(ctx, f.g, f.pc, (hipStream_t)stream, a.cam)) return rc;
+  return ray_query(ctx, scene, stream, a.cam.n_px * f.samples, a, launch);
+}
+
+// The host-pointer half of the same three: the rows of the band through buf[kBufRgba], around dev(image) — the form's own
+// *_dev call on the default stream.  The kernel indexes the full image, so dev is handed the staging block's address less
+// the rows before the band (include/trt.h, trt_render_dev: "buffers offset by -row_begin*W").  Refusals in this order:
+// check_shade_camera; for an empty band whatever dev refuses (it validates, launches and writes nothing); the band's size
+// (TRT_E_NOMEM); staging (TRT_E_NOMEM / TRT_E_HIP); whatever dev refuses.
+template <class Dev>
+static int shade_camera_host(trt_ctx* ctx, const char* who, const CameraFrame& f, float* rgba_out, Dev&& dev)
+{
+  CameraArgs c;
+  if(int rc = check_shade_camera(ctx, who, f, rgba_out, c)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(c.n_px == 0) return dev(rgba_out);
+  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "%s: the band does not fit the address space", who);
+  const size_t before = (size_t)f.row_begin * f.W * 4;   // floats of the image in front of the band
+  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
+  if(int rc = stage_outs(ctx, &image, 1)) return rc;
+  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
+  if(int rc = dev(full)) return rc;
+  return fetch_outs(ctx, &image, 1);
+}
+
 extern "C" int trt_shade_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
                                     uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
                                     float* rgba, void* stream)
 {
-  ShadeCameraArgs a;
-  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba, a.cam)) return rc;
-  a.pc   = *pc;
-  a.rgba = rgba;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(int rc = camera_tables(ctx, g, pc, (hipStream_t)stream, a.cam)) return rc;
-  return ray_query(ctx, scene, stream, a.cam.n_px * samples, a, launch_shade_camera);
+  return shade_camera_dev(ctx, "trt_shade_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
+                          launch_shade_camera, [](ShadeCameraArgs&) { return TRT_OK; });
 }
 
-// Host buffers: the rows of the band through buf[kBufRgba]; the kernel indexes the full image, so it is handed the
-// staging block's address less the rows before the band (include/trt.h, trt_render_dev: "buffers offset by -row_begin*W").
 extern "C" int trt_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
                                 uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
                                 float* rgba_out)
 {
-  CameraArgs c;
-  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, c)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(c.n_px == 0)   // validates the scene, launches and writes nothing
-    return trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, nullptr);
-  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "trt_shade_camera: the band does not fit the address space");
-  const size_t before = (size_t)row_begin * W * 4;   // floats of the image in front of the band
-  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
-  if(int rc = trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_camera_host(ctx, "trt_shade_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
+    return trt_shade_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1449,65 +1481,33 @@ static int refract_glass(trt_ctx* ctx, const char* who, const trt_scene* scene, 
 extern "C" int trt_shade_refract_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                                      float* rgba, void* stream)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba, "trt_shade_refract")) return rc;
-  ShadeRefractArgs a;
-  if(int rc = refract_glass(ctx, "trt_shade_refract", scene, a.glass)) return rc;
-  a.rays    = *in;
-  a.n_out   = in->n / samples;
-  a.samples = samples;
-  a.pc      = *pc;
-  a.rgba    = rgba;
-  return ray_query(ctx, scene, stream, in->n, a, launch_shade_refract);
+  return shade_stream_dev(ctx, "trt_shade_refract", in, samples, pc, scene, rgba, stream, launch_shade_refract,
+                          [&](ShadeRefractArgs& a) { return refract_glass(ctx, "trt_shade_refract", scene, a.glass); });
 }
 
-// Host buffers: as trt_shade's.
 extern "C" int trt_shade_refract(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
                                  float* rgba_out)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, "trt_shade_refract")) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0) return trt_shade_refract_dev(ctx, in, samples, pc, scene, rgba_out, nullptr);   // validates, launches and writes nothing
-  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
-  trt_rays  din;
-  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  if(int rc = trt_shade_refract_dev(ctx, &din, samples, pc, scene, (float*)image.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_stream_host(ctx, "trt_shade_refract", in, samples, pc, rgba_out,
+                           [&](const trt_rays* rays, float* image) { return trt_shade_refract_dev(ctx, rays, samples, pc, scene, image, nullptr); });
 }
 
-// The scene is checked before the toroidal tables are touched: a refused call leaves them as they were.
 extern "C" int trt_shade_refract_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
                                             uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
                                             float* rgba, void* stream)
 {
-  ShadeRefractCameraArgs a;
-  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba, a.cam, "trt_shade_refract_camera")) return rc;
-  if(int rc = refract_glass(ctx, "trt_shade_refract_camera", scene, a.glass)) return rc;
-  a.pc   = *pc;
-  a.rgba = rgba;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(int rc = camera_tables(ctx, g, pc, (hipStream_t)stream, a.cam)) return rc;
-  return ray_query(ctx, scene, stream, a.cam.n_px * samples, a, launch_shade_refract_camera);
+  return shade_camera_dev(ctx, "trt_shade_refract_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
+                          launch_shade_refract_camera,
+                          [&](ShadeRefractCameraArgs& a) { return refract_glass(ctx, "trt_shade_refract_camera", scene, a.glass); });
 }
 
-// Host buffers: as trt_shade_camera's.
 extern "C" int trt_shade_refract_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
                                         uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
                                         float* rgba_out)
 {
-  CameraArgs c;
-  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, c, "trt_shade_refract_camera")) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(c.n_px == 0)   // validates the scene, launches and writes nothing
-    return trt_shade_refract_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, nullptr);
-  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "trt_shade_refract_camera: the band does not fit the address space");
-  const size_t before = (size_t)row_begin * W * 4;   // floats of the image in front of the band
-  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
-  if(int rc = trt_shade_refract_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_camera_host(ctx, "trt_shade_refract_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
+    return trt_shade_refract_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1558,65 +1558,33 @@ static int lit_lights(trt_ctx* ctx, const char* who, const trt_lights* in, const
 extern "C" int trt_shade_lit_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
                                  const trt_scene* scene, float* rgba, void* stream)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba, "trt_shade_lit")) return rc;
-  ShadeLitArgs a;
-  if(int rc = lit_lights(ctx, "trt_shade_lit", lights, scene, a.lights)) return rc;
-  a.rays    = *in;
-  a.n_out   = in->n / samples;
-  a.samples = samples;
-  a.pc      = *pc;
-  a.rgba    = rgba;
-  return ray_query(ctx, scene, stream, in->n, a, launch_shade_lit);
+  return shade_stream_dev(ctx, "trt_shade_lit", in, samples, pc, scene, rgba, stream, launch_shade_lit,
+                          [&](ShadeLitArgs& a) { return lit_lights(ctx, "trt_shade_lit", lights, scene, a.lights); });
 }
 
-// Host buffers: as trt_shade's.
 extern "C" int trt_shade_lit(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
                              const trt_scene* scene, float* rgba_out)
 {
-  if(int rc = check_shade(ctx, in, samples, pc, rgba_out, "trt_shade_lit")) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0) return trt_shade_lit_dev(ctx, in, samples, pc, lights, scene, rgba_out, nullptr);   // validates, launches and writes nothing
-  const size_t bytes = (size_t)(in->n / samples) * 4 * sizeof(float);
-  trt_rays  din;
-  StagedOut image = {rgba_out, bytes, kBufRgba, nullptr};
-  if(int rc = stage_rays(ctx, in, din)) return rc;
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  if(int rc = trt_shade_lit_dev(ctx, &din, samples, pc, lights, scene, (float*)image.dev, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_stream_host(ctx, "trt_shade_lit", in, samples, pc, rgba_out,
+                           [&](const trt_rays* rays, float* image) { return trt_shade_lit_dev(ctx, rays, samples, pc, lights, scene, image, nullptr); });
 }
 
-// The lights and the scene are checked before the toroidal tables are touched: a refused call leaves them as they were.
 extern "C" int trt_shade_lit_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, const trt_scene* scene,
                                         uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
                                         const float* offsets, float* rgba, void* stream)
 {
-  ShadeLitCameraArgs a;
-  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba, a.cam, "trt_shade_lit_camera")) return rc;
-  if(int rc = lit_lights(ctx, "trt_shade_lit_camera", lights, scene, a.lights)) return rc;
-  a.pc   = *pc;
-  a.rgba = rgba;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(int rc = camera_tables(ctx, g, pc, (hipStream_t)stream, a.cam)) return rc;
-  return ray_query(ctx, scene, stream, a.cam.n_px * samples, a, launch_shade_lit_camera);
+  return shade_camera_dev(ctx, "trt_shade_lit_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
+                          launch_shade_lit_camera,
+                          [&](ShadeLitCameraArgs& a) { return lit_lights(ctx, "trt_shade_lit_camera", lights, scene, a.lights); });
 }
 
-// Host buffers: as trt_shade_camera's.
 extern "C" int trt_shade_lit_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, const trt_scene* scene,
                                     uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
                                     const float* offsets, float* rgba_out)
 {
-  CameraArgs c;
-  if(int rc = check_shade_camera(ctx, g, pc, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, c, "trt_shade_lit_camera")) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(c.n_px == 0)   // validates the lights and the scene, launches and writes nothing
-    return trt_shade_lit_camera_dev(ctx, g, pc, lights, scene, W, H, row_begin, row_end, camera, samples, offsets, rgba_out, nullptr);
-  if(c.n_px > SIZE_MAX / (4 * sizeof(float))) return fail(ctx, TRT_E_NOMEM, "trt_shade_lit_camera: the band does not fit the address space");
-  const size_t before = (size_t)row_begin * W * 4;   // floats of the image in front of the band
-  StagedOut image = {rgba_out + before, (size_t)c.n_px * 4 * sizeof(float), kBufRgba, nullptr};
-  if(int rc = stage_outs(ctx, &image, 1)) return rc;
-  float* const full = (float*)((uintptr_t)image.dev - before * sizeof(float));
-  if(int rc = trt_shade_lit_camera_dev(ctx, g, pc, lights, scene, W, H, row_begin, row_end, camera, samples, offsets, full, nullptr)) return rc;
-  return fetch_outs(ctx, &image, 1);
+  return shade_camera_host(ctx, "trt_shade_lit_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
+    return trt_shade_lit_camera_dev(ctx, g, pc, lights, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
+  });
 }
 
 // ------------------------------------------------------------------------------------------

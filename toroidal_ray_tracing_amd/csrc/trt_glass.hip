@@ -55,119 +55,38 @@ struct GlassPath {
   }
 };
 
-__device__ __forceinline__ void stage_glass(Glass* lds, const Glass& arg)   // no barrier: the caller's stage_scene has one
-{
-  static_assert(sizeof(Glass) % 4 == 0 && sizeof(Glass) / 4 <= 256, "one dword per thread of a 256-thread block");
-  if(threadIdx.x < sizeof(Glass) / 4)
-    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&arg)[threadIdx.x];
-}
-
 // ------------------------------------------------------------------------------------------
-// shade_refract(rays_in → one colour per output)
+// shade_refract(rays_in → one colour per output), shade_refract_camera(camera → the band of an image)
 // ------------------------------------------------------------------------------------------
-// shade_kernel, line for line: one lane owns one OUTPUT and walks its samples in order — the same layout, the same
-// accumulation, the same division.  LDS: the scene and the 41 words of Glass.
+// shade_kernel and shade_camera_kernel (trt_rays.hip) with GlassPath handed to the loop: the two walks of trt_render.hpp,
+// so the camera form's image is, bit for bit, camera_rays_kernel's rays put through shade_refract_kernel.
+// LDS: the scene, the 41 words of Glass and, in the camera form, the camera.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_refract_kernel(const SceneK scene, const ShadeRefractArgs a)
 {
   __shared__ SceneK S;
   __shared__ Glass  G;
-  stage_glass(&G, a.glass);
+  stage_words(&G, a.glass);
   stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  const GlassPath glass = {G};
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_out; i += stride)
-  {
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < a.samples; ++s)
-    {
-      const uint64_t r = (uint64_t)s * a.n_out + i;
-      const v3 o = {ox[r], oy[r], oz[r]};
-      const v3 d = {dx[r], dy[r], dz[r]};
-      const v3 c = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
-                                                  n_primary, n_bounce, n_shadow, wc, glass);
-      if(s == 0u) acc = c;
-      else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
-    }
-    if(a.samples != 1u)
-    {
-      const float k = (float)a.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * i, make_float4(acc.x, acc.y, acc.z, 1.0f));           // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc, GlassPath{G});
+  });
 }
 
-// ------------------------------------------------------------------------------------------
-// shade_refract_camera(camera → the band of an image)
-// ------------------------------------------------------------------------------------------
-// shade_camera_kernel, line for line: a wave owns one 8×8 tile of the band, a lane one pixel and its samples; the ray of
-// (sample, pixel) is raygen_offset()'s — the image is, bit for bit, camera_rays_kernel's rays put through
-// shade_refract_kernel.  LDS: the scene, the camera and Glass.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_refract_camera_kernel(const SceneK scene, const ShadeRefractCameraArgs a)
 {
   __shared__ SceneK     S;
   __shared__ CameraArgs cam;
   __shared__ Glass      G;
-  stage_camera(&cam, a.cam);
-  stage_glass(&G, a.glass);
+  stage_words(&cam, a.cam);
+  stage_words(&G, a.glass);
   stage_scene<ORIENT>(&S, scene);   // (its barrier publishes all three)
 
-  const CameraArgs& c = cam;
-  const GlassPath glass = {G};
-  const uint32_t rows = c.row_end - c.row_begin, tiles_x = camera_tiles(c.W);
-  const uint64_t n_tiles = (uint64_t)tiles_x * camera_tiles(rows);
-  const uint32_t lane = threadIdx.x & 63u, xl = lane % kTile, yl = lane / kTile;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  static_assert(kTile * kTile == 64, "one tile per wave");
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * 4u;
-  for(uint64_t t = (uint64_t)blockIdx.x * 4u + wave; t < n_tiles; t += stride)
-  {
-    uint32_t tx, ty;
-    if(n_tiles <= 0xffffffffull)   // (kernel-uniform) one 32-bit division per tile
-    {
-      ty = (uint32_t)t / tiles_x;
-      tx = (uint32_t)t - ty * tiles_x;
-    }
-    else
-    {
-      ty = (uint32_t)(t / tiles_x);
-      tx = (uint32_t)(t - (uint64_t)ty * tiles_x);
-    }
-    const uint32_t x = tx * kTile + xl, ly = ty * kTile + yl, y = c.row_begin + ly;
-    if(x >= c.W || ly >= rows)
-      continue;
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < c.samples; ++s)
-    {
-      const CameraArgs* cs = &cam;   // read through an opaque pointer, once per sample (shade_camera_kernel has the reason)
-      asm volatile("" : "+v"(cs));
-      v3 o, d;
-      raygen_offset(cs->g, camera_sample(*cs, s), cs->W, cs->H, cs->camera, x, y, cs->jx[s], cs->jy[s], o, d);
-      const v3 col = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
-                                                    n_primary, n_bounce, n_shadow, wc, glass);
-      if(s == 0u) acc = col;
-      else acc = {acc.x + col.x, acc.y + col.y, acc.z + col.z};
-    }
-    if(c.samples != 1u)
-    {
-      const float k = (float)c.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * ((size_t)y * c.W + x), make_float4(acc.x, acc.y, acc.z, 1.0f));   // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_camera_walk(cam, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc, GlassPath{G});
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -190,8 +109,7 @@ hipError_t launch_shade_refract_camera(const SceneK& scene, const ShadeRefractCa
 {
   if(a.cam.n_px == 0)
     return hipSuccess;
-  const uint64_t n_tiles = (uint64_t)camera_tiles(a.cam.W) * camera_tiles(a.cam.row_end - a.cam.row_begin);
-  const uint32_t grid = stream_grid(n_tiles * 64u, tn);
+  const uint32_t grid = camera_grid(a.cam, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     hipLaunchKernelGGL((shade_refract_camera_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();

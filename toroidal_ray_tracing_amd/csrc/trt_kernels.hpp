@@ -346,13 +346,19 @@ struct ShadeLitCameraArgs {
   unsigned long long* stats;
 };
 
-// The grid of the ray-stream kernels (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, the two camera kernels,
-// the fan kernels, transmittance_kernel, shade_through_kernel, chords_kernel, glow_kernel, the two shade_refract kernels, the two shade_lit kernels; grid-stride loops): one block per 256 rays (shade_kernel: outputs; camera kernels: pixels; fan kernels:
-// points), at most 4096 blocks (TRT_TRACE_BLOCKS).
+// The grid of a ray-stream kernel — any kernel of 256-thread blocks whose lanes walk `n` items in a grid-stride loop, one
+// item per lane: rays, outputs of a shade kernel, pixels of a camera's band, points of a fan.  One block per 256 items, at
+// most 4096 blocks (TRT_TRACE_BLOCKS).
 inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
 {
   const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;
   return (uint32_t)(want < cap ? want : cap);
+}
+// The grid of a kernel that runs shade_camera_walk (trt_render.hpp): one wave per 8×8 tile of the band, four to a block.
+inline uint32_t camera_grid(const CameraArgs& c, const Tuning& tn)
+{
+  const uint64_t n_tiles = (uint64_t)camera_tiles(c.W) * camera_tiles(c.row_end - c.row_begin);
+  return stream_grid(n_tiles * 64u, tn);
 }
 
 enum RenderVariant { kRenderStatic = 0, kRenderPersistent = 1, kRenderListed = 2 };

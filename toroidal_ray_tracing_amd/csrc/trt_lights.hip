@@ -97,7 +97,7 @@ __device__ __forceinline__ v3 lit_hit(const SceneK& S, const Lights& lt, const H
 // ------------------------------------------------------------------------------------------
 // the payload loop of one ray under the light table
 // ------------------------------------------------------------------------------------------
-// bounce_loop() (trt_render.hpp) line for line — the raygen loop rgen:54-87, the miss shader, the enclosure mask that starts
+// bounce_loop() (trt_render.hpp) — the raygen loop rgen:54-87, the miss shader, the enclosure mask that starts
 // empty and grows at a hit from outside when `grow`, the mirror step (hit_mirror: stated once, there) — with the light of
 // pc replaced by the table: hit_point, lit_hit, hit_mirror where bounce_loop has hit_begin, any_hit, hit_end.
 template <class Real, bool ALT, bool ORIENT>
@@ -139,103 +139,33 @@ __device__ __forceinline__ v3 lit_loop(const SceneK& S, const trt_push& pc, cons
 }
 
 // ------------------------------------------------------------------------------------------
-// shade_lit(rays_in → one colour per output)
+// shade_lit(rays_in → one colour per output), shade_lit_camera(camera → the band of an image)
 // ------------------------------------------------------------------------------------------
-// shade_kernel, line for line: one lane owns one OUTPUT and walks its samples in order — the same layout, the same
-// accumulation, the same division.  LDS: the scene.
+// shade_kernel and shade_camera_kernel (trt_rays.hip) with lit_loop: the two walks of trt_render.hpp, so the camera form's
+// image is, bit for bit, camera_rays_kernel's rays put through shade_lit_kernel.  LDS: the scene and, in the camera form,
+// the camera.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_lit_kernel(const SceneK scene, const ShadeLitArgs a)
 {
   __shared__ SceneK S;
   stage_scene<ORIENT>(&S, scene);
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_out; i += stride)
-  {
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < a.samples; ++s)
-    {
-      const uint64_t r = (uint64_t)s * a.n_out + i;
-      const v3 o = {ox[r], oy[r], oz[r]};
-      const v3 d = {dx[r], dy[r], dz[r]};
-      const v3 c = lit_loop<Real, ALT, ORIENT>(S, a.pc, a.lights, o, d, dot3(d, d) <= kCullUnitDD, n_primary, n_bounce, n_shadow, wc);
-      if(s == 0u) acc = c;
-      else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
-    }
-    if(a.samples != 1u)
-    {
-      const float k = (float)a.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * i, make_float4(acc.x, acc.y, acc.z, 1.0f));           // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return lit_loop<Real, ALT, ORIENT>(S, a.pc, a.lights, o, d, dot3(d, d) <= kCullUnitDD, n_primary, n_bounce, n_shadow, wc);
+  });
 }
 
-// ------------------------------------------------------------------------------------------
-// shade_lit_camera(camera → the band of an image)
-// ------------------------------------------------------------------------------------------
-// shade_camera_kernel, line for line: a wave owns one 8×8 tile of the band, a lane one pixel and its samples; the ray of
-// (sample, pixel) is raygen_offset()'s — the image is, bit for bit, camera_rays_kernel's rays put through shade_lit_kernel.
-// LDS: the scene and the camera.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_lit_camera_kernel(const SceneK scene, const ShadeLitCameraArgs a)
 {
   __shared__ SceneK     S;
   __shared__ CameraArgs cam;
-  stage_camera(&cam, a.cam);
+  stage_words(&cam, a.cam);
   stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
 
-  const CameraArgs& c = cam;
-  const uint32_t rows = c.row_end - c.row_begin, tiles_x = camera_tiles(c.W);
-  const uint64_t n_tiles = (uint64_t)tiles_x * camera_tiles(rows);
-  const uint32_t lane = threadIdx.x & 63u, xl = lane % kTile, yl = lane / kTile;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  static_assert(kTile * kTile == 64, "one tile per wave");
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * 4u;
-  for(uint64_t t = (uint64_t)blockIdx.x * 4u + wave; t < n_tiles; t += stride)
-  {
-    uint32_t tx, ty;
-    if(n_tiles <= 0xffffffffull)   // (kernel-uniform) one 32-bit division per tile
-    {
-      ty = (uint32_t)t / tiles_x;
-      tx = (uint32_t)t - ty * tiles_x;
-    }
-    else
-    {
-      ty = (uint32_t)(t / tiles_x);
-      tx = (uint32_t)(t - (uint64_t)ty * tiles_x);
-    }
-    const uint32_t x = tx * kTile + xl, ly = ty * kTile + yl, y = c.row_begin + ly;
-    if(x >= c.W || ly >= rows)
-      continue;
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < c.samples; ++s)
-    {
-      const CameraArgs* cs = &cam;   // read through an opaque pointer, once per sample (shade_camera_kernel has the reason)
-      asm volatile("" : "+v"(cs));
-      v3 o, d;
-      raygen_offset(cs->g, camera_sample(*cs, s), cs->W, cs->H, cs->camera, x, y, cs->jx[s], cs->jy[s], o, d);
-      const v3 col = lit_loop<Real, ALT, ORIENT>(S, a.pc, a.lights, o, d, dot3(d, d) <= kCullUnitDD, n_primary, n_bounce, n_shadow, wc);
-      if(s == 0u) acc = col;
-      else acc = {acc.x + col.x, acc.y + col.y, acc.z + col.z};
-    }
-    if(c.samples != 1u)
-    {
-      const float k = (float)c.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * ((size_t)y * c.W + x), make_float4(acc.x, acc.y, acc.z, 1.0f));   // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_camera_walk(cam, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return lit_loop<Real, ALT, ORIENT>(S, a.pc, a.lights, o, d, dot3(d, d) <= kCullUnitDD, n_primary, n_bounce, n_shadow, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -258,8 +188,7 @@ hipError_t launch_shade_lit_camera(const SceneK& scene, const ShadeLitCameraArgs
 {
   if(a.cam.n_px == 0)
     return hipSuccess;
-  const uint64_t n_tiles = (uint64_t)camera_tiles(a.cam.W) * camera_tiles(a.cam.row_end - a.cam.row_begin);
-  const uint32_t grid = stream_grid(n_tiles * 64u, tn);
+  const uint32_t grid = camera_grid(a.cam, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     hipLaunchKernelGGL((shade_lit_camera_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();

@@ -4,9 +4,9 @@
 //   trace_kernel       trace(rays_in → hits_out): SoA rays in, closest hit out.
 //   occluded_kernel    occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
 //   crossings_kernel   crossings(rays_in → slots_out): SoA rays in, every surface crossing out, in order, slot-major.
-//   shade_kernel       shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour (trt_render.hpp) out, samples averaged.
+//   shade_kernel       shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour out, samples averaged (shade_stream_walk, trt_render.hpp).
 //   camera_rays_kernel   camera(frame → rays_out): the two cameras' rays with sub-pixel offsets, SoA and sample-major, out.
-//   shade_camera_kernel  shade_kernel with the rays made in registers by the camera: the supersampled frame.
+//   shade_camera_kernel  shade_kernel with the rays made in registers by the camera: the supersampled frame (shade_camera_walk).
 //   launch_trace, launch_occluded, launch_crossings, launch_shade, launch_camera_rays, launch_shade_camera
 //                        their grid and launch wrappers.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
@@ -159,49 +159,16 @@ __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, cons
 // ------------------------------------------------------------------------------------------
 // shade(rays_in → one colour per output): the payload loop on caller-supplied rays
 // ------------------------------------------------------------------------------------------
-// The colour of one ray is the render's loop — bounce_loop() (trt_render.hpp), what trace_pixel runs for a pixel — on a
-// caller's ray: the enclosure mask starts empty (nobody has certified anything about a caller's origins) and grows only
-// along a path of at most unit-length directions (kCullUnitDD, trt_render.hpp), the attenuation starts at 1, and nothing
-// but the colour leaves (no first-hit record, no RenderedData: two empty callables).
-//
-// One lane owns one OUTPUT and walks its samples in order (sample s of output i is ray s·n_out + i, so the six loads of
-// a sample are coalesced like trace_kernel's): acc = c_0, then acc += c_s as plain FP32 adds, then one correctly rounded
-// division by (float)samples — skipped, kernel-uniformly, for one sample, whose colour therefore leaves untouched.  No
-// atomics, nothing depends on the order of waves.  One dwordx4 store per output: a wave writes 1 KiB contiguous.
-// No wave-level compaction of finished paths: see DESIGN.md §5 (assumed from the render's measurement, not measured here).
+// shade_stream_walk (trt_render.hpp: the walk and the colour of a caller's ray are described there) around the render's loop.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const ShadeArgs a)
 {
   __shared__ SceneK S;
   stage_scene<ORIENT>(&S, scene);
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_out; i += stride)
-  {
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < a.samples; ++s)
-    {
-      const uint64_t r = (uint64_t)s * a.n_out + i;
-      const v3 o = {ox[r], oy[r], oz[r]};
-      const v3 d = {dx[r], dy[r], dz[r]};
-      const v3 c = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
-                                                  n_primary, n_bounce, n_shadow, wc);
-      if(s == 0u) acc = c;
-      else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
-    }
-    if(a.samples != 1u)
-    {
-      const float k = (float)a.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * i, make_float4(acc.x, acc.y, acc.z, 1.0f));           // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -254,77 +221,25 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const CameraRaysArgs a
   }
 }
 
-// shade_kernel's loop with the ray of (sample, pixel) produced in registers instead of loaded: one lane owns one pixel of
-// the band and walks its samples in order — the same bounce_loop() call, the same accumulation and division, so the
-// image is, bit for bit, camera_rays_kernel's rays put through shade_kernel.
-// Lane ↔ pixel: a wave owns one 8×8 tile of the band (kTile, the render's tile: lane = yl·8 + xl), not 64 pixels of a
-// row — the paths of a wave stay together where the image is coherent, and a silhouette cuts through far fewer waves
-// (DESIGN.md §5 has the measurement against linear rows).  The grid-stride loop runs on the wave's tile index, a scalar;
-// lanes beyond the right or lower edge of a ragged tile idle.  No output bit depends on the mapping.
-// The camera (CameraArgs) is staged into LDS beside the scene (stage_camera, trt_render.hpp, has the reason); the sample
-// index is wave-uniform: offsets and table pointers are broadcast reads.
+// shade_camera_walk (trt_render.hpp) around the render's loop: the image is, bit for bit, camera_rays_kernel's rays put
+// through shade_kernel.  LDS: the scene and the camera.
 template <class Real, bool ALT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, const ShadeCameraArgs a)
 {
   __shared__ SceneK     S;
   __shared__ CameraArgs cam;
-  stage_camera(&cam, a.cam);
+  stage_words(&cam, a.cam);
   stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
 
-  const CameraArgs& c = cam;
-  const uint32_t rows = c.row_end - c.row_begin, tiles_x = camera_tiles(c.W);
-  const uint64_t n_tiles = (uint64_t)tiles_x * camera_tiles(rows);
-  const uint32_t lane = threadIdx.x & 63u, xl = lane % kTile, yl = lane / kTile;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  static_assert(kTile * kTile == 64, "one tile per wave");
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * 4u;
-  for(uint64_t t = (uint64_t)blockIdx.x * 4u + wave; t < n_tiles; t += stride)
-  {
-    uint32_t tx, ty;
-    if(n_tiles <= 0xffffffffull)   // (kernel-uniform) one 32-bit division per tile
-    {
-      ty = (uint32_t)t / tiles_x;
-      tx = (uint32_t)t - ty * tiles_x;
-    }
-    else
-    {
-      ty = (uint32_t)(t / tiles_x);
-      tx = (uint32_t)(t - (uint64_t)ty * tiles_x);
-    }
-    const uint32_t x = tx * kTile + xl, ly = ty * kTile + yl, y = c.row_begin + ly;
-    if(x >= c.W || ly >= rows)
-      continue;
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < c.samples; ++s)
-    {
-      // The camera is read through a pointer hipcc cannot see through, once per sample: read through `cam` itself the
-      // matrices are loop-invariant, get hoisted and stay in ~50 VGPRs across the bounce loop.
-      const CameraArgs* cs = &cam;
-      asm volatile("" : "+v"(cs));
-      v3 o, d;
-      raygen_offset(cs->g, camera_sample(*cs, s), cs->W, cs->H, cs->camera, x, y, cs->jx[s], cs->jy[s], o, d);
-      const v3 col = bounce_loop<Real, ALT, ORIENT>(S, a.pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
-                                                    n_primary, n_bounce, n_shadow, wc);
-      if(s == 0u) acc = col;
-      else acc = {acc.x + col.x, acc.y + col.y, acc.z + col.z};
-    }
-    if(c.samples != 1u)
-    {
-      const float k = (float)c.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * ((size_t)y * c.W + x), make_float4(acc.x, acc.y, acc.z, 1.0f));   // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_camera_walk(cam, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
-// (stream_grid, the grid of these kernels: trt_kernels.hpp)
+// (stream_grid and camera_grid, the grids of these kernels: trt_kernels.hpp)
 hipError_t launch_trace(const SceneK& scene, const TraceArgs& a, const Tuning& tn, hipStream_t stream)
 {
   if(a.rays.n == 0)
@@ -402,8 +317,7 @@ hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, co
 {
   if(a.cam.n_px == 0)
     return hipSuccess;
-  const uint64_t n_tiles = (uint64_t)camera_tiles(a.cam.W) * camera_tiles(a.cam.row_end - a.cam.row_begin);
-  const uint32_t grid = stream_grid(n_tiles * 64u, tn);
+  const uint32_t grid = camera_grid(a.cam, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     hipLaunchKernelGGL((shade_camera_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
     return hipGetLastError();

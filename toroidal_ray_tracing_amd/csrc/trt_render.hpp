@@ -8,11 +8,13 @@
 //   image_row, out_index, rendered_record pixel addressing
 //   miss_id, miss_colour, miss_rgba, store_first_hit, store_first_miss   the first-hit record and the miss record
 //   block_add_stats                       the query counters of a block → the global totals
-//   settle_loads, stage_args, stage_block256   staging into LDS
+//   settle_loads, stage_args, stage_block256, stage_words   staging into LDS
 //   kTMin, kTMax                          the ray window of the render kernels
-//   bounce_loop, NoGlass                  the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (shade_kernel,
-//                                         shade_refract_kernel: the same loop with a dielectric asked at every hit)
-//   camera_sample, stage_camera           the camera of the fused kernels: a sample's tables, the CameraArgs in LDS
+//   bounce_loop, NoGlass                  the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (the shade
+//                                         kernels; with a dielectric asked at every hit: the shade_refract kernels)
+//   camera_sample                         the camera of the fused kernels: a sample's tables
+//   shade_stream_walk, shade_camera_walk  the two walks of the shade kernels: the samples of an output of a ray stream, the
+//                                         samples of a pixel of a camera's band — each around the one loop that colours a ray
 //   kCrossingSlotBytes, column_insert     the sorted crossing column of a lane in LDS
 //   live_slot, list_counts, TileCode, tile_x / tile_y, frame_args, LaunchArgs   the tile-list layout
 //   clear_macro                           the constant fill of one CLEAR macro tile
@@ -280,6 +282,17 @@ __device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const S
   __syncthreads();
 }
 
+// A small table of the kernel arguments (CameraArgs, Opacity, Glass) into LDS, one dword per thread of a 256-thread block.
+// No barrier: the caller's stage_scene, which follows, has one and publishes both.  (Once three copies: stage_camera, the
+// name trt_fan.hip's note on its own table still uses, stage_glass and shade_through_kernel's lines.)
+template <class T>
+__device__ __forceinline__ void stage_words(T* lds, const T& arg)
+{
+  static_assert(sizeof(T) % 4 == 0 && sizeof(T) / 4 <= 256, "one dword per thread of a 256-thread block");
+  if(threadIdx.x < sizeof(T) / 4)
+    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&arg)[threadIdx.x];
+}
+
 // ------------------------------------------------------------------------------------------
 // the orthonormal basis about a unit vector (trt_fan.hip: about N; trt_lights.hip: about L)
 // ------------------------------------------------------------------------------------------
@@ -300,7 +313,7 @@ constexpr float kTMin = 0.001f;    // rgen:51, rchit:114
 constexpr float kTMax = 10000.0f;  // rgen:52
 
 // ------------------------------------------------------------------------------------------
-// the bounce loop of one ray: a pixel's primary ray (trace_pixel) or a caller's (shade_kernel)
+// the bounce loop of one ray: a pixel's primary ray (trace_pixel) or a caller's (the shade kernels)
 // ------------------------------------------------------------------------------------------
 // The raygen payload loop (REFL/shaders/raytrace.rgen:54-87) with the closest-hit, miss and shadow-miss shaders inlined;
 // returns hitValue.  Stated once, so that trt_shade gives a ray bit for bit the colour trt_render* gives the pixel whose
@@ -375,8 +388,70 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
 }
 
 // ------------------------------------------------------------------------------------------
-// the camera of a fused kernel (shade_camera_kernel, shade_refract_camera_kernel)
+// the two walks of the shade kernels: a ray stream's outputs, a camera's pixels
 // ------------------------------------------------------------------------------------------
+// A shade kernel (trt_shade*, trt_shade_camera* and their _through, _refract and _lit forms) is its LDS staging and one of
+// these two walks around `loop`, the one expression in which the kernels differ: loop(o, d, n_primary, n_bounce, n_shadow,
+// wc) colours one ray — bounce_loop() plain or with a GlassPath, through_loop(), lit_loop() — and counts its tests.
+//
+// The colour of one ray is the render's loop — bounce_loop(), what trace_pixel runs for a pixel — on a caller's ray: the
+// enclosure mask starts empty (nobody has certified anything about a caller's origins) and grows only along a path of at
+// most unit-length directions (kCullUnitDD), the attenuation starts at 1, and nothing but the colour leaves (no first-hit
+// record, no RenderedData: shade_ray() passes two empty callables).
+//
+// shade_stream_walk: one lane owns one OUTPUT and walks its samples in order (sample s of output i is ray s·n_out + i, so
+// the six loads of a sample are coalesced like trace_kernel's): acc = c_0, then acc += c_s as plain FP32 adds, then one
+// correctly rounded division by (float)samples — skipped, kernel-uniformly, for one sample, whose colour therefore leaves
+// untouched.  No atomics, nothing depends on the order of waves.  One dwordx4 store per output: a wave writes 1 KiB
+// contiguous.  No wave-level compaction of finished paths: see DESIGN.md §5 (assumed from the render's measurement, not
+// measured here).
+template <class Real, bool ALT, bool ORIENT, class GlassT = NoGlass>
+__device__ __forceinline__ v3 shade_ray(const SceneK& S, const trt_push& pc, v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce,
+                                        uint32_t& n_shadow, WorkCount& wc, GlassT glass = GlassT{})
+{
+  return bounce_loop<Real, ALT, ORIENT>(S, pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
+                                        n_primary, n_bounce, n_shadow, wc, glass);
+}
+
+// The accumulation of both walks, as stated above: the colours c_s = sample(s), s = 0 .. samples - 1, in order → the pixel.
+template <class Sample>
+__device__ __forceinline__ float4 average_samples(uint32_t samples, Sample&& sample)
+{
+  v3 acc = {0.0f, 0.0f, 0.0f};
+  for(uint32_t s = 0; s < samples; ++s)
+  {
+    const v3 c = sample(s);
+    if(s == 0u) acc = c;
+    else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
+  }
+  if(samples != 1u)
+  {
+    const float k = (float)samples;
+    acc = {acc.x / k, acc.y / k, acc.z / k};
+  }
+  return make_float4(acc.x, acc.y, acc.z, 1.0f);                           // rgen:87
+}
+
+template <class Loop>
+__device__ __forceinline__ void shade_stream_walk(const trt_rays& rays, uint64_t n_out, uint32_t samples, float* rgba,
+                                                  unsigned long long* stats, Loop&& loop)
+{
+  const gptr<const float> ox = (gptr<const float>)rays.ox, oy = (gptr<const float>)rays.oy, oz = (gptr<const float>)rays.oz;
+  const gptr<const float> dx = (gptr<const float>)rays.dx, dy = (gptr<const float>)rays.dy, dz = (gptr<const float>)rays.dz;
+  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;   // the block of every shade kernel (as the camera walk's four waves)
+  for(uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_out; i += stride)
+    st4(rgba + 4 * i, average_samples(samples, [&](uint32_t s) {
+          const uint64_t r = (uint64_t)s * n_out + i;
+          const v3 o = {ox[r], oy[r], oz[r]};
+          const v3 d = {dx[r], dy[r], dz[r]};
+          return loop(o, d, n_primary, n_bounce, n_shadow, wc);
+        }));
+  if(stats)
+    block_add_stats(stats, n_primary, n_bounce, n_shadow, wc);
+}
+
 // The camera of sample s: the toroidal tables of that sample (CameraArgs::toro_stride floats per sample).
 __device__ __forceinline__ ToroCam camera_sample(const CameraArgs& c, uint32_t s)
 {
@@ -385,14 +460,59 @@ __device__ __forceinline__ ToroCam camera_sample(const CameraArgs& c, uint32_t s
   t.cos_a += off; t.sin_a += off; t.cos_b += off; t.sin_b += off;
   return t;
 }
-// The camera (CameraArgs) is staged into LDS beside the scene: left in the kernel-argument segment the matrices sit in
-// SGPRs across the bounce loop — the default-solver kernels then spill 70 of them to VGPR lanes and report an 84-byte
-// stack frame — and from LDS raygen reads them where it runs, as the render kernels read their RenderArgs (stage_args).
-__device__ __forceinline__ void stage_camera(CameraArgs* lds, const CameraArgs& arg)   // no barrier: the caller's stage_scene has one
+
+// shade_camera_walk: shade_stream_walk with the ray of (sample, pixel) produced in registers instead of loaded — one lane
+// owns one pixel of the band and walks its samples in order, through the same `loop`, the same accumulation and division,
+// so the image is, bit for bit, camera_rays_kernel's rays put through the stream kernel of the same loop.
+// Lane ↔ pixel: a wave owns one 8×8 tile of the band (kTile, the render's tile: lane = yl·8 + xl), not 64 pixels of a
+// row — the paths of a wave stay together where the image is coherent, and a silhouette cuts through far fewer waves
+// (DESIGN.md §5 has the measurement against linear rows).  The grid-stride loop runs on the wave's tile index, a scalar;
+// lanes beyond the right or lower edge of a ragged tile idle.  No output bit depends on the mapping.
+// `cam` is the kernel's CameraArgs, staged into LDS beside the scene (stage_words) by the kernel: left in the
+// kernel-argument segment the matrices sit in SGPRs across the bounce loop — the default-solver kernels then spill 70 of
+// them to VGPR lanes and report an 84-byte stack frame — and from LDS raygen reads them where it runs, as the render
+// kernels read their RenderArgs (stage_args).  The sample index is wave-uniform: offsets and table pointers are broadcast
+// reads.  rgba is the FULL image: pixel (x, y) at y·W + x.
+template <class Loop>
+__device__ __forceinline__ void shade_camera_walk(const CameraArgs& cam, float* rgba, unsigned long long* stats, Loop&& loop)
 {
-  static_assert(sizeof(CameraArgs) % 4 == 0 && sizeof(CameraArgs) / 4 <= 256, "one dword per thread of a 256-thread block");
-  if(threadIdx.x < sizeof(CameraArgs) / 4)
-    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&arg)[threadIdx.x];
+  const CameraArgs& c = cam;
+  const uint32_t rows = c.row_end - c.row_begin, tiles_x = camera_tiles(c.W);
+  const uint64_t n_tiles = (uint64_t)tiles_x * camera_tiles(rows);
+  const uint32_t lane = threadIdx.x & 63u, xl = lane % kTile, yl = lane / kTile;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  static_assert(kTile * kTile == 64, "one tile per wave");
+  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * 4u;
+  for(uint64_t t = (uint64_t)blockIdx.x * 4u + wave; t < n_tiles; t += stride)
+  {
+    uint32_t tx, ty;
+    if(n_tiles <= 0xffffffffull)   // (kernel-uniform) one 32-bit division per tile
+    {
+      ty = (uint32_t)t / tiles_x;
+      tx = (uint32_t)t - ty * tiles_x;
+    }
+    else
+    {
+      ty = (uint32_t)(t / tiles_x);
+      tx = (uint32_t)(t - (uint64_t)ty * tiles_x);
+    }
+    const uint32_t x = tx * kTile + xl, ly = ty * kTile + yl, y = c.row_begin + ly;
+    if(x >= c.W || ly >= rows)
+      continue;
+    st4(rgba + 4 * ((size_t)y * c.W + x), average_samples(c.samples, [&](uint32_t s) {
+          // The camera is read through a pointer hipcc cannot see through, once per sample: read through `cam` itself the
+          // matrices are loop-invariant, get hoisted and stay in ~50 VGPRs across the bounce loop.
+          const CameraArgs* cs = &cam;
+          asm volatile("" : "+v"(cs));
+          v3 o, d;
+          raygen_offset(cs->g, camera_sample(*cs, s), cs->W, cs->H, cs->camera, x, y, cs->jx[s], cs->jy[s], o, d);
+          return loop(o, d, n_primary, n_bounce, n_shadow, wc);
+        }));
+  }
+  if(stats)
+    block_add_stats(stats, n_primary, n_bounce, n_shadow, wc);
 }
 
 // ------------------------------------------------------------------------------------------

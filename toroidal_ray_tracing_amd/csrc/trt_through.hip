@@ -167,49 +167,24 @@ __device__ __forceinline__ v3 through_loop(const SceneK& S, const trt_push& pc, 
   return acc;
 }
 
-// One lane owns one OUTPUT and walks its samples in order, exactly as shade_kernel does: the same layout, the same
-// accumulation, the same division.  LDS: the scene, 16 opacity words, and the block's columns (K · kCrossingSlotBytes).
+// shade_kernel (trt_rays.hip) with through_loop: shade_stream_walk (trt_render.hpp).  LDS: the scene, 16 opacity words, and
+// the block's columns (K · kCrossingSlotBytes).
 template <class Real, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_through_kernel(const SceneK scene, const ShadeThroughArgs a)
 {
   __shared__ SceneK  S;
   __shared__ Opacity O;
   extern __shared__ float crossing_lds[];   // [K][256] t, then [K][256] bytes
-  static_assert(sizeof(Opacity) % 4 == 0 && sizeof(Opacity) / 4 <= 256, "one dword per thread of a 256-thread block");
-  if(threadIdx.x < sizeof(Opacity) / 4)
-    reinterpret_cast<uint32_t*>(&O)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&a.op)[threadIdx.x];
+  stage_words(&O, a.op);
   stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
 
   const uint32_t K  = 4u * (uint32_t)S.n_tori;
   float*         ct = crossing_lds + threadIdx.x;
   uint8_t*       cw = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  uint32_t       n_primary = 0, n_bounce = 0, n_shadow = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_out; i += stride)
-  {
-    v3 acc = {0.0f, 0.0f, 0.0f};
-    for(uint32_t s = 0; s < a.samples; ++s)
-    {
-      const uint64_t r = (uint64_t)s * a.n_out + i;
-      const v3 o = {ox[r], oy[r], oz[r]};
-      const v3 d = {dx[r], dy[r], dz[r]};
-      const v3 c = through_loop<Real, ORIENT>(S, a.pc, O.a, O.p, ct, cw, K, o, d, n_primary, n_bounce, n_shadow, wc);
-      if(s == 0u) acc = c;
-      else acc = {acc.x + c.x, acc.y + c.y, acc.z + c.z};
-    }
-    if(a.samples != 1u)
-    {
-      const float k = (float)a.samples;
-      acc = {acc.x / k, acc.y / k, acc.z / k};
-    }
-    st4(a.rgba + 4 * i, make_float4(acc.x, acc.y, acc.z, 1.0f));           // rgen:87
-  }
-  if(a.stats)
-    block_add_stats(a.stats, n_primary, n_bounce, n_shadow, wc);
+  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return through_loop<Real, ORIENT>(S, a.pc, O.a, O.p, ct, cw, K, o, d, n_primary, n_bounce, n_shadow, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -162,16 +162,29 @@ void HelloHip::updateUniformBuffer()
   std::memcpy(m_globals.center, m_center.data(), sizeof m_globals.center);      // BEF :70
 }
 
-void HelloHip::raytrace(void* stream, const std::array<float, 4>& clearColor)
+const trt_push* HelloHip::pushFor(const std::array<float, 4>& clearColor, bool withLight)
 {
   // Initializing push constant values (hello_vulkan.cpp:917-920)
   std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
-  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
-  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
-  m_pcRay.lightType      = m_pcRaster.lightType;
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  if(withLight)
+  {
+    std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
+    m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
+    m_pcRay.lightType      = m_pcRaster.lightType;
+  }
+  return &m_pcRay;
+}
+
+trt_scene HelloHip::scene() const
+{
+  return trt_scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+}
+
+void HelloHip::raytrace(void* stream, const std::array<float, 4>& clearColor)
+{
+  const trt_scene sc = scene();
   // vkCmdTraceRaysKHR(..., width, height, 1) (:931)
-  check(trt_render_dev(m_ctx, &m_globals, &m_pcRay, &scene, m_size.width, m_size.height, 0, m_size.height,
+  check(trt_render_dev(m_ctx, &m_globals, pushFor(clearColor, true), &sc, m_size.width, m_size.height, 0, m_size.height,
                        m_camera, m_dColor, nullptr, m_dRendered, stream),
         "HelloHip::raytrace");
 }
@@ -179,78 +192,64 @@ void HelloHip::raytrace(void* stream, const std::array<float, 4>& clearColor)
 void HelloHip::occluded(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax,
                         uint8_t* flagDev, uint64_t* maskDev)
 {
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_occluded_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, flagDev, maskDev, stream), "HelloHip::occluded");
+  const trt_scene sc = scene();
+  check(trt_occluded_dev(m_ctx, &raysDev, tmaxPerRayDev, &sc, tmin, tmax, flagDev, maskDev, stream), "HelloHip::occluded");
 }
 
 void HelloHip::shadeThrough(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev)
 {
-  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
-  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
-  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
-  m_pcRay.lightType      = m_pcRaster.lightType;
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_shade_through_dev(m_ctx, &raysDev, samples, &m_pcRay, &scene, rgbaDev, stream), "HelloHip::shadeThrough");
+  const trt_scene sc = scene();
+  check(trt_shade_through_dev(m_ctx, &raysDev, samples, pushFor(clearColor, true), &sc, rgbaDev, stream), "HelloHip::shadeThrough");
 }
 
 void HelloHip::shadeRefract(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev)
 {
-  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
-  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
-  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
-  m_pcRay.lightType      = m_pcRaster.lightType;
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_shade_refract_dev(m_ctx, &raysDev, samples, &m_pcRay, &scene, rgbaDev, stream), "HelloHip::shadeRefract");
+  const trt_scene sc = scene();
+  check(trt_shade_refract_dev(m_ctx, &raysDev, samples, pushFor(clearColor, true), &sc, rgbaDev, stream), "HelloHip::shadeRefract");
 }
 
 void HelloHip::raytraceRefract(void* stream, const std::array<float, 4>& clearColor, uint32_t samples, const float* offsets)
 {
-  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
-  std::memcpy(m_pcRay.lightPosition, m_pcRaster.lightPosition, sizeof m_pcRay.lightPosition);
-  m_pcRay.lightIntensity = m_pcRaster.lightIntensity;
-  m_pcRay.lightType      = m_pcRaster.lightType;
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_shade_refract_camera_dev(m_ctx, &m_globals, &m_pcRay, &scene, m_size.width, m_size.height, 0, m_size.height, m_camera,
-                                     samples, offsets, m_dColor, stream),
+  const trt_scene sc = scene();
+  check(trt_shade_refract_camera_dev(m_ctx, &m_globals, pushFor(clearColor, true), &sc, m_size.width, m_size.height, 0, m_size.height,
+                                     m_camera, samples, offsets, m_dColor, stream),
         "HelloHip::raytraceRefract");
 }
 
 void HelloHip::shadeLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, const trt_rays& raysDev,
                         uint32_t samples, float* rgbaDev)
 {
-  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_shade_lit_dev(m_ctx, &raysDev, samples, &m_pcRay, &lights, &scene, rgbaDev, stream), "HelloHip::shadeLit");
+  const trt_scene sc = scene();
+  check(trt_shade_lit_dev(m_ctx, &raysDev, samples, pushFor(clearColor, false), &lights, &sc, rgbaDev, stream), "HelloHip::shadeLit");
 }
 
 void HelloHip::raytraceLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, uint32_t samples,
                            const float* offsets)
 {
-  std::memcpy(m_pcRay.clearColor, clearColor.data(), sizeof m_pcRay.clearColor);
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_shade_lit_camera_dev(m_ctx, &m_globals, &m_pcRay, &lights, &scene, m_size.width, m_size.height, 0, m_size.height, m_camera,
-                                 samples, offsets, m_dColor, stream),
+  const trt_scene sc = scene();
+  check(trt_shade_lit_camera_dev(m_ctx, &m_globals, pushFor(clearColor, false), &lights, &sc, m_size.width, m_size.height, 0, m_size.height,
+                                 m_camera, samples, offsets, m_dColor, stream),
         "HelloHip::raytraceLit");
 }
 
 void HelloHip::chords(void* stream,const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
 {
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_chords_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, tmin, tmax, lengthDev, stream), "HelloHip::chords");
+  const trt_scene sc = scene();
+  check(trt_chords_dev(m_ctx, &raysDev, tmaxPerRayDev, &sc, tmin, tmax, lengthDev, stream), "HelloHip::chords");
 }
 
 void HelloHip::glow(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_medium* media, float tmin, float tmax,
                     float* rgbaDev)
 {
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_glow_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, media, tmin, tmax, rgbaDev, stream), "HelloHip::glow");
+  const trt_scene sc = scene();
+  check(trt_glow_dev(m_ctx, &raysDev, tmaxPerRayDev, &sc, media, tmin, tmax, rgbaDev, stream), "HelloHip::glow");
 }
 
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {
-  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
-  check(trt_fan_occluded_dev(m_ctx, &atDev, n, frame, samples, dirs, &scene, tmin, tmax, bitsDev, openDev, stream), "HelloHip::fanOccluded");
+  const trt_scene sc = scene();
+  check(trt_fan_occluded_dev(m_ctx, &atDev, n, frame, samples, dirs, &sc, tmin, tmax, bitsDev, openDev, stream), "HelloHip::fanOccluded");
 }
 
 void HelloHip::copyRenderedPosition(void* stream)

@@ -147,6 +147,9 @@ public:
 
 private:
   void check(int rc, const char* what) const;
+  // m_pcRay with the clear colour and — withLight — the light state of m_pcRaster (hello_vulkan.cpp:917-920)
+  const trt_push* pushFor(const std::array<float, 4>& clearColor, bool withLight);
+  trt_scene       scene() const;   // the tori and materials added so far
 
   trt_ctx*                   m_ctx{nullptr};
   int                        m_device{0};

@@ -125,13 +125,50 @@ class Tracer:
         self._check(self._L.trt_get_stats(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k in abi.STAT_FIELDS}
 
-    # -- trace(rays_in -> hits_out) ----------------------------------------------------
-    def trace(self, scene, o, d, tmin=0.001, tmax=10000.0):
-        """Host arrays: o, d of shape (n,3).  Returns a dict of SoA hit arrays."""
+    # -- what the ray queries share ------------------------------------------------------
+    @staticmethod
+    def _host_rays(o, d):
+        """Host arrays o, d of shape (n,3) -> (kept SoA arrays, trt_rays over them, n)."""
         o = np.ascontiguousarray(np.asarray(o, np.float32).T)
         d = np.ascontiguousarray(np.asarray(d, np.float32).T)
         n = o.shape[1]
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        return (o, d), abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n), n
+
+    @staticmethod
+    def _dev_rays(ray_ptrs, n):
+        """6 device addresses (ints) of n floats each -> trt_rays."""
+        return abi.rays_struct([int(p) for p in ray_ptrs], n)
+
+    @staticmethod
+    def _bounds(tmax_per_ray, n):
+        return None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+
+    def _shade_host(self, fn, o, d, pc, samples, *extra):
+        """A stream form of shade on host arrays, fn(ctx, rays, samples, pc, *extra, rgba): the image of n / samples outputs."""
+        keep, rays, n = self._host_rays(o, d)
+        samples = int(samples)
+        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
+        self._check(fn(self._h, C.byref(rays), samples, C.byref(pc), *extra, rgba.ctypes.data))
+        return rgba
+
+    def _shade_camera_dev(self, fn, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows, *extra, stream=None):
+        """A camera form of shade, fn(ctx, g, pc, *extra, W, H, row_begin, row_end, camera, samples, offsets, rgba[, stream]);
+        stream None: the host-pointer form, which takes none."""
+        r0, r1 = (0, H) if rows is None else rows
+        keep, off = self._offsets(offsets, samples)
+        tail = () if stream is None else (_vp(stream),)
+        self._check(fn(self._h, C.byref(g), C.byref(pc), *extra, W, H, r0, r1, camera, int(samples), off, _vp(rgba_ptr), *tail))
+
+    def _shade_camera_host(self, fn, g, pc, W, H, camera, samples, offsets, rows, *extra):
+        """The same on a host buffer: rgba (H, W, 4), rows outside ``rows`` 0."""
+        rgba = np.zeros((H, W, 4), np.float32)
+        self._shade_camera_dev(fn, g, pc, W, H, rgba.ctypes.data, camera, samples, offsets, rows, *extra)
+        return rgba
+
+    # -- trace(rays_in -> hits_out) ----------------------------------------------------
+    def trace(self, scene, o, d, tmin=0.001, tmax=10000.0):
+        """Host arrays: o, d of shape (n,3).  Returns a dict of SoA hit arrays."""
+        keep, rays, n = self._host_rays(o, d)
         out = abi.alloc_hits(n)
         hs = abi.hits_struct(out)
         self._check(self._L.trt_trace(self._h, C.byref(rays), self._scene(scene), tmin, tmax, C.byref(hs)))
@@ -139,7 +176,7 @@ class Tracer:
 
     def trace_dev(self, scene, ray_ptrs, n, hit_ptrs, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses, hit_ptrs = dict name -> address."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         hs = _hits(hit_ptrs) or abi.trt_hits()   # (an empty dict: every stream null, for the library to refuse)
         self._check(self._L.trt_trace_dev(self._h, C.byref(rays), self._scene(scene), tmin, tmax,
                                           C.byref(hs), _vp(stream)))
@@ -148,11 +185,8 @@ class Tracer:
     def occluded(self, scene, o, d, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
         """Any-hit query on host arrays (trt_occluded): o, d of shape (n,3); tmax_per_ray: None or n bounds, one per ray
         (a segment query "is B visible from A": d = B - A, tmax = 1).  Returns a bool array."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
         flag = np.empty(n, np.uint8)
         self._check(self._L.trt_occluded(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), tmin, tmax,
                                          abi.ptr(flag), None))
@@ -161,7 +195,7 @@ class Tracer:
     def occluded_dev(self, scene, ray_ptrs, n, flag_ptr=0, mask_ptr=0, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses; flag_ptr: n bytes and / or mask_ptr: abi.mask_words(n) uint64
         (abi.unpack_mask reads them); tmax_ptr: n per-ray bounds or 0.  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_occluded_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
                                              _vp(flag_ptr), _vp(mask_ptr), _vp(stream)))
 
@@ -170,10 +204,7 @@ class Tracer:
         """Every surface crossing of every ray, in order along it (trt_crossings), on host arrays: o, d of shape (n,3).
         Returns (t, id, entering, count): t float32, id int32 and entering bool of shape (max_per_ray, n) — slot k of
         ray i at [k, i], unused slots (inf, -1, False) — and count (n,), the crossings found (it may exceed max_per_ray)."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        keep, rays, n = self._host_rays(o, d)
         out = abi.alloc_crossings(n, int(max_per_ray))
         cs = abi.crossing_streams_struct(out)
         self._check(self._L.trt_crossings(self._h, C.byref(rays), self._scene(scene), tmin, tmax, int(max_per_ray), C.byref(cs)))
@@ -183,7 +214,7 @@ class Tracer:
         """Device pointers (ints): ray_ptrs = 6 addresses; out_ptrs: dict over abi.CROSSING_FIELDS -> address (0 / None /
         absent: stream not wanted) — t float32, id int32, entering uint8 of max_per_ray * n elements each, slot-major, and
         count uint32 of n.  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         cs = abi.crossing_streams_struct({k: (int(v) if v else None) for k, v in out_ptrs.items()})
         self._check(self._L.trt_crossings_dev(self._h, C.byref(rays), self._scene(scene), tmin, tmax, int(max_per_ray),
                                               C.byref(cs), _vp(stream)))
@@ -193,19 +224,12 @@ class Tracer:
         """Radiance along caller-supplied rays (trt_shade) on host arrays: o, d of shape (n,3), sample-major — sample s of
         output i is ray s * n_out + i, n_out = n / samples.  Every ray gets the colour trt_render* gives a pixel with
         that primary ray; the samples of an output are averaged.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        samples = int(samples)
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
-        self._check(self._L.trt_shade(self._h, C.byref(rays), samples, C.byref(pc), self._scene(scene), rgba.ctypes.data))
-        return rgba
+        return self._shade_host(self._L.trt_shade, o, d, pc, samples, self._scene(scene))
 
     def shade_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses of n floats each, sample-major; rgba_ptr: (n / samples) * 4
         floats, 16-byte aligned.  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_shade_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
                                           _vp(rgba_ptr), _vp(stream)))
 
@@ -214,11 +238,8 @@ class Tracer:
         """The fraction of light that gets along each ray (trt_transmittance) on host arrays: o, d of shape (n,3),
         tmax_per_ray as in ``occluded``.  The product over the walls crossed of 1 - clamp(dissolve, 0, 1) of their
         material — a material with dissolve 0 (a zero-initialised one!) is invisible.  Returns float32 (n,)."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
         T = np.empty(n, np.float32)
         self._check(self._L.trt_transmittance(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), tmin, tmax, T.ctypes.data))
         return T
@@ -226,7 +247,7 @@ class Tracer:
     def transmittance_dev(self, scene, ray_ptrs, n, T_ptr, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses; T_ptr: n floats; tmax_ptr: n per-ray bounds or 0.
         Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_transmittance_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
                                                   _vp(T_ptr), _vp(stream)))
 
@@ -234,18 +255,11 @@ class Tracer:
         """``shade`` with translucent surfaces (trt_shade_through) on host arrays: the crossings of every segment composited
         front to back with the materials' ``dissolve`` as opacity, the shadow ray a transmittance.  Layout and averaging as
         in ``shade``.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        samples = int(samples)
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
-        self._check(self._L.trt_shade_through(self._h, C.byref(rays), samples, C.byref(pc), self._scene(scene), rgba.ctypes.data))
-        return rgba
+        return self._shade_host(self._L.trt_shade_through, o, d, pc, samples, self._scene(scene))
 
     def shade_through_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
         """Device pointers (ints): as ``shade_dev``.  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_shade_through_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
                                                   _vp(rgba_ptr), _vp(stream)))
 
@@ -254,11 +268,8 @@ class Tracer:
         """The length of each ray inside each torus' tube (trt_chords) on host arrays: o, d of shape (n,3), tmax_per_ray
         as in ``occluded`` (here clipped by ``tmax``).  World units, not units of t; a ray that starts or ends inside a
         tube counts from / to its window's end.  Returns float32 (n_tori, n)."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
         length = np.empty((scene.n_tori, n), np.float32)
         self._check(self._L.trt_chords(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), tmin, tmax, length.ctypes.data))
         return length
@@ -266,7 +277,7 @@ class Tracer:
     def chords_dev(self, scene, ray_ptrs, n, length_ptr, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses; length_ptr: n_tori * n floats, torus-major; tmax_ptr: n per-ray
         bounds or 0.  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_chords_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), tmin, tmax,
                                            _vp(length_ptr), _vp(stream)))
 
@@ -274,11 +285,8 @@ class Tracer:
         """Emission and absorption of the media that fill the tubes, integrated along each ray (trt_glow) on host arrays:
         media as ``abi.media`` takes them, one per torus — ((er, eg, eb), sigma) per unit world length.  Returns float32
         (n, 4): the radiance that reaches the origin and the transmittance left; composite ``L + T * behind``."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
         rgba = np.empty((n, 4), np.float32)
         self._check(self._L.trt_glow(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), self._media(scene, media),
                                      tmin, tmax, rgba.ctypes.data))
@@ -287,7 +295,7 @@ class Tracer:
     def glow_dev(self, scene, ray_ptrs, n, media, rgba_ptr, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
         """Device pointers (ints): ray_ptrs = 6 addresses; rgba_ptr: n * 4 floats, 16-byte aligned; tmax_ptr: n per-ray
         bounds or 0; ``media`` stays on the host (it travels in the launch's arguments).  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_glow_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), self._media(scene, media),
                                          tmin, tmax, _vp(rgba_ptr), _vp(stream)))
 
@@ -333,21 +341,14 @@ class Tracer:
     def shade_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None):
         """The supersampled frame (trt_shade_camera) on a host buffer: per pixel the colours of its ``samples`` camera rays
         (offsets as in camera_rays) averaged as ``shade`` averages them.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
-        r0, r1 = (0, H) if rows is None else rows
-        rgba = np.zeros((H, W, 4), np.float32)
-        keep, off = self._offsets(offsets, samples)
-        self._check(self._L.trt_shade_camera(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
-                                             int(samples), off, rgba.ctypes.data))
-        return rgba
+        return self._shade_camera_host(self._L.trt_shade_camera, g, pc, W, H, camera, samples, offsets, rows, self._scene(scene))
 
     def shade_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None,
                          stream=0):
         """Device image (int address of the FULL W x H x 4 float image, 16-byte aligned; only the rows of ``rows`` are
         written).  Asynchronous on ``stream``."""
-        r0, r1 = (0, H) if rows is None else rows
-        keep, off = self._offsets(offsets, samples)
-        self._check(self._L.trt_shade_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
-                                                 int(samples), off, _vp(rgba_ptr), _vp(stream)))
+        self._shade_camera_dev(self._L.trt_shade_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows, self._scene(scene),
+                               stream=stream)
 
     # -- glass tori: shade and shade_camera with refraction at the materials of illum 6 / 7 -------
     def shade_refract(self, scene, o, d, pc, samples=1):
@@ -355,38 +356,24 @@ class Tracer:
         path by Snell's law with the material's ``ior`` (total internal reflection where there is no refracted ray) and
         filters it by ``transmittance`` once per passage.  A glass material in use needs ior > 0 — a zero-initialised one
         is refused.  Layout and averaging as in ``shade``.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        samples = int(samples)
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
-        self._check(self._L.trt_shade_refract(self._h, C.byref(rays), samples, C.byref(pc), self._scene(scene), rgba.ctypes.data))
-        return rgba
+        return self._shade_host(self._L.trt_shade_refract, o, d, pc, samples, self._scene(scene))
 
     def shade_refract_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
         """Device pointers (ints): as ``shade_dev``.  Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         self._check(self._L.trt_shade_refract_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
                                                   _vp(rgba_ptr), _vp(stream)))
 
     def shade_refract_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None):
         """``shade_camera`` with glass tori (trt_shade_refract_camera) on a host buffer: bit for bit ``camera_rays`` put
         through ``shade_refract``.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
-        r0, r1 = (0, H) if rows is None else rows
-        rgba = np.zeros((H, W, 4), np.float32)
-        keep, off = self._offsets(offsets, samples)
-        self._check(self._L.trt_shade_refract_camera(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1, camera,
-                                                     int(samples), off, rgba.ctypes.data))
-        return rgba
+        return self._shade_camera_host(self._L.trt_shade_refract_camera, g, pc, W, H, camera, samples, offsets, rows, self._scene(scene))
 
     def shade_refract_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None,
                                  rows=None, stream=0):
         """Device image: as ``shade_camera_dev``.  Asynchronous on ``stream``."""
-        r0, r1 = (0, H) if rows is None else rows
-        keep, off = self._offsets(offsets, samples)
-        self._check(self._L.trt_shade_refract_camera_dev(self._h, C.byref(g), C.byref(pc), self._scene(scene), W, H, r0, r1,
-                                                         camera, int(samples), off, _vp(rgba_ptr), _vp(stream)))
+        self._shade_camera_dev(self._L.trt_shade_refract_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows,
+                               self._scene(scene), stream=stream)
 
     # -- several lights, area lights: shade and shade_camera with a light table -------------------
     def shade_lit(self, scene, o, d, pc, samples=1, lights=(), shadow_samples=1, disc=None):
@@ -395,20 +382,13 @@ class Tracer:
         light with radius > 0 casts a soft shadow: ``shadow_samples`` any-hit rays per hit towards the positions ``disc``
         ((K, 2) on the unit disc; None: ``abi.disc_samples(K)``) of its disc.  Layout and averaging as in ``shade``.
         Returns rgba float32 of shape (n_out, 4), alpha 1."""
-        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
-        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
-        n = o.shape[1]
-        samples = int(samples)
-        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
-        rgba = np.empty((n // samples if samples > 0 else 0, 4), np.float32)
         lt, keep = abi.lights_struct(lights, shadow_samples, disc)
-        self._check(self._L.trt_shade_lit(self._h, C.byref(rays), samples, C.byref(pc), C.byref(lt), self._scene(scene), rgba.ctypes.data))
-        return rgba
+        return self._shade_host(self._L.trt_shade_lit, o, d, pc, samples, C.byref(lt), self._scene(scene))
 
     def shade_lit_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0, lights=(), shadow_samples=1, disc=None):
         """Device pointers (ints): as ``shade_dev``; the lights stay on the host (they travel in the launch's arguments).
         Asynchronous on ``stream``."""
-        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        rays = self._dev_rays(ray_ptrs, n)
         lt, keep = abi.lights_struct(lights, shadow_samples, disc)
         self._check(self._L.trt_shade_lit_dev(self._h, C.byref(rays), int(samples), C.byref(pc), C.byref(lt), self._scene(scene),
                                               _vp(rgba_ptr), _vp(stream)))
@@ -417,22 +397,16 @@ class Tracer:
                          lights=(), shadow_samples=1, disc=None):
         """``shade_camera`` under a table of lights (trt_shade_lit_camera) on a host buffer: bit for bit ``camera_rays`` put
         through ``shade_lit``.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
-        r0, r1 = (0, H) if rows is None else rows
-        rgba = np.zeros((H, W, 4), np.float32)
-        keep, off = self._offsets(offsets, samples)
-        lt, keep_l = abi.lights_struct(lights, shadow_samples, disc)
-        self._check(self._L.trt_shade_lit_camera(self._h, C.byref(g), C.byref(pc), C.byref(lt), self._scene(scene), W, H, r0, r1,
-                                                 camera, int(samples), off, rgba.ctypes.data))
-        return rgba
+        lt, keep = abi.lights_struct(lights, shadow_samples, disc)
+        return self._shade_camera_host(self._L.trt_shade_lit_camera, g, pc, W, H, camera, samples, offsets, rows, C.byref(lt),
+                                       self._scene(scene))
 
     def shade_lit_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None,
                              rows=None, stream=0, lights=(), shadow_samples=1, disc=None):
         """Device image: as ``shade_camera_dev``; the lights stay on the host.  Asynchronous on ``stream``."""
-        r0, r1 = (0, H) if rows is None else rows
-        keep, off = self._offsets(offsets, samples)
-        lt, keep_l = abi.lights_struct(lights, shadow_samples, disc)
-        self._check(self._L.trt_shade_lit_camera_dev(self._h, C.byref(g), C.byref(pc), C.byref(lt), self._scene(scene), W, H, r0, r1,
-                                                     camera, int(samples), off, _vp(rgba_ptr), _vp(stream)))
+        lt, keep = abi.lights_struct(lights, shadow_samples, disc)
+        self._shade_camera_dev(self._L.trt_shade_lit_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows, C.byref(lt),
+                               self._scene(scene), stream=stream)
 
     # -- ray fans: K rays from every surface point, as streams or as fused ambient occlusion --
     @staticmethod
