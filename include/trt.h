@@ -31,6 +31,8 @@
  *   refraction, total reflection   with the materials' ior)              trt_shade_refract_camera*
  *   payload loop with a table of   (none: rchit:79-155 once per light, the   trt_shade_lit* /
  *   lights, area lights among them shadow bit a fraction of K any-hit rays)  trt_shade_lit_camera*
+ *   payload loop with textures:    REFL/shaders/raytrace.rchit:101-106       trt_set_textures* / trt_shade_textured* /
+ *   diffuse *= texture(uv)         (the uv a torus' own two angles)          trt_shade_textured_camera* / trt_hit_uv*
  *   length of a ray inside every   (none: build-defined, the pairing of
  *   torus' tube                    trt_crossings' entries and exits)     trt_chords*
  *   emission and absorption of     (none: build-defined, the line integral
@@ -120,7 +122,8 @@ typedef struct trt_material {
   float   ior;       /* MTL `Ni`.  Read by trt_shade_refract* ONLY, for the materials of illum 6 / 7; see there */
   float   dissolve;  /* MTL `d`, the opacity.  Read by trt_transmittance* and trt_shade_through* ONLY; see there */
   int32_t illum;
-  int32_t textureId; /* must be -1: tori are untextured (REFL rchit:100)                */
+  int32_t textureId; /* -1: none.  >= 0: an index into the textures bound with trt_set_textures*, read by
+                        trt_shade_textured* ONLY (REFL rchit:101-106); every other call refuses it: tori are untextured there */
 } trt_material;      /* 80 bytes                                                        */
 
 /* One analytic torus: centre C, major radius R, tube radius r, 0 < r < R; symmetry axis +y (the
@@ -531,6 +534,108 @@ int trt_shade_lit_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, co
 int trt_shade_lit_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights,
                              const trt_scene* scene, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera,
                              uint32_t samples, const float* offsets, float* rgba_dev, void* stream);
+
+/* ---- textures on tori: set_textures, shade_textured(rays_in -> colours), shade_textured_camera, hit_uv(points -> (u, v)) -- */
+/* The closest-hit shader's `if(mat.textureId >= 0) diffuse *= texture(...)` (REFL/shaders/raytrace.rchit:101-106).  A torus
+ * has a parametrisation of its own — the angle about its axis and the angle about its tube — so these calls need no UV
+ * streams: a material's textureId names one of the textures bound to the ctx, and the (u, v) of a hit follow from the hit
+ * point.  Every other call still refuses a material with textureId >= 0 (TRT_E_SCENE, "tori are untextured").
+ *
+ * Binding.  trt_set_textures copies n images from HOST memory into device memory the ctx owns (it allocates and
+ * synchronises: not capturable); trt_set_textures_dev copies only the n descriptors and BORROWS the images, which are
+ * device memory, 4-byte aligned, and stay alive and unchanged while they are bound.  The binding holds for the later calls
+ * of this section; tex == NULL or n == 0 unbinds.  A refused call (TRT_E_INVALID, the message begins "trt_set_textures:" or
+ * "trt_set_textures_dev:" and names the texture: NULL texels, a side of 0 or above 16384, a repeat that is 0, negative,
+ * NaN, infinite or above 4096, an unknown encoding, n > TRT_MAX_TEXTURES, device texels that are not 4-byte aligned) leaves
+ * the previous binding in place.  A call resolves every material's textureId against the table at CALL time: outside
+ * [-1, n) it is refused with TRT_E_SCENE and a message that names "material i".  The reference's `textureId + txtOffset`
+ * (the ObjDesc's offset into the global texture array) is the table index: add the offset when filling trt_material
+ * (INTEGRATION.md).  A captured graph reads the images and descriptors that were bound when it was captured, and must
+ * not be replayed after that binding was replaced or removed (trt_set_textures frees the images it replaces).
+ * sRGB images (TRT_TEX_SRGB: what the reference loads, VK_FORMAT_R8G8B8A8_SRGB) are decoded through a table of 256 floats
+ * in device memory of the ctx, built once on the host in double by the piecewise formula (c <= 0.04045 ? c / 12.92 :
+ * pow((c + 0.055) / 1.055, 2.4), c = byte / 255) and rounded to float; entry 255 is exactly 1.0f.  No pow per hit.
+ *
+ * trt_shade_textured* / trt_shade_textured_camera* are trt_shade* / trt_shade_camera* argument for argument, and everything
+ * that is not about textures is theirs: rays, the `samples` layout, the averaging rule, the alignment of the image, the
+ * window (0.001, 10000) on every segment, pc->maxDepth, clearColor * 0.8 on a miss, the light of pc and its opaque shadow
+ * query, the mirror of illum == 3, every TRT_SOLVE_*, the torus axes, the enclosure cull, band addressing, offsets, the
+ * toroidal-table contract, the refusals and their order, stats, and n == 0 / row_begin == row_end, which launch nothing.
+ * `dissolve`, `ior` and `transmittance` are not read: the families do not mix.
+ *
+ * The one new step, after diffuse = computeDiffuse(mat, L, N) (rchit:100) and before the shadow query, for a hit at P on
+ * torus `id` (centre C, major radius R) whose material has textureId = k >= 0 — FP32, one rounding per operation, in the
+ * order written, fma only where written:
+ *   1. q = m * (P - C): P - C in the torus' frame.  m is the identity for the default +y axis; for a unit axis a
+ *      (trt_set_torus_axes) its rows are (u, a, w) with  h = e_x if |a_x| <= |a_z| else e_z;  u = normalize(h - a_h * a);
+ *      w = u x a  (formed in double, each entry rounded to float once);  q.k = fma(m[k][2], p.z, fma(m[k][1], p.y, m[k][0] * p.x)).
+ *      The rule fixes where u = 0 lies: on the side of u.
+ *   2. rho = sqrt(fma(q.z, q.z, q.x * q.x));  phi = atan2(q.z, q.x);  theta = atan2(q.y, rho - R).
+ *      atan2(y, x) is the library's own, exact operations only (it does not change with the ROCm release):
+ *        ax = |x|; ay = |y|; mx = max(ax, ay); mn = min(ax, ay); far = mn > 0.414213568f * mx;
+ *        t = (far ? mn - mx : mn) / (far ? mn + mx : mx);  s = t * t;
+ *        p = fma(s, fma(s, fma(s, 0.07902598f, -0.13824454f), 0.19971879f), -0.33332756f);  r = fma(p * s, t, t);
+ *        if(far) r = r + 0.785398163f;  if(ay > ax) r = 1.57079633f - r;  if(x < 0) r = 3.14159265f - r;  if(y < 0) r = -r.
+ *      Both arguments are well away from (0, 0) on a ring torus: rho >= R - r > 0 and (rho - R)^2 + q.y^2 = r^2.
+ *   3. u = phi * 0.159154943f;  u = u - floor(u);  a result that is not < 1 (a tiny negative angle rounds up to 1) is 0.
+ *      v likewise from theta.  u runs about the axis from the frame's +x towards its +z, v about the tube from the outer
+ *      equator towards the axis direction.
+ *   4. With the texture's W, H, repeat_u, repeat_v:  x = (u * repeat_u) * (float)W - 0.5f;  i0 = floor(x);  fx = x - i0;
+ *      y = (v * repeat_v) * (float)H - 0.5f;  j0 = floor(y);  fy = y - j0.  The columns i0, i0 + 1 and the rows j0, j0 + 1
+ *      are each reduced into [0, W) / [0, H) in INTEGER arithmetic after the conversion (repeat addressing): no u, v or
+ *      repeat addresses outside the image.  Four texels, each one 4-byte load; row 0 is at v = 0.
+ *   5. Each channel c (a byte) of each texel: TRT_TEX_SRGB the decode table's entry c; TRT_TEX_LINEAR (float)c * (1.0f / 255.0f).
+ *      lerp(a, b, f) = fma(f, b - a, a);  texel = lerp(lerp(t00, t10, fx), lerp(t01, t11, fx), fy)  per channel: along x
+ *      first, then along y.  A constant image filters to its own value exactly.  Alpha is not read.
+ *   6. diffuse = diffuse * texel, per channel (rchit:105).  Then the shadow query, the specular term, the mirror step and
+ *      hitValue = fma(prd, attenuation, hitValue) follow as in trt_shade.
+ * Consequences:
+ *   - A scene whose every textureId is -1, whatever is bound, gives trt_shade's colours and counters bit for bit; so does a
+ *     texture whose every byte is 255, in either encoding (255 * (1.0f / 255.0f) == 1.0f).  A texture changes no path:
+ *     the counters are trt_shade's on the same geometry.
+ *   - (u * repeat) * W: an image with repeat (2, 1) is, bit for bit, the image of two copies side by side with repeat (1, 1).
+ *   - No hardware sampler: its filter weights are fixed-point and unspecified.  Filtering beyond bilinear is the caller's
+ *     `samples`: trt_shade_textured_camera with offsets supersamples the texture as it does edges.
+ * trt_shade_textured_camera is, bit for bit and counter for counter, trt_camera_rays put through trt_shade_textured.
+ *
+ * trt_hit_uv: the (u, v) of steps 1-3 — the SAME device function — for n points (px, py, pz) on the tori `id` names: the
+ * streams of trt_hits as trt_trace / trt_render leave them, or one slot of trt_crossings.  No repeat and no texture is
+ * applied: a per-wall quantity (heat flux, a tile pattern) is looked up by the caller.  id < 0 (a miss) or id >= n_tori
+ * gives u = v = 0; u_out or v_out may be NULL, not both; n == 0 launches nothing.  The scene's materials are validated
+ * but not read, and a textureId >= 0 is accepted.
+ * Not here: textures inside trt_render*, or in the translucent, glass and light-table families; mip levels and anisotropy
+ * (none are built: supersample); nearest filtering; alpha; textures on anything but `diffuse` (specular, normal or
+ * emission maps); a repeat per torus rather than per texture.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+#define TRT_MAX_TEXTURES 8
+enum { TRT_TEX_SRGB = 0, TRT_TEX_LINEAR = 1 };
+typedef struct trt_texture {
+  const uint8_t* texels;   /* RGBA8, row-major, width*height*4 bytes, row 0 at v = 0; alpha is not read */
+  uint32_t width, height;  /* 1..16384 each */
+  float repeat_u, repeat_v;/* finite, in (0, 4096]: how often the image repeats around the axis / the tube */
+  int32_t encoding;        /* TRT_TEX_SRGB or TRT_TEX_LINEAR */
+} trt_texture;             /* 32 bytes */
+
+int trt_set_textures(trt_ctx* ctx, const trt_texture* tex, uint32_t n);     /* host images, copied to the device */
+int trt_set_textures_dev(trt_ctx* ctx, const trt_texture* tex, uint32_t n); /* device images, borrowed */
+
+int trt_shade_textured(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                       float* rgba_out);
+int trt_shade_textured_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                              uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                              float* rgba_out);
+int trt_hit_uv(trt_ctx* ctx, const trt_scene* scene, const float* px, const float* py, const float* pz, const int32_t* id,
+               uint64_t n, float* u_out, float* v_out);
+/* Device-resident buffers, asynchronous on `stream`.  The descriptors of the binding travel in the kernel arguments; the
+ * calls use no scratch of the ctx beyond the toroidal tables of the camera form, allocate nothing, synchronise nothing, put
+ * only kernel nodes on the stream and may be captured (the toroidal camera: as trt_shade_camera_dev; the binding: above). */
+int trt_shade_textured_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                           float* rgba_dev, void* stream);
+int trt_shade_textured_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W,
+                                  uint32_t H, uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples,
+                                  const float* offsets, float* rgba_dev, void* stream);
+int trt_hit_uv_dev(trt_ctx* ctx, const trt_scene* scene, const float* px_dev, const float* py_dev, const float* pz_dev,
+                   const int32_t* id_dev, uint64_t n, float* u_dev, float* v_dev, void* stream);
 
 /* ---- media inside the tubes: chords(rays_in -> a length per ray and torus), glow(rays_in -> radiance, transmittance) -- */
 /* Every other call sees a torus as a surface.  These four see its tube as a volume: trt_chords returns how long every ray

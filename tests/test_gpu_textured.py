@@ -1,0 +1,555 @@
+"""trt_set_textures[_dev], trt_shade_textured[_dev], trt_shade_textured_camera[_dev], trt_hit_uv[_dev]: textures on tori
+along caller and camera rays, and the (u, v) of surface points (include/trt.h).
+
+Anchors, from the strictest down:
+  1. trt_shade_dev / trt_shade_camera_dev — no texture in use, or an all-255 texture in either encoding, is their call: the
+     colours bit for bit on every ray, the counters too; a texture changes no path, so the counters with textures are
+     trt_shade_dev's on the same geometry;
+  2. the fused camera form is trt_camera_rays_dev followed by trt_shade_textured_dev, bit for bit, stats included;
+  3. the FP64 truth of tests/textured_truth.py at the bars of tests/test_oracle.py's FP64 comparison;
+  4. (u * repeat) * W: an image with repeat (2, 1) is the image of two copies with repeat (1, 1), in bits;
+  5. copied and borrowed images give the same bits;
+  6. trt_hit_uv_dev against the FP64 uv of the same FP32 points.
+Then capture and replay, and the refusals.  Sets are crossings_truth's 4096 rays, frames 24x16.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import camera_truth
+import crossings_truth as ct
+import textured_truth as xt
+from camera_support import image as frame_image, n_rays, ray_buffers, read_image, shade_camera_dev, stream_handle
+from toroidal_ray_tracing_amd import abi, camera
+
+pytestmark = pytest.mark.gpu
+
+SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64]
+SOLVER_IDS = ["f32", "f64"]
+ALL_SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64, abi.TRT_SOLVE_DK_F32, abi.TRT_SOLVE_DK_F64, abi.TRT_SOLVE_FERRARI_F32,
+               abi.TRT_SOLVE_FERRARI_F64]
+ALL_SOLVER_IDS = ["f32", "f64", "dk32", "dk64", "ferrari32", "ferrari64"]
+SENTINEL = -7.25
+PAD = 8
+W, H = 24, 16
+BAND = (3, 13)
+QUERY_KEYS = ("primary_tests", "bounce_tests", "shadow_tests")
+f32 = np.float32
+
+# trt_hit_uv_dev against the FP64 uv of the same FP32 points, as circular distance in u and in v: the largest deviation
+# measured on an MI355X over the hits of `single`, `thin` and `rings2` is UV_MEASURED — v on `thin`, where rho - R loses the
+# most digits; u stays at 7.3e-8 and v at 8.6e-8 (single) and 1.3e-7 (rings2): profiles/r21_textures.txt has them per set.
+# Four times that is allowed, because a few thousand points under-sample the worst octant of an atan2.  It must stay
+# below 1e-5, a hundredth of a texel of a 1024-wide image — if it does not, the polynomial is too short.
+UV_MEASURED = 2.909e-7
+UV_BAR = 4.0 * UV_MEASURED
+assert UV_BAR < 1e-5
+
+
+@pytest.fixture(scope="module")
+def tr():
+    from toroidal_ray_tracing_amd.tracer import Tracer
+    t = Tracer(0)
+    yield t
+    t.close()
+
+
+def u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def upload(o, d):
+    import torch
+    dev = torch.device("cuda:0")
+    soa = [torch.from_numpy(np.array(a[:, k], np.float32)).to(dev) for a in (o, d) for k in range(3)]   # (a writable copy)
+    return soa, [a.data_ptr() for a in soa]
+
+
+def image(n_floats):
+    import torch
+    return torch.full((n_floats + PAD,), SENTINEL, dtype=torch.float32, device="cuda:0")
+
+
+def read(buf, n_floats):
+    raw = buf.cpu().numpy()
+    assert (raw[n_floats:] == f32(SENTINEL)).all(), "written beyond the output"
+    return raw[:n_floats].copy()
+
+
+def _rays_call(tr, which, sc, o, d, pc, samples, solver, stats):
+    """One trt_shade_dev / trt_shade_textured_dev call into a sentinel-padded image: (n_out, 4) [, stats]."""
+    import torch
+    n_out = len(o) // samples
+    keep, ptrs = upload(o, d) if len(o) else (None, [0] * 6)
+    buf = image(n_out * 4)
+    tr.set_solver(solver)
+    tr.enable_stats(stats)
+    try:
+        getattr(tr, which)(sc, ptrs, len(o), pc, buf.data_ptr(), samples=samples, stream=stream_handle())
+        st = tr.stats() if stats else None
+    finally:
+        tr.enable_stats(False)
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    torch.cuda.synchronize()
+    out = read(buf, n_out * 4).reshape(n_out, 4)
+    return (out, st) if stats else out
+
+
+def tex_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
+    return _rays_call(tr, "shade_textured_dev", sc, o, d, pc, samples, solver, stats)
+
+
+def shade_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
+    return _rays_call(tr, "shade_dev", sc, o, d, pc, samples, solver, stats)
+
+
+def tex_camera_dev(tr, sc, g, pc, cam, samples=1, offsets=None, rows=None, solver=abi.TRT_SOLVE_F32, stats=False):
+    """One trt_shade_textured_camera_dev call into a sentinel-filled full-frame image: (H, W, 4) [, stats]."""
+    import torch
+    buf = frame_image(W, H)
+    tr.set_solver(solver)
+    tr.enable_stats(stats)
+    try:
+        tr.shade_textured_camera_dev(sc, g, pc, W, H, buf.data_ptr(), camera=cam, samples=samples, offsets=offsets, rows=rows,
+                                     stream=stream_handle())
+        st = tr.stats() if stats else None
+    finally:
+        tr.enable_stats(False)
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    torch.cuda.synchronize()
+    out = read_image(buf, W, H, rows)
+    return (out, st) if stats else out
+
+
+def scene_of(set_name, mats):
+    geo, axes = ct.SCENES[set_name]
+    return abi.Scene([(C_, R, r, j) for j, (C_, R, r) in enumerate(geo)], mats, axes=axes)
+
+
+def with_tex(mats, ids):
+    return [dict(m, textureId=k) for m, k in zip(mats, ids)]
+
+
+WHITE = np.full((4, 8, 4), 255, np.uint8)
+SOME = [abi.make_texture(xt.noise_image(16, 8, 31), (2, 1)), abi.make_texture(xt.checker_image(8, 4), (4, 2), abi.TRT_TEX_LINEAR)]
+
+# illum 2 alone, and the oriented pair of a mirror and a plastic ring
+PLAIN = {"single": [camera.PLASTIC], "rings2": [camera.MIRROR, camera.PLASTIC]}
+
+
+def textured_frame(cam_name):
+    """A textured plastic ring over a textured matte one in front of the pinhole camera, or a textured plastic shell around
+    a mirror core about the toroidal one's line of sight: (scene, the same scene without textures, g, pc, camera)."""
+    if cam_name == "pinhole":
+        tori = [((0.0, 0.6, 0.0), 0.5, 0.12, 0), ((0.0, 0.0, 0.0), 1.0, 0.3, 1)]
+        mats = [camera.PLASTIC, camera.MATTE]
+        g, pc, cam = camera.baseline_camera(W, H), camera.baseline_push(4), abi.TRT_CAMERA_PINHOLE
+        ids = [0, 1]
+    else:
+        tori = [((0.0, 0.0, 0.0), 6.0, 1.5, 0), ((0.0, 0.0, 0.0), 6.0, 0.6, 1)]
+        mats = [camera.PLASTIC, camera.MIRROR]
+        g, pc, cam = (camera.toroidal_camera(W, H, eye=(0.5, 0.4, -0.3), center=(4.0, -1.0, 7.0)),
+                      abi.make_push(max_depth=4, rho=3.0), abi.TRT_CAMERA_TOROIDAL)
+        ids = [1, -1]
+    return abi.Scene(tori, with_tex(mats, ids)), abi.Scene(tori, mats), g, pc, cam
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. no texture in use, an all-255 texture, the counters: trt_shade_dev
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("solver", ALL_SOLVERS, ids=ALL_SOLVER_IDS)
+def test_without_a_texture_in_use_it_is_shade_bit_for_bit(tr, solver):
+    """Every textureId -1, a table bound or not; 1 and 3 samples (4095 of the 4096 rays), depth 5."""
+    for name, mats in PLAIN.items():
+        sc = scene_of(name, mats)
+        s = ct.ray_set(name)
+        o, d = s["o"][:4095], s["d"][:4095]
+        pc = abi.make_push(max_depth=5)
+        for samples in (1, 3):
+            want, wst = shade_dev(tr, sc, o, d, pc, samples, solver, stats=True)
+            for bound in (None, SOME):
+                tr.set_textures(bound)
+                got, st = tex_dev(tr, sc, o, d, pc, samples, solver, stats=True)
+                key = (name, samples, bound is not None)
+                assert np.array_equal(u32(got), u32(want)), (key, int((u32(got) != u32(want)).any(axis=1).sum()))
+                assert st == wst and st["pixels"] == len(o) and st["primary_tests"] == len(o) * sc.n_tori, key
+        assert len(np.unique(u32(want), axis=0)) > 20 and wst["shadow_tests"] > 0, name
+    tr.set_textures(None)
+
+
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("cam_name", ["pinhole", "toroidal"])
+def test_without_a_texture_in_use_the_camera_form_is_shade_camera(tr, cam_name, solver):
+    tsc, sc, g, pc, cam = textured_frame(cam_name)
+    off = camera_truth.grid_2x2(cam)
+    for bound in (None, SOME):
+        tr.set_textures(bound)
+        for samples, offsets, rows in ((1, None, None), (4, off, BAND)):
+            want, wst = shade_camera_dev(tr, sc, g, pc, W, H, cam, samples, offsets, rows, solver, stats=True)
+            got, st = tex_camera_dev(tr, sc, g, pc, cam, samples, offsets, rows, solver, stats=True)
+            r0, r1 = (0, H) if rows is None else rows
+            assert np.array_equal(u32(got[r0:r1]), u32(want[r0:r1])) and st == wst, (bound is not None, samples)
+    tr.set_textures(None)
+
+
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("encoding", [abi.TRT_TEX_SRGB, abi.TRT_TEX_LINEAR], ids=["srgb", "linear"])
+def test_an_all_255_texture_is_shade_bit_for_bit(tr, encoding, solver):
+    """On every material: entry 255 of the decode table is exactly 1.0f, 255 * (1.0f / 255.0f) is, and a constant image
+    filters to its own value exactly."""
+    tr.set_textures([abi.make_texture(WHITE, (3, 2), encoding), abi.make_texture(WHITE[:3, :5], (1, 7), encoding)])
+    for name, mats in PLAIN.items():
+        s = ct.ray_set(name)
+        pc = abi.make_push(max_depth=5)
+        want, wst = shade_dev(tr, scene_of(name, mats), s["o"], s["d"], pc, 1, solver, stats=True)
+        got, st = tex_dev(tr, scene_of(name, with_tex(mats, [1, 0])), s["o"], s["d"], pc, 1, solver, stats=True)
+        assert np.array_equal(u32(got), u32(want)), (name, int((u32(got) != u32(want)).any(axis=1).sum()))
+        assert st == wst, name
+    tr.set_textures(None)
+
+
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+def test_a_texture_changes_no_path(tr, solver):
+    """The counters with textures are trt_shade_dev's on the same geometry — and the picture is another one."""
+    for name in xt.cases():
+        c = xt.case(name)
+        tr.set_textures(c["tex"])
+        got, st = tex_dev(tr, c["sc"], c["o"], c["d"], c["pc"], 1, solver, stats=True)
+        plain = xt.case_scene(name, textured=False)[0]
+        want, wst = shade_dev(tr, plain, c["o"], c["d"], c["pc"], 1, solver, stats=True)
+        assert st == wst and st["shadow_tests"] > 0, name
+        assert (u32(got) != u32(want)).any(axis=1).mean() > 0.3, name
+    tr.set_textures(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. the fused camera form is camera_rays_dev -> shade_textured_dev
+# ---------------------------------------------------------------------------------------------------------------------
+def chain(tr, sc, g, pc, cam, samples, offsets, rows, solver):
+    """trt_camera_rays_dev into device streams, then trt_shade_textured_dev on them: the band's image and the stats."""
+    import torch
+    r0, r1 = (0, H) if rows is None else rows
+    n = n_rays(W, H, samples, rows)
+    bufs = ray_buffers(n)
+    ptrs = [b.data_ptr() for b in bufs]
+    out = torch.full(((r1 - r0) * W * 4,), SENTINEL, dtype=torch.float32, device="cuda:0")
+    tr.set_solver(solver)
+    tr.enable_stats(True)
+    try:
+        tr.camera_rays_dev(g, pc, W, H, ptrs, camera=cam, samples=samples, offsets=offsets, rows=rows, stream=stream_handle())
+        tr.shade_textured_dev(sc, ptrs, n, pc, out.data_ptr(), samples=samples, stream=stream_handle())
+        st = tr.stats()
+    finally:
+        tr.enable_stats(False)
+        tr.set_solver(abi.TRT_SOLVE_F32)
+    torch.cuda.synchronize()
+    return out.cpu().numpy().reshape(r1 - r0, W, 4), st
+
+
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("samples", [1, 4])
+@pytest.mark.parametrize("cam_name", ["pinhole", "toroidal"])
+def test_the_fused_camera_is_camera_rays_then_shade_textured(tr, cam_name, samples, solver):
+    tsc, sc, g, pc, cam = textured_frame(cam_name)
+    tr.set_textures(SOME)
+    off = None if samples == 1 else camera_truth.grid_2x2(cam)
+    for rows in (None, BAND):
+        got, st = tex_camera_dev(tr, tsc, g, pc, cam, samples=samples, offsets=off, rows=rows, solver=solver, stats=True)
+        want, wst = chain(tr, tsc, g, pc, cam, samples, off, rows, solver)
+        r0, r1 = (0, H) if rows is None else rows
+        n_px = (r1 - r0) * W
+        assert np.array_equal(u32(got[r0:r1]), u32(want)), (rows, int((u32(got[r0:r1]) != u32(want)).any(axis=2).sum()))
+        assert st == wst and st["pixels"] == samples * n_px and st["primary_tests"] == samples * n_px * tsc.n_tori
+        assert (u32(got[r0:r1, :, 3]) == u32(f32(1.0))).all()
+    full = tex_camera_dev(tr, tsc, g, pc, cam, solver=solver)
+    bare = shade_camera_dev(tr, sc, g, pc, W, H, cam, solver=solver)
+    assert (u32(full) != u32(bare)).any(axis=2).sum() >= 8   # the texture is in the picture
+    tr.set_solver(solver)
+    try:
+        host = tr.shade_textured_camera(tsc, g, pc, W, H, camera=cam, rows=BAND)   # the host form: the band, zeros around it
+    finally:
+        tr.set_solver(abi.TRT_SOLVE_F32)
+        tr.set_torus_axes(None)
+    assert np.array_equal(u32(host[BAND[0]:BAND[1]]), u32(full[BAND[0]:BAND[1]])) and not host[:BAND[0]].any() and not host[BAND[1]:].any()
+    tr.set_textures(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. the FP64 truth
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("solver", SOLVERS, ids=SOLVER_IDS)
+@pytest.mark.parametrize("name", list(xt.cases()))
+def test_against_the_fp64_truth(tr, name, solver):
+    """The bars of tests/test_oracle.py's FP64 comparison: rel = |got - want| / (|want| + 1e-5), rel <= 1e-4 on at least
+    99.5 % of the robust rays and max <= 2e-3."""
+    c = xt.case(name)
+    hit = c["first"] >= 0
+    assert 1.0 - c["robust"].mean() <= 0.1
+    assert (np.abs(c["rgb"] - c["plain"]).max(1) > 1e-3)[hit].mean() >= 0.5
+    tr.set_textures(c["tex"])
+    got = tex_dev(tr, c["sc"], c["o"], c["d"], c["pc"], solver=solver)
+    host = tr.shade_textured(c["sc"], c["o"], c["d"], c["pc"])
+    tr.set_torus_axes(None)
+    tr.set_textures(None)
+    if solver == abi.TRT_SOLVE_F32:
+        assert np.array_equal(u32(host), u32(got))                 # host and device forms
+    got = got[:, :3].astype(np.float64)
+    rel = (np.abs(got - c["rgb"]) / (np.abs(c["rgb"]) + 1e-5)).max(axis=-1)[c["robust"]]
+    print(f"{name} {SOLVER_IDS[SOLVERS.index(solver)]}: robust {c['robust'].mean():.4f}, rel max {rel.max():.3e}, "
+          f"over 1e-4: {int((rel > 1e-4).sum())} of {len(rel)}")
+    assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (name, rel.max(), int((rel > 1e-4).sum()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. repeat arithmetic; 5. copied and borrowed images
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("encoding", [abi.TRT_TEX_SRGB, abi.TRT_TEX_LINEAR], ids=["srgb", "linear"])
+def test_repeat_two_is_two_copies(tr, encoding):
+    """(u * repeat) * W: u * 2 is exact, so (u * 2) * W and (u * 1) * (2 W) are the same product rounded once — along u and,
+    with the copies stacked, along v."""
+    c = xt.case("rings2_both")
+    img = xt.noise_image(5, 3, 41)                                   # odd sizes: the wrap is not a mask
+    sc = scene_of("rings2", with_tex([camera.PLASTIC, camera.MATTE], [0, 0]))
+    pc = abi.make_push(max_depth=1)
+    out = []
+    for tex in (abi.make_texture(img, (2, 1), encoding), abi.make_texture(np.concatenate([img, img], axis=1), (1, 1), encoding),
+                abi.make_texture(img, (1, 4), encoding), abi.make_texture(np.concatenate([img] * 4, axis=0), (1, 1), encoding)):
+        tr.set_textures([tex])
+        out.append(tex_dev(tr, sc, c["o"], c["d"], pc))
+    tr.set_textures(None)
+    assert np.array_equal(u32(out[0]), u32(out[1])) and np.array_equal(u32(out[2]), u32(out[3]))
+    assert (u32(out[0]) != u32(out[2])).any(axis=1).mean() > 0.3
+
+
+def test_copied_and_borrowed_images_give_the_same_bits(tr):
+    import torch
+    from toroidal_ray_tracing_amd.tracer import TrtError
+    c = xt.case("rings2_both")
+    tr.set_textures(c["tex"])
+    want = tex_dev(tr, c["sc"], c["o"], c["d"], c["pc"])
+    dev = [torch.from_numpy(t["img"].copy()).to("cuda:0") for t in c["textures"]]
+    tr.set_textures_dev([abi.texture_at(b.data_ptr(), t["img"].shape[1], t["img"].shape[0], t["repeat"],
+                                        abi.TRT_TEX_SRGB if t["srgb"] else abi.TRT_TEX_LINEAR) for b, t in zip(dev, c["textures"])])
+    got = tex_dev(tr, c["sc"], c["o"], c["d"], c["pc"])
+    assert np.array_equal(u32(got), u32(want)) and len(np.unique(u32(want), axis=0)) > 50
+    dev[0].fill_(255)                                                 # borrowed: the call reads the caller's memory
+    assert (u32(tex_dev(tr, c["sc"], c["o"], c["d"], c["pc"])) != u32(want)).any()
+    for unbind in (lambda: tr.set_textures_dev(None), lambda: tr.set_textures([])):
+        tr.set_textures(c["tex"])
+        unbind()
+        with pytest.raises(TrtError) as e:
+            tex_dev(tr, c["sc"], c["o"], c["d"], c["pc"])
+        assert e.value.code == abi.TRT_E_SCENE and "material 0" in str(e.value) and "no textures are bound" in str(e.value)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. trt_hit_uv_dev
+# ---------------------------------------------------------------------------------------------------------------------
+def test_hit_uv_against_fp64(tr):
+    import torch
+    worst = {}
+    for name in ("single", "thin", "rings2"):
+        geo, axes = ct.SCENES[name]
+        sc = ct.scene(name)
+        s = ct.ray_set(name)
+        hits = tr.trace(sc, s["o"], s["d"])
+        n = len(hits["id"])
+        ids = hits["id"].copy()
+        ids[:7] = [len(geo), len(geo) + 5, 2**31 - 1, -1, -2, -2**31, abi.TRT_MAX_TORI]     # never an index
+        dev = {k: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for k, a in (("px", hits["px"]), ("py", hits["py"]), ("pz", hits["pz"]), ("id", ids))}
+        ptrs = {k: a.data_ptr() for k, a in dev.items()}
+        u, v = image(n), image(n)
+        tr.hit_uv_dev(sc, ptrs, n, u.data_ptr(), v.data_ptr(), stream=stream_handle())
+        only_u, only_v = image(n), image(n)
+        tr.hit_uv_dev(sc, ptrs, n, u_ptr=only_u.data_ptr(), stream=stream_handle())
+        tr.hit_uv_dev(sc, ptrs, n, v_ptr=only_v.data_ptr(), stream=stream_handle())
+        torch.cuda.synchronize()
+        u, v = read(u, n), read(v, n)
+        assert np.array_equal(u32(read(only_u, n)), u32(u)) and np.array_equal(u32(read(only_v, n)), u32(v))   # either output may be NULL
+        hu, hv = tr.hit_uv(sc, dict(hits, id=ids))
+        tr.set_torus_axes(None)
+        assert np.array_equal(u32(hu), u32(u)) and np.array_equal(u32(hv), u32(v))       # host and device forms
+        ok = (ids >= 0) & (ids < len(geo))
+        assert 0.3 < ok.mean() < 0.98 and not ok[:7].any()
+        assert (u32(u[~ok]) == 0).all() and (u32(v[~ok]) == 0).all()                      # a miss, an id >= n_tori: exactly 0
+        assert (u >= 0.0).all() and (u < 1.0).all() and (v >= 0.0).all() and (v < 1.0).all()
+        du, dv = np.zeros(n), np.zeros(n)
+        for j, (C_, R, r) in enumerate(geo):
+            sel = ok & (ids == j)
+            P = np.stack([hits["px"][sel], hits["py"][sel], hits["pz"][sel]], 1).astype(np.float64)
+            wu, wv = xt.uv(P, C_, None if axes is None else axes[j], R)
+            du[sel], dv[sel] = xt.circular(u[sel], wu), xt.circular(v[sel], wv)
+        worst[name] = (du.max(), dv.max())
+        print(f"hit_uv {name}: {int(ok.sum())} points, circular distance max u {du.max():.3e} v {dv.max():.3e}")
+        assert len(np.unique(u32(u[ok]))) > 1000 and len(np.unique(u32(v[ok]))) > 1000
+    assert max(max(w) for w in worst.values()) <= UV_BAR, worst
+    # n == 0 launches nothing; both outputs NULL, or a NULL stream, is refused
+    from toroidal_ray_tracing_amd.tracer import TrtError
+    keep = image(4)
+    tr.hit_uv_dev(sc, {}, 0, keep.data_ptr(), keep.data_ptr())
+    for call in (lambda: tr.hit_uv_dev(sc, ptrs, n), lambda: tr.hit_uv_dev(sc, dict(ptrs, id=0), n, keep.data_ptr())):
+        with pytest.raises(TrtError) as e:
+            call()
+        assert e.value.code == abi.TRT_E_INVALID and "trt_hit_uv:" in str(e.value)
+    tr.set_torus_axes(None)
+    torch.cuda.synchronize()
+    assert (keep.cpu().numpy() == f32(SENTINEL)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. capture and replay
+# ---------------------------------------------------------------------------------------------------------------------
+def test_capture_and_replay(tr):
+    """Both _dev calls captured on one stream into a graph and replayed twice give the eager bits (kernel nodes only, no ctx
+    scratch but the toroidal tables: the toroidal call is made eagerly once first).  The binding is NOT replaced between
+    capture and replay; an eager textured call with another scene in between changes nothing."""
+    import torch
+    c = xt.case("rings2_both")
+    tsc, sc, g, pc, cam = textured_frame("toroidal")
+    tr.set_textures(c["tex"])
+    n = 256 * 5 + 33
+    o, d = c["o"][:2 * n], c["d"][:2 * n]
+    eager = tex_dev(tr, c["sc"], o, d, c["pc"], samples=2)
+    off = camera_truth.grid_2x2(cam)
+    eager_img = tex_camera_dev(tr, tsc, g, pc, cam, samples=4, offsets=off, rows=BAND)   # (uploads the tables)
+    keep, ptrs = upload(o, d)
+    buf, img = image(n * 4), frame_image(W, H)
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=side):
+            tr.shade_textured_dev(c["sc"], ptrs, 2 * n, c["pc"], buf.data_ptr(), samples=2, stream=side.cuda_stream)
+            tr.shade_textured_camera_dev(tsc, g, pc, W, H, img.data_ptr(), camera=cam, samples=4, offsets=off, rows=BAND, stream=side.cuda_stream)
+    cur.wait_stream(side)
+    tr.set_torus_axes(None)
+    other = xt.case("single_checker_linear")
+    for k in range(2):
+        buf.fill_(SENTINEL)
+        img.fill_(SENTINEL)
+        gr.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(u32(read(buf, n * 4).reshape(n, 4)), u32(eager)), k
+        assert np.array_equal(u32(read_image(img, W, H, BAND)), u32(eager_img)), k
+        tex_dev(tr, other["sc"], other["o"][:500], other["d"][:500], other["pc"])   # an eager call in between (texture 0 of the binding)
+    assert len(np.unique(u32(eager), axis=0)) > 50
+    del gr
+    tr.set_textures(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. refusals
+# ---------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_binding_the_ctx_and_the_outputs_as_they_were(tr):
+    import torch
+    from toroidal_ray_tracing_amd.tracer import TrtError
+    c = xt.case("rings2_both")
+    sc, pc = c["sc"], c["pc"]
+    n = 300
+    o, d = c["o"][:n], c["d"][:n]
+    tr.set_textures(c["tex"])
+    want = tex_dev(tr, sc, o, d, pc)
+    tsc, _, g, gpc, cam = textured_frame("pinhole")
+    want_img = tex_camera_dev(tr, tsc, g, gpc, cam)
+    keep, ptrs = upload(o, d)
+    out, img = image(n * 4), frame_image(W, H)
+
+    def good():
+        assert np.array_equal(u32(tex_dev(tr, sc, o, d, pc)), u32(want))
+        assert np.array_equal(u32(tex_camera_dev(tr, tsc, g, gpc, cam)), u32(want_img))
+
+    def refused(call, code, *needles):
+        with pytest.raises(TrtError) as e:
+            call()
+        tr.set_torus_axes(None)
+        assert e.value.code == code, str(e.value)
+        for needle in needles:
+            assert needle in str(e.value), str(e.value)
+        good()
+
+    good()
+    st, stc = "trt_shade_textured:", "trt_shade_textured_camera:"
+    # a textureId the binding does not hold (two textures are bound), through all four calls; then with nothing bound
+    far = scene_of("rings2", with_tex([camera.MIRROR, camera.PLASTIC], [1, 2]))
+    neg = scene_of("rings2", with_tex([camera.MIRROR, camera.PLASTIC], [-2, 0]))
+    gfar = abi.Scene(tsc.tori_list(), with_tex([camera.PLASTIC, camera.MATTE], [0, 7]))
+    refused(lambda: tr.shade_textured_dev(far, ptrs, n, pc, out.data_ptr()), abi.TRT_E_SCENE, st, "material 1", "textureId=2")
+    refused(lambda: tr.shade_textured(far, o, d, pc), abi.TRT_E_SCENE, st, "material 1", "textureId=2")
+    refused(lambda: tr.shade_textured_dev(neg, ptrs, n, pc, out.data_ptr()), abi.TRT_E_SCENE, st, "material 0", "textureId=-2")
+    refused(lambda: tr.shade_textured_camera_dev(gfar, g, gpc, W, H, img.data_ptr(), camera=cam), abi.TRT_E_SCENE, stc, "material 1", "textureId=7")
+    refused(lambda: tr.shade_textured_camera(gfar, g, gpc, W, H, camera=cam), abi.TRT_E_SCENE, stc, "material 1")
+    # everything trt_shade* / trt_shade_camera* refuse, with this call's name
+    refused(lambda: tr.shade_textured_dev(sc, ptrs, n, pc, out.data_ptr(), samples=0), abi.TRT_E_INVALID, st, "samples")
+    refused(lambda: tr.shade_textured_dev(sc, ptrs, n, pc, out.data_ptr(), samples=7), abi.TRT_E_INVALID, st, "multiple")
+    refused(lambda: tr.shade_textured_dev(sc, ptrs, n, pc, out.data_ptr() + 4), abi.TRT_E_INVALID, st, "aligned")
+    refused(lambda: tr.shade_textured_dev(sc, ptrs, n, pc, 0), abi.TRT_E_INVALID, st, "NULL")
+    refused(lambda: tr.shade_textured_dev(sc, ptrs[:2] + [0] + ptrs[3:], n, pc, out.data_ptr()), abi.TRT_E_INVALID, st, "NULL ray stream")
+    refused(lambda: tr.shade_textured_camera_dev(tsc, g, gpc, 0, H, img.data_ptr(), camera=cam), abi.TRT_E_INVALID, stc, "bad size")
+    refused(lambda: tr.shade_textured_camera_dev(tsc, g, gpc, W, H, img.data_ptr(), camera=cam, rows=(9, 5)), abi.TRT_E_INVALID, stc, "bad size")
+    refused(lambda: tr.shade_textured_camera_dev(tsc, g, gpc, W, H, img.data_ptr(), camera=5), abi.TRT_E_INVALID, stc, "unknown camera")
+    refused(lambda: tr.shade_textured_camera_dev(tsc, g, gpc, W, H, img.data_ptr(), camera=cam, samples=0), abi.TRT_E_INVALID, stc, "samples")
+    refused(lambda: tr.shade_textured_camera_dev(tsc, g, gpc, W, H, img.data_ptr() + 4, camera=cam), abi.TRT_E_INVALID, stc, "aligned")
+    L = tr._L
+    rays = abi.rays_struct(ptrs, n)
+    assert L.trt_shade_textured_dev(tr._h, C.byref(rays), 1, C.byref(pc), None, C.c_void_p(out.data_ptr()), None) == abi.TRT_E_INVALID
+    assert b"scene" in L.trt_last_error(tr._h)
+    good()
+
+    # trt_set_textures*: a refused table names the texture and leaves the previous binding in place
+    ok = xt.noise_image(4, 4, 1)
+    nan, inf = float("nan"), float("inf")
+    host_at = lambda **kw: abi.texture_at(kw.pop("address", ok.ctypes.data), kw.pop("w", 4), kw.pop("h", 4), kw.pop("repeat", (1, 1)), kw.pop("encoding", 0))
+    devimg = torch.from_numpy(ok.copy()).to("cuda:0")
+    dev_at = lambda **kw: host_at(address=kw.pop("address", devimg.data_ptr()), **kw)
+    for setter, at, who in ((tr.set_textures, host_at, "trt_set_textures:"), (tr.set_textures_dev, dev_at, "trt_set_textures_dev:")):
+        lead = at()
+        refused(lambda: setter([lead, at(address=0)]), abi.TRT_E_INVALID, who, "texture 1", "NULL texels")
+        refused(lambda: setter([at(w=0)]), abi.TRT_E_INVALID, who, "texture 0", "1..16384")
+        refused(lambda: setter([lead, at(h=0)]), abi.TRT_E_INVALID, who, "texture 1", "1..16384")
+        refused(lambda: setter([at(w=16385)]), abi.TRT_E_INVALID, who, "texture 0", "1..16384")
+        refused(lambda: setter([lead, lead, at(h=16385)]), abi.TRT_E_INVALID, who, "texture 2", "1..16384")
+        for bad in (0.0, -1.0, nan, inf, -inf, 4096.5):
+            refused(lambda: setter([at(repeat=(bad, 1.0))]), abi.TRT_E_INVALID, who, "texture 0", "repeat")
+            refused(lambda: setter([lead, at(repeat=(1.0, bad))]), abi.TRT_E_INVALID, who, "texture 1", "repeat")
+        for bad in (2, -1):
+            refused(lambda: setter([lead, at(encoding=bad)]), abi.TRT_E_INVALID, who, "texture 1", "encoding")
+        refused(lambda: setter([lead] * (abi.TRT_MAX_TEXTURES + 1)), abi.TRT_E_INVALID, who, "TRT_MAX_TEXTURES")
+    for k in (1, 2, 3):
+        refused(lambda: tr.set_textures_dev([dev_at(), dev_at(address=devimg.data_ptr() + k, w=3, h=3)]), abi.TRT_E_INVALID,
+                "trt_set_textures_dev:", "texture 1", "aligned")
+    # accepted at the limits: repeat 4096, a 1 x 1 image, TRT_MAX_TEXTURES textures — then the case's binding again
+    tr.set_textures([abi.make_texture(ok[:1, :1], (4096, 4096))] * abi.TRT_MAX_TEXTURES)
+    one = tex_dev(tr, scene_of("rings2", with_tex([camera.MIRROR, camera.PLASTIC], [7, 7])), o, d, pc)
+    assert np.isfinite(one).all()
+    tr.set_textures(c["tex"])
+    good()
+
+    # the other calls still refuse a textured scene — also right after a successful textured call on those very scene bytes
+    def untextured(call):
+        good()
+        assert np.array_equal(u32(tex_dev(tr, sc, o, d, pc)), u32(want))      # (the scene cache now holds sc, from a textured call)
+        with pytest.raises(TrtError) as e:
+            call()
+        tr.set_torus_axes(None)
+        assert e.value.code == abi.TRT_E_SCENE and "tori are untextured" in str(e.value) and "material 0" in str(e.value), str(e.value)
+
+    untextured(lambda: tr.shade_dev(sc, ptrs, n, pc, out.data_ptr()))
+    untextured(lambda: tr.trace(sc, o, d))
+    untextured(lambda: tr.shade_lit_dev(sc, ptrs, n, pc, out.data_ptr(), lights=[abi.light_from_push(pc)]))
+    untextured(lambda: tr.render(abi.Scene(sc.tori_list(), c["mats"]), g, gpc, W, H))      # (+y axes: another scene, built and refused)
+
+    def render_after_textured():
+        # trt_render on the bytes of the textured frame's scene, which the textured camera call has just cached
+        assert np.array_equal(u32(tex_camera_dev(tr, tsc, g, gpc, cam)), u32(want_img))
+        tr.render(tsc, g, gpc, W, H)
+    with pytest.raises(TrtError) as e:
+        render_after_textured()
+    assert e.value.code == abi.TRT_E_SCENE and "tori are untextured" in str(e.value)
+    good()
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == f32(SENTINEL)).all() and (img.cpu().numpy() == f32(SENTINEL)).all()   # a refused call writes nothing
+    tr.set_textures(None)

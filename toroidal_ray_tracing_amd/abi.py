@@ -151,6 +151,49 @@ def lights_struct(lights, shadow_samples=1, disc=None):
     return st, (arr, d)
 
 
+TRT_MAX_TEXTURES = 8                    # textures bound to a ctx (trt_set_textures*)
+TRT_TEX_SRGB, TRT_TEX_LINEAR = 0, 1
+
+
+class trt_texture(C.Structure):
+    """One texture of trt_set_textures*: RGBA8 texels (host memory, or device memory for the _dev form), row 0 at v = 0,
+    how often the image repeats about the axis / the tube, and the encoding of its bytes."""
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("repeat_u", C.c_float), ("repeat_v", C.c_float), ("encoding", C.c_int32)]
+
+
+assert C.sizeof(trt_texture) == 32
+
+
+def make_texture(array, repeat=(1, 1), encoding=TRT_TEX_SRGB):
+    """A ``trt_texture`` over a host image: ``array`` of shape (H, W, 4) uint8 (anything else convertible is copied once).
+    The struct keeps the array alive (``.keep``).  For device images fill a ``trt_texture`` by hand, ``texels`` the
+    device address (``texture_at``)."""
+    a = np.ascontiguousarray(array, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"a texture is (H, W, 4) uint8, not {a.shape}")
+    t = trt_texture(a.ctypes.data, a.shape[1], a.shape[0], float(repeat[0]), float(repeat[1]), int(encoding))
+    t.keep = a
+    return t
+
+
+def texture_at(address, width, height, repeat=(1, 1), encoding=TRT_TEX_SRGB):
+    """A ``trt_texture`` over RGBA8 texels at ``address`` (an int: device memory for trt_set_textures_dev)."""
+    return trt_texture(int(address) or None, int(width), int(height), float(repeat[0]), float(repeat[1]), int(encoding))
+
+
+def textures_array(textures):
+    """(ctypes array of trt_texture | None, n) from an iterable of ``trt_texture`` (None or empty: unbind)."""
+    items = [] if textures is None else list(textures)
+    if not items:
+        return None, 0
+    arr = (trt_texture * len(items))()
+    for dst, t in zip(arr, items):
+        C.memmove(C.byref(dst), C.byref(t), C.sizeof(trt_texture))
+    arr.keep = items
+    return arr, len(items)
+
+
 class trt_rays(C.Structure):
     _fields_ = [("ox", C.c_void_p), ("oy", C.c_void_p), ("oz", C.c_void_p),
                 ("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p),

@@ -148,12 +148,25 @@ struct trt_ctx {
     trt_torus    tori[TRT_MAX_TORI];
     trt_material mat[TRT_MAX_MATERIALS];
     double       axis[TRT_MAX_TORI][3];   // the axes K was built with (+y where none was set)
+    bool         has_textures = false;    // some material has textureId >= 0: only a textured call may take this scene from the cache
     SceneK       K;
   } scene_cache;
   // trt_set_torus_axes: unit axes in double, exactly (0,1,0) for a torus that is not oriented; n_axes == 0: none set.
   uint32_t n_axes = 0;
   double   axis[TRT_MAX_TORI][3];
   uint64_t scene_gen = 0;   // bumped whenever scene_cache is rebuilt
+
+  // trt_set_textures*: the descriptors of the bound textures (n == 0: none bound), the one device block that holds the
+  // images trt_set_textures copied (nullptr: none, or borrowed images), and the sRGB decode table (256 floats, filled in
+  // trt_create).  The descriptors travel in the kernel arguments of every textured call: a captured graph keeps the ones
+  // it was captured with.
+  struct TextureBinding {
+    uint32_t n = 0;
+    TextureK t[TRT_MAX_TEXTURES] = {};
+    bool     any_srgb = false;
+    void*    owned = nullptr;
+  } textures;
+  float* d_srgb = nullptr;
 
   // The tile lists the last classification left in buf[kBufTiles] / d_queue, by what it read (ListKey): the third product a
   // frame loop recomputes for nothing, and the only one that costs GPU time (8 µs of a 116-µs frame at 4096²).
@@ -366,7 +379,7 @@ void torus_prepare(const trt_torus& t, TorusK<Real>& k)
   k.fourR2 = (Real)4 * R2;
 }
 
-int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], SceneK& out);
+int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], bool textured, SceneK& out);
 
 // Frame of an oriented torus with unit axis a: h = the world axis x or z along which |a| is smaller (x on a tie — never
 // within 45° of a), u = normalize(h − (h·a)·a), w = u × a.  (u, a, w) is right-handed and plays (x, y, z) of the torus'
@@ -390,8 +403,17 @@ void torus_frame(const double a[3], TorusRot& out)
 bool is_plus_y(const double a[3]) { return a[0] == 0.0 && a[1] == 1.0 && a[2] == 0.0; }
 
 // The validated kernel constants of `s` — from the ctx's cache when the caller passes the scene of the previous call
-// again (compared byte for byte, solver included), else built and cached.
-int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
+// again (compared byte for byte, solver included), else built and cached.  `textured`: the call reads textureId
+// (trt_shade_textured*, trt_hit_uv*); every other call refuses a material that names a texture — also when the scene comes
+// from the cache, where a textured call may have left it (the cache compares bytes, and SceneK knows no textures).
+int scene_untextured(trt_ctx* ctx, const trt_scene* s)
+{
+  for(uint32_t i = 0; i < s->n_materials; ++i)
+    if(s->materials[i].textureId >= 0)
+      return fail(ctx, TRT_E_SCENE, "scene: material %u has textureId=%d; tori are untextured", i, s->materials[i].textureId);
+  return TRT_OK;
+}
+int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out, bool textured = false)
 {
   if(!s || !s->tori || !s->materials)
     return fail(ctx, TRT_E_INVALID, "scene: NULL scene / tori / materials");
@@ -414,7 +436,9 @@ int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
   {
     c.valid = false;
     ++ctx->scene_gen;
-    if(int rc = build_scene_uncached(ctx, s, axis, c.K)) return rc;
+    if(int rc = build_scene_uncached(ctx, s, axis, textured, c.K)) return rc;
+    c.has_textures = false;
+    for(uint32_t i = 0; i < s->n_materials; ++i) c.has_textures = c.has_textures || s->materials[i].textureId >= 0;
     std::memcpy(c.axis, axis, s->n_tori * sizeof axis[0]);
     c.precision = ctx->precision;
     c.n_tori = s->n_tori;
@@ -422,6 +446,10 @@ int build_scene(trt_ctx* ctx, const trt_scene* s, const SceneK*& out)
     std::memcpy(c.tori, s->tori, s->n_tori * sizeof(trt_torus));
     std::memcpy(c.mat, s->materials, s->n_materials * sizeof(trt_material));
     c.valid = true;
+  }
+  else if(c.has_textures && !textured)
+  {
+    if(int rc = scene_untextured(ctx, s)) return rc;
   }
   out = &c.K;
   return TRT_OK;
@@ -467,7 +495,7 @@ bool cull_keeps_clear(const trt_torus& J, const double aJ[3], const trt_torus& M
          || hi_d + slack + (double)J.r + margin < (double)M.r;      // M's tube wraps J's
 }
 
-int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], SceneK& out)
+int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[3], bool textured, SceneK& out)
 {
   std::memset(&out, 0, sizeof out);
   out.n_tori = (int)s->n_tori;
@@ -537,7 +565,7 @@ int build_scene_uncached(trt_ctx* ctx, const trt_scene* s, const double (*axis)[
   for(uint32_t i = 0; i < s->n_materials; ++i)
   {
     const trt_material& m = s->materials[i];
-    if(m.textureId >= 0)
+    if(m.textureId >= 0 && !textured)
       return fail(ctx, TRT_E_SCENE, "scene: material %u has textureId=%d; tori are untextured", i,
                   m.textureId);
     MaterialK& k = out.mat[i];
@@ -680,6 +708,17 @@ int build_toro(trt_ctx* ctx, ToroTables& T, const trt_globals& g, const trt_push
   return TRT_OK;
 }
 
+// The sRGB decode table of a ctx: entry c = the linear value of byte c by the piecewise formula, in double, rounded to
+// float once.  Entry 0 is 0 and entry 255 exactly 1.0f (pow(1.0, 2.4) == 1.0).
+void srgb_decode_table(float out[256])
+{
+  for(int c = 0; c < 256; ++c)
+  {
+    const double x = (double)c / 255.0;
+    out[c] = (float)(x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4));
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -713,7 +752,14 @@ extern "C" int trt_create(int device, trt_ctx** out)
             && (e = hipMalloc((void**)&ctx->d_queue, kQueueWords * sizeof(unsigned int))) == hipSuccess
             && (e = hipMemset(ctx->d_stats, 0, kStatWords * sizeof(unsigned long long))) == hipSuccess
             && (e = hipMemset(ctx->d_queue, 0, kQueueWords * sizeof(unsigned int))) == hipSuccess
-            && (e = hipEventCreateWithFlags(&ctx->ev_stats, hipEventDisableTiming)) == hipSuccess;
+            && (e = hipEventCreateWithFlags(&ctx->ev_stats, hipEventDisableTiming)) == hipSuccess
+            && (e = hipMalloc((void**)&ctx->d_srgb, sizeof(float) * 256)) == hipSuccess;
+  if(ok)
+  {
+    float table[256];
+    srgb_decode_table(table);
+    ok = (e = hipMemcpy(ctx->d_srgb, table, sizeof table, hipMemcpyHostToDevice)) == hipSuccess;
+  }
   for(ToroTables& t : ctx->toro) ok = ok && (e = hipEventCreateWithFlags(&t.ev, hipEventDisableTiming)) == hipSuccess;
   if(!ok)
   {
@@ -739,6 +785,8 @@ extern "C" void trt_destroy(trt_ctx* ctx)
   if(ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
   if(ctx->d_stats) (void)hipFree(ctx->d_stats);
   if(ctx->d_queue) (void)hipFree(ctx->d_queue);
+  if(ctx->d_srgb) (void)hipFree(ctx->d_srgb);
+  if(ctx->textures.owned) (void)hipFree(ctx->textures.owned);
   for(DevBuf& b : ctx->buf)
     if(b.p) (void)hipFree(b.p);
   for(void* q : ctx->retired) (void)hipFree(q);
@@ -897,10 +945,10 @@ static int check_rays(trt_ctx* ctx, const trt_rays* in, const char* who)
 // `launch` of the filled `a` on `stream`.
 template <class Args>
 static int ray_query(trt_ctx* ctx, const trt_scene* scene, void* stream, uint64_t n, Args& a,
-                     hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t))
+                     hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), bool textured = false)
 {
   const SceneK* S = nullptr;
-  if(int rc = build_scene(ctx, scene, S)) return rc;
+  if(int rc = build_scene(ctx, scene, S, textured)) return rc;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   if(int rc = stats_begin(ctx, st, n, a.stats)) return rc;
@@ -1066,12 +1114,14 @@ static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const
 }
 
 // The device half of the four stream forms (`who`), which differ in the kernel and in the table that travels with its
-// arguments: `table(a)` validates and fills it (through_opacity, refract_glass, lit_lights; nothing for trt_shade).
+// arguments: `table(a)` validates and fills it (through_opacity, refract_glass, lit_lights, textured_table; nothing for
+// trt_shade).  `textured`: the form reads textureId (build_scene).
 // Refusals in this order: check_shade; the table's own checks, the scene's among them; the scene (trt_shade, whose table
 // checks nothing); HIP errors of the launch.
 template <class Args, class Table>
 static int shade_stream_dev(trt_ctx* ctx, const char* who, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
-                            float* rgba, void* stream, hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), Table&& table)
+                            float* rgba, void* stream, hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), Table&& table,
+                            bool textured = false)
 {
   if(int rc = check_shade(ctx, in, samples, pc, rgba, who)) return rc;
   Args a;
@@ -1081,7 +1131,7 @@ static int shade_stream_dev(trt_ctx* ctx, const char* who, const trt_rays* in, u
   a.samples = samples;
   a.pc      = *pc;
   a.rgba    = rgba;
-  return ray_query(ctx, scene, stream, in->n, a, launch);
+  return ray_query(ctx, scene, stream, in->n, a, launch, textured);
 }
 
 // The host-pointer half of the same four: the rays staged like trt_trace's, the image through buf[kBufRgba] like
@@ -1389,13 +1439,13 @@ static int check_shade_camera(trt_ctx* ctx, const char* who, const CameraFrame& 
 }
 
 // The device half of the three camera forms, which differ as the stream forms do: `table(a)` validates and fills the table
-// that travels with the kernel's arguments (refract_glass, lit_lights; nothing for trt_shade_camera).  Refusals in this
+// that travels with the kernel's arguments (refract_glass, lit_lights, textured_table; nothing for trt_shade_camera).  Refusals in this
 // order: check_shade_camera; the table's own checks, the scene's among them — BEFORE the toroidal tables are touched, so
 // that a call refused for its table or its scene leaves them as they were; the toroidal tables (camera_tables); the scene
 // (trt_shade_camera, whose table checks nothing); HIP errors of the launch.
 template <class Args, class Table>
 static int shade_camera_dev(trt_ctx* ctx, const char* who, const CameraFrame& f, const trt_scene* scene, float* rgba, void* stream,
-                            hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), Table&& table)
+                            hipError_t (*launch)(const SceneK&, const Args&, const Tuning&, hipStream_t), Table&& table, bool textured = false)
 {
   Args a;
   if(int rc = check_shade_camera(ctx, who, f, rgba, a.cam)) return rc;
@@ -1404,7 +1454,7 @@ static int shade_camera_dev(trt_ctx* ctx, const char* who, const CameraFrame& f,
   a.rgba = rgba;
   TRT_HIP(ctx, hipSetDevice(ctx->device));
   if(int rc = camera_tables(ctx, f.g, f.pc, (hipStream_t)stream, a.cam)) return rc;
-  return ray_query(ctx, scene, stream, a.cam.n_px * f.samples, a, launch);
+  return ray_query(ctx, scene, stream, a.cam.n_px * f.samples, a, launch, textured);
 }
 
 // The host-pointer half of the same three: the rows of the band through buf[kBufRgba], around dev(image) — the form's own
@@ -1585,6 +1635,195 @@ extern "C" int trt_shade_lit_camera(trt_ctx* ctx, const trt_globals* g, const tr
   return shade_camera_host(ctx, "trt_shade_lit_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
     return trt_shade_lit_camera_dev(ctx, g, pc, lights, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
   });
+}
+
+// ------------------------------------------------------------------------------------------
+// textures on tori: the binding, trt_shade and trt_shade_camera with the texel in the diffuse term, the (u, v) of points
+// ------------------------------------------------------------------------------------------
+// The checks of include/trt.h on a texture table (`who`: trt_set_textures | trt_set_textures_dev), and the descriptors it
+// describes with `texels` as the caller gave them.
+static int check_textures(trt_ctx* ctx, const char* who, const trt_texture* tex, uint32_t n, bool dev, TextureK* out)
+{
+  if(n > TRT_MAX_TEXTURES) return fail(ctx, TRT_E_INVALID, "%s: n = %u textures, at most %d (TRT_MAX_TEXTURES)", who, n, TRT_MAX_TEXTURES);
+  for(uint32_t k = 0; k < n; ++k)
+  {
+    const trt_texture& t = tex[k];
+    if(!t.texels) return fail(ctx, TRT_E_INVALID, "%s: texture %u has NULL texels", who, k);
+    if(t.width < 1 || t.width > 16384 || t.height < 1 || t.height > 16384)
+      return fail(ctx, TRT_E_INVALID, "%s: texture %u is %u x %u texels; each side must be 1..16384", who, k, t.width, t.height);
+    if(!(t.repeat_u > 0.0f && t.repeat_u <= 4096.0f) || !(t.repeat_v > 0.0f && t.repeat_v <= 4096.0f))   // (NaN fails both)
+      return fail(ctx, TRT_E_INVALID, "%s: texture %u has repeat (%g, %g); each must be finite and in (0, 4096]", who, k,
+                  (double)t.repeat_u, (double)t.repeat_v);
+    if(t.encoding != TRT_TEX_SRGB && t.encoding != TRT_TEX_LINEAR)
+      return fail(ctx, TRT_E_INVALID, "%s: texture %u has the unknown encoding %d (TRT_TEX_SRGB, TRT_TEX_LINEAR)", who, k, (int)t.encoding);
+    if(dev && ((uintptr_t)t.texels & 3))
+      return fail(ctx, TRT_E_INVALID, "%s: the device texels of texture %u are not 4-byte aligned (a texel is one 4-byte load)", who, k);
+    out[k] = {t.texels, t.width, t.height, t.repeat_u, t.repeat_v, t.encoding == TRT_TEX_SRGB ? 1 : 0, 0u};
+  }
+  return TRT_OK;
+}
+
+// Puts the checked descriptors `t` in force; `owned`: the block that holds their images, or nullptr for borrowed ones.
+// The block of the binding it replaces is freed (hipFree waits for the device: nothing reads it any more).
+static int bind_textures(trt_ctx* ctx, const TextureK* t, uint32_t n, void* owned)
+{
+  auto& b = ctx->textures;
+  void* const old = b.owned;
+  b.n = n;
+  b.any_srgb = false;
+  b.owned = owned;
+  for(uint32_t k = 0; k < n; ++k)
+  {
+    b.t[k] = t[k];
+    b.any_srgb = b.any_srgb || t[k].srgb != 0;
+  }
+  if(old) TRT_HIP(ctx, hipFree(old));
+  return TRT_OK;
+}
+
+extern "C" int trt_set_textures_dev(trt_ctx* ctx, const trt_texture* tex, uint32_t n)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(!tex) n = 0;
+  TextureK t[TRT_MAX_TEXTURES];
+  if(int rc = check_textures(ctx, "trt_set_textures_dev", tex, n, true, t)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  return bind_textures(ctx, t, n, nullptr);
+}
+
+// The images go into ONE device block, each at a multiple of 256 bytes; the binding changes only after every copy is done.
+extern "C" int trt_set_textures(trt_ctx* ctx, const trt_texture* tex, uint32_t n)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(!tex) n = 0;
+  TextureK t[TRT_MAX_TEXTURES];
+  if(int rc = check_textures(ctx, "trt_set_textures", tex, n, false, t)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  size_t at[TRT_MAX_TEXTURES], total = 0;
+  for(uint32_t k = 0; k < n; ++k)
+  {
+    at[k] = total;
+    total += ((size_t)t[k].W * t[k].H * 4 + 255) & ~(size_t)255;
+  }
+  void* block = nullptr;
+  if(total)
+  {
+    TRT_HIP(ctx, hipMalloc(&block, total));
+    for(uint32_t k = 0; k < n; ++k)
+    {
+      const hipError_t e = hipMemcpy((uint8_t*)block + at[k], t[k].texels, (size_t)t[k].W * t[k].H * 4, hipMemcpyHostToDevice);
+      if(e != hipSuccess)
+      {
+        (void)hipFree(block);
+        return fail(ctx, TRT_E_HIP, "trt_set_textures: copying texture %u: %s", k, hipGetErrorString(e));
+      }
+      t[k].texels = (const uint8_t*)block + at[k];
+    }
+  }
+  return bind_textures(ctx, t, n, block);
+}
+
+// What the four trt_shade_textured* calls (`who`) share behind their own checks: the scene (validated here, with textures
+// allowed, so that a refused call has touched nothing of the ctx — the toroidal tables of the camera form come after it)
+// and every material's textureId resolved against the binding as it stands NOW.  No scratch of the ctx: the descriptors
+// travel in the kernel arguments.
+static int textured_table(trt_ctx* ctx, const char* who, const trt_scene* scene, Textures& tx)
+{
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S, true)) return rc;
+  const auto& b = ctx->textures;
+  std::memset(&tx, 0, sizeof tx);
+  for(uint32_t i = 0; i < TRT_MAX_MATERIALS; ++i) tx.of_mat[i] = -1;
+  for(uint32_t i = 0; i < scene->n_materials; ++i)
+  {
+    const int32_t k = scene->materials[i].textureId;
+    if(k < -1 || (k >= 0 && (uint32_t)k >= b.n))
+      return b.n ? fail(ctx, TRT_E_SCENE, "%s: material %u has textureId=%d outside -1..%u, the textures bound with trt_set_textures*", who, i,
+                        (int)k, b.n - 1)
+                 : fail(ctx, TRT_E_SCENE, "%s: material %u has textureId=%d, but no textures are bound (trt_set_textures*)", who, i, (int)k);
+    tx.of_mat[i] = k;
+  }
+  for(uint32_t k = 0; k < b.n; ++k) tx.t[k] = b.t[k];
+  tx.n        = b.n;
+  tx.any_srgb = b.any_srgb ? 1u : 0u;
+  tx.decode   = ctx->d_srgb;
+  return TRT_OK;
+}
+
+extern "C" int trt_shade_textured_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                                      float* rgba, void* stream)
+{
+  return shade_stream_dev(ctx, "trt_shade_textured", in, samples, pc, scene, rgba, stream, launch_shade_textured,
+                          [&](ShadeTexturedArgs& a) { return textured_table(ctx, "trt_shade_textured", scene, a.tex); }, true);
+}
+
+extern "C" int trt_shade_textured(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
+                                  float* rgba_out)
+{
+  return shade_stream_host(ctx, "trt_shade_textured", in, samples, pc, rgba_out,
+                           [&](const trt_rays* rays, float* image) { return trt_shade_textured_dev(ctx, rays, samples, pc, scene, image, nullptr); });
+}
+
+extern "C" int trt_shade_textured_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                                             uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                                             float* rgba, void* stream)
+{
+  return shade_camera_dev(ctx, "trt_shade_textured_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
+                          launch_shade_textured_camera,
+                          [&](ShadeTexturedCameraArgs& a) { return textured_table(ctx, "trt_shade_textured_camera", scene, a.tex); }, true);
+}
+
+extern "C" int trt_shade_textured_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
+                                         uint32_t row_begin, uint32_t row_end, int camera, uint32_t samples, const float* offsets,
+                                         float* rgba_out)
+{
+  return shade_camera_host(ctx, "trt_shade_textured_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
+    return trt_shade_textured_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
+  });
+}
+
+static int check_hit_uv(trt_ctx* ctx, const float* px, const float* py, const float* pz, const int32_t* id, uint64_t n, const float* u,
+                        const float* v)
+{
+  if(!ctx) return TRT_E_INVALID;
+  if(n && (!px || !py || !pz || !id)) return fail(ctx, TRT_E_INVALID, "trt_hit_uv: NULL point or id stream");
+  if(!u && !v) return fail(ctx, TRT_E_INVALID, "trt_hit_uv: no output (u and v both NULL)");
+  return TRT_OK;
+}
+
+// No test is executed: no counted bracket, the stats stay (as trt_camera_rays_dev).
+extern "C" int trt_hit_uv_dev(trt_ctx* ctx, const trt_scene* scene, const float* px, const float* py, const float* pz, const int32_t* id,
+                              uint64_t n, float* u, float* v, void* stream)
+{
+  if(int rc = check_hit_uv(ctx, px, py, pz, id, n, u, v)) return rc;
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S, true)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  const HitUvArgs a = {px, py, pz, id, n, u, v};
+  TRT_HIP(ctx, launch_hit_uv(*S, a, ctx->tn, (hipStream_t)stream));
+  return TRT_OK;
+}
+
+// Host buffers: the points through buf[kBufIn] .. [kBufIn + 2], the ids through buf[kBufTmax], u and v through
+// buf[kBufOut], [kBufOut + 1].
+extern "C" int trt_hit_uv(trt_ctx* ctx, const trt_scene* scene, const float* px, const float* py, const float* pz, const int32_t* id,
+                          uint64_t n, float* u_out, float* v_out)
+{
+  if(int rc = check_hit_uv(ctx, px, py, pz, id, n, u_out, v_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(n == 0) return trt_hit_uv_dev(ctx, scene, px, py, pz, id, 0, u_out, v_out, nullptr);   // validated; nothing to launch or to write
+  const size_t bytes = (size_t)n * sizeof(float);
+  const void*  p[3] = {px, py, pz};
+  void**       streams[3] = {(void**)&p[0], (void**)&p[1], (void**)&p[2]};
+  if(int rc = stage_streams(ctx, streams, 3, bytes)) return rc;
+  const int32_t* d_id = nullptr;
+  if(int rc = stage_in(ctx, kBufTmax, id, bytes, (void**)&d_id)) return rc;
+  StagedOut outs[2] = {{u_out, bytes, kBufOut, nullptr}, {v_out, bytes, kBufOut + 1, nullptr}};
+  if(int rc = stage_outs(ctx, outs, 2)) return rc;
+  if(int rc = trt_hit_uv_dev(ctx, scene, (const float*)p[0], (const float*)p[1], (const float*)p[2], d_id, n, (float*)outs[0].dev,
+                             (float*)outs[1].dev, nullptr))
+    return rc;
+  return fetch_outs(ctx, outs, 2);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1112,4 +1112,56 @@ __device__ __forceinline__ float post_gamma(float c)
   return exp2_poly(0.454545455f * log2_poly(c));
 }
 
+// ------------------------------------------------------------------------------------------
+// the (u, v) of a point on a torus (trt_shade_textured*, trt_hit_uv*; include/trt.h states the rule)
+// ------------------------------------------------------------------------------------------
+// atan2(y, x) in (-pi, pi] with exact operations only — like log2_poly / exp2_poly it does not move with the ROCm release
+// (OCML's atan2f may).  Octant reduction to mn / mx in [0, 1], folded once more at tan(pi/8) by
+// atan(a) = pi/4 + atan((a - 1) / (a + 1)) BEFORE the division, so that there is one division and |q| <= tan(pi/8); then
+// atan(q) = q + q·s·(c1 + s·(c2 + s·(c3 + s·c4))), s = q², a least-maximum fit on that interval (|error| < 5e-9 rad before
+// rounding; with it, against FP64 atan2 over two million points: 2.6e-7 rad, 4.2e-8 of a turn — the roundings of the
+// constants of pi).  (0, 0) gives 0 / 0 = NaN: a caller on a ring torus never passes it (rho >= R - r > 0, and
+// (rho - R)² + y² = r²), and torus_uv() turns a NaN into 0.
+__device__ __forceinline__ float atan2_poly(float y, float x)
+{
+  const float ax = abs_(x), ay = abs_(y);
+  const float mx = max_(ax, ay), mn = min_(ax, ay);
+  const bool  far = mn > 0.414213568f * mx;                  // tan(pi/8)
+  const float q  = (far ? mn - mx : mn) / (far ? mn + mx : mx);
+  const float s  = q * q;
+  float p = fma_(s, 0.07902598f, -0.13824454f);
+  p = fma_(s, p, 0.19971879f);
+  p = fma_(s, p, -0.33332756f);
+  float r = fma_(p * s, q, q);
+  if(far) r += 0.785398163f;                                 // pi/4
+  if(ay > ax) r = 1.57079633f - r;                           // pi/2
+  if(x < 0.0f) r = 3.14159265f - r;                          // pi
+  return y < 0.0f ? -r : r;
+}
+// An angle in radians as a fraction of a turn in [0, 1): one multiplication by 1/(2 pi), less its floor; a value that
+// rounds up to 1 (a tiny negative angle) is 0, the same point of the circle — and so is a NaN.
+__device__ __forceinline__ float angle_to_turn(float a)
+{
+  const float t = a * 0.159154943f;
+  const float f = t - floorf(t);
+  return f < 1.0f ? f : 0.0f;
+}
+// (u, v) of point P on torus i: q = P − C in the torus' frame (the rows (u, a, w) of TorusRot; the identity for +y),
+// u the angle of (q.x, q.z) about the axis, v the angle of (rho − R, q.y) about the tube — rho exactly as torus_normal
+// forms it.  ONE function for the shading kernels and trt_hit_uv.
+template <bool ORIENT>
+__device__ __forceinline__ void torus_uv(const SceneK& S, int i, v3 P, float& u, float& v)
+{
+  const TorusShade& T = S.shade[i];
+  v3 q = sub3(P, v3{T.cx, T.cy, T.cz});
+  if(ORIENT && is_oriented(S, i))
+  {
+    const v3 pw = q;
+    rotate_to_local<float>(S.rot[i], pw.x, pw.y, pw.z, q.x, q.y, q.z);
+  }
+  const float rho = sqrt_(fma_(q.z, q.z, q.x * q.x));
+  u = angle_to_turn(atan2_poly(q.z, q.x));
+  v = angle_to_turn(atan2_poly(q.y, rho - T.R));
+}
+
 }  // namespace trt

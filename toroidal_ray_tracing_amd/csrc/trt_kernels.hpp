@@ -1,5 +1,5 @@
 // trt_kernels.hpp — launch interface between the C ABI (trt_api.hip) and the gfx950 kernels
-// (trt_rays.hip, trt_through.hip, trt_glass.hip, trt_lights.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
+// (trt_rays.hip, trt_through.hip, trt_glass.hip, trt_lights.hip, trt_textured.hip, trt_media.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip, trt_kernels.hip, trt_post.hip; the re-projection's half is
 // trt_splat.hpp).  Host-side only types; no HIP runtime types leak past this header except hipStream_t / hipError_t.
 // What the kernels' translation units share on the device side is trt_render.hpp.
 #pragma once
@@ -346,6 +346,55 @@ struct ShadeLitCameraArgs {
   unsigned long long* stats;
 };
 
+// trt_shade_textured*, trt_shade_textured_camera*: the textures bound to the ctx (trt_set_textures*) as a call resolved
+// them — one 32-byte descriptor per texture, the texture of every MATERIAL (of_mat[m] = its textureId, -1: none; checked
+// against n on the host), the ctx's sRGB decode table (256 floats in device memory) and whether any bound texture is sRGB
+// (only then do the kernels stage the table).  It travels here, in the kernel-argument segment (312 B); the kernels index
+// it by the material of the hit, which differs from lane to lane, so they stage it into LDS (stage_words) first.
+struct TextureK {
+  const uint8_t* texels;     // RGBA8, row-major, 4-byte aligned, device memory
+  uint32_t       W, H;       // 1 .. 16384
+  float          ru, rv;     // repeat_u, repeat_v
+  int32_t        srgb;       // 1: through the decode table; 0: * (1.0f / 255.0f)
+  uint32_t       reserved;
+};
+struct Textures {
+  TextureK     t[TRT_MAX_TEXTURES];
+  const float* decode;       // [256]
+  int32_t      of_mat[TRT_MAX_MATERIALS];
+  uint32_t     n;            // 0 .. TRT_MAX_TEXTURES
+  uint32_t     any_srgb;
+};
+static_assert(sizeof(TextureK) == 32 && sizeof(Textures) == 8 * 32 + 8 + 4 * TRT_MAX_MATERIALS + 8, "Textures: at most 8 x 32 bytes, the table's pointer, a word per material");
+// trt_shade_textured*: ShadeArgs with the textures.
+struct ShadeTexturedArgs {
+  trt_rays            rays;
+  uint64_t            n_out;
+  uint32_t            samples;   // >= 1, divides rays.n
+  trt_push            pc;
+  Textures            tex;
+  float*              rgba;
+  unsigned long long* stats;
+};
+// trt_shade_textured_camera*: ShadeCameraArgs with the textures.
+struct ShadeTexturedCameraArgs {
+  CameraArgs          cam;
+  trt_push            pc;
+  Textures            tex;
+  float*              rgba;
+  unsigned long long* stats;
+};
+// trt_hit_uv*: the (u, v) of n points (px, py, pz) on the tori `id` names; u and v are each optional.
+struct HitUvArgs {
+  const float*   px;
+  const float*   py;
+  const float*   pz;
+  const int32_t* id;
+  uint64_t       n;
+  float*         u;
+  float*         v;
+};
+
 // The grid of a ray-stream kernel — any kernel of 256-thread blocks whose lanes walk `n` items in a grid-stride loop, one
 // item per lane: rays, outputs of a shade kernel, pixels of a camera's band, points of a fan.  One block per 256 items, at
 // most 4096 blocks (TRT_TRACE_BLOCKS).
@@ -382,6 +431,9 @@ hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, 
 hipError_t launch_shade_refract_camera(const SceneK& scene, const ShadeRefractCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_lit(const SceneK& scene, const ShadeLitArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_lit_camera(const SceneK& scene, const ShadeLitCameraArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_textured(const SceneK& scene, const ShadeTexturedArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_textured_camera(const SceneK& scene, const ShadeTexturedCameraArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_hit_uv(const SceneK& scene, const HitUvArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only
 // — the counted and the alternative-solver instantiations go without, and do not know the heavy-from-the-end layout of

@@ -232,6 +232,25 @@ void HelloHip::raytraceLit(void* stream, const std::array<float, 4>& clearColor,
         "HelloHip::raytraceLit");
 }
 
+void HelloHip::setTextures(const trt_texture* textures, uint32_t n)
+{
+  check(trt_set_textures(m_ctx, textures, n), "HelloHip::setTextures");
+}
+
+void HelloHip::shadeTextured(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev)
+{
+  const trt_scene sc = scene();
+  check(trt_shade_textured_dev(m_ctx, &raysDev, samples, pushFor(clearColor, true), &sc, rgbaDev, stream), "HelloHip::shadeTextured");
+}
+
+void HelloHip::raytraceTextured(void* stream, const std::array<float, 4>& clearColor, uint32_t samples, const float* offsets)
+{
+  const trt_scene sc = scene();
+  check(trt_shade_textured_camera_dev(m_ctx, &m_globals, pushFor(clearColor, true), &sc, m_size.width, m_size.height, 0, m_size.height,
+                                      m_camera, samples, offsets, m_dColor, stream),
+        "HelloHip::raytraceTextured");
+}
+
 void HelloHip::chords(void* stream,const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
 {
   const trt_scene sc = scene();

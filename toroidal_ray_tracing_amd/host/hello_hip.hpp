@@ -85,6 +85,19 @@ public:
   void raytraceLit(void* stream, const std::array<float, 4>& clearColor, const trt_lights& lights, uint32_t samples = 1,
                    const float* offsets = nullptr);
 
+  // Textures on the tori (trt_set_textures, trt_shade_textured_dev, trt_shade_textured_camera_dev): the role of
+  // createTextureImages() and of `diffuse *= texture(...)` in the closest-hit shader (REFL/shaders/raytrace.rchit:101-106).
+  // setTextures: n host images (RGBA8, copied to the device; nullptr / 0 unbinds); a material added with textureId = k >= 0
+  // then takes texture k at the (u, v) of a hit — the angle about the torus' axis, the angle about its tube.  The push
+  // constants are refreshed as raytrace() refreshes them.  shadeTextured: every ray of raysDev (sample-major, `samples` per
+  // output) into rgbaDev ((raysDev.n / samples) * 4 floats, 16-byte aligned).  raytraceTextured: the frame of m_camera into
+  // the colour image raytrace() writes, `samples` rays per pixel at the sub-pixel offsets (2 floats per sample; nullptr:
+  // the pixel centres), which filter the texture as they do edges; no RenderedData is written.  raytrace() itself refuses
+  // a scene with a textured material.
+  void setTextures(const trt_texture* textures, uint32_t n);
+  void shadeTextured(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
+  void raytraceTextured(void* stream, const std::array<float, 4>& clearColor, uint32_t samples = 1, const float* offsets = nullptr);
+
   // Media inside the tubes of the tori added so far (trt_chords_dev, trt_glow_dev; materials are not read).  chords: the
   // length of every ray of raysDev inside every tube, lengthDev[j * raysDev.n + i] for torus j (the order of the
   // addTorus calls).  glow: emission and absorption of media (one trt_medium per torus, host memory) integrated along

@@ -81,6 +81,21 @@ SYMBOLS = {
     "trt_shade_lit_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
                                            C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                            abi.f32p, C.c_void_p, C.c_void_p]),
+    "trt_set_textures": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_texture), C.c_uint32]),
+    "trt_set_textures_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_texture), C.c_uint32]),
+    "trt_shade_textured": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push),
+                                     C.POINTER(abi.trt_scene), C.c_void_p]),
+    "trt_shade_textured_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push),
+                                         C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p]),
+    "trt_shade_textured_camera": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, abi.f32p, C.c_void_p]),
+    "trt_shade_textured_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, abi.f32p,
+                                                C.c_void_p, C.c_void_p]),
+    "trt_hit_uv": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                             C.c_void_p, C.c_void_p]),
+    "trt_hit_uv_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "trt_fan_rays": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,
                                C.POINTER(abi.trt_rays_out)]),
     "trt_fan_rays_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_hits), C.c_uint64, C.c_int, C.c_uint32, abi.f32p,

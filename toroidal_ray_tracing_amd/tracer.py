@@ -408,6 +408,62 @@ class Tracer:
         self._shade_camera_dev(self._L.trt_shade_lit_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows, C.byref(lt),
                                self._scene(scene), stream=stream)
 
+    # -- textures on tori: the binding, shade and shade_camera with the texel, the (u, v) of points --
+    def set_textures(self, textures):
+        """Bind host images (trt_set_textures): an iterable of ``abi.trt_texture`` (``abi.make_texture``), at most
+        abi.TRT_MAX_TEXTURES; the images are copied to the device.  None or empty: unbind.  A material's ``textureId``
+        indexes this table in the ``shade_textured*`` calls."""
+        arr, n = abi.textures_array(textures)
+        self._check(self._L.trt_set_textures(self._h, arr, n))
+
+    def set_textures_dev(self, textures):
+        """Bind device images (trt_set_textures_dev): ``abi.trt_texture`` whose ``texels`` are device addresses
+        (``abi.texture_at``), 4-byte aligned; they are borrowed — keep them alive while they are bound."""
+        arr, n = abi.textures_array(textures)
+        self._check(self._L.trt_set_textures_dev(self._h, arr, n))
+
+    def shade_textured(self, scene, o, d, pc, samples=1):
+        """``shade`` with textures (trt_shade_textured) on host arrays: at a hit whose material has textureId >= 0 the
+        bilinear texel at the hit's (u, v) — the angle about the torus' axis and the angle about its tube — scales the
+        diffuse term.  Layout and averaging as in ``shade``.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
+        return self._shade_host(self._L.trt_shade_textured, o, d, pc, samples, self._scene(scene))
+
+    def shade_textured_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0):
+        """Device pointers (ints): as ``shade_dev``.  Asynchronous on ``stream``."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_shade_textured_dev(self._h, C.byref(rays), int(samples), C.byref(pc), self._scene(scene),
+                                                   _vp(rgba_ptr), _vp(stream)))
+
+    def shade_textured_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None):
+        """``shade_camera`` with textures (trt_shade_textured_camera) on a host buffer: bit for bit ``camera_rays`` put
+        through ``shade_textured``; the samples of a pixel filter the texture as they do edges.  Returns rgba (H, W, 4);
+        rows outside ``rows`` are 0."""
+        return self._shade_camera_host(self._L.trt_shade_textured_camera, g, pc, W, H, camera, samples, offsets, rows, self._scene(scene))
+
+    def shade_textured_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None,
+                                  rows=None, stream=0):
+        """Device image: as ``shade_camera_dev``.  Asynchronous on ``stream``."""
+        self._shade_camera_dev(self._L.trt_shade_textured_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows,
+                               self._scene(scene), stream=stream)
+
+    def hit_uv(self, scene, at):
+        """The (u, v) in [0, 1) of surface points (trt_hit_uv) on host arrays: ``at`` a dict of hit arrays as ``trace`` /
+        ``render`` return them (px, py, pz, id).  u turns about the torus' axis, v about its tube; a point with id < 0 or
+        id >= n_tori gets (0, 0).  Returns (u, v), float32 (n,) each."""
+        p = [np.ascontiguousarray(at[k], np.float32).reshape(-1) for k in ("px", "py", "pz")]
+        ids = np.ascontiguousarray(at["id"], np.int32).reshape(-1)
+        n = len(ids)
+        u, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._check(self._L.trt_hit_uv(self._h, self._scene(scene), abi.ptr(p[0]), abi.ptr(p[1]), abi.ptr(p[2]), abi.ptr(ids), n,
+                                       abi.ptr(u), abi.ptr(v)))
+        return u, v
+
+    def hit_uv_dev(self, scene, at_ptrs, n, u_ptr=0, v_ptr=0, stream=0):
+        """Device pointers (ints): at_ptrs a dict with px, py, pz, id — the hit_ptrs of ``trace_dev`` / ``render_dev`` as
+        they stand; u_ptr and / or v_ptr: n float32 each.  Asynchronous on ``stream``."""
+        self._check(self._L.trt_hit_uv_dev(self._h, self._scene(scene), *[_vp(at_ptrs.get(k) or 0) for k in ("px", "py", "pz", "id")],
+                                           int(n), _vp(u_ptr), _vp(v_ptr), _vp(stream)))
+
     # -- ray fans: K rays from every surface point, as streams or as fused ambient occlusion --
     @staticmethod
     def _fan_points(at, frame):
