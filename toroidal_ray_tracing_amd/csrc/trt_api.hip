@@ -1226,7 +1226,7 @@ extern "C" int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in, uint32_t 
                                      float* rgba, void* stream)
 {
   return shade_stream_dev(ctx, "trt_shade_through", in, samples, pc, scene, rgba, stream, launch_shade_through,
-                          [&](ShadeThroughArgs& a) { return through_opacity(ctx, "trt_shade_through", scene, a.op); });
+                          [&](ShadeThroughArgs& a) { return through_opacity(ctx, "trt_shade_through", scene, a.table); });
 }
 
 extern "C" int trt_shade_through(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
@@ -1532,7 +1532,7 @@ extern "C" int trt_shade_refract_dev(trt_ctx* ctx, const trt_rays* in, uint32_t 
                                      float* rgba, void* stream)
 {
   return shade_stream_dev(ctx, "trt_shade_refract", in, samples, pc, scene, rgba, stream, launch_shade_refract,
-                          [&](ShadeRefractArgs& a) { return refract_glass(ctx, "trt_shade_refract", scene, a.glass); });
+                          [&](ShadeRefractArgs& a) { return refract_glass(ctx, "trt_shade_refract", scene, a.table); });
 }
 
 extern "C" int trt_shade_refract(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
@@ -1548,7 +1548,7 @@ extern "C" int trt_shade_refract_camera_dev(trt_ctx* ctx, const trt_globals* g, 
 {
   return shade_camera_dev(ctx, "trt_shade_refract_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
                           launch_shade_refract_camera,
-                          [&](ShadeRefractCameraArgs& a) { return refract_glass(ctx, "trt_shade_refract_camera", scene, a.glass); });
+                          [&](ShadeRefractCameraArgs& a) { return refract_glass(ctx, "trt_shade_refract_camera", scene, a.table); });
 }
 
 extern "C" int trt_shade_refract_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,
@@ -1609,7 +1609,7 @@ extern "C" int trt_shade_lit_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samp
                                  const trt_scene* scene, float* rgba, void* stream)
 {
   return shade_stream_dev(ctx, "trt_shade_lit", in, samples, pc, scene, rgba, stream, launch_shade_lit,
-                          [&](ShadeLitArgs& a) { return lit_lights(ctx, "trt_shade_lit", lights, scene, a.lights); });
+                          [&](ShadeLitArgs& a) { return lit_lights(ctx, "trt_shade_lit", lights, scene, a.table); });
 }
 
 extern "C" int trt_shade_lit(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
@@ -1625,7 +1625,7 @@ extern "C" int trt_shade_lit_camera_dev(trt_ctx* ctx, const trt_globals* g, cons
 {
   return shade_camera_dev(ctx, "trt_shade_lit_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
                           launch_shade_lit_camera,
-                          [&](ShadeLitCameraArgs& a) { return lit_lights(ctx, "trt_shade_lit_camera", lights, scene, a.lights); });
+                          [&](ShadeLitCameraArgs& a) { return lit_lights(ctx, "trt_shade_lit_camera", lights, scene, a.table); });
 }
 
 extern "C" int trt_shade_lit_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, const trt_scene* scene,
@@ -1754,7 +1754,7 @@ extern "C" int trt_shade_textured_dev(trt_ctx* ctx, const trt_rays* in, uint32_t
                                       float* rgba, void* stream)
 {
   return shade_stream_dev(ctx, "trt_shade_textured", in, samples, pc, scene, rgba, stream, launch_shade_textured,
-                          [&](ShadeTexturedArgs& a) { return textured_table(ctx, "trt_shade_textured", scene, a.tex); }, true);
+                          [&](ShadeTexturedArgs& a) { return textured_table(ctx, "trt_shade_textured", scene, a.table); }, true);
 }
 
 extern "C" int trt_shade_textured(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
@@ -1770,7 +1770,7 @@ extern "C" int trt_shade_textured_camera_dev(trt_ctx* ctx, const trt_globals* g,
 {
   return shade_camera_dev(ctx, "trt_shade_textured_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
                           launch_shade_textured_camera,
-                          [&](ShadeTexturedCameraArgs& a) { return textured_table(ctx, "trt_shade_textured_camera", scene, a.tex); }, true);
+                          [&](ShadeTexturedCameraArgs& a) { return textured_table(ctx, "trt_shade_textured_camera", scene, a.table); }, true);
 }
 
 extern "C" int trt_shade_textured_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_scene* scene, uint32_t W, uint32_t H,

@@ -130,7 +130,7 @@ struct Tuning {
   uint64_t persist_blocks     = 0;    // TRT_PERSIST_BLOCKS   (0 = default)
   uint64_t listed_blocks      = 0;    // TRT_LISTED_BLOCKS
   int      static_tile        = 8;    // TRT_TILE
-  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel, shade_kernel, shade_camera_kernel, the fan kernels)
+  uint64_t trace_blocks       = 0;    // TRT_TRACE_BLOCKS (trace_kernel, occluded_kernel, crossings_kernel, the shade kernels, the fan kernels)
   int      occluded_walk      = kOccludedWalk;   // TRT_OCCLUDED_WALK: kWalkNested (0) | kWalkTable (1), occluded_kernel only
   int      fan_form           = -1;   // TRT_FAN_FORM: kFanLane (0) | kFanBlock (1), trt_fan_occluded* only; -1 = kFanForm (below)
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
@@ -197,17 +197,31 @@ struct CrossingsArgs {
   unsigned long long*  stats;
 };
 
-// trt_shade*: the colour of every ray by the render's bounce loop, `samples` rays averaged per output.  The rays are
-// sample-major (sample s of output i is ray s * n_out + i, n_out = rays.n / samples: the samples of a stream are
+// trt_shade* and its forms: the colour of every ray by the render's bounce loop, `samples` rays averaged per output.  The
+// rays are sample-major (sample s of output i is ray s * n_out + i, n_out = rays.n / samples: the samples of a stream are
 // themselves ray streams); rgba holds n_out * 4 floats, 16-byte aligned.  pc.rho is not read.
-struct ShadeArgs {
+// `table`: what a form of the family adds to the call (Opacity, Glass, Lights, Textures: below), by value in the
+// kernel-argument segment between pc and rgba; trt_shade itself has none (<void>: no member, not an empty one).
+template <class Table>
+struct StreamShade {
   trt_rays            rays;
   uint64_t            n_out;
   uint32_t            samples;   // >= 1, divides rays.n
   trt_push            pc;        // PushConstantRay, by value in the kernel-argument segment
+  Table               table;
   float*              rgba;
   unsigned long long* stats;
 };
+template <>
+struct StreamShade<void> {
+  trt_rays            rays;
+  uint64_t            n_out;
+  uint32_t            samples;
+  trt_push            pc;
+  float*              rgba;
+  unsigned long long* stats;
+};
+using ShadeArgs = StreamShade<void>;
 
 // trt_transmittance*, trt_shade_through*: the opacity a_j = clamp(dissolve, 0, 1) of torus j's material and its pass factor
 // p_j = 1.0f - a_j, resolved on the host and indexed by TORUS id (not by material).  They travel here, in the
@@ -225,15 +239,7 @@ struct TransmittanceArgs {
   unsigned long long* stats;
 };
 // trt_shade_through*: ShadeArgs with the opacities; the kernel's dynamic LDS holds 4 * n_tori crossing slots per lane.
-struct ShadeThroughArgs {
-  trt_rays            rays;
-  uint64_t            n_out;
-  uint32_t            samples;   // >= 1, divides rays.n
-  trt_push            pc;
-  Opacity             op;
-  float*              rgba;
-  unsigned long long* stats;
-};
+using ShadeThroughArgs = StreamShade<Opacity>;
 
 // trt_chords*, trt_glow*: ray i has the window (tmin, min(tmax_per_ray[i], tmax)); tmax_per_ray == nullptr: every ray ends at tmax.
 // trt_chords*: the length of ray i inside torus j's tube at length[j * rays.n + i] (torus-major: n_tori streams).
@@ -282,13 +288,24 @@ struct CameraRaysArgs {
 };
 // Tiles of shade_camera_kernel along one side of a band of n >= 0 pixels (no wrap-around up to n = 2^32 - 1, which tile_count has).
 __host__ __device__ constexpr uint32_t camera_tiles(uint32_t n) { return n ? (n - 1) / kTile + 1 : 0; }
-// trt_shade_camera*: ShadeArgs with the rays from CameraArgs; rgba is the FULL W x H image (pixel (x, y) at y * W + x).
-struct ShadeCameraArgs {
+// trt_shade_camera* and its forms: StreamShade with the rays from CameraArgs; rgba is the FULL W x H image (pixel (x, y) at
+// y * W + x).
+template <class Table>
+struct CameraShade {
+  CameraArgs          cam;
+  trt_push            pc;
+  Table               table;
+  float*              rgba;
+  unsigned long long* stats;
+};
+template <>
+struct CameraShade<void> {
   CameraArgs          cam;
   trt_push            pc;
   float*              rgba;
   unsigned long long* stats;
 };
+using ShadeCameraArgs = CameraShade<void>;
 
 // trt_shade_refract*, trt_shade_refract_camera*: the dielectrics of the scene, indexed by TORUS id (not by material),
 // validated and resolved on the host.  Bit j of `mask`: torus j's material has illum 6 or 7; n[j] its ior, inv_n[j] =
@@ -299,24 +316,8 @@ struct Glass {
   float    n[TRT_MAX_TORI], inv_n[TRT_MAX_TORI];
   float    tf[TRT_MAX_TORI][3];
 };
-// trt_shade_refract*: ShadeArgs with the dielectrics.
-struct ShadeRefractArgs {
-  trt_rays            rays;
-  uint64_t            n_out;
-  uint32_t            samples;   // >= 1, divides rays.n
-  trt_push            pc;
-  Glass               glass;
-  float*              rgba;
-  unsigned long long* stats;
-};
-// trt_shade_refract_camera*: ShadeCameraArgs with the dielectrics.
-struct ShadeRefractCameraArgs {
-  CameraArgs          cam;
-  trt_push            pc;
-  Glass               glass;
-  float*              rgba;
-  unsigned long long* stats;
-};
+using ShadeRefractArgs       = StreamShade<Glass>;
+using ShadeRefractCameraArgs = CameraShade<Glass>;
 
 // trt_shade_lit*, trt_shade_lit_camera*: the light table and the disc table (u[s], v[s]) of the area lights, validated and
 // copied on the host.  They travel here, in the kernel-argument segment, as FanArgs' table and Glass do (808 B): the calls
@@ -327,24 +328,9 @@ struct Lights {
   uint32_t  K;   // 1 .. TRT_MAX_LIGHT_SAMPLES: shadow rays per area light per hit
   float     u[TRT_MAX_LIGHT_SAMPLES], v[TRT_MAX_LIGHT_SAMPLES];
 };
-// trt_shade_lit*: ShadeArgs with the lights (pc's own light is not read).
-struct ShadeLitArgs {
-  trt_rays            rays;
-  uint64_t            n_out;
-  uint32_t            samples;   // >= 1, divides rays.n
-  trt_push            pc;
-  Lights              lights;
-  float*              rgba;
-  unsigned long long* stats;
-};
-// trt_shade_lit_camera*: ShadeCameraArgs with the lights.
-struct ShadeLitCameraArgs {
-  CameraArgs          cam;
-  trt_push            pc;
-  Lights              lights;
-  float*              rgba;
-  unsigned long long* stats;
-};
+// (pc's own light is not read)
+using ShadeLitArgs       = StreamShade<Lights>;
+using ShadeLitCameraArgs = CameraShade<Lights>;
 
 // trt_shade_textured*, trt_shade_textured_camera*: the textures bound to the ctx (trt_set_textures*) as a call resolved
 // them — one 32-byte descriptor per texture, the texture of every MATERIAL (of_mat[m] = its textureId, -1: none; checked
@@ -366,24 +352,8 @@ struct Textures {
   uint32_t     any_srgb;
 };
 static_assert(sizeof(TextureK) == 32 && sizeof(Textures) == 8 * 32 + 8 + 4 * TRT_MAX_MATERIALS + 8, "Textures: at most 8 x 32 bytes, the table's pointer, a word per material");
-// trt_shade_textured*: ShadeArgs with the textures.
-struct ShadeTexturedArgs {
-  trt_rays            rays;
-  uint64_t            n_out;
-  uint32_t            samples;   // >= 1, divides rays.n
-  trt_push            pc;
-  Textures            tex;
-  float*              rgba;
-  unsigned long long* stats;
-};
-// trt_shade_textured_camera*: ShadeCameraArgs with the textures.
-struct ShadeTexturedCameraArgs {
-  CameraArgs          cam;
-  trt_push            pc;
-  Textures            tex;
-  float*              rgba;
-  unsigned long long* stats;
-};
+using ShadeTexturedArgs       = StreamShade<Textures>;
+using ShadeTexturedCameraArgs = CameraShade<Textures>;
 // trt_hit_uv*: the (u, v) of n points (px, py, pz) on the tori `id` names; u and v are each optional.
 struct HitUvArgs {
   const float*   px;

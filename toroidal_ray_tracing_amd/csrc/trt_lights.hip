@@ -2,13 +2,13 @@
 //
 //   lit_hit                  the colour of one hit under the light table: per light the light half of hit_begin, the shadow
 //                            stage — one any-hit ray, or K towards a disc about the light — and the colour half of hit_end
-//   lit_loop                 bounce_loop (trt_render.hpp) with lit_hit in the place of hit_begin / the shadow query / hit_end
-//   shade_lit_kernel         shade_kernel (trt_rays.hip) with lit_loop
-//   shade_lit_camera_kernel  shade_camera_kernel (trt_rays.hip) with lit_loop
-//   launch_shade_lit, launch_shade_lit_camera   their grid and launch wrappers.
+//   LitHit                   the hit step of bounce_loop (trt_render.hpp) with hit_point / lit_hit / hit_mirror in the place of
+//                            hit_begin / the shadow query / hit_end
+//   ShadeLit                 the form: shade_kernel / shade_camera_kernel (trt_render.hpp) with LitHit, nothing staged
+//   launch_shade_lit, launch_shade_lit_camera   the two shared launches with that form.
 //
 // Only the closest hit of a segment and any-hit queries are needed, so every solver and the oriented tori apply —
-// instantiated for <float | double> × ALT × ORIENT like shade_kernel.  The lights come in the kernel arguments (Lights,
+// instantiated for <float | double> × ALT × ORIENT like the plain form.  The lights come in the kernel arguments (Lights,
 // trt_kernels.hpp) and stay there: the loops over lights and samples have kernel-uniform trip counts and indices, so every
 // table read is a scalar load from the argument segment, as in fan_occluded_kernel.  SceneK and trt_push know nothing of them.
 // Compiled with -ffp-contract=off like every unit: each operation below is one FP32 rounding, in the order written.
@@ -95,104 +95,39 @@ __device__ __forceinline__ v3 lit_hit(const SceneK& S, const Lights& lt, const H
 }
 
 // ------------------------------------------------------------------------------------------
-// the payload loop of one ray under the light table
-// ------------------------------------------------------------------------------------------
-// bounce_loop() (trt_render.hpp) — the raygen loop rgen:54-87, the miss shader, the enclosure mask that starts
-// empty and grows at a hit from outside when `grow`, the mirror step (hit_mirror: stated once, there) — with the light of
-// pc replaced by the table: hit_point, lit_hit, hit_mirror where bounce_loop has hit_begin, any_hit, hit_end.
-template <class Real, bool ALT, bool ORIENT>
-__device__ __forceinline__ v3 lit_loop(const SceneK& S, const trt_push& pc, const Lights& lt, v3 origin, v3 direction, bool grow,
-                                       uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc)
-{
-  int      depth = 0, done = 1;                                            // rgen:54,57
-  uint32_t skip = 0u;
-  v3       attenuation = {1.0f, 1.0f, 1.0f};                               // rgen:56
-  v3       hitValue = {0.0f, 0.0f, 0.0f};                                  // rgen:61
-  for(;;)                                                                  // rgen:62
-  {
-    v3    prdHit, nextO = origin, nextD = direction;
-    float t;
-    const int id = closest_hit<Real, ALT, kRenderWalk, ORIENT>(S, origin, direction, kTMin, kTMax, t, depth == 0 ? n_primary : n_bounce, wc, skip);
-    if(id < 0)
-      prdHit = miss_colour(pc);                                            // rmiss:37
-    else
-    {
-      HitState h;
-      hit_point<ORIENT>(S, id, t, origin, direction, h);
-      const uint32_t inside = S.inside[id];
-      prdHit = lit_hit<Real, ALT, ORIENT>(S, lt, h, direction, skip, inside, n_shadow, wc);
-      if(grow && dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
-        skip |= inside;
-      hit_mirror(S.mat[h.matId], h, direction, attenuation, done, nextO, nextD);
-    }
-    hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
-    hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
-    hitValue.z = fma_(prdHit.z, attenuation.z, hitValue.z);
-    depth++;                                                               // rgen:78
-    if(done == 1 || depth >= pc.maxDepth)                                  // rgen:79
-      break;
-    origin    = nextO;                                                     // rgen:82
-    direction = nextD;                                                     // rgen:83
-    done      = 1;                                                         // rgen:84
-  }
-  return hitValue;
-}
-
-// ------------------------------------------------------------------------------------------
 // shade_lit(rays_in → one colour per output), shade_lit_camera(camera → the band of an image)
 // ------------------------------------------------------------------------------------------
-// shade_kernel and shade_camera_kernel (trt_rays.hip) with lit_loop: the two walks of trt_render.hpp, so the camera form's
-// image is, bit for bit, camera_rays_kernel's rays put through shade_lit_kernel.  LDS: the scene and, in the camera form,
-// the camera.
-template <class Real, bool ALT, bool ORIENT = false>
-__global__ __launch_bounds__(256) void shade_lit_kernel(const SceneK scene, const ShadeLitArgs a)
-{
-  __shared__ SceneK S;
-  stage_scene<ORIENT>(&S, scene);
+// The hit step under the light table: the light of pc replaced by the table — hit_point, lit_hit, hit_mirror where
+// PcLightHit (trt_render.hpp) has hit_begin, any_hit, hit_end; the mirror step is stated once, there.
+template <class Real, bool ALT, bool ORIENT>
+struct LitHit : PcLightHit<Real, ALT, ORIENT> {
+  const Lights& lt;
+  __device__ __forceinline__ explicit LitHit(const Lights& lights) : lt(lights) {}
+  __device__ __forceinline__ void begin(const SceneK& S, const trt_push&, int id, float t, v3 o, v3 d, HitState& h) const
+  {
+    hit_point<ORIENT>(S, id, t, o, d, h);
+  }
+  __device__ __forceinline__ v3 light(const SceneK& S, const HitState& h, v3 d, uint32_t skip, uint32_t inside, uint32_t& n_shadow, WorkCount& wc) const
+  {
+    return lit_hit<Real, ALT, ORIENT>(S, lt, h, d, skip, inside, n_shadow, wc);
+  }
+  __device__ __forceinline__ v3 end(const SceneK& S, const HitState& h, v3 d, v3 prd, v3& attenuation, int& done, v3& nextO, v3& nextD) const
+  {
+    hit_mirror(S.mat[h.matId], h, d, attenuation, done, nextO, nextD);
+    return prd;
+  }
+};
 
-  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
-    return lit_loop<Real, ALT, ORIENT>(S, a.pc, a.lights, o, d, dot3(d, d) <= kCullUnitDD, n_primary, n_bounce, n_shadow, wc);
-  });
-}
+// The form: nothing staged — the table stays in the argument segment (above) — and LitHit on it.
+struct ShadeLit {
+  using Table  = Lights;
+  using Staged = NotStaged;
+  template <class Args> static __device__ __forceinline__ void stage(Staged*, const Args&) {}
+  template <class Real, bool ALT, bool ORIENT, class Args>
+  static __device__ __forceinline__ LitHit<Real, ALT, ORIENT> hit(const Args& a, const Staged&) { return LitHit<Real, ALT, ORIENT>{a.table}; }
+};
 
-template <class Real, bool ALT, bool ORIENT = false>
-__global__ __launch_bounds__(256) void shade_lit_camera_kernel(const SceneK scene, const ShadeLitCameraArgs a)
-{
-  __shared__ SceneK     S;
-  __shared__ CameraArgs cam;
-  stage_words(&cam, a.cam);
-  stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
-
-  shade_camera_walk(cam, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
-    return lit_loop<Real, ALT, ORIENT>(S, a.pc, a.lights, o, d, dot3(d, d) <= kCullUnitDD, n_primary, n_bounce, n_shadow, wc);
-  });
-}
-
-// ------------------------------------------------------------------------------------------
-// launch wrappers
-// ------------------------------------------------------------------------------------------
-// One lane per output (a.n_out = a.rays.n / a.samples); every solver, like launch_shade.
-hipError_t launch_shade_lit(const SceneK& scene, const ShadeLitArgs& a, const Tuning& tn, hipStream_t stream)
-{
-  if(a.n_out == 0)
-    return hipSuccess;
-  const uint32_t grid = stream_grid(a.n_out, tn);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    hipLaunchKernelGGL((shade_lit_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
-    return hipGetLastError();
-  });
-}
-
-// One wave per 8×8 tile of the band, four to a block; every solver, like launch_shade_camera.
-hipError_t launch_shade_lit_camera(const SceneK& scene, const ShadeLitCameraArgs& a, const Tuning& tn, hipStream_t stream)
-{
-  if(a.cam.n_px == 0)
-    return hipSuccess;
-  const uint32_t grid = camera_grid(a.cam, tn);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    hipLaunchKernelGGL((shade_lit_camera_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
-    return hipGetLastError();
-  });
-}
+hipError_t launch_shade_lit(const SceneK& scene, const ShadeLitArgs& a, const Tuning& tn, hipStream_t stream) { return launch_stream_form<ShadeLit>(scene, a, tn, stream); }
+hipError_t launch_shade_lit_camera(const SceneK& scene, const ShadeLitCameraArgs& a, const Tuning& tn, hipStream_t stream) { return launch_camera_form<ShadeLit>(scene, a, tn, stream); }
 
 }  // namespace trt

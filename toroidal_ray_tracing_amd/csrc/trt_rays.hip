@@ -4,11 +4,12 @@
 //   trace_kernel       trace(rays_in → hits_out): SoA rays in, closest hit out.
 //   occluded_kernel    occluded(rays_in → bits_out): SoA rays in, any hit out as a bit mask and / or flag bytes.
 //   crossings_kernel   crossings(rays_in → slots_out): SoA rays in, every surface crossing out, in order, slot-major.
-//   shade_kernel       shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour out, samples averaged (shade_stream_walk, trt_render.hpp).
+//   ShadePlain         shade(rays_in → colours_out): SoA rays in, bounce_loop()'s colour out, samples averaged — the plain form
+//                      of the shade family, whose two kernels (shade_kernel, shade_camera_kernel) are in trt_render.hpp.
 //   camera_rays_kernel   camera(frame → rays_out): the two cameras' rays with sub-pixel offsets, SoA and sample-major, out.
-//   shade_camera_kernel  shade_kernel with the rays made in registers by the camera: the supersampled frame (shade_camera_walk).
 //   launch_trace, launch_occluded, launch_crossings, launch_shade, launch_camera_rays, launch_shade_camera
-//                        their grid and launch wrappers.
+//                        their grid and launch wrappers; launch_shade and launch_shade_camera (the supersampled frame:
+//                        shade_kernel with the rays made in registers by the camera) are the two shared launches with ShadePlain.
 //   zero_words_kernel, launch_zero_words         zeroes the query counters of a counted launch.
 //
 // One lane = one ray; the scene is staged into LDS once per block.  Compiled with -ffp-contract=off (see trt_device.hpp
@@ -159,17 +160,15 @@ __global__ __launch_bounds__(256) void crossings_kernel(const SceneK scene, cons
 // ------------------------------------------------------------------------------------------
 // shade(rays_in → one colour per output): the payload loop on caller-supplied rays
 // ------------------------------------------------------------------------------------------
-// shade_stream_walk (trt_render.hpp: the walk and the colour of a caller's ray are described there) around the render's loop.
-template <class Real, bool ALT, bool ORIENT = false>
-__global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const ShadeArgs a)
-{
-  __shared__ SceneK S;
-  stage_scene<ORIENT>(&S, scene);
-
-  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
-    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc);
-  });
-}
+// The plain form of the shade family (trt_render.hpp has the two kernels, the walks and the colour of a caller's ray):
+// no table, nothing staged, the render's own hit step.
+struct ShadePlain {
+  using Table  = void;
+  using Staged = NotStaged;
+  template <class Args> static __device__ __forceinline__ void stage(Staged*, const Args&) {}
+  template <class Real, bool ALT, bool ORIENT, class Args>
+  static __device__ __forceinline__ PcLightHit<Real, ALT, ORIENT> hit(const Args&, const Staged&) { return {}; }
+};
 
 // ------------------------------------------------------------------------------------------
 // camera rays: the cameras of the render as ray streams, and shade_kernel fed by them
@@ -219,21 +218,6 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const CameraRaysArgs a
     if(dy) dy[r] = d.y;
     if(dz) dz[r] = d.z;
   }
-}
-
-// shade_camera_walk (trt_render.hpp) around the render's loop: the image is, bit for bit, camera_rays_kernel's rays put
-// through shade_kernel.  LDS: the scene and the camera.
-template <class Real, bool ALT, bool ORIENT = false>
-__global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, const ShadeCameraArgs a)
-{
-  __shared__ SceneK     S;
-  __shared__ CameraArgs cam;
-  stage_words(&cam, a.cam);
-  stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
-
-  shade_camera_walk(cam, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
-    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc);
-  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -290,17 +274,9 @@ hipError_t launch_crossings(const SceneK& scene, const CrossingsArgs& a, const T
   });
 }
 
-// One lane per output (a.n_out = a.rays.n / a.samples); every solver, like launch_trace.
-hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream)
-{
-  if(a.n_out == 0)
-    return hipSuccess;
-  const uint32_t grid = stream_grid(a.n_out, tn);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    hipLaunchKernelGGL((shade_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
-    return hipGetLastError();
-  });
-}
+// The plain form of the two shade launches (trt_render.hpp).
+hipError_t launch_shade(const SceneK& scene, const ShadeArgs& a, const Tuning& tn, hipStream_t stream) { return launch_stream_form<ShadePlain>(scene, a, tn, stream); }
+hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream) { return launch_camera_form<ShadePlain>(scene, a, tn, stream); }
 
 // One block per 256 pixels of the band (at most 4096: grid-stride) times one grid row per sample; no scene, no solver.
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream)
@@ -310,18 +286,6 @@ hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStre
   const uint32_t grid = stream_grid(a.cam.n_px, tn);
   hipLaunchKernelGGL(camera_rays_kernel, dim3(grid, a.cam.samples), dim3(256), 0, stream, a);
   return hipGetLastError();
-}
-
-// One wave per 8×8 tile of the band, four to a block; every solver, like launch_shade.
-hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream)
-{
-  if(a.cam.n_px == 0)
-    return hipSuccess;
-  const uint32_t grid = camera_grid(a.cam, tn);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    hipLaunchKernelGGL((shade_camera_kernel<decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
-    return hipGetLastError();
-  });
 }
 
 // Zeroes up to 64 words (the query counters of a counted launch) with a one-wave kernel: a kernel

@@ -3,15 +3,18 @@
 //
 //   gptr, st1 / st4 / st4c, ld1           global-memory accessors
 //   HitState, hit_begin, hit_end          the closest-hit shader body, split at the shadow query
-//   hit_point, hit_mirror                 its two halves that know no light: the geometry of the hit, the mirror step
+//   hit_point, hit_mirror                 its two halves that know no light: the geometry of the hit, the mirror step (LitHit,
+//                                         trt_lights.hip, has the table's lights between them)
 //   FanBasis, fan_basis                   Duff et al.'s basis about a unit vector (the fans about N, the area lights about L)
 //   image_row, out_index, rendered_record pixel addressing
 //   miss_id, miss_colour, miss_rgba, store_first_hit, store_first_miss   the first-hit record and the miss record
 //   block_add_stats                       the query counters of a block → the global totals
 //   settle_loads, stage_args, stage_block256, stage_words   staging into LDS
 //   kTMin, kTMax                          the ray window of the render kernels
-//   bounce_loop, NoGlass                  the payload loop of one ray, for a pixel (trace_pixel) and a caller's ray (the shade
-//                                         kernels; with a dielectric asked at every hit: the shade_refract kernels)
+//   bounce_loop, PcLightHit               the payload loop of one ray — the only copy of rgen:54-87 but through_loop
+//                                         (trt_through.hip) — for a pixel (trace_pixel) and a caller's ray (every form of the
+//                                         shade kernels), and its hit step: the render's, which a form derives from
+//   shade_ray                             bounce_loop on a caller's ray
 //   camera_sample                         the camera of the fused kernels: a sample's tables
 //   shade_stream_walk, shade_camera_walk  the two walks of the shade kernels: the samples of an output of a ray stream, the
 //                                         samples of a pixel of a camera's band — each around the one loop that colours a ray
@@ -19,6 +22,9 @@
 //   live_slot, list_counts, TileCode, tile_x / tile_y, frame_args, LaunchArgs   the tile-list layout
 //   clear_macro                           the constant fill of one CLEAR macro tile
 //   with_orient, with_solver              launch dispatch: scene → <Real, ALT, ORIENT>
+//   shade_kernel, shade_camera_kernel, NotStaged, launch_stream_form, launch_camera_form
+//                                         the two kernels of the shade family over <Form, Real, ALT, ORIENT> and their launches;
+//                                         what a form is (ShadePlain, ShadeRefract, ShadeLit, ShadeTextured: one per unit)
 //
 // Everything here is __forceinline__ (or a host template): no device function is called across translation units.
 #pragma once
@@ -68,7 +74,7 @@ struct HitState {
   bool  wantShadow;  // dot(N,L) > 0  (rchit:112)
 };
 
-// The geometry half of hit_begin: the material, P and N of the hit — what does not depend on the light (lit_loop,
+// The geometry half of hit_begin: the material, P and N of the hit — what does not depend on the light (LitHit,
 // trt_lights.hip, forms the light half once per light of its table).
 template <bool ORIENT = false>
 __device__ __forceinline__ void hit_point(const SceneK& S, int id, float t, v3 o, v3 d, HitState& h)
@@ -99,7 +105,7 @@ __device__ __forceinline__ void hit_begin(const SceneK& S, const trt_push& pc, i
   h.wantShadow = dot3(h.N, h.L) > 0.0f;                                      // rchit:112
 }
 
-// The mirror step of the closest-hit shader (rchit:145-153), stated once for hit_end and lit_loop (trt_lights.hip): an
+// The mirror step of the closest-hit shader (rchit:145-153), stated once for hit_end and LitHit (trt_lights.hip): an
 // illum == 3 material scales the payload's attenuation by Ks and sets the next segment.
 __device__ __forceinline__ void hit_mirror(const MaterialK& mat, const HitState& h, v3 d, v3& attenuation, int& done, v3& nextO, v3& nextD)
 {
@@ -282,7 +288,7 @@ __device__ __forceinline__ void stage_block256(SceneK* S, RenderArgs* A, const S
   __syncthreads();
 }
 
-// A small table of the kernel arguments (CameraArgs, Opacity, Glass) into LDS, one dword per thread of a 256-thread block.
+// A small table of the kernel arguments (CameraArgs, Opacity, Glass, Textures) into LDS, one dword per thread of a 256-thread block.
 // No barrier: the caller's stage_scene, which follows, has one and publishes both.  (Once three copies: stage_camera, the
 // name trt_fan.hip's note on its own table still uses, stage_glass and shade_through_kernel's lines.)
 template <class T>
@@ -317,8 +323,10 @@ constexpr float kTMax = 10000.0f;  // rgen:52
 // ------------------------------------------------------------------------------------------
 // The raygen payload loop (REFL/shaders/raytrace.rgen:54-87) with the closest-hit, miss and shadow-miss shaders inlined;
 // returns hitValue.  Stated once, so that trt_shade gives a ray bit for bit the colour trt_render* gives the pixel whose
-// primary ray it is.  What the caller owns of the FIRST ray's record goes through the two callables: first_miss(t) on a
-// miss at depth 0 (t = +inf: what closest_hit leaves without a hit), first_hit(t, h, id) right after hit_begin at depth 0.
+// primary ray it is — and once for every form of the shade family (the light table of trt_shade_lit*, the textures of
+// trt_shade_textured*, the glass of trt_shade_refract*), which contribute their hit step (below) and nothing else of the
+// loop.  What the caller owns of the FIRST ray's record goes through the two callables: first_miss(t) on a
+// miss at depth 0 (t = +inf: what closest_hit leaves without a hit), first_hit(t, h, id) right after hit.begin() at depth 0.
 // `skip` is the enclosure cull (trt_device.hpp closest_hit): the tori this path's rays cannot hit first — tubes strictly
 // inside a tube the ray origin is outside of by more than the tMin·|d| within which a crossing is dropped.  The caller
 // passes what is certified of the origin (the camera's share, per frame on the host; nothing for a caller's ray); a hit
@@ -328,18 +336,51 @@ constexpr float kTMax = 10000.0f;  // rgen:52
 // close enough to enter it unseen — and `grow` says that the path's directions are no longer than that: the render's
 // cameras always; a caller's ray when |d|² <= kCullUnitDD (reflect keeps the length).
 constexpr float kCullUnitDD = 1.001953125f;   // 1 + 2^-9: |d| <= 1 + 2^-10, the length the host's margin allows for
-// `glass` (trt_shade_refract*, trt_glass.hip): asked after hit_end() and before the fma of rgen:76 — where the mirror has
-// just chosen its successor — whether the torus hit is a dielectric; it then sets the refracted successor ray, filters the
-// attenuation and clears `done`.  From the first glass hit on the path runs without the enclosure mask: the mask was
-// collected OUTSIDE the tubes it names, and the refracted segment starts inside one.  With NoGlass, the
-// default, nothing of this is instantiated: the loop of every other kernel is the code it was.
-struct NoGlass {};
-template <class Real, bool ALT, bool ORIENT, class FirstMiss, class FirstHit, class GlassT = NoGlass>
+
+// What happens AT a hit is the loop's `hit` step, one small object with five members, called at five fixed places so that
+// the order of operations inside a hit is the same text for every form:
+//   begin(S, pc, id, t, o, d, h)   the HitState of the hit: hit_begin (the light of pc), or hit_point alone (a light table)
+//   tint(S, id, h)                 between the first-hit record and the shadow stage; nothing by default (textures: the
+//                                  texel into h.diffuse, trt_textured.hip)
+//   light(S, h, d, skip, inside, n_shadow, wc)   the shadow stage: the opaque any-hit ray of rchit:114-131 → shadowed, or the
+//                                  light table's rays → the hit's colour (trt_lights.hip)
+//   end(S, h, d, lit, attenuation, done, nextO, nextD)   what light() gave → prd.hitValue, and the mirror's successor
+//   glass(id, h, d, attenuation, done, nextO, nextD)     asked after end() and before the fma of rgen:76 — where the mirror
+//                                  has just chosen its successor — whether the torus hit is a dielectric; false by default
+//                                  (trt_shade_refract*, trt_glass.hip: it then sets the refracted successor ray, filters
+//                                  the attenuation and clears `done`)
+// The enclosure mask grows between light() and end().  From the first glass hit on the path runs without the mask: it was
+// collected OUTSIDE the tubes it names, and the refracted segment starts inside one.
+// PcLightHit is the render's hit step and the default: with it nothing of tint() or glass() is left in the loop, which is
+// then the code it was for every render kernel (tools/isa_diff.py: all of trt_kernels.hip compares `same`).  A form derives
+// from it and replaces what it must.
+template <class Real, bool ALT, bool ORIENT>
+struct PcLightHit {
+  __device__ __forceinline__ void begin(const SceneK& S, const trt_push& pc, int id, float t, v3 o, v3 d, HitState& h) const
+  {
+    hit_begin<ORIENT>(S, pc, id, t, o, d, h);
+  }
+  __device__ __forceinline__ void tint(const SceneK&, int, HitState&) const {}
+  __device__ __forceinline__ bool light(const SceneK& S, const HitState& h, v3, uint32_t skip, uint32_t inside, uint32_t& n_shadow, WorkCount& wc) const
+  {
+    bool shadowed = false;
+    if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
+      shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
+    return shadowed;
+  }
+  __device__ __forceinline__ v3 end(const SceneK& S, const HitState& h, v3 d, bool shadowed, v3& attenuation, int& done, v3& nextO, v3& nextD) const
+  {
+    return hit_end(S, h, d, shadowed, attenuation, done, nextO, nextD);
+  }
+  __device__ __forceinline__ bool glass(int, const HitState&, v3, v3&, int&, v3&, v3&) const { return false; }
+};
+
+template <class Real, bool ALT, bool ORIENT, class FirstMiss, class FirstHit, class Hit = PcLightHit<Real, ALT, ORIENT>>
 __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v3 origin, v3 direction,
                                           uint32_t skip, bool grow, v3 attenuation,        // rgen:56
                                           FirstMiss&& first_miss, FirstHit&& first_hit,
                                           uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc,
-                                          GlassT glass = GlassT{})
+                                          Hit hit = Hit{})
 {
   int depth = 0, done = 1;                                                 // rgen:54,57
   v3  hitValue = {0.0f, 0.0f, 0.0f};                                       // rgen:61
@@ -357,22 +398,20 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
     else
     {
       HitState h;
-      hit_begin<ORIENT>(S, pc, id, t, origin, direction, h);
+      hit.begin(S, pc, id, t, origin, direction, h);
       if(depth == 0)                                                       // BEF rgen:94-97
         first_hit(t, h, id);
-      bool shadowed = false;
+      hit.tint(S, id, h);
       const uint32_t inside = S.inside[id];
-      if(h.wantShadow)   // (N·L > 0: the shadow ray leaves the surface outwards)
-        shadowed = any_hit<Real, ALT, ORIENT>(S, h.P, h.L, kTMin, h.lightDistance, n_shadow, wc, skip | inside);  // rchit:114-131
+      const auto lit = hit.light(S, h, direction, skip, inside, n_shadow, wc);
       if(grow && dot3(h.N, direction) < 0.0f)   // hit from outside: reflect(D, N) leaves outwards
         skip |= inside;
-      prdHit = hit_end(S, h, direction, shadowed, attenuation, done, nextO, nextD);
-      if constexpr(!std::is_same<GlassT, NoGlass>::value)
-        if(glass.hit(id, h, direction, attenuation, done, nextO, nextD))
-        {
-          skip = 0u;
-          grow = false;
-        }
+      prdHit = hit.end(S, h, direction, lit, attenuation, done, nextO, nextD);
+      if(hit.glass(id, h, direction, attenuation, done, nextO, nextD))
+      {
+        skip = 0u;
+        grow = false;
+      }
     }
     hitValue.x = fma_(prdHit.x, attenuation.x, hitValue.x);                // rgen:76
     hitValue.y = fma_(prdHit.y, attenuation.y, hitValue.y);
@@ -388,16 +427,22 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
 }
 
 // ------------------------------------------------------------------------------------------
-// the two walks of the shade kernels: a ray stream's outputs, a camera's pixels
+// a caller's ray, and the two walks of the shade kernels: a ray stream's outputs, a camera's pixels
 // ------------------------------------------------------------------------------------------
-// A shade kernel (trt_shade*, trt_shade_camera* and their _through, _refract and _lit forms) is its LDS staging and one of
-// these two walks around `loop`, the one expression in which the kernels differ: loop(o, d, n_primary, n_bounce, n_shadow,
-// wc) colours one ray — bounce_loop() plain or with a GlassPath, through_loop(), lit_loop() — and counts its tests.
-//
 // The colour of one ray is the render's loop — bounce_loop(), what trace_pixel runs for a pixel — on a caller's ray: the
 // enclosure mask starts empty (nobody has certified anything about a caller's origins) and grows only along a path of at
 // most unit-length directions (kCullUnitDD), the attenuation starts at 1, and nothing but the colour leaves (no first-hit
-// record, no RenderedData: shade_ray() passes two empty callables).
+// record, no RenderedData: shade_ray() passes two empty callables).  `hit`: the form's hit step.
+template <class Real, bool ALT, bool ORIENT, class Hit = PcLightHit<Real, ALT, ORIENT>>
+__device__ __forceinline__ v3 shade_ray(const SceneK& S, const trt_push& pc, v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce,
+                                        uint32_t& n_shadow, WorkCount& wc, Hit hit = Hit{})
+{
+  return bounce_loop<Real, ALT, ORIENT>(S, pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
+                                        n_primary, n_bounce, n_shadow, wc, hit);
+}
+
+// A walk takes `loop`, the one expression that colours a ray: loop(o, d, n_primary, n_bounce, n_shadow, wc) — shade_ray()
+// with a form's hit step (shade_kernel, shade_camera_kernel: below), or through_loop() (trt_through.hip) — and counts its tests.
 //
 // shade_stream_walk: one lane owns one OUTPUT and walks its samples in order (sample s of output i is ray s·n_out + i, so
 // the six loads of a sample are coalesced like trace_kernel's): acc = c_0, then acc += c_s as plain FP32 adds, then one
@@ -405,14 +450,7 @@ __device__ __forceinline__ v3 bounce_loop(const SceneK& S, const trt_push& pc, v
 // untouched.  No atomics, nothing depends on the order of waves.  One dwordx4 store per output: a wave writes 1 KiB
 // contiguous.  No wave-level compaction of finished paths: see DESIGN.md §5 (assumed from the render's measurement, not
 // measured here).
-template <class Real, bool ALT, bool ORIENT, class GlassT = NoGlass>
-__device__ __forceinline__ v3 shade_ray(const SceneK& S, const trt_push& pc, v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce,
-                                        uint32_t& n_shadow, WorkCount& wc, GlassT glass = GlassT{})
-{
-  return bounce_loop<Real, ALT, ORIENT>(S, pc, o, d, 0u, dot3(d, d) <= kCullUnitDD, {1.0f, 1.0f, 1.0f}, [](float) {}, [](float, const HitState&, int) {},
-                                        n_primary, n_bounce, n_shadow, wc, glass);
-}
-
+//
 // The accumulation of both walks, as stated above: the colours c_s = sample(s), s = 0 .. samples - 1, in order → the pixel.
 template <class Sample>
 __device__ __forceinline__ float4 average_samples(uint32_t samples, Sample&& sample)
@@ -672,6 +710,77 @@ hipError_t with_solver(const SceneK& scene, F&& f)
     if(scene.f64) return f(double{}, Alt<false>{}, ori);
     if(alt) return f(float{}, Alt<true>{}, ori);
     return f(float{}, Alt<false>{}, ori);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// the shade kernels: one for ray streams, one for cameras, over the forms of the family
+// ------------------------------------------------------------------------------------------
+// A form (ShadePlain in trt_rays.hip, ShadeRefract in trt_glass.hip, ShadeLit in trt_lights.hip, ShadeTextured in
+// trt_textured.hip) is one small type next to its hit step, in the unit that instantiates it:
+//   Table                          what travels with the arguments (StreamShade<Table> / CameraShade<Table>, trt_kernels.hpp)
+//   Staged, stage(&staged, a)      what of it the block copies into LDS, and how — a table indexed per lane (by the torus
+//                                  or the material of a hit); NotStaged and nothing for a table every lane reads at
+//                                  kernel-uniform indices, which stays in the argument segment for scalar loads.  No
+//                                  barrier: stage_scene, which follows, has one and publishes everything
+//   hit<Real, ALT, ORIENT>(a, staged)   its hit step (PcLightHit or what derives from it): shade_ray() with it colours a ray
+// so a kernel is its staging and one of the two walks, and the camera form's image is, bit for bit, camera_rays_kernel's
+// rays put through the stream kernel of the same form.  LDS: the scene, the form's Staged and, in the camera kernel, the
+// camera.  Every solver and the oriented tori apply: only the closest hit of a segment and any-hit queries are asked.
+struct NotStaged {};
+
+template <class Form, class Real, bool ALT, bool ORIENT = false>
+__global__ __launch_bounds__(256) void shade_kernel(const SceneK scene, const StreamShade<typename Form::Table> a)
+{
+  __shared__ SceneK                S;
+  __shared__ typename Form::Staged T;
+  Form::stage(&T, a);
+  stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
+
+  shade_stream_walk(a.rays, a.n_out, a.samples, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc, Form::template hit<Real, ALT, ORIENT>(a, T));
+  });
+}
+
+template <class Form, class Real, bool ALT, bool ORIENT = false>
+__global__ __launch_bounds__(256) void shade_camera_kernel(const SceneK scene, const CameraShade<typename Form::Table> a)
+{
+  __shared__ SceneK                S;
+  __shared__ CameraArgs            cam;
+  __shared__ typename Form::Staged T;
+  stage_words(&cam, a.cam);
+  Form::stage(&T, a);
+  stage_scene<ORIENT>(&S, scene);   // (its barrier publishes all three)
+
+  shade_camera_walk(cam, a.rgba, a.stats, [&](v3 o, v3 d, uint32_t& n_primary, uint32_t& n_bounce, uint32_t& n_shadow, WorkCount& wc) {
+    return shade_ray<Real, ALT, ORIENT>(S, a.pc, o, d, n_primary, n_bounce, n_shadow, wc, Form::template hit<Real, ALT, ORIENT>(a, T));
+  });
+}
+
+// Their launches (stream_grid and camera_grid: trt_kernels.hpp); the launch_shade* functions the host takes by pointer are
+// one line around these, each in its form's unit, so that a unit instantiates only its own kernels.
+// One lane per output (a.n_out = a.rays.n / a.samples); every solver, like launch_trace.
+template <class Form>
+hipError_t launch_stream_form(const SceneK& scene, const StreamShade<typename Form::Table>& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.n_out == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.n_out, tn);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    hipLaunchKernelGGL((shade_kernel<Form, decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+    return hipGetLastError();
+  });
+}
+// One wave per 8×8 tile of the band, four to a block; every solver.
+template <class Form>
+hipError_t launch_camera_form(const SceneK& scene, const CameraShade<typename Form::Table>& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.cam.n_px == 0)
+    return hipSuccess;
+  const uint32_t grid = camera_grid(a.cam, tn);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    hipLaunchKernelGGL((shade_camera_kernel<Form, decltype(real), decltype(alt)::value, decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+    return hipGetLastError();
   });
 }
 

@@ -3,7 +3,10 @@
 //   transmittance        the soft shadow query of one ray: the product of the pass factors of every wall it crosses
 //   transmittance_kernel transmittance(rays_in → T_out): SoA rays in, one float per ray out.
 //   through_loop         the payload loop of one ray with front-to-back "over" compositing of its crossings
-//   shade_through_kernel shade_through(rays_in → colours_out): shade_kernel with through_loop in place of bounce_loop.
+//   shade_through_kernel shade_through(rays_in → colours_out): shade_stream_walk around through_loop.  A kernel of its own and
+//                        not a form of shade_kernel (trt_render.hpp): it has no camera kernel, sizes its dynamic LDS by the
+//                        scene and runs with the default solver only — three things a form would have to say for it alone,
+//                        and the shared kernel and launch to ask.  It shares the argument template (StreamShade<Opacity>).
 //   launch_transmittance, launch_shade_through   their grid and launch wrappers.
 //
 // The crossings of a segment are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
@@ -167,7 +170,7 @@ __device__ __forceinline__ v3 through_loop(const SceneK& S, const trt_push& pc, 
   return acc;
 }
 
-// shade_kernel (trt_rays.hip) with through_loop: shade_stream_walk (trt_render.hpp).  LDS: the scene, 16 opacity words, and
+// shade_stream_walk (trt_render.hpp) around through_loop.  LDS: the scene, 16 opacity words, and
 // the block's columns (K · kCrossingSlotBytes).
 template <class Real, bool ORIENT = false>
 __global__ __launch_bounds__(256) void shade_through_kernel(const SceneK scene, const ShadeThroughArgs a)
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(256) void shade_through_kernel(const SceneK scene, 
   __shared__ SceneK  S;
   __shared__ Opacity O;
   extern __shared__ float crossing_lds[];   // [K][256] t, then [K][256] bytes
-  stage_words(&O, a.op);
+  stage_words(&O, a.table);
   stage_scene<ORIENT>(&S, scene);   // (its barrier publishes both)
 
   const uint32_t K  = 4u * (uint32_t)S.n_tori;
