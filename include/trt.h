@@ -426,7 +426,8 @@ int trt_shade_through_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples
  * pixels = samples x the pixels of the band.
  *
  * Not here: a Fresnel split or a reflected branch (a path has one successor); light through glass in the shadow query —
- * glass casts an opaque shadow — and caustics; Beer-Lambert absorption along the inside chord; nested or overlapping
+ * glass casts an opaque shadow here; trt_shade_scene* with TRT_SCENE_GLASS_SHADOWS filters it — and caustics; a light
+ * table or textures beside the glass (trt_shade_scene*); Beer-Lambert absorption along the inside chord; nested or overlapping
  * dielectrics with a medium stack; glass inside trt_render*.
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_shade_refract(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_scene* scene,
@@ -501,7 +502,8 @@ int trt_shade_refract_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_p
  * infinite or negative; a position, intensity or colour that is NaN or infinite; shadow_samples outside
  * 1..TRT_MAX_LIGHT_SAMPLES; a NULL disc while some light has radius > 0; a disc entry that is NaN or infinite; and
  * everything trt_shade / trt_shade_camera refuse.  A refused call leaves the ctx usable and the outputs unwritten.
- * Not here: lights inside trt_render*, or in the translucent and glass families; textured or spot lights; importance
+ * Not here: lights inside trt_render* or in the translucent family; the table beside glass or textures (trt_shade_scene*
+ * takes all three); textured or spot lights; importance
  * sampling; a rotation of the disc table per pixel (every hit uses the same K positions: the penumbra is banded, not noisy).
  * Host buffers: copy in, launch, copy out, synchronise. */
 #define TRT_MAX_LIGHTS        8
@@ -603,7 +605,8 @@ int trt_shade_lit_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push*
  * applied: a per-wall quantity (heat flux, a tile pattern) is looked up by the caller.  id < 0 (a miss) or id >= n_tori
  * gives u = v = 0; u_out or v_out may be NULL, not both; n == 0 launches nothing.  The scene's materials are validated
  * but not read, and a textureId >= 0 is accepted.
- * Not here: textures inside trt_render*, or in the translucent, glass and light-table families; mip levels and anisotropy
+ * Not here: textures inside trt_render* or in the translucent family; textures beside glass or a light table
+ * (trt_shade_scene* takes all three); mip levels and anisotropy
  * (none are built: supersample); nearest filtering; alpha; textures on anything but `diffuse` (specular, normal or
  * emission maps); a repeat per torus rather than per texture.
  * Host buffers: copy in, launch, copy out, synchronise. */
@@ -636,6 +639,92 @@ int trt_shade_textured_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_
                                   const float* offsets, float* rgba_dev, void* stream);
 int trt_hit_uv_dev(trt_ctx* ctx, const trt_scene* scene, const float* px_dev, const float* py_dev, const float* pz_dev,
                    const int32_t* id_dev, uint64_t n, float* u_dev, float* v_dev, void* stream);
+
+/* ---- lights, textures and glass in one call: shade_scene(rays_in -> colours), shade_scene_camera(camera -> the band) ---- */
+/* The three sections above each add one thing to trt_shade and refuse the others.  These four calls take all three: the
+ * light table of trt_shade_lit (or the one light of pc), the textures bound with trt_set_textures*, and the glass of
+ * trt_shade_refract — the picture of a textured ring under a soft key light and a coloured fill light, seen through a glass
+ * ring.  With TRT_SCENE_GLASS_SHADOWS they also let light through glass in the shadow query, filtered by transmittance[3].
+ * Everything that is not named here is trt_shade's (trt_shade_scene*) or trt_shade_camera's (trt_shade_scene_camera*):
+ * rays, the `samples` layout, the averaging rule, the alignment of the image, the window (0.001, 10000) on every segment,
+ * pc->maxDepth (the body runs once even for maxDepth <= 0), clearColor * 0.8 on a miss, the mirror of illum == 3, every
+ * TRT_SOLVE_*, the torus axes, band addressing, offsets, the toroidal-table contract, the order of refusals, and n == 0 /
+ * row_begin == row_end, which launch nothing.  `dissolve` is not read.
+ *
+ * Lights.  lights == NULL: the one light of pc, exactly as trt_shade reads it (lightType 0 a point light, any other value
+ *   directional; nothing about it is validated) — taken as a table of one light of colour (1, 1, 1) and radius 0, which by
+ *   the first consequence of the light-table section is that light bit for bit and counter for counter.  Otherwise the
+ *   table of trt_shade_lit with all its refusals, and pc->lightPosition, lightIntensity and lightType are not read.
+ * Textures.  Every material's textureId is resolved at CALL time against the binding of trt_set_textures*, as in
+ *   trt_shade_textured, with its refusals (TRT_E_SCENE, "material i").  A glass material may carry a texture: it tints the
+ *   wall's own colour.
+ * Glass.  A torus whose material has illum 6 or 7 is a dielectric with the data, the checks (TRT_E_SCENE: ior NaN,
+ *   infinite or <= 0 — a ZERO-INITIALISED trt_material has ior == 0 —, a transmittance component NaN, infinite or
+ *   negative; only on a glass material some torus uses) and the step of trt_shade_refract.
+ * flags: 0 or TRT_SCENE_GLASS_SHADOWS; any other bit is refused (TRT_E_INVALID).
+ *
+ * One hit, at P on torus `id` with the outward normal N and the material mat, d the segment's direction; FP32, one
+ * rounding per operation, in the order written, fma only where written:
+ *   a. texel = steps 1-5 of the textured section for a material with textureId >= 0, fetched ONCE, before the light loop;
+ *      texel = (1, 1, 1) otherwise (the products below are then their other factor, exactly).
+ *   b. for light l = 0, 1, ... in table order, steps 1-5 of the light-table section with
+ *        step 2:  diffuse_l = computeDiffuse(mat, L_l, N) * texel, per channel                                  (rchit:105)
+ *        step 3, flags == 0: as written there — every shadow ray is the opaque any-hit query, glass casts the opaque shadow.
+ *        step 3, TRT_SCENE_GLASS_SHADOWS: a shadow ray (P, Ls) over (0.001, tmax_s) — the same rays, the same windows — has
+ *          a filter f = (1, 1, 1).  The tori are tested in trt_trace's test order, each with exactly the per-torus test of
+ *          the any-hit query (the full window, whatever was hit before).  A torus that is hit and is not glass: f = 0, and
+ *          the query ends.  A glass torus j that is hit: f.c = f.c * Tf_j.c per channel, and the query goes on.  The filter
+ *          is applied once per torus hit, however often the ray crosses its wall — stateless, like the refraction rule.
+ *          !want: no shadow ray, f = (1, 1, 1).
+ *          radius == 0:  v = f.     radius > 0:  acc = f_0, then acc = acc + f_s for s = 1 .. K - 1 in table order (FP32
+ *          adds), v.c = acc.c / (float)K, one correctly rounded division per channel.
+ *        step 4, per channel c, with v a vector under the flag and v.c = v without it:
+ *          att.c = fma(0.3f, 1.0f - v.c, v.c);  spec.c = (want && max(v.x, v.y, v.z) > 0) ? computeSpecular(mat, d, L_l, N).c * v.c : 0;
+ *          c.c = (att.c * I) * (diffuse_l.c + spec.c)
+ *        step 5 as written there.
+ *   c. the mirror step (rchit:145-153), as in trt_shade.
+ *   d. the glass step of trt_shade_refract for a glass torus (I, c, Nf, eta, cosi, k, nextD, the filter on the way in,
+ *      nextO = P), before hitValue = fma(prd, attenuation, hitValue).
+ * Consequences:
+ *   - lights == NULL, no glass material in use, no textureId >= 0: trt_shade's colours and three query counters, bit for
+ *     bit.  lights == NULL with glass: trt_shade_refract's.  lights == NULL with textures: trt_shade_textured's.  A table, no
+ *     glass, no textures: trt_shade_lit's.  Each with flags == 0 or, no glass in use, with the flag set.
+ *   - Without a glass hit every f is 0 or 1, so acc is the integer K - occ and v the count's quotient, exactly: with no
+ *     glass material in use the flag changes no bit and no counter.  Glass of Tf = (0, 0, 0) under the flag gives the
+ *     colours of flags == 0 bit for bit; its queries go on behind the glass, so shadow_tests is at least what it was.
+ *   - With the flag set and glass in use v is a SUM and no longer a count: the order of the disc table may change its last
+ *     bit.
+ *   - Light that passes glass is filtered, not bent: no caustics, and a shadow ray is straight.
+ * Enclosure cull: the path's mask as in trt_shade_refract — cleared from the first glass hit of a path on — and the
+ * shadow rays' masks as in trt_shade_lit, except that with the flag set and glass in use the shadow rays run without any
+ * mask: "cannot be hit first" holds for the tubes inside an OPAQUE host only.  By the contract at trt_scene no colour and
+ * no query count depends on it.
+ * Stats (trt_enable_stats): primary_tests and bounce_tests as trt_shade counts them; shadow_tests as trt_shade_lit counts
+ * them (lights == NULL: as trt_shade), where under the flag a shadow ray counts every torus it starts — it goes on past
+ * glass; pixels = n or samples x the pixels of the band; traced_tests, solved_tests and evaluations as defined at trt_stats.
+ * trt_shade_scene_camera is, bit for bit and counter for counter, trt_camera_rays put through trt_shade_scene.
+ * Refusals, with a message that begins "trt_shade_scene:" or "trt_shade_scene_camera:" for all but the scene's own: what
+ * trt_shade / trt_shade_camera refuse; then a bad flag; then what trt_shade_lit refuses of a table; then the scene; then
+ * what trt_shade_textured refuses of a textureId; then what trt_shade_refract refuses of a glass material.  A refused call
+ * leaves the ctx, the binding and the outputs as they were.
+ * Not here: translucency (`dissolve`: trt_shade_through, a different walk); a Fresnel split; Beer-Lambert absorption; a
+ * medium stack; caustics; any of this inside trt_render*.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+#define TRT_SCENE_GLASS_SHADOWS 1u
+int trt_shade_scene(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                    uint32_t flags, const trt_scene* scene, float* rgba_out);
+int trt_shade_scene_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, uint32_t flags,
+                           const trt_scene* scene, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera,
+                           uint32_t samples, const float* offsets, float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  `lights` and what it points at stay in host memory; the three tables
+ * travel in the kernel arguments.  The calls use no scratch of the ctx beyond the toroidal tables of the camera form,
+ * allocate nothing, synchronise nothing, put only kernel nodes on the stream and may be captured (the toroidal camera: as
+ * trt_shade_camera_dev; the binding: as trt_shade_textured_dev). */
+int trt_shade_scene_dev(trt_ctx* ctx, const trt_rays* in_dev, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                        uint32_t flags, const trt_scene* scene, float* rgba_dev, void* stream);
+int trt_shade_scene_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, uint32_t flags,
+                               const trt_scene* scene, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera,
+                               uint32_t samples, const float* offsets, float* rgba_dev, void* stream);
 
 /* ---- media inside the tubes: chords(rays_in -> a length per ray and torus), glow(rays_in -> radiance, transmittance) -- */
 /* Every other call sees a torus as a surface.  These four see its tube as a volume: trt_chords returns how long every ray

@@ -151,6 +151,8 @@ def lights_struct(lights, shadow_samples=1, disc=None):
     return st, (arr, d)
 
 
+TRT_SCENE_GLASS_SHADOWS = 1             # trt_shade_scene* flags: shadow rays pass glass, filtered by transmittance[3]
+
 TRT_MAX_TEXTURES = 8                    # textures bound to a ctx (trt_set_textures*)
 TRT_TEX_SRGB, TRT_TEX_LINEAR = 0, 1
 

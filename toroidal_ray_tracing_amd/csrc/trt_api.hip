@@ -1114,7 +1114,7 @@ static int check_shade(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const
 }
 
 // The device half of the four stream forms (`who`), which differ in the kernel and in the table that travels with its
-// arguments: `table(a)` validates and fills it (through_opacity, refract_glass, lit_lights, textured_table; nothing for
+// arguments: `table(a)` validates and fills it (through_opacity, refract_glass, lit_lights, textured_table, scene_mix; nothing for
 // trt_shade).  `textured`: the form reads textureId (build_scene).
 // Refusals in this order: check_shade; the table's own checks, the scene's among them; the scene (trt_shade, whose table
 // checks nothing); HIP errors of the launch.
@@ -1439,7 +1439,7 @@ static int check_shade_camera(trt_ctx* ctx, const char* who, const CameraFrame& 
 }
 
 // The device half of the three camera forms, which differ as the stream forms do: `table(a)` validates and fills the table
-// that travels with the kernel's arguments (refract_glass, lit_lights, textured_table; nothing for trt_shade_camera).  Refusals in this
+// that travels with the kernel's arguments (refract_glass, lit_lights, textured_table, scene_mix; nothing for trt_shade_camera).  Refusals in this
 // order: check_shade_camera; the table's own checks, the scene's among them — BEFORE the toroidal tables are touched, so
 // that a call refused for its table or its scene leaves them as they were; the toroidal tables (camera_tables); the scene
 // (trt_shade_camera, whose table checks nothing); HIP errors of the launch.
@@ -1500,12 +1500,12 @@ extern "C" int trt_shade_camera(trt_ctx* ctx, const trt_globals* g, const trt_pu
 // ------------------------------------------------------------------------------------------
 // What the four trt_shade_refract* calls (`who`) share behind their own checks: the scene (validated here, so that a matId
 // can be trusted) and the dielectric of every torus whose material has illum 6 or 7 — the only readers of `ior` and
-// `transmittance`.  Only a glass material that some torus uses is checked.  No scratch of the ctx: the table travels in
-// the kernel arguments.
-static int refract_glass(trt_ctx* ctx, const char* who, const trt_scene* scene, Glass& gl)
+// `transmittance` but trt_shade_scene* (`textured`: that call, which reads textureId as well).  Only a glass material that
+// some torus uses is checked.  No scratch of the ctx: the table travels in the kernel arguments.
+static int refract_glass(trt_ctx* ctx, const char* who, const trt_scene* scene, Glass& gl, bool textured = false)
 {
   const SceneK* S = nullptr;
-  if(int rc = build_scene(ctx, scene, S)) return rc;
+  if(int rc = build_scene(ctx, scene, S, textured)) return rc;
   std::memset(&gl, 0, sizeof gl);
   for(uint32_t j = 0; j < scene->n_tori; ++j)
   {
@@ -1564,10 +1564,10 @@ extern "C" int trt_shade_refract_camera(trt_ctx* ctx, const trt_globals* g, cons
 // several lights, area lights: trt_shade and trt_shade_camera with a light table in the place of pc's light
 // ------------------------------------------------------------------------------------------
 // What the four trt_shade_lit* calls (`who`) share behind their own checks: the checks of include/trt.h on the light table
-// and the disc table, the Lights they describe, and the scene (validated here, so that a refused call has touched nothing
-// of the ctx — the toroidal tables of the camera form come after it).  No scratch of the ctx: both tables travel in the
-// kernel arguments.
-static int lit_lights(trt_ctx* ctx, const char* who, const trt_lights* in, const trt_scene* scene, Lights& lt)
+// and the disc table and the Lights they describe (check_lights: also trt_shade_scene*'s), and the scene (validated here,
+// so that a refused call has touched nothing of the ctx — the toroidal tables of the camera form come after it).  No
+// scratch of the ctx: both tables travel in the kernel arguments.
+static int check_lights(trt_ctx* ctx, const char* who, const trt_lights* in, Lights& lt)
 {
   if(!in) return fail(ctx, TRT_E_INVALID, "%s: NULL lights", who);
   if(in->n_lights > TRT_MAX_LIGHTS)
@@ -1601,6 +1601,11 @@ static int lit_lights(trt_ctx* ctx, const char* who, const trt_lights* in, const
     if(!std::isfinite(lt.u[s]) || !std::isfinite(lt.v[s]))
       return fail(ctx, TRT_E_INVALID, "%s: the disc position of sample %u, (%g, %g), is not finite", who, s, (double)lt.u[s], (double)lt.v[s]);
   }
+  return TRT_OK;
+}
+static int lit_lights(trt_ctx* ctx, const char* who, const trt_lights* in, const trt_scene* scene, Lights& lt)
+{
+  if(int rc = check_lights(ctx, who, in, lt)) return rc;
   const SceneK* S = nullptr;
   return build_scene(ctx, scene, S);
 }
@@ -1779,6 +1784,76 @@ extern "C" int trt_shade_textured_camera(trt_ctx* ctx, const trt_globals* g, con
 {
   return shade_camera_host(ctx, "trt_shade_textured_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
     return trt_shade_textured_camera_dev(ctx, g, pc, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// lights, textures and glass in one call: trt_shade and trt_shade_camera with all three tables
+// ------------------------------------------------------------------------------------------
+// What the four trt_shade_scene* calls (`who`) share behind their own checks, in this order: the flags; the light table
+// (check_lights) or, for lights == NULL, the light of pc written as a table of one light — white, radius 0, the type pc's
+// reading of lightType gives it (0: point, anything else: directional) — which include/trt.h shows to be that light bit
+// for bit, and which nothing validates, as nothing validates pc's light in trt_shade; the scene with textures allowed and
+// the binding (textured_table); the dielectrics (refract_glass).  A refused call has touched nothing of the ctx.
+static int scene_mix(trt_ctx* ctx, const char* who, const trt_push* pc, const trt_lights* lights, uint32_t flags, const trt_scene* scene,
+                     SceneMix& m)
+{
+  if(flags & ~(uint32_t)TRT_SCENE_GLASS_SHADOWS)
+    return fail(ctx, TRT_E_INVALID, "%s: flags = 0x%x; the only flag is TRT_SCENE_GLASS_SHADOWS (0x%x)", who, flags, TRT_SCENE_GLASS_SHADOWS);
+  if(lights)
+  {
+    if(int rc = check_lights(ctx, who, lights, m.lights)) return rc;
+  }
+  else
+  {
+    std::memset(&m.lights, 0, sizeof m.lights);
+    m.lights.n = 1;
+    m.lights.K = 1;
+    trt_light& q = m.lights.l[0];
+    for(int k = 0; k < 3; ++k)
+    {
+      q.position[k] = pc->lightPosition[k];
+      q.color[k]    = 1.0f;
+    }
+    q.intensity = pc->lightIntensity;
+    q.type      = pc->lightType == 0 ? 0 : 1;
+  }
+  if(int rc = textured_table(ctx, who, scene, m.tx)) return rc;
+  if(int rc = refract_glass(ctx, who, scene, m.glass, true)) return rc;
+  m.clear = (flags & TRT_SCENE_GLASS_SHADOWS) ? m.glass.mask : 0u;
+  return TRT_OK;
+}
+
+extern "C" int trt_shade_scene_dev(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                                   uint32_t flags, const trt_scene* scene, float* rgba, void* stream)
+{
+  return shade_stream_dev(ctx, "trt_shade_scene", in, samples, pc, scene, rgba, stream, launch_shade_scene,
+                          [&](ShadeSceneArgs& a) { return scene_mix(ctx, "trt_shade_scene", pc, lights, flags, scene, a.table); }, true);
+}
+
+extern "C" int trt_shade_scene(trt_ctx* ctx, const trt_rays* in, uint32_t samples, const trt_push* pc, const trt_lights* lights,
+                               uint32_t flags, const trt_scene* scene, float* rgba_out)
+{
+  return shade_stream_host(ctx, "trt_shade_scene", in, samples, pc, rgba_out, [&](const trt_rays* rays, float* image) {
+    return trt_shade_scene_dev(ctx, rays, samples, pc, lights, flags, scene, image, nullptr);
+  });
+}
+
+extern "C" int trt_shade_scene_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, uint32_t flags,
+                                          const trt_scene* scene, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera,
+                                          uint32_t samples, const float* offsets, float* rgba, void* stream)
+{
+  return shade_camera_dev(ctx, "trt_shade_scene_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, scene, rgba, stream,
+                          launch_shade_scene_camera,
+                          [&](ShadeSceneCameraArgs& a) { return scene_mix(ctx, "trt_shade_scene_camera", pc, lights, flags, scene, a.table); }, true);
+}
+
+extern "C" int trt_shade_scene_camera(trt_ctx* ctx, const trt_globals* g, const trt_push* pc, const trt_lights* lights, uint32_t flags,
+                                      const trt_scene* scene, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, int camera,
+                                      uint32_t samples, const float* offsets, float* rgba_out)
+{
+  return shade_camera_host(ctx, "trt_shade_scene_camera", {g, pc, W, H, row_begin, row_end, camera, samples, offsets}, rgba_out, [&](float* image) {
+    return trt_shade_scene_camera_dev(ctx, g, pc, lights, flags, scene, W, H, row_begin, row_end, camera, samples, offsets, image, nullptr);
   });
 }
 

@@ -896,13 +896,14 @@ __device__ __forceinline__ int closest_hit(const SceneK& S, v3 o, v3 d, float tm
   return id;
 }
 
-// Any hit — the shadow query with gl_RayFlagsTerminateOnFirstHitEXT (REFL/shaders/raytrace.rchit:114-131).
-// Up to and including the first torus (in S.order) with a root in the window this runs the torus_hit calls of
-// closest_hit with the same arguments — closest_hit's interval shrinks only after that torus — so, for the same WALK or
-// any other (the forms are bit-identical), any_hit() == (closest_hit() >= 0) bit for bit (DESIGN.md §4 T3).
-template <class Real, bool ALT = false, bool ORIENT = false, int WALK = kRenderWalk>
-__device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
-                                        uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
+// The shadow query: any hit — gl_RayFlagsTerminateOnFirstHitEXT (REFL/shaders/raytrace.rchit:114-131) — with a say for
+// the caller at every torus i that is hit: pass(i) == true lets the ray through that torus (trt_shade_scene* with
+// TRT_SCENE_GLASS_SHADOWS: the caller filters the light there, once per torus however often the ray crosses it) and the
+// query goes on.  Returns whether a torus that does not pass was hit.  Tori are tested in S.order, each over the full
+// window; every torus started counts one test, a skipped one too.
+template <class Real, bool ALT = false, bool ORIENT = false, int WALK = kRenderWalk, class Pass>
+__device__ __forceinline__ bool blocked_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
+                                            uint32_t& tests, WorkCount& wc, uint32_t skip, Pass&& pass)
 {
   RayK<Real> r;
   r.set(o, d, tmin, tmax);
@@ -912,10 +913,22 @@ __device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin,
     ++tests;
     if((skip >> k) & 1u)
       continue;
-    if(torus_hit<Real, ALT, WALK, ORIENT>(S, S.order[k], r, tmin, tmax, t, wc))
+    const int i = S.order[k];
+    if(torus_hit<Real, ALT, WALK, ORIENT>(S, i, r, tmin, tmax, t, wc) && !pass(i))
       return true;
   }
   return false;
+}
+
+// Any hit: the query above with nothing let through.
+// Up to and including the first torus (in S.order) with a root in the window this runs the torus_hit calls of
+// closest_hit with the same arguments — closest_hit's interval shrinks only after that torus — so, for the same WALK or
+// any other (the forms are bit-identical), any_hit() == (closest_hit() >= 0) bit for bit (DESIGN.md §4 T3).
+template <class Real, bool ALT = false, bool ORIENT = false, int WALK = kRenderWalk>
+__device__ __forceinline__ bool any_hit(const SceneK& S, v3 o, v3 d, float tmin, float tmax,
+                                        uint32_t& tests, WorkCount& wc, uint32_t skip = 0u)
+{
+  return blocked_hit<Real, ALT, ORIENT, WALK>(S, o, d, tmin, tmax, tests, wc, skip, [](int) { return false; });
 }
 
 // Every crossing of one ray with torus i inside the open interval (r.tmin, r.tmax), left to right: emit(t, entering) per

@@ -11,48 +11,18 @@
 // F32 and F64 are separate instantiations, as everywhere: the FP64 solve needs about twice the VGPRs of the FP32 one, and
 // a kernel that held both would run the FP32 scenes at the FP64 kernel's occupancy.
 // Compiled with -ffp-contract=off like every unit: each operation below is one FP32 rounding, in the order written.
-#include "trt_render.hpp"
+#include "trt_hits.hpp"
 
 namespace trt {
 
-// ------------------------------------------------------------------------------------------
-// the dielectric: GLSL refract() at a glass hit, stateless
-// ------------------------------------------------------------------------------------------
-// The glass() of bounce_loop()'s hit step: called after end() — the hit is shaded as any non-mirror hit — and before the fma
-// of rgen:76, as the mirror scales the attenuation by Ks before its own colour is added (rchit:149 before rgen:76).  Only
-// the sign of N·I decides between entering and leaving: the path carries no "inside" flag, and the far side of a wall is
-// vacuum.  `g` lives in LDS: the id of a hit differs from lane to lane.
+// The render's hit step with the dielectric (glass_step, trt_hits.hpp) as the glass() of bounce_loop().
 template <class Real, bool ALT, bool ORIENT>
 struct GlassHit : PcLightHit<Real, ALT, ORIENT> {
   const Glass& g;
   __device__ __forceinline__ explicit GlassHit(const Glass& glass) : g(glass) {}
   __device__ __forceinline__ bool glass(int id, const HitState& h, v3 d, v3& attenuation, int& done, v3& nextO, v3& nextD) const
   {
-    if(((g.mask >> id) & 1u) == 0u)
-      return false;
-    const v3    I        = normalize3(d);
-    const float c        = dot3(h.N, I);
-    const bool  entering = c < 0.0f;
-    const v3    Nf       = entering ? h.N : neg3(h.N);
-    const float eta      = entering ? g.inv_n[id] : g.n[id];
-    const float cosi     = -dot3(Nf, I);
-    const float k        = 1.0f - (eta * eta) * (1.0f - cosi * cosi);
-    if(k < 0.0f)   // total internal reflection: the attenuation is untouched
-      nextD = reflect3(I, Nf);
-    else
-    {
-      const float m = eta * cosi - sqrt_(k);
-      nextD = {fma_(m, Nf.x, eta * I.x), fma_(m, Nf.y, eta * I.y), fma_(m, Nf.z, eta * I.z)};
-      if(entering)   // the filter, once per passage, on the way in
-      {
-        attenuation.x *= g.tf[id][0];
-        attenuation.y *= g.tf[id][1];
-        attenuation.z *= g.tf[id][2];
-      }
-    }
-    nextO = h.P;
-    done  = 0;
-    return true;
+    return glass_step(g, id, h, d, attenuation, done, nextO, nextD);
   }
 };
 

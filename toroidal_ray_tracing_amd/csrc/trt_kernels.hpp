@@ -354,6 +354,19 @@ struct Textures {
 static_assert(sizeof(TextureK) == 32 && sizeof(Textures) == 8 * 32 + 8 + 4 * TRT_MAX_MATERIALS + 8, "Textures: at most 8 x 32 bytes, the table's pointer, a word per material");
 using ShadeTexturedArgs       = StreamShade<Textures>;
 using ShadeTexturedCameraArgs = CameraShade<Textures>;
+// trt_shade_scene*, trt_shade_scene_camera*: the three tables above in one call.  `lights` holds the caller's table, or
+// — lights == NULL — the one light of pc as a table of one white light of radius 0, which is that light bit for bit
+// (include/trt.h); `clear`: the glass tori (Glass::mask) when TRT_SCENE_GLASS_SHADOWS is set, else 0 — the tori a shadow
+// ray passes through, filtered.  By value in the kernel-argument segment (1288 B); the kernels read `lights` and `clear`
+// there, with scalar loads, and stage `glass` and `tx`, which they index per lane, into LDS.
+struct SceneMix {
+  Lights   lights;
+  Textures tx;
+  Glass    glass;
+  uint32_t clear;
+};
+using ShadeSceneArgs       = StreamShade<SceneMix>;
+using ShadeSceneCameraArgs = CameraShade<SceneMix>;
 // trt_hit_uv*: the (u, v) of n points (px, py, pz) on the tori `id` names; u and v are each optional.
 struct HitUvArgs {
   const float*   px;
@@ -403,6 +416,8 @@ hipError_t launch_shade_lit(const SceneK& scene, const ShadeLitArgs& a, const Tu
 hipError_t launch_shade_lit_camera(const SceneK& scene, const ShadeLitCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_textured(const SceneK& scene, const ShadeTexturedArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_textured_camera(const SceneK& scene, const ShadeTexturedCameraArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_scene(const SceneK& scene, const ShadeSceneArgs& a, const Tuning& tn, hipStream_t stream);
+hipError_t launch_shade_scene_camera(const SceneK& scene, const ShadeSceneCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_hit_uv(const SceneK& scene, const HitUvArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_zero_words(unsigned int* words, uint32_t n, hipStream_t stream);
 // Whether a launch of variant `v` takes part in the cost feedback (RenderArgs::tile_cost): the plain listed kernels only

@@ -1,5 +1,5 @@
 // trt_render.hpp — what more than one kernel family of the render path uses.  Device side: included only by
-// trt_rays.hip, trt_through.hip, trt_glass.hip, trt_lights.hip, trt_textured.hip, trt_fan.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
+// trt_rays.hip, trt_through.hip, trt_hits.hpp (trt_glass.hip, trt_lights.hip, trt_textured.hip, trt_scene.hip), trt_fan.hip, trt_classify.hip, trt_persistent.hip and trt_kernels.hip, never by the host (trt_api.hip).
 //
 //   gptr, st1 / st4 / st4c, ld1           global-memory accessors
 //   HitState, hit_begin, hit_end          the closest-hit shader body, split at the shadow query
@@ -24,7 +24,7 @@
 //   with_orient, with_solver              launch dispatch: scene → <Real, ALT, ORIENT>
 //   shade_kernel, shade_camera_kernel, NotStaged, launch_stream_form, launch_camera_form
 //                                         the two kernels of the shade family over <Form, Real, ALT, ORIENT> and their launches;
-//                                         what a form is (ShadePlain, ShadeRefract, ShadeLit, ShadeTextured: one per unit)
+//                                         what a form is (ShadePlain, ShadeRefract, ShadeLit, ShadeTextured, ShadeScene: one per unit)
 //
 // Everything here is __forceinline__ (or a host template): no device function is called across translation units.
 #pragma once

@@ -1,7 +1,7 @@
 // trt_textured.hip — textures on tori along caller and camera rays (trt_shade_textured*, trt_shade_textured_camera*), and the
 // (u, v) of surface points (trt_hit_uv*), gfx950.
 //
-//   texture_fetch                 the bilinear texel of one hit: four 4-byte loads, repeat addressing in integers
+//   texture_fetch, with_texel     (trt_hits.hpp) the bilinear texel of one hit: four 4-byte loads, repeat addressing in integers
 //   TexturedHit                   the render's hit step with the texel multiplied into the hit's diffuse term between
 //                                 hit_begin and the shadow query (the tint() of bounce_loop, trt_render.hpp), where
 //                                 REFL/shaders/raytrace.rchit:101-106 has it
@@ -16,66 +16,17 @@
 // table of the ctx — only when some bound texture is sRGB.  No hardware sampler: its filter weights are fixed-point and
 // unspecified, and the contract here is one FP32 rounding per written operation (include/trt.h states them).
 // Compiled with -ffp-contract=off like every unit: each operation below is one FP32 rounding, in the order written.
-#include "trt_render.hpp"
+#include "trt_hits.hpp"
 
 namespace trt {
 
 // SceneK and the larger of the two argument structs travel in one kernel-argument segment.
 static_assert(sizeof(SceneK) + sizeof(ShadeTexturedCameraArgs) <= 4096 && sizeof(SceneK) + sizeof(ShadeTexturedArgs) <= 4096,
               "the kernel-argument segment of the shade_textured kernels");
-static_assert(sizeof(trt_texture) == 32, "trt_texture: include/trt.h");
-
-// ------------------------------------------------------------------------------------------
-// the texel of one hit (include/trt.h states the rule operation for operation)
-// ------------------------------------------------------------------------------------------
-// `i` reduced into [0, n) for ANY i: the remainder in integers, after the conversion — no u, v or repeat addresses outside
-// the image.
-__device__ __forceinline__ int wrap_texel(int i, int n)
-{
-  const int r = i % n;
-  return r < 0 ? r + n : r;
-}
-// One channel of an RGBA8 texel (byte `k` of the little-endian word): through the decode table, or scaled.
-__device__ __forceinline__ float texel_channel(uint32_t t, uint32_t k, bool srgb, const float* lut)
-{
-  const uint32_t c = (t >> (8u * k)) & 255u;
-  return srgb ? lut[c] : (float)c * (1.0f / 255.0f);
-}
-__device__ __forceinline__ float lerp_(float a, float b, float f) { return fma_(f, b - a, a); }
-
-// Bilinear, repeat addressing, texel centres at (i + 0.5) / W; `lut` is the sRGB decode table in LDS.
-__device__ __forceinline__ v3 texture_fetch(const TextureK& T, const float* lut, float u, float v)
-{
-  const int   W = (int)T.W, H = (int)T.H;
-  const float x = (u * T.ru) * (float)W - 0.5f, y = (v * T.rv) * (float)H - 0.5f;
-  const float xf = floorf(x), yf = floorf(y);
-  const float fx = x - xf, fy = y - yf;
-  const int   i0 = wrap_texel((int)xf, W), j0 = wrap_texel((int)yf, H);
-  const int   i1 = i0 + 1 == W ? 0 : i0 + 1, j1 = j0 + 1 == H ? 0 : j0 + 1;
-  const gptr<const uint32_t> img = (gptr<const uint32_t>)(const void*)T.texels;
-  const size_t   r0 = (size_t)j0 * (size_t)W, r1 = (size_t)j1 * (size_t)W;
-  const uint32_t t00 = img[r0 + i0], t10 = img[r0 + i1], t01 = img[r1 + i0], t11 = img[r1 + i1];
-  const bool     srgb = T.srgb != 0;
-  float c[3];
-#pragma unroll
-  for(uint32_t k = 0; k < 3; ++k)
-  {
-    const float top = lerp_(texel_channel(t00, k, srgb, lut), texel_channel(t10, k, srgb, lut), fx);
-    const float bot = lerp_(texel_channel(t01, k, srgb, lut), texel_channel(t11, k, srgb, lut), fx);
-    c[k] = lerp_(top, bot, fy);
-  }
-  return {c[0], c[1], c[2]};
-}
 
 // ------------------------------------------------------------------------------------------
 // shade_textured(rays_in → one colour per output), shade_textured_camera(camera → the band of an image)
 // ------------------------------------------------------------------------------------------
-// The descriptor table and the decode table in LDS.
-struct TexturesLds {
-  Textures tx;
-  float    lut[256];
-};
-
 // The hit step with textures: the render's (PcLightHit, trt_render.hpp — the light of pc, the opaque shadow query, the
 // mirror) with one step more between hit_begin and the shadow query, the loop's tint(): diffuse *= texel (rchit:101-106)
 // for a material that names a texture.  A material without one runs trt_shade's arithmetic, so its colours are trt_shade's
@@ -87,17 +38,12 @@ struct TexturedHit : PcLightHit<Real, ALT, ORIENT> {
   __device__ __forceinline__ explicit TexturedHit(const TexturesLds& t) : T(t) {}
   __device__ __forceinline__ void tint(const SceneK& S, int id, HitState& h) const
   {
-    const int k = T.tx.of_mat[h.matId];
-    if(k >= 0)                                                             // rchit:101
-    {
-      float u, v;
-      torus_uv<ORIENT>(S, id, h.P, u, v);
-      const v3 texel = texture_fetch(T.tx.t[k], T.lut, u, v);
+    with_texel<ORIENT>(S, T, id, h, [&](v3 texel) {
       h.diffuse = {h.diffuse.x * texel.x, h.diffuse.y * texel.y, h.diffuse.z * texel.z};   // rchit:105
       // The products are pinned HERE: nothing reads them before hit_end, so hipcc is free to sink the filter — four texel
       // words and two weights instead of three floats — below the shadow ray's solve.
       asm volatile("" : "+v"(h.diffuse.x), "+v"(h.diffuse.y), "+v"(h.diffuse.z));
-    }
+    });
   }
 };
 
@@ -108,10 +54,7 @@ struct ShadeTextured {
   using Staged = TexturesLds;
   template <class Args> static __device__ __forceinline__ void stage(Staged* T, const Args& a)
   {
-    static_assert(sizeof(float) * 256 == 1024, "one decode entry per thread of a 256-thread block");
-    stage_words(&T->tx, a.table);
-    if(a.table.any_srgb)
-      T->lut[threadIdx.x] = ((gptr<const float>)a.table.decode)[threadIdx.x];
+    stage_textures(T, a.table);
   }
   template <class Real, bool ALT, bool ORIENT, class Args>
   static __device__ __forceinline__ TexturedHit<Real, ALT, ORIENT> hit(const Args&, const Staged& T) { return TexturedHit<Real, ALT, ORIENT>{T}; }

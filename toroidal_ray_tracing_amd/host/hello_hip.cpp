@@ -251,6 +251,23 @@ void HelloHip::raytraceTextured(void* stream, const std::array<float, 4>& clearC
         "HelloHip::raytraceTextured");
 }
 
+void HelloHip::shadeScene(void* stream, const std::array<float, 4>& clearColor, const trt_lights* lights, uint32_t flags,
+                          const trt_rays& raysDev, uint32_t samples, float* rgbaDev)
+{
+  const trt_scene sc = scene();
+  check(trt_shade_scene_dev(m_ctx, &raysDev, samples, pushFor(clearColor, lights == nullptr), lights, flags, &sc, rgbaDev, stream),
+        "HelloHip::shadeScene");
+}
+
+void HelloHip::raytraceScene(void* stream, const std::array<float, 4>& clearColor, const trt_lights* lights, uint32_t flags,
+                             uint32_t samples, const float* offsets)
+{
+  const trt_scene sc = scene();
+  check(trt_shade_scene_camera_dev(m_ctx, &m_globals, pushFor(clearColor, lights == nullptr), lights, flags, &sc, m_size.width,
+                                   m_size.height, 0, m_size.height, m_camera, samples, offsets, m_dColor, stream),
+        "HelloHip::raytraceScene");
+}
+
 void HelloHip::chords(void* stream,const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev)
 {
   const trt_scene sc = scene();

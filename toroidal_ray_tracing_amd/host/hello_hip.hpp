@@ -98,6 +98,18 @@ public:
   void shadeTextured(void* stream, const std::array<float, 4>& clearColor, const trt_rays& raysDev, uint32_t samples, float* rgbaDev);
   void raytraceTextured(void* stream, const std::array<float, 4>& clearColor, uint32_t samples = 1, const float* offsets = nullptr);
 
+  // Lights, textures and glass at once (trt_shade_scene_dev, trt_shade_scene_camera_dev): the table of shadeLit — or
+  // nullptr for the light of the push constants, refreshed as raytrace() refreshes it —, the textures of setTextures and
+  // the glass materials of shadeRefract in one call; flags: 0, or TRT_SCENE_GLASS_SHADOWS to let light through glass in
+  // the shadow query, filtered by the glass' transmittance (include/trt.h).  shadeScene: every ray of raysDev
+  // (sample-major, `samples` per output) into rgbaDev ((raysDev.n / samples) * 4 floats, 16-byte aligned).  raytraceScene:
+  // the frame of m_camera into the colour image raytrace() writes, `samples` rays per pixel at the sub-pixel offsets
+  // (2 floats per sample; nullptr: the pixel centres); no RenderedData is written.
+  void shadeScene(void* stream, const std::array<float, 4>& clearColor, const trt_lights* lights, uint32_t flags, const trt_rays& raysDev,
+                  uint32_t samples, float* rgbaDev);
+  void raytraceScene(void* stream, const std::array<float, 4>& clearColor, const trt_lights* lights, uint32_t flags, uint32_t samples = 1,
+                     const float* offsets = nullptr);
+
   // Media inside the tubes of the tori added so far (trt_chords_dev, trt_glow_dev; materials are not read).  chords: the
   // length of every ray of raysDev inside every tube, lengthDev[j * raysDev.n + i] for torus j (the order of the
   // addTorus calls).  glow: emission and absorption of media (one trt_medium per torus, host memory) integrated along

@@ -92,6 +92,16 @@ SYMBOLS = {
     "trt_shade_textured_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_scene),
                                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, abi.f32p,
                                                 C.c_void_p, C.c_void_p]),
+    "trt_shade_scene": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                  C.c_uint32, C.POINTER(abi.trt_scene), C.c_void_p]),
+    "trt_shade_scene_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_uint32, C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                      C.c_uint32, C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p]),
+    "trt_shade_scene_camera": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                         C.c_uint32, C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                         C.c_uint32, abi.f32p, C.c_void_p]),
+    "trt_shade_scene_camera_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.POINTER(abi.trt_lights),
+                                             C.c_uint32, C.POINTER(abi.trt_scene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_int, C.c_uint32, abi.f32p, C.c_void_p, C.c_void_p]),
     "trt_hit_uv": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                              C.c_void_p, C.c_void_p]),
     "trt_hit_uv_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_scene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

@@ -446,6 +446,49 @@ class Tracer:
         self._shade_camera_dev(self._L.trt_shade_textured_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows,
                                self._scene(scene), stream=stream)
 
+    # -- lights, textures and glass in one call ----------------------------------------------------
+    @staticmethod
+    def _scene_lights(lights, shadow_samples, disc, glass_shadows):
+        """(pointer to the trt_lights or None, flags, keep) of the shade_scene* calls."""
+        flags = abi.TRT_SCENE_GLASS_SHADOWS if glass_shadows is True else int(glass_shadows)
+        if lights is None:
+            return None, flags, None
+        lt, keep = abi.lights_struct(lights, shadow_samples, disc)
+        return C.byref(lt), flags, (lt, keep)
+
+    def shade_scene(self, scene, o, d, pc, samples=1, lights=None, shadow_samples=1, disc=None, glass_shadows=False):
+        """``shade`` with a light table, the bound textures and glass tori at once (trt_shade_scene) on host arrays.
+        ``lights`` None: the one light of ``pc``, as ``shade`` reads it; else as in ``shade_lit``.  Materials may name a
+        texture (``set_textures``) and may be glass (illum 6 or 7, ior > 0).  ``glass_shadows``: shadow rays pass glass tori,
+        filtered by their ``transmittance``; off, glass casts an opaque shadow.  (An int is passed on as the flags word.)
+        Layout and averaging as in ``shade``.  Returns rgba float32 of shape (n_out, 4), alpha 1."""
+        lt, flags, keep = self._scene_lights(lights, shadow_samples, disc, glass_shadows)
+        return self._shade_host(self._L.trt_shade_scene, o, d, pc, samples, lt, flags, self._scene(scene))
+
+    def shade_scene_dev(self, scene, ray_ptrs, n, pc, rgba_ptr, samples=1, stream=0, lights=None, shadow_samples=1, disc=None,
+                        glass_shadows=False):
+        """Device pointers (ints): as ``shade_dev``; the lights stay on the host (they travel in the launch's arguments).
+        Asynchronous on ``stream``."""
+        rays = self._dev_rays(ray_ptrs, n)
+        lt, flags, keep = self._scene_lights(lights, shadow_samples, disc, glass_shadows)
+        self._check(self._L.trt_shade_scene_dev(self._h, C.byref(rays), int(samples), C.byref(pc), lt, flags, self._scene(scene),
+                                                _vp(rgba_ptr), _vp(stream)))
+
+    def shade_scene_camera(self, scene, g, pc, W, H, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None, rows=None,
+                           lights=None, shadow_samples=1, disc=None, glass_shadows=False):
+        """``shade_camera`` with lights, textures and glass (trt_shade_scene_camera) on a host buffer: bit for bit
+        ``camera_rays`` put through ``shade_scene``.  Returns rgba (H, W, 4); rows outside ``rows`` are 0."""
+        lt, flags, keep = self._scene_lights(lights, shadow_samples, disc, glass_shadows)
+        return self._shade_camera_host(self._L.trt_shade_scene_camera, g, pc, W, H, camera, samples, offsets, rows, lt, flags,
+                                       self._scene(scene))
+
+    def shade_scene_camera_dev(self, scene, g, pc, W, H, rgba_ptr, camera=abi.TRT_CAMERA_PINHOLE, samples=1, offsets=None,
+                               rows=None, stream=0, lights=None, shadow_samples=1, disc=None, glass_shadows=False):
+        """Device image: as ``shade_camera_dev``; the lights stay on the host.  Asynchronous on ``stream``."""
+        lt, flags, keep = self._scene_lights(lights, shadow_samples, disc, glass_shadows)
+        self._shade_camera_dev(self._L.trt_shade_scene_camera_dev, g, pc, W, H, rgba_ptr, camera, samples, offsets, rows, lt, flags,
+                               self._scene(scene), stream=stream)
+
     def hit_uv(self, scene, at):
         """The (u, v) in [0, 1) of surface points (trt_hit_uv) on host arrays: ``at`` a dict of hit arrays as ``trace`` /
         ``render`` return them (px, py, pz, id).  u turns about the torus' axis, v about its tube; a point with id < 0 or
