@@ -1,32 +1,20 @@
 """FP64 truth for trt_shade_refract* — TEST INFRASTRUCTURE (a helper module: no tests, no fixtures).
 
-The rule of include/trt.h in numpy float64: the hit of a segment is the first entry of ``crossings_truth.all_crossings``
-(every real root of every torus' quartic from the companion-matrix solver, merged in ascending t), the Phong chain is
-restated from the GLSL as ``through_truth.py`` restates it, the shadow query is the opaque one (any crossing inside
-(tmin, lightDistance)), and a glass hit (illum 6 / 7) goes on along GLSL refract() — or reflect() where there is no
-refracted ray — with the filter applied on the way in.  No arithmetic shared with the kernels.
+The rule of include/trt.h: the payload loop of ``shade_truth`` with the one light of pc, the opaque shadow query (any
+crossing inside (tmin, lightDistance)) and no textures; a glass hit (illum 6 / 7) goes on along GLSL refract() — or
+reflect() where there is no refracted ray — with the filter applied on the way in.  That step, ``refract_step``, is
+stated here in numpy float64 and called by the loop.  No arithmetic shared with the kernels.
 
-``robust`` is the conjunction, over every segment of a ray's path, of
-  * ``crossings_truth.classify_margin_all`` of the segment,
-  * |N·L| > 1e-3 at every hit,
-  * ``classify_margin_all`` of every shadow ray over (tmin, lightDistance), no shadow crossing within 1e-3 of the light,
-  * at every glass hit |N·I| > 1e-3 and |k| > 1e-3,
-and of a stability test: the truth run again with every hit t scaled by 1 + 2e-6 and by 1 - 2e-6 (what the FP32 rounding
-of t and of P amounts to, with room for a few ulps of the solver) keeps every channel within ``STABLE_REL`` of the
-unperturbed colour, relative to |colour| + 1e-5.  Refraction magnifies the rounding of t at a lens-like wall; a ray
-that sensitive is non-robust by construction.  STABLE_REL is 1e-4, the bar 99.5 % of the robust rays have to meet: a ray
-that a perturbation 30 times one FP32 rounding moves by less than that bar has no excuse to miss it.
+``robust`` is shade_truth's: the margins of every segment and every shadow ray, |N·L| > 1e-3 at every hit, at every glass
+hit |N·I| > 1e-3 and |k| > 1e-3, and the stability run.  Refraction magnifies the rounding of t at a lens-like wall; a
+ray that sensitive is non-robust by construction.
 """
 import numpy as np
 
 import crossings_truth as ct
-import oriented_truth
+import shade_truth
 import through_truth
-from oracle import truth
 
-TMIN, TMAX = ct.TMIN, ct.TMAX
-T_EPS = 2e-6
-STABLE_REL = 1e-4
 MAX_DEPTH = 8
 
 
@@ -46,133 +34,18 @@ def refract_step(I, N, n, Tf, A):
     return np.where(tir[:, None], refl, refr), A, tir, entering, k, eta, cosi
 
 
-def _normals(P, hid, geo, axes):
-    N = np.zeros_like(P)
-    for i, (C, R, r) in enumerate(geo):
-        s = hid == i
-        if s.any():
-            N[s] = truth.normal(P[s], C, R) if axes is None else oriented_truth.normal(P[s], C, axes[i], R)
-    return N
-
-
-def _trace(o, d, geo, axes, mat_of, M, shin, illum, ior, Tf, push, t_scale, margins):
-    """One run of the rule.  margins: also form `robust` and the record of the glass hits (the perturbed runs skip both)."""
-    clear = np.asarray(push["clearColor"], np.float64)[:3]
-    lp = np.asarray(push["lightPosition"], np.float64)
-    n = len(o)
-    acc = np.zeros((n, 3))
-    A = np.ones((n, 3))                                                                       # rgen:56
-    robust = np.ones(n, bool)
-    ev = dict(ray=[], depth=[], sin_i=[], sin_t=[], n=[], entering=[], tir=[])
-    first = dict(id=np.full(n, -1), entering=np.zeros(n, bool))
-    live = np.arange(n)
-    depth = 0
-    while len(live):                                                                          # rgen:62
-        t, tid, _, _ = ct.all_crossings(o, d, geo, axes, TMIN, TMAX)
-        if margins:
-            robust[live] &= ct.classify_margin_all(o, d, geo, axes, TMIN, TMAX)
-        hit = tid[:, 0] >= 0
-        acc[live[~hit]] += clear * 0.8 * A[live[~hit]]                                        # rmiss:37
-        sel = np.flatnonzero(hit)
-        if len(sel) == 0:
-            break
-        px, hid, hd = live[sel], tid[sel, 0], d[sel]
-        P = o[sel] + (t[sel, 0] * t_scale)[:, None] * hd                                      # BEF rchit:134
-        N = _normals(P, hid, geo, axes)
-        if int(push["lightType"]) == 0:                                                       # rchit:82-88
-            ldir = lp - P
-            ldist = np.linalg.norm(ldir, axis=1)
-            lint = float(push["lightIntensity"]) / (ldist * ldist)
-            L = ldir / ldist[:, None]
-        else:                                                                                 # rchit:89-92
-            L = np.tile(lp / np.linalg.norm(lp), (len(P), 1))
-            ldist = np.full(len(P), 100000.0)
-            lint = np.full(len(P), float(push["lightIntensity"]))
-        mi = mat_of[hid]
-        ndl = np.einsum("ni,ni->n", N, L)
-        diffuse = M["diffuse"][mi] * np.maximum(ndl, 0.0)[:, None]                            # wavefront.glsl:25-26
-        diffuse = diffuse + np.where((illum[mi] >= 1)[:, None], M["ambient"][mi], 0.0)        # :27-28
-        want = ndl > 0                                                                        # rchit:112
-        shadowed = np.zeros(len(P), bool)
-        if want.any():                                                                        # rchit:114-131: opaque, any hit
-            ts, sid, _, _ = ct.all_crossings(P[want], L[want], geo, axes, TMIN, np.inf)
-            with np.errstate(invalid="ignore"):
-                shadowed[want] = np.any((sid >= 0) & (ts < ldist[want][:, None]), axis=1)
-            if margins:
-                _, stable = through_truth.transmittance(P[want], L[want], geo, np.ones(len(geo)), axes, TMIN, ldist[want])
-                robust[px[want]] &= stable
-        att = np.where(want & shadowed, 0.3, 1.0)                                             # rchit:133-136
-        specular = np.zeros_like(P)
-        lit = np.flatnonzero(want & ~shadowed)
-        if len(lit):                                                                          # rchit:140 -> wavefront.glsl:32-48
-            ml = mi[lit]
-            ks = np.maximum(shin[ml], 4.0)
-            energy = (2.0 + ks) / (2.0 * 3.14159265)
-            V = truth._normalize(-hd[lit])
-            Rr = truth._reflect(-L[lit], N[lit])
-            s = energy * np.power(np.maximum(np.einsum("ni,ni->n", V, Rr), 0.0), ks)
-            specular[lit] = np.where((illum[ml] >= 2)[:, None], M["specular"][ml] * s[:, None], 0.0)
-        c = (att * lint)[:, None] * (diffuse + specular)                                      # rchit:155
-        mirror = illum[mi] == 3                                                               # rchit:145
-        glass = (illum[mi] == 6) | (illum[mi] == 7)
-        Ah = A[px]
-        Ah[mirror] *= M["specular"][mi][mirror]                                               # rchit:149, before rgen:76
-        nxt_d = hd.copy()
-        nxt_d[mirror] = truth._reflect(hd[mirror], N[mirror])                                 # rchit:148,152
-        g = np.flatnonzero(glass)
-        if len(g):
-            I = truth._normalize(hd[g])
-            nd, Ag, tir, entering, k, eta, cosi = refract_step(I, N[g], ior[hid[g]], Tf[hid[g]], Ah[g])
-            Ah[g] = Ag
-            nxt_d[g] = nd
-            if margins:
-                robust[px[g]] &= (np.abs(cosi) > 1e-3) & (np.abs(k) > 1e-3)
-                ev["ray"].append(px[g]); ev["depth"].append(np.full(len(g), depth)); ev["n"].append(ior[hid[g]])
-                ev["sin_i"].append(np.linalg.norm(np.cross(N[g], I), axis=1))
-                ev["sin_t"].append(np.linalg.norm(np.cross(N[g], nd), axis=1))
-                ev["entering"].append(entering); ev["tir"].append(tir)
-        if margins:
-            robust[px] &= np.abs(ndl) > 1e-3
-            if depth == 0:
-                first["id"][px] = hid
-                first["entering"][px] = np.einsum("ni,ni->n", N, hd) < 0.0
-        acc[px] += c * Ah                                                                     # rgen:76
-        A[px] = Ah
-        depth += 1                                                                            # rgen:78
-        if depth >= int(push["maxDepth"]):                                                    # rgen:79
-            break
-        go = mirror | glass
-        live, o, d = px[go], P[go], nxt_d[go]                                                 # rgen:82-84
-    if margins:
-        ev = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in ev.items()}
-    return acc, robust, ev, first
-
-
 def shade_refract(o, d, tori, materials, push, axes=None, info=False):
     """The colour of every ray o, d (n, 3) by the rule of trt_shade_refract.  tori: [(C, R, r, matId)]; materials: dicts
     (ambient, diffuse, specular, shininess, illum, ior, transmittance); push: dict as for truth.shade_frame.
     Returns (rgb (n, 3) float64, robust (n,) bool), and with info also (events, first): the record of every glass hit
     (ray, depth, sin_i, sin_t, n, entering, tir) and the first hit of every ray (id, entering)."""
-    o = np.atleast_2d(np.asarray(o, np.float64))
-    d = np.atleast_2d(np.asarray(d, np.float64))
-    geo = [(np.asarray(C, np.float64), float(R), float(r)) for C, R, r, _ in tori]
-    mat_of = np.array([m for _, _, _, m in tori])
-    M = {k: np.array([np.asarray(m[k], np.float64) for m in materials]) for k in ("ambient", "diffuse", "specular")}
-    shin = np.array([float(m["shininess"]) for m in materials])
-    illum = np.array([int(m["illum"]) for m in materials])
-    ior = np.array([float(materials[m].get("ior", 1.0)) for m in mat_of])                     # by TORUS
-    Tf = np.array([np.asarray(materials[m].get("transmittance", (0.0, 0.0, 0.0)), np.float64) for m in mat_of])
-    args = (o, d, geo, axes, mat_of, M, shin, illum, ior, Tf, push)
-    rgb, robust, ev, first = _trace(*args, 1.0, True)
-    for s in (1.0 + T_EPS, 1.0 - T_EPS):
-        moved, _, _, _ = _trace(*args, s, False)
-        robust &= np.all(np.abs(moved - rgb) <= STABLE_REL * (np.abs(rgb) + 1e-5), axis=1)
-    return (rgb, robust, ev, first) if info else (rgb, robust)
+    rgb, robust, ev, first = shade_truth.shade(o, d, tori, materials, None, [shade_truth.push_light(push)], clear=push["clearColor"],
+                                               max_depth=push["maxDepth"], axes=axes)
+    return (rgb, robust, ev, dict(id=first["id"], entering=first["entering"])) if info else (rgb, robust)
 
 
 def material_dicts(sc):
-    return [dict(ambient=tuple(m.ambient), diffuse=tuple(m.diffuse), specular=tuple(m.specular), shininess=m.shininess,
-                 illum=m.illum, ior=m.ior, transmittance=tuple(m.transmittance)) for m in sc._mats]
+    return shade_truth.material_dicts(sc)
 
 
 def glass(n=1.5, tf=(0.9, 0.95, 1.0), illum=7, **phong):
@@ -241,16 +114,11 @@ def case_scene(name):
     return sc, tori, axes, pc
 
 
-_cases = {}
-
-
 def case(name):
     """The truth of a case on its ray set, made once and never written: dict(o, d, rgb, robust, events, first) plus sc, pc."""
-    if name not in _cases:
+    def make():
         sc, tori, axes, pc = case_scene(name)
         o, d = rays_of(cases()[name][0])
         rgb, robust, ev, first = shade_refract(o, d, tori, material_dicts(sc), through_truth.push_dict(pc), axes, info=True)
-        for a in (rgb, robust, *ev.values(), *first.values()):
-            a.setflags(write=False)
-        _cases[name] = dict(o=o, d=d, rgb=rgb, robust=robust, events=ev, first=first, sc=sc, pc=pc)
-    return _cases[name]
+        return dict(o=o, d=d, rgb=rgb, robust=robust, events=ev, first=first, sc=sc, pc=pc)
+    return shade_truth.cached(("refract", name), make)

@@ -1,161 +1,19 @@
 """FP64 truth for trt_shade_scene* — TEST INFRASTRUCTURE (a helper module: no tests, no fixtures).
 
-The composed rule of include/trt.h in numpy float64, from the pieces of the truth modules of its three ingredients: the
-payload loop and the light table of ``lights_truth`` (``basis``, ``_normals``), the texel of ``textured_truth`` (``uv``,
-``sample``) fetched once per hit and multiplied into every light's diffuse term, the glass step of ``refract_truth``
-(``refract_step``) after the mirror step.  The shadow query is stated here: the crossings of the shadow ray inside its
-window from ``crossings_truth.all_crossings``; a torus that is crossed and is not let through makes the filter 0, one
-that is let through — a glass torus, with the flag — multiplies it by its transmittance once, however often it is
-crossed.  Without the flag nothing is let through and the filter is the opaque query's 0 or 1.  No arithmetic shared
-with the kernels.
-
-``robust`` is the conjunction, over every segment of a ray's path, of
-  * ``crossings_truth.classify_margin_all`` of the segment,
-  * |N·L_l| > 1e-3 at every hit, for every light l,
-  * for EVERY shadow ray, the samples of the area lights included, ``through_truth.transmittance``'s flag over the ray's
-    own window (classify_margin_all there, and no crossing within 1e-3 of a point light's distance),
-  * at every glass hit |N·I| > 1e-3 and |k| > 1e-3,
-and of the stability test of the ingredients: the truth run again with every hit t scaled by 1 + 2e-6 and by 1 - 2e-6
-keeps every channel within ``STABLE_REL`` of the unperturbed colour, relative to |colour| + 1e-5.
+The composed rule of include/trt.h is the whole payload loop of ``shade_truth``: the light table of ``lights_truth`` (or
+the one light of pc), the texel of ``textured_truth`` fetched once per hit and multiplied into every light's diffuse
+term, the glass step of ``refract_truth`` after the mirror step, and the shadow query that, with the flag, lets light
+through a glass torus, multiplied by its transmittance once.  ``robust`` is shade_truth's, every clause of it.  This
+module holds the mixed cases.
 """
-import numpy as np
-
 import crossings_truth as ct
 import lights_truth as lt
 import refract_truth
+import shade_truth
 import textured_truth
 import through_truth
-from oracle import truth
 
-TMIN, TMAX = ct.TMIN, ct.TMAX
-T_EPS, STABLE_REL = lt.T_EPS, lt.STABLE_REL
 MAX_DEPTH = 8
-
-
-def _filter(P, D, geo, axes, bound, through, Tf, margins):
-    """The shadow query of rays (P, D) over (TMIN, bound): (f (m, 3), stable (m,) bool | None).  through (n_tori,) bool:
-    the tori that let light through, filtered by Tf (n_tori, 3)."""
-    ts, sid, _, _ = ct.all_crossings(P, D, geo, axes, TMIN, np.inf)
-    with np.errstate(invalid="ignore"):
-        inside = (sid >= 0) & (ts < np.asarray(bound)[:, None])
-    f = np.ones((len(P), 3))
-    for j in range(len(geo)):
-        hit_j = np.any(inside & (sid == j), axis=1)
-        f[hit_j] *= Tf[j] if through[j] else 0.0
-    stable = None
-    if margins:
-        _, stable = through_truth.transmittance(P, D, geo, np.ones(len(geo)), axes, TMIN, bound)
-    return f, stable
-
-
-def _trace(o, d, geo, axes, mat_of, M, shin, illum, ior, Tf, tex_of, textures, lights, K, disc, through, clear, max_depth, t_scale, margins):
-    """One run of the rule.  margins: also form `robust` (the perturbed runs skip it)."""
-    n = len(o)
-    acc = np.zeros((n, 3))
-    A = np.ones((n, 3))                                                                       # rgen:56
-    robust = np.ones(n, bool)
-    live = np.arange(n)
-    depth = 0
-    while len(live):                                                                          # rgen:62
-        t, tid, _, _ = ct.all_crossings(o, d, geo, axes, TMIN, TMAX)
-        if margins:
-            robust[live] &= ct.classify_margin_all(o, d, geo, axes, TMIN, TMAX)
-        hit = tid[:, 0] >= 0
-        acc[live[~hit]] += clear * 0.8 * A[live[~hit]]                                        # rmiss:37
-        sel = np.flatnonzero(hit)
-        if len(sel) == 0:
-            break
-        px, hid, hd = live[sel], tid[sel, 0], d[sel]
-        P = o[sel] + (t[sel, 0] * t_scale)[:, None] * hd                                      # BEF rchit:134
-        N = lt._normals(P, hid, geo, axes)
-        mi = mat_of[hid]
-        texel = np.ones_like(P)                                                               # step a: once per hit
-        for j, (C, R, r) in enumerate(geo):
-            k = tex_of[mat_of[j]]
-            s = hid == j
-            if k >= 0 and s.any():
-                u, v = textured_truth.uv(P[s], C, None if axes is None else axes[j], R)
-                texel[s] = textured_truth.sample(textures[k], u, v)
-        prd = np.zeros_like(P)
-        for q in lights:                                                                      # step b
-            lp = np.asarray(q["position"], np.float64)
-            if q["type"] == 0:                                                                # rchit:82-88
-                ldir = lp - P
-                ldist = np.linalg.norm(ldir, axis=1)
-                lint = q["intensity"] / (ldist * ldist)
-                L = ldir / ldist[:, None]
-            else:                                                                             # rchit:89-92
-                L = np.tile(lp / np.linalg.norm(lp), (len(P), 1))
-                ldist = np.full(len(P), 100000.0)
-                lint = np.full(len(P), q["intensity"])
-                ldir = L
-            ndl = np.einsum("ni,ni->n", N, L)
-            diffuse = M["diffuse"][mi] * np.maximum(ndl, 0.0)[:, None]                        # wavefront.glsl:25-26
-            diffuse = diffuse + np.where((illum[mi] >= 1)[:, None], M["ambient"][mi], 0.0)    # :27-28
-            diffuse = diffuse * texel                                                         # rchit:105
-            want = ndl > 0                                                                    # rchit:112
-            w = np.flatnonzero(want)
-            v = np.ones((len(P), 3))
-            if len(w):
-                if q["radius"] > 0.0:
-                    Tb, Bb = lt.basis(L[w])
-                    fsum = np.zeros((len(w), 3))
-                    for s in range(K):
-                        a, b = q["radius"] * disc[s, 0], q["radius"] * disc[s, 1]
-                        e = ldir[w] + a * Tb + b * Bb
-                        ln = np.linalg.norm(e, axis=1)
-                        f, stable = _filter(P[w], e / ln[:, None], geo, axes, ln if q["type"] == 0 else np.full(len(w), 100000.0),
-                                            through, Tf, margins)
-                        fsum += f
-                        if margins:
-                            robust[px[w]] &= stable
-                    v[w] = fsum / K
-                else:
-                    f, stable = _filter(P[w], L[w], geo, axes, ldist[w], through, Tf, margins)
-                    v[w] = f
-                    if margins:
-                        robust[px[w]] &= stable
-            att = 0.3 * (1.0 - v) + v                                                         # rchit:133-136, per channel
-            specular = np.zeros_like(P)
-            lit = np.flatnonzero(want & (v.max(axis=1) > 0.0))
-            if len(lit):                                                                      # rchit:140 -> wavefront.glsl:32-48
-                ml = mi[lit]
-                ks = np.maximum(shin[ml], 4.0)
-                energy = (2.0 + ks) / (2.0 * 3.14159265)
-                V = truth._normalize(-hd[lit])
-                Rr = truth._reflect(-L[lit], N[lit])
-                s = energy * np.power(np.maximum(np.einsum("ni,ni->n", V, Rr), 0.0), ks)
-                specular[lit] = np.where((illum[ml] >= 2)[:, None], M["specular"][ml] * s[:, None], 0.0) * v[lit]
-            prd += (att * lint[:, None]) * (diffuse + specular) * np.asarray(q["color"], np.float64)   # rchit:155, per light
-            if margins:
-                robust[px] &= np.abs(ndl) > 1e-3
-        mirror = illum[mi] == 3                                                               # step c, rchit:145
-        glass = (illum[mi] == 6) | (illum[mi] == 7)
-        Ah = A[px]
-        Ah[mirror] *= M["specular"][mi][mirror]                                               # rchit:149, before rgen:76
-        nxt_d = hd.copy()
-        nxt_d[mirror] = truth._reflect(hd[mirror], N[mirror])                                 # rchit:148,152
-        g = np.flatnonzero(glass)
-        if len(g):                                                                            # step d
-            I = truth._normalize(hd[g])
-            nd, Ag, tir, entering, k, eta, cosi = refract_truth.refract_step(I, N[g], ior[hid[g]], Tf[hid[g]], Ah[g])
-            Ah[g] = Ag
-            nxt_d[g] = nd
-            if margins:
-                robust[px[g]] &= (np.abs(cosi) > 1e-3) & (np.abs(k) > 1e-3)
-        acc[px] += prd * Ah                                                                   # rgen:76
-        A[px] = Ah
-        depth += 1                                                                            # rgen:78
-        if depth >= max_depth:                                                                # rgen:79
-            break
-        go = mirror | glass
-        live, o, d = px[go], P[go], nxt_d[go]                                                 # rgen:82-84
-    return acc, robust
-
-
-def push_light(push):
-    """The light of a push-constant dict as the one light of a table: white, radius 0."""
-    return lt.light(push["lightPosition"], push["lightIntensity"], (1.0, 1.0, 1.0), 0 if int(push["lightType"]) == 0 else 1, 0.0)
 
 
 def shade_scene(o, d, tori, materials, textures, push, lights=None, K=1, disc=None, glass_shadows=False, axes=None):
@@ -163,33 +21,8 @@ def shade_scene(o, d, tori, materials, textures, push, lights=None, K=1, disc=No
     (ambient, diffuse, specular, shininess, illum and, optionally, ior, transmittance, textureId); textures: dicts as
     ``textured_truth.texture`` makes them; push: through_truth.push_dict (clearColor, maxDepth and, for lights None, the
     light); lights: dicts as ``lights_truth.light`` makes them, or None.  Returns (rgb (n, 3) float64, robust (n,) bool)."""
-    o = np.atleast_2d(np.asarray(o, np.float64))
-    d = np.atleast_2d(np.asarray(d, np.float64))
-    geo = [(np.asarray(C, np.float64), float(R), float(r)) for C, R, r, _ in tori]
-    mat_of = np.array([m for _, _, _, m in tori])
-    M = {k: np.array([np.asarray(m[k], np.float64) for m in materials]) for k in ("ambient", "diffuse", "specular")}
-    shin = np.array([float(m["shininess"]) for m in materials])
-    illum = np.array([int(m["illum"]) for m in materials])
-    ior = np.array([float(materials[m].get("ior", 1.0)) for m in mat_of])                     # by TORUS
-    Tf = np.array([np.asarray(materials[m].get("transmittance", (0.0, 0.0, 0.0)), np.float64) for m in mat_of])
-    tex_of = np.array([int(m.get("textureId", -1)) for m in materials])
-    assert tex_of.max(initial=-1) < len(textures)
-    is_glass = (illum[mat_of] == 6) | (illum[mat_of] == 7)
-    through = is_glass & bool(glass_shadows)
-    table = [push_light(push)] if lights is None else list(lights)
-    disc = None if disc is None else np.asarray(disc, np.float64).reshape(-1, 2)
-    args = (o, d, geo, axes, mat_of, M, shin, illum, ior, Tf, tex_of, list(textures), table, int(K), disc, through,
-            np.asarray(push["clearColor"], np.float64)[:3], max(int(push["maxDepth"]), 1))
-    rgb, robust = _trace(*args, 1.0, True)
-    for s in (1.0 + T_EPS, 1.0 - T_EPS):
-        moved, _ = _trace(*args, s, False)
-        robust &= np.all(np.abs(moved - rgb) <= STABLE_REL * (np.abs(rgb) + 1e-5), axis=1)
-    return rgb, robust
-
-
-def material_dicts(sc):
-    return [dict(ambient=tuple(m.ambient), diffuse=tuple(m.diffuse), specular=tuple(m.specular), shininess=m.shininess,
-                 illum=m.illum, ior=m.ior, transmittance=tuple(m.transmittance), textureId=m.textureId) for m in sc._mats]
+    return shade_truth.shade(o, d, tori, materials, list(textures), [shade_truth.push_light(push)] if lights is None else lights, K, disc,
+                             glass_shadows, push["clearColor"], push["maxDepth"], axes)[:2]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -233,21 +66,15 @@ def case_scene(name):
     return abi.Scene(tori, mats, axes=axes), tori, axes, pc, mats, textures, lights, K
 
 
-_cases = {}
-
-
 def case(name, glass_shadows):
     """The truth of a mixed case on its ray set, flag off or on, made once and never written: dict(o, d, rgb, robust) plus
     sc, pc, the textures and the lights as the binding takes them, K and the disc table (abi.disc_samples(K))."""
-    key = (name, bool(glass_shadows))
-    if key not in _cases:
+    def make():
         from toroidal_ray_tracing_amd import abi
         sc, tori, axes, pc, mats, textures, lights, K = case_scene(name)
         s = ct.ray_set(cases()[name][0])
         disc = abi.disc_samples(K)
-        rgb, robust = shade_scene(s["o"], s["d"], tori, mats, textures, through_truth.push_dict(pc), lights, K, disc, key[1], axes)
-        for a in (rgb, robust, disc):
-            a.setflags(write=False)
-        _cases[key] = dict(o=s["o"], d=s["d"], rgb=rgb, robust=robust, sc=sc, pc=pc, tex=textured_truth.abi_textures(textures),
-                           lights=lt.abi_lights(lights), K=K, disc=disc)
-    return _cases[key]
+        rgb, robust = shade_scene(s["o"], s["d"], tori, mats, textures, through_truth.push_dict(pc), lights, K, disc, glass_shadows, axes)
+        return dict(o=s["o"], d=s["d"], rgb=rgb, robust=robust, sc=sc, pc=pc, tex=textured_truth.abi_textures(textures),
+                    lights=lt.abi_lights(lights), K=K, disc=disc)
+    return shade_truth.cached(("scene", name, bool(glass_shadows)), make)

@@ -17,100 +17,25 @@ import camera_truth
 import crossings_truth as ct
 import refract_truth as rt
 import through_truth as tt
-from camera_support import image as frame_image, n_rays, ray_buffers, read_image, stream_handle
+from camera_support import n_rays, ray_buffers, stream_handle
+from shade_support import (ALL_SOLVER_IDS, ALL_SOLVERS, QUERY_KEYS, SENTINEL, SOLVER_IDS, SOLVERS, camera_call, frame_image, image,
+                           meets_truth_bars, rays_call, read, read_image, shade_dev, tr, u32, upload)  # noqa: F401 (tr: a fixture)
 from toroidal_ray_tracing_amd import abi, camera
 
 pytestmark = pytest.mark.gpu
 
 COLOR_RTOL, COLOR_ATOL = 1e-5, 1e-6   # the project's bars on colours (tests/test_gpu_parity.py)
-SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64]
-SOLVER_IDS = ["f32", "f64"]
-ALL_SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64, abi.TRT_SOLVE_DK_F32, abi.TRT_SOLVE_DK_F64, abi.TRT_SOLVE_FERRARI_F32,
-               abi.TRT_SOLVE_FERRARI_F64]
-ALL_SOLVER_IDS = ["f32", "f64", "dk32", "dk64", "ferrari32", "ferrari64"]
-SENTINEL = -7.25
-PAD = 8
 W = H = 64
 BAND = (5, 59)
-QUERY_KEYS = ("primary_tests", "bounce_tests", "shadow_tests")
 f32 = np.float32
 
 
-@pytest.fixture(scope="module")
-def tr():
-    from toroidal_ray_tracing_amd.tracer import Tracer
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def upload(o, d):
-    import torch
-    dev = torch.device("cuda:0")
-    soa = [torch.from_numpy(np.array(a[:, k], np.float32)).to(dev) for a in (o, d) for k in range(3)]   # (a writable copy)
-    return soa, [a.data_ptr() for a in soa]
-
-
-def image(n_floats):
-    import torch
-    return torch.full((n_floats + PAD,), SENTINEL, dtype=torch.float32, device="cuda:0")
-
-
-def read(buf, n_floats):
-    raw = buf.cpu().numpy()
-    assert (raw[n_floats:] == f32(SENTINEL)).all(), "written beyond the output"
-    return raw[:n_floats].copy()
-
-
-def _rays_call(tr, which, sc, o, d, pc, samples, solver, stats):
-    """One trt_shade_dev / trt_shade_refract_dev call into a sentinel-padded image: (n_out, 4) [, stats]."""
-    import torch
-    n_out = len(o) // samples
-    keep, ptrs = upload(o, d) if len(o) else (None, [0] * 6)
-    buf = image(n_out * 4)
-    tr.set_solver(solver)
-    tr.enable_stats(stats)
-    try:
-        getattr(tr, which)(sc, ptrs, len(o), pc, buf.data_ptr(), samples=samples, stream=stream_handle())
-        st = tr.stats() if stats else None
-    finally:
-        tr.enable_stats(False)
-        tr.set_solver(abi.TRT_SOLVE_F32)
-        tr.set_torus_axes(None)
-    torch.cuda.synchronize()
-    out = read(buf, n_out * 4).reshape(n_out, 4)
-    return (out, st) if stats else out
-
-
 def refract_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
-    return _rays_call(tr, "shade_refract_dev", sc, o, d, pc, samples, solver, stats)
-
-
-def shade_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
-    return _rays_call(tr, "shade_dev", sc, o, d, pc, samples, solver, stats)
+    return rays_call(tr, "shade_refract_dev", sc, o, d, pc, samples, solver, stats)
 
 
 def refract_camera_dev(tr, sc, g, pc, cam, samples=1, offsets=None, rows=None, solver=abi.TRT_SOLVE_F32, stats=False):
-    """One trt_shade_refract_camera_dev call into a sentinel-filled full-frame image: (H, W, 4) [, stats]."""
-    import torch
-    buf = frame_image(W, H)
-    tr.set_solver(solver)
-    tr.enable_stats(stats)
-    try:
-        tr.shade_refract_camera_dev(sc, g, pc, W, H, buf.data_ptr(), camera=cam, samples=samples, offsets=offsets, rows=rows,
-                                    stream=stream_handle())
-        st = tr.stats() if stats else None
-    finally:
-        tr.enable_stats(False)
-        tr.set_solver(abi.TRT_SOLVE_F32)
-        tr.set_torus_axes(None)
-    torch.cuda.synchronize()
-    out = read_image(buf, W, H, rows)
-    return (out, st) if stats else out
+    return camera_call(tr, "shade_refract_camera_dev", sc, g, pc, W, H, cam, samples, offsets, rows, solver, stats)
 
 
 _camera_rays = {}
@@ -226,10 +151,7 @@ def test_against_the_fp64_truth(tr, name, solver):
     c = rt.case(name)
     assert c["robust"].mean() > 0.9
     got = refract_dev(tr, c["sc"], c["o"], c["d"], c["pc"], solver=solver)[:, :3].astype(np.float64)
-    rel = (np.abs(got - c["rgb"]) / (np.abs(c["rgb"]) + 1e-5)).max(axis=-1)[c["robust"]]
-    print(f"{name} {SOLVER_IDS[SOLVERS.index(solver)]}: robust {c['robust'].mean():.4f}, rel max {rel.max():.3e}, "
-          f"over 1e-4: {int((rel > 1e-4).sum())} of {len(rel)}")
-    assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (name, rel.max(), int((rel > 1e-4).sum()))
+    meets_truth_bars(got, c, f"{name} {SOLVER_IDS[SOLVERS.index(solver)]}")
     miss = np.asarray(c["pc"].clearColor[:3]) * 0.8
     assert (np.abs(c["rgb"] - miss).max(1) > 1e-3).mean() > 0.5   # (most rays of a set see a surface)
 

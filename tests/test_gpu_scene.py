@@ -24,109 +24,25 @@ import lights_truth as lt
 import refract_truth as rt
 import scene_truth as sct
 import textured_truth as tt
-from camera_support import image as frame_image, n_rays, ray_buffers, read_image, stream_handle
+from camera_support import n_rays, ray_buffers, stream_handle
+from shade_support import (ALL_SOLVER_IDS, ALL_SOLVERS, SENTINEL, SOLVER_IDS, SOLVERS, camera_call, frame_image, image,
+                           meets_truth_bars, rays_call, read, read_image, same, tr, u32, upload)  # noqa: F401 (tr: a fixture)
 from toroidal_ray_tracing_amd import abi, camera
 
 pytestmark = pytest.mark.gpu
 
-SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64]
-SOLVER_IDS = ["f32", "f64"]
-ALL_SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64, abi.TRT_SOLVE_DK_F32, abi.TRT_SOLVE_DK_F64, abi.TRT_SOLVE_FERRARI_F32,
-               abi.TRT_SOLVE_FERRARI_F64]
-ALL_SOLVER_IDS = ["f32", "f64", "dk32", "dk64", "ferrari32", "ferrari64"]
-SENTINEL = -7.25
-PAD = 8
 W, H = 24, 16
 BAND = (3, 13)
-QUERY_KEYS = ("primary_tests", "bounce_tests", "shadow_tests")
 f32 = np.float32
 
 
-@pytest.fixture(scope="module")
-def tr():
-    from toroidal_ray_tracing_amd.tracer import Tracer
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def queries(st):
-    return {k: st[k] for k in QUERY_KEYS}
-
-
-def upload(o, d):
-    import torch
-    dev = torch.device("cuda:0")
-    soa = [torch.from_numpy(np.array(a[:, k], np.float32)).to(dev) for a in (o, d) for k in range(3)]   # (a writable copy)
-    return soa, [a.data_ptr() for a in soa]
-
-
-def image(n_floats):
-    import torch
-    return torch.full((n_floats + PAD,), SENTINEL, dtype=torch.float32, device="cuda:0")
-
-
-def read(buf, n_floats):
-    raw = buf.cpu().numpy()
-    assert (raw[n_floats:] == f32(SENTINEL)).all(), "written beyond the output"
-    return raw[:n_floats].copy()
-
-
-def rays_call(tr, which, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False, textures=None, **kw):
-    """One *_dev call of a stream form into a sentinel-padded image, `textures` bound around it: (n_out, 4) [, stats]."""
-    import torch
-    n_out = len(o) // samples
-    keep, ptrs = upload(o, d)
-    buf = image(n_out * 4)
-    tr.set_solver(solver)
-    tr.enable_stats(stats)
-    tr.set_textures(textures)
-    try:
-        getattr(tr, which)(sc, ptrs, len(o), pc, buf.data_ptr(), samples=samples, stream=stream_handle(), **kw)
-        st = tr.stats() if stats else None
-        torch.cuda.synchronize()
-    finally:
-        tr.enable_stats(False)
-        tr.set_solver(abi.TRT_SOLVE_F32)
-        tr.set_torus_axes(None)
-        tr.set_textures(None)
-    out = read(buf, n_out * 4).reshape(n_out, 4)
-    return (out, st) if stats else out
-
-
-def scene_dev(tr, sc, o, d, pc, **kw):
-    return rays_call(tr, "shade_scene_dev", sc, o, d, pc, **kw)
+def scene_dev(tr, sc, o, d, pc, textures=None, **kw):
+    """(`textures` bound around the call; without, nothing is bound)"""
+    return rays_call(tr, "shade_scene_dev", sc, o, d, pc, textures=textures, **kw)
 
 
 def scene_camera_dev(tr, sc, g, pc, cam, samples=1, offsets=None, rows=None, solver=abi.TRT_SOLVE_F32, stats=False, textures=None, **kw):
-    """One trt_shade_scene_camera_dev call into a sentinel-filled full-frame image: (H, W, 4) [, stats]."""
-    import torch
-    buf = frame_image(W, H)
-    tr.set_solver(solver)
-    tr.enable_stats(stats)
-    tr.set_textures(textures)
-    try:
-        tr.shade_scene_camera_dev(sc, g, pc, W, H, buf.data_ptr(), camera=cam, samples=samples, offsets=offsets, rows=rows,
-                                  stream=stream_handle(), **kw)
-        st = tr.stats() if stats else None
-        torch.cuda.synchronize()
-    finally:
-        tr.enable_stats(False)
-        tr.set_solver(abi.TRT_SOLVE_F32)
-        tr.set_torus_axes(None)
-        tr.set_textures(None)
-    out = read_image(buf, W, H, rows)
-    return (out, st) if stats else out
-
-
-def same(got, want, key):
-    (g, gs), (w, ws) = got, want
-    assert np.array_equal(u32(g), u32(w)), (key, int((u32(g) != u32(w)).any(axis=1).sum()))
-    assert queries(gs) == queries(ws), key
+    return camera_call(tr, "shade_scene_camera_dev", sc, g, pc, W, H, cam, samples, offsets, rows, solver, stats, textures, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -326,10 +242,7 @@ def test_against_the_fp64_truth(tr, name, flag, solver):
     max <= 2e-3."""
     c = sct.case(name, flag)
     got = scene_dev(tr, c["sc"], c["o"], c["d"], c["pc"], solver=solver, **mixed_kw(c, flag))[:, :3].astype(np.float64)
-    rel = (np.abs(got - c["rgb"]) / (np.abs(c["rgb"]) + 1e-5)).max(axis=-1)[c["robust"]]
-    print(f"{name} flag={flag} {SOLVER_IDS[SOLVERS.index(solver)]}: robust {c['robust'].mean():.4f}, rel max {rel.max():.3e}, "
-          f"over 1e-4: {int((rel > 1e-4).sum())} of {len(rel)}")
-    assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (name, flag, rel.max(), int((rel > 1e-4).sum()))
+    meets_truth_bars(got, c, f"{name} flag={flag} {SOLVER_IDS[SOLVERS.index(solver)]}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

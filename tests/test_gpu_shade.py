@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import seeded_rays
+from shade_support import PAD, SENTINEL, SOLVER_IDS, SOLVERS, shade_dev, tr, u32, upload  # noqa: F401 (tr: a fixture)
 from toroidal_ray_tracing_amd import abi, camera
 
 pytestmark = pytest.mark.gpu
@@ -25,10 +26,6 @@ W, H = 100, 68
 N = W * H
 COLOR_RTOL, COLOR_ATOL = 1e-5, 1e-6   # the project's bars on colours against the oracle (tests/test_gpu_parity.py)
 QUERY_KEYS = ("primary_tests", "bounce_tests", "shadow_tests", "pixels")
-SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64]
-SOLVER_IDS = ["f32", "f64"]
-SENTINEL = -7.25
-PAD = 8   # floats behind the image that must keep the sentinel
 
 # the frames of RENDERS in tests/test_gpu_parity.py, restated
 RENDERS = {
@@ -80,27 +77,8 @@ ORIENTED = {
 }
 
 
-@pytest.fixture(scope="module")
-def tr():
-    from toroidal_ray_tracing_amd.tracer import Tracer
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def q(stats):
     return {k: stats[k] for k in QUERY_KEYS}
-
-
-def upload(o, d):
-    import torch
-    dev = torch.device("cuda:0")
-    soa = [torch.from_numpy(np.ascontiguousarray(a[:, k])).to(dev) for a in (o, d) for k in range(3)]
-    return soa, [a.data_ptr() for a in soa]
 
 
 def image(n_out):
@@ -113,25 +91,6 @@ def read_image(buf, n_out):
     raw = buf.cpu().numpy()
     assert (raw[n_out * 4:] == np.float32(SENTINEL)).all(), "written beyond the image"
     return raw[:n_out * 4].reshape(n_out, 4).copy()
-
-
-def shade_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
-    """One trt_shade_dev call on uploaded rays into a sentinel-filled image: (n / samples, 4) float32 [, stats]."""
-    import torch
-    n = len(o)
-    keep, ptrs = upload(o, d) if n else (None, [0] * 6)
-    buf = image(n // samples)
-    tr.set_solver(solver)
-    tr.enable_stats(stats)
-    try:
-        tr.shade_dev(sc, ptrs, n, pc, buf.data_ptr(), samples=samples, stream=torch.cuda.current_stream().cuda_stream)
-        st = tr.stats() if stats else None
-    finally:
-        tr.enable_stats(False)
-        tr.set_solver(abi.TRT_SOLVE_F32)
-    torch.cuda.synchronize()
-    out = read_image(buf, n // samples)
-    return (out, st) if stats else out
 
 
 _frames = {}

@@ -17,48 +17,16 @@ import pytest
 
 import crossings_truth as ct
 import through_truth as tt
+from camera_support import stream_handle
+from shade_support import (QUERY_KEYS, SENTINEL, SOLVER_IDS, SOLVERS, bracket, image, meets_truth_bars, rays_call, read, shade_dev, tr,  # noqa: F401
+                           u32, upload)
 from toroidal_ray_tracing_amd import abi, camera
 
 pytestmark = pytest.mark.gpu
 
 COLOR_RTOL, COLOR_ATOL = 1e-5, 1e-6   # the project's bars on colours (tests/test_gpu_parity.py)
-SOLVERS = [abi.TRT_SOLVE_F32, abi.TRT_SOLVE_F64]
-SOLVER_IDS = ["f32", "f64"]
-SENTINEL = -7.25
-PAD = 8
 K_ALL = abi.TRT_MAX_CROSSINGS
-QUERY_KEYS = ("primary_tests", "bounce_tests", "shadow_tests")
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def tr():
-    from toroidal_ray_tracing_amd.tracer import Tracer
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def upload(o, d):
-    import torch
-    dev = torch.device("cuda:0")
-    soa = [torch.from_numpy(np.array(a[:, k], np.float32)).to(dev) for a in (o, d) for k in range(3)]   # (a writable copy)
-    return soa, [a.data_ptr() for a in soa]
-
-
-def image(n_floats):
-    import torch
-    return torch.full((n_floats + PAD,), SENTINEL, dtype=torch.float32, device="cuda:0")
-
-
-def read(buf, n_floats):
-    raw = buf.cpu().numpy()
-    assert (raw[n_floats:] == f32(SENTINEL)).all(), "written beyond the output"
-    return raw[:n_floats].copy()
 
 
 def scene_of(name, alpha, mats=None, only=None):
@@ -70,44 +38,21 @@ def scene_of(name, alpha, mats=None, only=None):
                      [dict(mats[j], dissolve=alpha[j]) for j in pick], axes=None if axes is None else [axes[j] for j in pick])
 
 
-def _call(tr, fn, sc, o, d, solver, stats, n_floats, **kw):
-    import torch
-    keep, ptrs = upload(o, d) if len(o) else (None, [0] * 6)
-    buf = image(n_floats)
-    tr.set_solver(solver)
-    tr.enable_stats(stats)
-    try:
-        fn(sc, ptrs, len(o), buf.data_ptr(), stream=torch.cuda.current_stream().cuda_stream, **kw)
-        st = tr.stats() if stats else None
-    finally:
-        tr.enable_stats(False)
-        tr.set_solver(abi.TRT_SOLVE_F32)
-        tr.set_torus_axes(None)
-    torch.cuda.synchronize()
-    return read(buf, n_floats), st
-
-
 def transmittance_dev(tr, sc, o, d, solver=abi.TRT_SOLVE_F32, tmin=ct.TMIN, tmax=ct.TMAX, bound=None, stats=False):
+    """One float per ray, not an image: the bracket of rays_call around trt_transmittance_dev."""
     import torch
     b = None if bound is None else torch.from_numpy(np.ascontiguousarray(bound, np.float32)).to("cuda:0")
-    T, st = _call(tr, lambda sc_, p, n, out, stream: tr.transmittance_dev(sc_, p, n, out, tmax_ptr=0 if b is None else b.data_ptr(),
-                                                                         tmin=tmin, tmax=tmax, stream=stream),
-                  sc, o, d, solver, stats, len(o))
-    return (T, st) if stats else T
+    keep, ptrs = upload(o, d) if len(o) else (None, [0] * 6)
+    buf = image(len(o))
+    with bracket(tr, solver, stats) as got:
+        tr.transmittance_dev(sc, ptrs, len(o), buf.data_ptr(), tmax_ptr=0 if b is None else b.data_ptr(), tmin=tmin, tmax=tmax,
+                             stream=stream_handle())
+    T = read(buf, len(o))
+    return (T, got["stats"]) if stats else T
 
 
 def through_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
-    n_out = len(o) // samples
-    out, st = _call(tr, lambda sc_, p, n, img, stream: tr.shade_through_dev(sc_, p, n, pc, img, samples=samples, stream=stream),
-                    sc, o, d, solver, stats, n_out * 4)
-    return (out.reshape(n_out, 4), st) if stats else out.reshape(n_out, 4)
-
-
-def shade_dev(tr, sc, o, d, pc, samples=1, solver=abi.TRT_SOLVE_F32, stats=False):
-    n_out = len(o) // samples
-    out, st = _call(tr, lambda sc_, p, n, img, stream: tr.shade_dev(sc_, p, n, pc, img, samples=samples, stream=stream),
-                    sc, o, d, solver, stats, n_out * 4)
-    return (out.reshape(n_out, 4), st) if stats else out.reshape(n_out, 4)
+    return rays_call(tr, "shade_through_dev", sc, o, d, pc, samples, solver, stats)
 
 
 def crossings_dev(tr, sc, o, d, solver, tmin=ct.TMIN, tmax=ct.TMAX):
@@ -117,14 +62,9 @@ def crossings_dev(tr, sc, o, d, solver, tmin=ct.TMIN, tmax=ct.TMAX):
     keep, ptrs = upload(o, d)
     t = torch.empty((K_ALL, n), dtype=torch.float32, device="cuda:0")
     tid = torch.empty((K_ALL, n), dtype=torch.int32, device="cuda:0")
-    tr.set_solver(solver)
-    try:
+    with bracket(tr, solver):
         tr.crossings_dev(sc, ptrs, n, {"t": t.data_ptr(), "id": tid.data_ptr()}, max_per_ray=K_ALL, tmin=tmin, tmax=tmax,
-                         stream=torch.cuda.current_stream().cuda_stream)
-    finally:
-        tr.set_solver(abi.TRT_SOLVE_F32)
-        tr.set_torus_axes(None)
-    torch.cuda.synchronize()
+                         stream=stream_handle())
     return t.cpu().numpy(), tid.cpu().numpy()
 
 
@@ -331,10 +271,7 @@ def test_against_the_fp64_truth(tr, name, solver):
     c = tt.case(name)
     assert 1.0 - c["robust"].mean() <= c["cap"]
     got = through_dev(tr, c["sc"], c["o"], c["d"], c["pc"], solver=solver)[:, :3].astype(np.float64)
-    rel = (np.abs(got - c["rgb"]) / (np.abs(c["rgb"]) + 1e-5)).max(axis=-1)[c["robust"]]
-    print(f"{name} {SOLVER_IDS[SOLVERS.index(solver)]}: robust {c['robust'].mean():.4f}, rel max {rel.max():.3e}, "
-          f"over 1e-4: {int((rel > 1e-4).sum())} of {len(rel)}")
-    assert (rel <= 1e-4).mean() >= 0.995 and rel.max() <= 2e-3, (name, rel.max(), int((rel > 1e-4).sum()))
+    meets_truth_bars(got, c, f"{name} {SOLVER_IDS[SOLVERS.index(solver)]}")
     miss = np.asarray(c["pc"].clearColor[:3]) * 0.8
     assert (np.abs(c["rgb"] - miss).max(1) > 1e-3).mean() > 0.5   # (most rays of a set see a shell)
 

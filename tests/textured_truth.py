@@ -1,24 +1,21 @@
 """FP64 truth for trt_shade_textured* and trt_hit_uv — TEST INFRASTRUCTURE (a helper module: no tests, no fixtures).
 
-``lights_truth.py``'s payload loop with the one hard white light of the push constants, and the texel of the hit
-multiplied into ``diffuse`` where the material names a texture (REFL/shaders/raytrace.rchit:101-106).  The (u, v) of a
-hit comes from the LIBRARY's frame rule, restated here from include/trt.h — h = e_x if |a_x| <= |a_z| else e_z,
-u = normalize(h - a_h a), w = u x a, rows (u, a, w) — and not from ``oriented_truth.frame``, which picks another
-u-direction in general: where u = 0 lies is part of the contract.  ``np.arctan2``, float64 bilinear with wrap, the
-piecewise sRGB formula: no arithmetic shared with the kernels.
+The rule of include/trt.h: the payload loop of ``shade_truth`` with the one hard white light of the push constants,
+glass not known, and the texel of the hit multiplied into ``diffuse`` where the material names a texture
+(REFL/shaders/raytrace.rchit:101-106).  The texel is stated here and called by the loop.  The (u, v) of a hit comes from
+the LIBRARY's frame rule, restated from include/trt.h — h = e_x if |a_x| <= |a_z| else e_z, u = normalize(h - a_h a),
+w = u x a, rows (u, a, w) — and not from ``oriented_truth.frame``, which picks another u-direction in general: where
+u = 0 lies is part of the contract.  ``np.arctan2``, float64 bilinear with wrap, the piecewise sRGB formula: no
+arithmetic shared with the kernels.
 
-``robust`` is lights_truth's: the margins of every segment and every shadow ray, |N.L| > 1e-3, and the stability run —
-the truth again with every hit t scaled by 1 +- 2e-6 keeps every channel within ``STABLE_REL`` relative to
-|colour| + 1e-5.  That run is what removes a ray whose colour hangs on a texel edge.
+``robust`` is shade_truth's: the margins of every segment and every shadow ray, |N.L| > 1e-3, and the stability run.
+That run is what removes a ray whose colour hangs on a texel edge.
 """
 import numpy as np
 
 import crossings_truth as ct
-import lights_truth as lt
-from oracle import truth
-
-TMIN, TMAX = ct.TMIN, ct.TMAX
-T_EPS, STABLE_REL = lt.T_EPS, lt.STABLE_REL
+import shade_truth
+import through_truth
 
 
 def frame(axis):
@@ -78,104 +75,14 @@ def sample(tex, u, v):
     return top * (1.0 - fy) + bot * fy
 
 
-def _trace(o, d, geo, axes, mat_of, M, shin, illum, tex_of, textures, push, max_depth, t_scale, margins):
-    """One run of the rule (lights_truth._trace with pc's light, and the texel)."""
-    n = len(o)
-    acc = np.zeros((n, 3))
-    A = np.ones((n, 3))                                                                       # rgen:56
-    robust = np.ones(n, bool)
-    first = np.full(n, -1)
-    live = np.arange(n)
-    clear = np.asarray(push["clearColor"], np.float64)[:3]
-    lp = np.asarray(push["lightPosition"], np.float64)
-    depth = 0
-    while len(live):                                                                          # rgen:62
-        t, tid, _, _ = ct.all_crossings(o, d, geo, axes, TMIN, TMAX)
-        if margins:
-            robust[live] &= ct.classify_margin_all(o, d, geo, axes, TMIN, TMAX)
-        hit = tid[:, 0] >= 0
-        acc[live[~hit]] += clear * 0.8 * A[live[~hit]]                                        # rmiss:37
-        sel = np.flatnonzero(hit)
-        if len(sel) == 0:
-            break
-        px, hid, hd = live[sel], tid[sel, 0], d[sel]
-        P = o[sel] + (t[sel, 0] * t_scale)[:, None] * hd                                      # BEF rchit:134
-        N = lt._normals(P, hid, geo, axes)
-        mi = mat_of[hid]
-        if push["lightType"] == 0:                                                            # rchit:82-88
-            ldir = lp - P
-            ldist = np.linalg.norm(ldir, axis=1)
-            lint = push["lightIntensity"] / (ldist * ldist)
-            L = ldir / ldist[:, None]
-        else:                                                                                 # rchit:89-92
-            L = np.tile(lp / np.linalg.norm(lp), (len(P), 1))
-            ldist = np.full(len(P), 100000.0)
-            lint = np.full(len(P), float(push["lightIntensity"]))
-        ndl = np.einsum("ni,ni->n", N, L)
-        diffuse = M["diffuse"][mi] * np.maximum(ndl, 0.0)[:, None]                            # wavefront.glsl:25-26
-        diffuse = diffuse + np.where((illum[mi] >= 1)[:, None], M["ambient"][mi], 0.0)        # :27-28
-        for j, (C, R, r) in enumerate(geo):                                                   # rchit:101-106
-            k = tex_of[mat_of[j]]
-            s = hid == j
-            if k >= 0 and s.any():
-                u, v = uv(P[s], C, None if axes is None else axes[j], R)
-                diffuse[s] *= sample(textures[k], u, v)
-        want = ndl > 0                                                                        # rchit:112
-        w = np.flatnonzero(want)
-        shadowed = np.zeros(len(P), bool)
-        if len(w):
-            h, stable = lt._occluded(P[w], L[w], geo, axes, ldist[w], margins)
-            shadowed[w] = h
-            if margins:
-                robust[px[w]] &= stable
-        att = np.where(shadowed, 0.3, 1.0)                                                    # rchit:133-136
-        specular = np.zeros_like(P)
-        lit = np.flatnonzero(want & ~shadowed)
-        if len(lit):                                                                          # rchit:140 -> wavefront.glsl:32-48
-            ml = mi[lit]
-            ks = np.maximum(shin[ml], 4.0)
-            energy = (2.0 + ks) / (2.0 * 3.14159265)
-            V = truth._normalize(-hd[lit])
-            Rr = truth._reflect(-L[lit], N[lit])
-            sp = energy * np.power(np.maximum(np.einsum("ni,ni->n", V, Rr), 0.0), ks)
-            specular[lit] = np.where((illum[ml] >= 2)[:, None], M["specular"][ml] * sp[:, None], 0.0)
-        prd = (att * lint)[:, None] * (diffuse + specular)                                    # rchit:155
-        if margins:
-            robust[px] &= np.abs(ndl) > 1e-3
-            if depth == 0:
-                first[px] = hid
-        mirror = illum[mi] == 3                                                               # rchit:145
-        Ah = A[px]
-        Ah[mirror] *= M["specular"][mi][mirror]                                               # rchit:149, before rgen:76
-        acc[px] += prd * Ah                                                                   # rgen:76
-        A[px] = Ah
-        depth += 1                                                                            # rgen:78
-        if depth >= max_depth:                                                                # rgen:79
-            break
-        live, o, d = px[mirror], P[mirror], truth._reflect(hd[mirror], N[mirror])             # rgen:82-84, rchit:148,152
-    return acc, robust, first
-
-
 def shade_textured(o, d, tori, materials, textures, push, axes=None, info=False):
     """The colour of every ray o, d (n, 3) by the rule of trt_shade_textured.  tori: [(C, R, r, matId)]; materials: dicts
     (ambient, diffuse, specular, shininess, illum and, optionally, textureId: -1 or an index into ``textures``); textures:
     dicts as ``texture`` makes them; push: through_truth.push_dict.  Returns (rgb (n, 3) float64, robust (n,) bool) and,
     with info, the id of the first hit (-1: a miss)."""
-    o = np.atleast_2d(np.asarray(o, np.float64))
-    d = np.atleast_2d(np.asarray(d, np.float64))
-    geo = [(np.asarray(C, np.float64), float(R), float(r)) for C, R, r, _ in tori]
-    mat_of = np.array([m for _, _, _, m in tori])
-    M = {k: np.array([np.asarray(m[k], np.float64) for m in materials]) for k in ("ambient", "diffuse", "specular")}
-    shin = np.array([float(m["shininess"]) for m in materials])
-    illum = np.array([int(m["illum"]) for m in materials])
-    tex_of = np.array([int(m.get("textureId", -1)) for m in materials])
-    assert tex_of.max(initial=-1) < len(textures)
-    args = (o, d, geo, axes, mat_of, M, shin, illum, tex_of, list(textures), push, max(int(push["maxDepth"]), 1))
-    rgb, robust, first = _trace(*args, 1.0, True)
-    for s in (1.0 + T_EPS, 1.0 - T_EPS):
-        moved, _, _ = _trace(*args, s, False)
-        robust &= np.all(np.abs(moved - rgb) <= STABLE_REL * (np.abs(rgb) + 1e-5), axis=1)
-    return (rgb, robust, first) if info else (rgb, robust)
+    rgb, robust, _, first = shade_truth.shade(o, d, tori, materials, list(textures), [shade_truth.push_light(push)],
+                                              clear=push["clearColor"], max_depth=push["maxDepth"], axes=axes, glass=False)
+    return (rgb, robust, first["id"]) if info else (rgb, robust)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -226,21 +133,15 @@ def case_scene(name, textured=True):
     return abi.Scene(tori, mats, axes=axes), tori, axes, abi.make_push(max_depth=depth), mats, textures
 
 
-_cases = {}
-
-
 def case(name):
     """The truth of a case on its ray set, made once and never written: dict(o, d, rgb, robust, first, plain) — plain the
     truth of the same scene without textures — plus sc, pc and the textures as the truth and as the binding take them."""
-    if name not in _cases:
-        import through_truth
+    def make():
         sc, tori, axes, pc, mats, textures = case_scene(name)
         s = ct.ray_set(cases()[name][0])
         push = through_truth.push_dict(pc)
         rgb, robust, first = shade_textured(s["o"], s["d"], tori, mats, textures, push, axes, info=True)
         plain, _ = shade_textured(s["o"], s["d"], tori, [dict(m, textureId=-1) for m in mats], [], push, axes)
-        for a in (rgb, robust, first, plain):
-            a.setflags(write=False)
-        _cases[name] = dict(o=s["o"], d=s["d"], rgb=rgb, robust=robust, first=first, plain=plain, sc=sc, pc=pc, tori=tori, axes=axes,
-                            mats=mats, textures=textures, tex=abi_textures(textures))
-    return _cases[name]
+        return dict(o=s["o"], d=s["d"], rgb=rgb, robust=robust, first=first, plain=plain, sc=sc, pc=pc, tori=tori, axes=axes,
+                    mats=mats, textures=textures, tex=abi_textures(textures))
+    return shade_truth.cached(("textured", name), make)

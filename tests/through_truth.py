@@ -14,7 +14,7 @@ on a path; no arithmetic shared with the kernels.
 import numpy as np
 
 import crossings_truth as ct
-import oriented_truth
+import shade_truth
 from oracle import truth
 
 TMIN, TMAX = ct.TMIN, ct.TMAX
@@ -86,11 +86,7 @@ def shade_through(o, d, tori, materials, alpha, push, axes=None, tmin=TMIN, tmax
             hid, hd = tid[sel, k], d[sel]
             px = live[sel]
             P = o[sel] + t[sel, k][:, None] * hd                                              # BEF rchit:134
-            N = np.zeros_like(P)
-            for i, (C, R, r) in enumerate(geo):
-                s = hid == i
-                if s.any():
-                    N[s] = truth.normal(P[s], C, R) if axes is None else oriented_truth.normal(P[s], C, axes[i], R)
+            N = shade_truth.normals(P, hid, geo, axes)
             if int(push["lightType"]) == 0:                                                   # rchit:82-88
                 ldir = lp - P
                 ldist = np.linalg.norm(ldir, axis=1)
