@@ -37,6 +37,8 @@
  *   torus' tube                    trt_crossings' entries and exits)     trt_chords*
  *   emission and absorption of     (none: build-defined, the line integral
  *   media that fill the tubes      of a synthetic diagnostic)            trt_glow*
+ *   the same with media that vary  (none: build-defined, emission and
+ *   across a tube                  absorption over the flux-surface label)   trt_glow_profile*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -781,8 +783,8 @@ int trt_shade_scene_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_pus
  * ctx usable and the outputs unwritten.
  * Stats (trt_enable_stats): primary_tests = the tori started, bounce_tests = shadow_tests = 0, pixels = n; traced_tests,
  * solved_tests and evaluations as defined at trt_stats.
- * Not here: a fused camera variant, media inside trt_render* / trt_shade*, scattering, a sigma per channel, density that
- * varies inside a tube.
+ * Not here: a fused camera variant, media inside trt_render* / trt_shade*, scattering, a sigma per channel.  Density that
+ * varies inside a tube is trt_glow_profile, below.
  * Host buffers: copy in, launch, copy out, synchronise. */
 typedef struct trt_medium {
   float emission[3]; /* radiance emitted per unit world length, rgb; >= 0 and finite */
@@ -800,6 +802,65 @@ int trt_chords_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_r
                    float tmin, float tmax, float* length_dev, void* stream);
 int trt_glow_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene, const trt_medium* media,
                  float tmin, float tmax, float* rgba_dev, void* stream);
+
+/* ---- media that vary across a tube: glow_profile(rays_in -> radiance, transmittance) ------------------------------- */
+/* trt_glow with a radial profile per torus in place of the homogeneous medium: emission and absorption are functions of
+ * x = rho^2 / r^2, the flux-surface label of a circular cross-section (rho: distance from the tube's centre circle; x = 0
+ * on the tube's axis, 1 on its wall), given as a table of TRT_PROFILE_KNOTS knots at x_k = k / 16 and interpolated
+ * linearly in x.  profiles[j] belongs to torus j: scene->n_tori host structs, copied before the call returns; the units
+ * are trt_medium's, per unit WORLD length.  Output, layout, window, per-ray bound and alignment are trt_glow's.
+ *
+ * Intervals, break points, pieces and active masks are exactly trt_glow's: the same crossings, pairing rule and merge.
+ * A torus whose 17 x 4 knots are all zero is not tested at all: it is absent, bit for bit, and counts no test.  Where
+ * tubes overlap, the media add.  L = 0, T = 1; then for every piece (u, v) with v > u and at least one active torus,
+ * front to back, with inv_steps = 1.0f / (float)steps formed on the host:
+ *   h = (v - u) * inv_steps;  l = h * len;  for k = 0 .. steps - 1, the sub-steps:
+ *     m = fma((float)k + 0.5f, h, u), the centre;  t- = fma(-0.288675135f, h, m) and t+ = fma(0.288675135f, h, m), the
+ *     two Gauss-Legendre points (the constant is 1 / (2 sqrt(3)));
+ *     at each of the two points, a = (0, 0, 0, 0), then for every active torus j in ascending id:
+ *       P = fma(t, d, o) - c per component with t converted to the solver's precision, in the frame the solver works in
+ *       — the expression of the inside test above, oriented tori included;  q = sqrt(fma(Pz, Pz, Px * Px)) - R;
+ *       rho2 = fma(q, q, Py * Py);  x = (float)rho2 * inv_r2_j, with inv_r2_j = 1.0f / (r * r) formed once on the host in
+ *       FP32 from the torus' r (the product rounded, then the quotient);
+ *       y = (x < 1 ? x : 1) * 16 (so a NaN x reads the wall);  the knot below, kn = min((int)y, 15);  f = y - (float)kn;
+ *       a_c = a_c + fma(f, knot[kn + 1][c] - knot[kn][c], knot[kn][c]) for the four channels c = (er, eg, eb, sigma);
+ *     e_c and s = (a-_c + a+_c) * 0.5f, the average of the two points;
+ *     then trt_glow's step with (e, s, l) as it stands: the same s == 0 branch, the same series below tau = 0.25, the same
+ *     exp2p;  L_c = fma(e_c * w, T, L_c), then T = T * E.
+ * With a flat profile (every knot of torus j equal to one medium) and steps == 1 the result is trt_glow's, bit for bit.
+ * Emissions scaled by a power of two scale L by it in bits and leave T alone.
+ * Choosing steps.  T is the exponential of a two-point Gauss sum of sigma; where the profiles are linear in x over a
+ * sub-step — no knot between its ends — that sum is of fourth order in h.  L is of fourth order there as well if either
+ * nothing absorbs or the summed emission and the summed sigma stay in one ratio along the sub-step (one line for the
+ * four channels of a torus): halving the sub-steps then divides the error of L by 16 (15.96 from 2 to 4 sub-steps in
+ * the median, in an FP64 restatement of the rule with absorption, over the 683 of the first 1024 lines of sight of the
+ * tests' single-torus set whose error at 8 sub-steps stands above 1e-9: tests/test_profile_cpu.py).  Where that ratio
+ * varies, the step — which takes e and s as constant over h — leaves (e s' - e' s) h^3 / 12 per sub-step, second order
+ * in all: the error of L falls by 4 per halving (3.45 and 3.87 in the median of the same test, with a line of its own
+ * per channel).  Where sub-steps straddle knots of a curved profile, the kinks of the table bound the order to about
+ * two as well: in an FP64 trial 5e-4 relative remained at 16 steps and 1e-5 at 64.  In FP32 the sums of a long walk add
+ * about steps * 6e-8 relative.  A table describes a curved profile as 16 linear pieces in x, whatever the steps.
+ *
+ * TRT_E_INVALID: everything trt_glow refuses (with "trt_glow_profile" in the message); NULL profiles; steps outside
+ * 1..TRT_MAX_GLOW_STEPS; a knot component that is negative, NaN or infinite (the message names torus and knot); a solver
+ * other than TRT_SOLVE_F32 / _F64.  n == 0 is valid and launches nothing.  A refused call leaves the ctx usable and the
+ * outputs unwritten.  Stats: as trt_glow's (primary_tests = the tori started, pixels = n).
+ * Not here: a fused camera form; profiles inside trt_shade* / trt_render*; scattering; a label other than rho^2 / r^2
+ * (shaped cross-sections); knot counts other than 17; step counts that adapt per piece.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+#define TRT_PROFILE_KNOTS  17 /* x_k = k / 16, x = rho^2 / r^2 in [0, 1]: 0 the tube's axis, 1 its wall */
+#define TRT_MAX_GLOW_STEPS 64
+typedef struct trt_profile {
+  float knot[TRT_PROFILE_KNOTS][4]; /* (er, eg, eb, sigma) per knot; >= 0 and finite */
+} trt_profile;                      /* 272 bytes                                     */
+
+int trt_glow_profile(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, const trt_profile* profiles,
+                     uint32_t steps, float tmin, float tmax, float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  `profiles` stays a host pointer: the tables travel in the kernel
+ * arguments.  The call uses no scratch of the ctx, allocates nothing, synchronises nothing, puts only kernel nodes on the
+ * stream and may be captured. */
+int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                         const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_dev, void* stream);
 
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal
@@ -1056,7 +1117,8 @@ int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t 
                   trt_point* points_dev, uint64_t capacity, uint64_t* counts_dev, void* stream);
 
 /* Counters of the last render, trace, occluded, crossings, shade, shade_camera, fan_occluded, transmittance or shade_through
- * call made with counting enabled.  trt_chords and trt_glow count as well. */
+ * call made with counting enabled.  trt_chords and trt_glow count as well.
+ * So does trt_glow_profile, as trt_glow does. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

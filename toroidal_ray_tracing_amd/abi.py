@@ -196,6 +196,50 @@ def textures_array(textures):
     return arr, len(items)
 
 
+TRT_PROFILE_KNOTS = 17
+TRT_MAX_GLOW_STEPS = 64
+
+
+class trt_profile(C.Structure):
+    """The medium of a torus' tube as a function of x = rho^2 / r^2 (trt_glow_profile): (er, eg, eb, sigma) at x_k = k / 16."""
+    _fields_ = [("knot", (C.c_float * 4) * TRT_PROFILE_KNOTS)]
+
+
+def profile_from(fn):
+    """A ``trt_profile`` filled from a callable: ``fn(x)`` returns ((er, eg, eb), sigma) — or four numbers — for x in
+    [0, 1] (0: the tube's axis, 1: its wall); it is asked at the 17 knots x_k = k / 16."""
+    p = trt_profile()
+    for k in range(TRT_PROFILE_KNOTS):
+        v = fn(k / 16.0)
+        v = (*v[0], v[1]) if len(v) == 2 else v
+        p.knot[k][:] = [float(c) for c in v]
+    return p
+
+
+def profiles(items):
+    """A ``trt_profile`` array for trt_glow_profile, one entry per torus: each item is a ``trt_profile``, a callable as
+    ``profile_from`` takes it, a (17, 4) array of knots, ((er, eg, eb), sigma) for a flat profile, or None for no medium.
+    An array made here is passed through."""
+    if isinstance(items, C.Array) and items._type_ is trt_profile:
+        return items
+    items = list(items)
+    arr = (trt_profile * max(len(items), 1))()
+    for j, it in enumerate(items):
+        if it is None:
+            continue
+        if isinstance(it, trt_profile):
+            arr[j] = it
+        elif callable(it):
+            arr[j] = profile_from(it)
+        elif len(it) == 2:
+            arr[j] = profile_from(lambda x, it=it: it)
+        else:
+            knots = np.asarray(it, np.float32).reshape(TRT_PROFILE_KNOTS, 4)
+            for k in range(TRT_PROFILE_KNOTS):
+                arr[j].knot[k][:] = [float(c) for c in knots[k]]
+    return arr
+
+
 class trt_rays(C.Structure):
     _fields_ = [("ox", C.c_void_p), ("oy", C.c_void_p), ("oz", C.c_void_p),
                 ("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p),

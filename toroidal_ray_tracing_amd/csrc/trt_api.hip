@@ -1336,6 +1336,70 @@ extern "C" int trt_glow(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_
   });
 }
 
+// The profiles of trt_glow_profile*, validated (the scene first, so that n_tori can be trusted) and copied into the kernel
+// arguments with the 1 / r² of every torus: r * r rounded to FP32, then the quotient.
+static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile* profiles, Profiles& out)
+{
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  std::memset(&out, 0, sizeof out);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)
+      for(int c = 0; c < 4; ++c)
+      {
+        const float v = profiles[j].knot[k][c];
+        if(!(v >= 0.0f) || std::isinf(v))
+          return fail(ctx, TRT_E_INVALID, "trt_glow_profile: the profile of torus %u has %s = %g at knot %u; emission and sigma must be "
+                                          "finite and not negative", j, c < 3 ? "an emission" : "sigma", (double)v, k);
+        if(v != 0.0f)
+          out.present |= 1u << j;
+      }
+    out.p[j] = profiles[j];
+    const float r2 = scene->tori[j].r * scene->tori[j].r;
+    out.inv_r2[j]  = 1.0f / r2;
+  }
+  return TRT_OK;
+}
+static int check_glow_profile(trt_ctx* ctx, const trt_rays* in, const trt_profile* profiles, uint32_t steps, const float* rgba)
+{
+  if(int rc = check_media(ctx, in, rgba, "trt_glow_profile")) return rc;
+  if(!profiles) return fail(ctx, TRT_E_INVALID, "trt_glow_profile: NULL profiles");
+  if(steps < 1 || steps > TRT_MAX_GLOW_STEPS)
+    return fail(ctx, TRT_E_INVALID, "trt_glow_profile: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", steps, TRT_MAX_GLOW_STEPS);
+  if((uintptr_t)rgba & 15)
+    return fail(ctx, TRT_E_INVALID, "trt_glow_profile: the rgba output must be 16-byte aligned (it is written as float4)");
+  return TRT_OK;
+}
+extern "C" int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                    const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba, void* stream)
+{
+  if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba)) return rc;
+  GlowProfileArgs a;
+  if(int rc = glow_profiles(ctx, scene, profiles, a.prof)) return rc;
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.steps        = steps;
+  a.inv_steps    = 1.0f / (float)steps;
+  a.rgba         = rgba;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_profile);
+}
+
+// Host buffers: trt_glow's staging.
+extern "C" int trt_glow_profile(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_out)
+{
+  if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return trt_glow_profile_dev(ctx, in, nullptr, scene, profiles, steps, tmin, tmax, rgba_out, nullptr);   // validates, launches and writes nothing
+  StagedOut image = {rgba_out, (size_t)in->n * 4 * sizeof(float), kBufRgba, nullptr};
+  return bounded_query_host(ctx, in, tmax_per_ray, &image, 1, [&](const trt_rays* rays, const float* bounds) {
+    return trt_glow_profile_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, (float*)image.dev, nullptr);
+  });
+}
+
 // ------------------------------------------------------------------------------------------
 // camera rays: the two cameras as ray streams, and the supersampled frame
 // ------------------------------------------------------------------------------------------

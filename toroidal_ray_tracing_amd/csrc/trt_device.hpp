@@ -126,6 +126,8 @@ struct SceneK {
 // n_mat materials, and — in the ORIENT kernels, which run only when some torus is oriented — n_tori rotation records):
 // 48 dwords for one FP32 torus instead of the 462 of the full struct, one load per thread.
 // Reads in the hot loops then hit LDS at wave-uniform (broadcast) or material-indexed addresses.
+// (trt_media.hip has a second staging routine, stage_scene_no_mat, for a SceneK that travels without its materials: a
+// change to SceneK's layout or to the words below has to be made there too.)
 // The dwords of a SceneK that are in use, numbered 0 .. scene_words() - 1: word i of them sits at dword scene_word(i) of the struct.
 constexpr uint32_t kSceneHdr = 22, kSceneK32 = kSceneHdr, kSceneK64 = kSceneK32 + 80, kSceneShade = kSceneK64 + 160, kSceneMat = kSceneShade + 40,
                    kSceneRot = kSceneMat + 88;

@@ -266,6 +266,25 @@ struct GlowArgs {
   float*              rgba;
   unsigned long long* stats;
 };
+// The profiles of trt_glow_profile*, indexed by TORUS id, validated and copied on the host (2176 B for eight tori; the
+// kernel stages them into LDS, where a knot is one 16-byte read).  inv_r2[j] = 1.0f / (r * r) of torus j in FP32, r * r
+// rounded first; bit j of `present`: profile j is not all zero (a torus without that bit is never tested).
+struct Profiles {
+  trt_profile p[TRT_MAX_TORI];
+  float       inv_r2[TRT_MAX_TORI];
+  uint32_t    present;
+};
+// trt_glow_profile*: GlowArgs with the profiles in place of the media and the sub-steps per piece (inv_steps = 1.0f / steps).
+struct GlowProfileArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  uint32_t            steps;
+  float               inv_steps;
+  Profiles            prof;
+  float*              rgba;
+  unsigned long long* stats;
+};
 
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
@@ -408,6 +427,7 @@ hipError_t launch_transmittance(const SceneK& scene, const TransmittanceArgs& a,
 hipError_t launch_shade_through(const SceneK& scene, const ShadeThroughArgs& a, const Tuning& tn, hipStream_t stream);    // default solver only
 hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream);       // default solver only
+hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);

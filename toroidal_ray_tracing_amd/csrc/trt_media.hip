@@ -1,16 +1,20 @@
-// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*), gfx950.
+// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*), gfx950.
 //
 //   tube_inside      whether the point of a ray at parameter t lies inside torus j's tube
 //   tube_intervals   the pairing rule: torus j's crossings and the two inside tests → at most two intervals
 //   chords_kernel    chords(rays_in → the length of every ray inside every tube): n_tori coalesced streams out.
 //   glow_kernel      glow(rays_in → radiance and the transmittance left): the emission–absorption integral over the
 //                    pieces between the merged interval ends, one float4 per ray out.
-//   launch_chords, launch_glow   their grid and launch wrappers.
+//   glow_profile_kernel   glow with a radial profile per torus: every piece cut into sub-steps, two Gauss–Legendre points
+//                    in each, the profile tables in LDS.
+//   launch_chords, launch_glow, launch_glow_profile   their grid and launch wrappers.
 //
 // The crossings of torus j are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
 // window, no enclosure cull); include/trt.h states the arithmetic of everything on top of them, expression by expression.
 // The media come in the kernel arguments (Media, trt_kernels.hpp); SceneK knows nothing of them and no material is read.
 // Default solver only: instantiated for <float | double> × ORIENT.  Compiled with -ffp-contract=off like every unit.
+#include <cstring>
+
 #include "trt_render.hpp"
 
 namespace trt {
@@ -157,6 +161,23 @@ __device__ __forceinline__ float one_minus_exp_over(float tau)
   return fma_(tau, p, 1.0f);
 }
 
+// The homogeneous step of trt_glow over the world length l, with the summed emission (e0, e1, e2) and absorption sg:
+// glow_kernel's piece and glow_profile_kernel's sub-step.
+__device__ __forceinline__ void glow_step(float e0, float e1, float e2, float sg, float l, float& Lr, float& Lg, float& Lb, float& T)
+{
+  const float tau = sg * l;
+  float E = 1.0f, wgt = l;
+  if(sg != 0.0f)
+  {
+    E   = exp2_poly(-tau * 1.44269504f);
+    wgt = tau < kGlowSeries ? l * one_minus_exp_over(tau) : (1.0f - E) / sg;
+  }
+  Lr = fma_(e0 * wgt, T, Lr);
+  Lg = fma_(e1 * wgt, T, Lg);
+  Lb = fma_(e2 * wgt, T, Lb);
+  T  = T * E;
+}
+
 // One lane owns one ray.  A torus with a medium (bit j of media.present) goes through the pairing rule; the ends of its
 // intervals go into the lane's sorted column in dynamic LDS (column_insert: crossings_kernel's layout, K = 4 · n_tori
 // slots — two intervals per torus at most, so nothing is ever truncated) with the byte id << 1 | 1 for a start and
@@ -222,18 +243,159 @@ __global__ __launch_bounds__(256) void glow_kernel(const SceneK scene, const Glo
               e2 = e2 + a.media.m[j].emission[2];
               sg = sg + a.media.m[j].sigma;
             }
-          const float l   = (v - u) * len;
-          const float tau = sg * l;
-          float E = 1.0f, wgt = l;
-          if(sg != 0.0f)
+          glow_step(e0, e1, e2, sg, (v - u) * len, Lr, Lg, Lb, T);
+        }
+        const uint32_t bit = 1u << (w >> 1);
+        if(!last)
+          active = (w & 1u) ? (active | bit) : (active & ~bit);
+        u = v;
+      }
+    }
+    st4(a.rgba + 4 * i, make_float4(Lr, Lg, Lb, T));
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
+// glow_profile(rays_in → radiance and transmittance, the media varying across the tubes)
+// ------------------------------------------------------------------------------------------
+// SceneK without its materials, which no kernel of this unit reads: with the profiles (2176 B) beside it the whole
+// struct would not fit the 4-KiB kernel-argument segment.  The members up to `shade` sit where SceneK has them.
+struct SceneNoMat {
+  uint32_t head[kSceneMat];   // SceneK's header, k32, k64 and shade
+  TorusRot rot[TRT_MAX_TORI];
+};
+static_assert(offsetof(SceneK, mat) == 4 * kSceneMat && sizeof(SceneNoMat) == 4 * (kSceneMat + 72), "SceneNoMat layout");
+static_assert(sizeof(SceneNoMat) + sizeof(GlowProfileArgs) <= 4096, "the kernel-argument segment of glow_profile_kernel");
+// stage_scene for a SceneNoMat: the records in use, each to its place in the SceneK in LDS (n_mat is not read behind it).
+template <bool ORIENT>
+__device__ __forceinline__ void stage_scene_no_mat(SceneK* lds, const SceneNoMat& arg)
+{
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&arg);
+  uint32_t*       dst = reinterpret_cast<uint32_t*>(lds);
+  const uint32_t  n = arg.head[0], f64 = arg.head[2];   // SceneK::n_tori, SceneK::f64
+  const uint32_t  c0 = kSceneHdr, c1 = c0 + (f64 ? 0u : 10u * n), c2 = c1 + (f64 ? 20u * n : 0u), c3 = c2 + 5u * n;
+  const uint32_t  c4 = c3 + (ORIENT ? 9u * n : 0u);
+  for(uint32_t i = threadIdx.x; i < c4; i += blockDim.x)
+  {
+    if(i >= c3)
+      dst[kSceneRot + (i - c3)] = src[kSceneMat + (i - c3)];
+    else
+    {
+      const uint32_t off = i < c0 ? i : i < c1 ? kSceneK32 + (i - c0) : i < c2 ? kSceneK64 + (i - c1) : kSceneShade + (i - c2);
+      dst[off] = src[off];
+    }
+  }
+}
+
+// The knots k and k + 1 of one profile, interpolated at x = rho² / r²: y = min(x, 1) · 16 (a NaN x goes to the wall),
+// k = min((int)y, 15), f = y − k, channel c = fma(f, knot[k+1][c] − knot[k][c], knot[k][c]); added to acc.
+__device__ __forceinline__ void profile_add(const float4* knots, float x, float4& acc)
+{
+  const float  y  = (x < 1.0f ? x : 1.0f) * 16.0f;
+  const int    k  = min((int)y, 15);
+  const float  f  = y - (float)k;
+  const float4 lo = knots[k], hi = knots[k + 1];
+  acc.x = acc.x + fma_(f, hi.x - lo.x, lo.x);
+  acc.y = acc.y + fma_(f, hi.y - lo.y, lo.y);
+  acc.z = acc.z + fma_(f, hi.z - lo.z, lo.z);
+  acc.w = acc.w + fma_(f, hi.w - lo.w, lo.w);
+}
+
+// glow_kernel with a radial profile per torus in place of its medium: intervals, column and pieces are glow_kernel's,
+// line for line.  Every piece with an active torus is cut into a.steps equal sub-steps; at the two Gauss–Legendre
+// points of a sub-step every active torus is asked for x = rho² / r² at the point — tube_inside's expression, in the
+// solver's frame and precision — and its table for the four channels there; the two sums are averaged and go through
+// glow_step.  The sub-step loop and the torus loop are uniform for the wave (their bounds come from the arguments) and
+// predicated by the lane's mask.  The knot index differs from lane to lane, so the tables are staged into LDS once per
+// block: a knot is one 16-byte read.  The ray in an oriented torus' frame depends on the ray and the torus alone, but
+// holding it for n_tori tori would take a private array or as much LDS again as the columns: it is formed once per
+// sub-step and torus, for both points.
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256) void glow_profile_kernel(const SceneNoMat scene, const GlowProfileArgs a)
+{
+  __shared__ SceneK S;
+  __shared__ float4 knots[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float crossing_lds[];   // [K][256] t, then [K][256] bytes
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&a.prof.p[0]);
+    uint32_t*       dst = reinterpret_cast<uint32_t*>(knots);
+    for(uint32_t i = threadIdx.x; i < 4u * TRT_PROFILE_KNOTS * scene.head[0]; i += blockDim.x)
+      dst[i] = src[i];
+  }
+  stage_scene_no_mat<ORIENT>(&S, scene);
+  __syncthreads();   // publishes the tables and the scene
+
+  const uint32_t K  = 4u * (uint32_t)S.n_tori;
+  float*         ct = crossing_lds + threadIdx.x;
+  uint8_t*       cw = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
+
+  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  const int      n_tori = (int)scene.head[0];
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
+  {
+    const float tmax = window_end(a.tmax_per_ray, i, a.tmax);
+    float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f;
+    if(tmax > a.tmin)
+    {
+      const v3 o = {ox[i], oy[i], oz[i]};
+      const v3 d = {dx[i], dy[i], dz[i]};
+      RayK<Real> r;
+      r.set(o, d, a.tmin, tmax);
+      const float len = ray_length(d);
+      uint32_t active = 0u, count = 0u;
+      for(int k = 0; k < S.n_tori; ++k)
+      {
+        const int j = S.order[k];
+        if(!((a.prof.present >> j) & 1u))
+          continue;
+        ++tests;
+        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
+          if(from_start) active |= 1u << j;
+          else column_insert(ct, cw, K, count, u, j, true);
+          if(!to_end) column_insert(ct, cw, K, count, v, j, false);
+        });
+      }
+      float u = a.tmin;
+      for(uint32_t k = 0; k <= count; ++k)
+      {
+        const bool     last = k == count;
+        const float    v    = last ? tmax : ct[k * 256u];
+        const uint32_t w    = last ? 0u : cw[k * 256u];
+        if(active != 0u && v > u)
+        {
+          const float h = (v - u) * a.inv_steps;
+          const float l = h * len;
+          for(uint32_t s = 0; s < a.steps; ++s)
           {
-            E   = exp2_poly(-tau * 1.44269504f);
-            wgt = tau < kGlowSeries ? l * one_minus_exp_over(tau) : (1.0f - E) / sg;
+            const float m  = fma_((float)s + 0.5f, h, u);
+            const Real  ta = (Real)fma_(-0.288675135f, h, m), tb = (Real)fma_(0.288675135f, h, m);
+            float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
+            for(int j = 0; j < n_tori; ++j)
+              if((active >> j) & 1u)
+              {
+                LocalRay<Real> lr = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+                TorusK<Real>   Tk = torus_k<Real>(S, j);
+                if constexpr(ORIENT)
+                  if(is_oriented(S, j))
+                  {
+                    lr.set(S, j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+                    Tk = centred(Tk);
+                  }
+                const Real  ax = fma_(ta, lr.dx, lr.ox) - Tk.cx, ay = fma_(ta, lr.dy, lr.oy) - Tk.cy, az = fma_(ta, lr.dz, lr.oz) - Tk.cz;
+                const Real  bx = fma_(tb, lr.dx, lr.ox) - Tk.cx, by = fma_(tb, lr.dy, lr.oy) - Tk.cy, bz = fma_(tb, lr.dz, lr.oz) - Tk.cz;
+                const Real  qa = sqrt_(fma_(az, az, ax * ax)) - Tk.R, qb = sqrt_(fma_(bz, bz, bx * bx)) - Tk.R;
+                const float ir = a.prof.inv_r2[j];
+                profile_add(knots + j * TRT_PROFILE_KNOTS, (float)fma_(qa, qa, ay * ay) * ir, A);
+                profile_add(knots + j * TRT_PROFILE_KNOTS, (float)fma_(qb, qb, by * by) * ir, B);
+              }
+            glow_step((A.x + B.x) * 0.5f, (A.y + B.y) * 0.5f, (A.z + B.z) * 0.5f, (A.w + B.w) * 0.5f, l, Lr, Lg, Lb, T);
           }
-          Lr = fma_(e0 * wgt, T, Lr);
-          Lg = fma_(e1 * wgt, T, Lg);
-          Lb = fma_(e2 * wgt, T, Lb);
-          T  = T * E;
         }
         const uint32_t bit = 1u << (w >> 1);
         if(!last)
@@ -280,6 +442,27 @@ hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn,
     else
     {
       hipLaunchKernelGGL((glow_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, scene, a);
+      return hipGetLastError();
+    }
+  });
+}
+
+// glow_kernel's columns; the tables are static LDS (2176 B).  The scene travels without its materials (SceneNoMat).
+hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.rays.n, tn);
+  const uint32_t lds  = 4u * (uint32_t)scene.n_tori * kCrossingSlotBytes;
+  SceneNoMat     sc;
+  std::memcpy(sc.head, &scene, sizeof sc.head);
+  std::memcpy(sc.rot, scene.rot, sizeof sc.rot);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;
+    else
+    {
+      hipLaunchKernelGGL((glow_profile_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, sc, a);
       return hipGetLastError();
     }
   });

@@ -118,6 +118,11 @@ public:
   void chords(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, float tmin, float tmax, float* lengthDev);
   void glow(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_medium* media, float tmin, float tmax,
             float* rgbaDev);
+  // glow with media that vary across the tubes (trt_glow_profile_dev): one trt_profile per torus (host memory), a table of
+  // emission and sigma over x = rho^2 / r^2 (0: the tube's axis, 1: its wall); every piece of a ray inside the tubes is
+  // integrated in `steps` sub-steps (1..TRT_MAX_GLOW_STEPS).  rgbaDev as glow's.
+  void glowProfile(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
+                   float tmin, float tmax, float* rgbaDev);
 
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the

@@ -299,6 +299,36 @@ class Tracer:
         self._check(self._L.trt_glow_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), self._media(scene, media),
                                          tmin, tmax, _vp(rgba_ptr), _vp(stream)))
 
+    def glow_profile(self, scene, o, d, profiles, steps=16, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """``glow`` with media that vary across the tubes (trt_glow_profile) on host arrays: profiles as ``abi.profiles``
+        takes them, one per torus — tables of ((er, eg, eb), sigma) over x = rho^2 / r^2; every piece of a ray inside
+        the tubes is integrated in ``steps`` sub-steps (1..64).  Returns float32 (n, 4) as ``glow`` does."""
+        o = np.ascontiguousarray(np.asarray(o, np.float32).T)
+        d = np.ascontiguousarray(np.asarray(d, np.float32).T)
+        n = o.shape[1]
+        rays = abi.rays_struct([o[0], o[1], o[2], d[0], d[1], d[2]], n)
+        bound = None if tmax_per_ray is None else np.ascontiguousarray(tmax_per_ray, np.float32).reshape(n)
+        rgba = np.empty((n, 4), np.float32)
+        self._check(self._L.trt_glow_profile(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene),
+                                             self._profiles(scene, profiles), int(steps), tmin, tmax, rgba.ctypes.data))
+        return rgba
+
+    def glow_profile_dev(self, scene, ray_ptrs, n, profiles, rgba_ptr, steps=16, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints) as in ``glow_dev``; ``profiles`` stays on the host (the tables travel in the launch's
+        arguments).  Asynchronous on ``stream``."""
+        rays = abi.rays_struct([int(p) for p in ray_ptrs], n)
+        self._check(self._L.trt_glow_profile_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
+                                                 self._profiles(scene, profiles), int(steps), tmin, tmax, _vp(rgba_ptr), _vp(stream)))
+
+    @staticmethod
+    def _profiles(scene, profiles):
+        if profiles is None:
+            return None
+        arr = abi.profiles(profiles)
+        if len(arr) < scene.n_tori:
+            raise ValueError(f"{len(arr)} profiles for {scene.n_tori} tori: trt_glow_profile reads one per torus")
+        return arr
+
     @staticmethod
     def _media(scene, media):
         if media is None:
