@@ -215,6 +215,9 @@ int         trt_set_solver(trt_ctx* ctx, int solver);    /* one of TRT_SOLVE_*  
 int trt_set_torus_axes(trt_ctx* ctx, const float* axes, uint32_t n_tori);
 
 /* ---- trace(rays_in -> hits_out): closest hit of every ray against the scene -------- */
+/* Directions of any non-zero length, scenes of any size: the default solvers (TRT_SOLVE_F32 / _F64) hold |t - exact|·|d|
+ * <= 1e-5 (2e-6) of max(R + r, t·|d|) for r/R >= 0.02 from origins up to 100 (1e4) bounding radii away and scale exactly
+ * with powers of two; the alternative solvers do so only while (R + r)/|d| is of order 1. */
 /* Host buffers: copies in, launches, copies out, synchronises. */
 int trt_trace(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene,
               float tmin, float tmax, trt_hits* out);

@@ -27,7 +27,9 @@
  *       parameter window |u| <= U = sqrt((Rb²-m)/dd), intersected with (tMin-tc, tMax-tc).
  *       (Inflated by ~0.1 % so that the walk starts strictly OUTSIDE the torus: on the
  *       exact bounding sphere f(-U) = 0 at the outer equator and its computed sign is noise.)
- *       The window is then clipped to the bounding slab (T1b in the code).
+ *       The window is then clipped to the bounding slab (T1b in the code).  tc is a rounded number, so a second,
+ *       small step tc2 of the same shift follows the cull (T1a in the code): q0 ⟂ d then holds to the rounding of q0
+ *       however far away the origin lies, and t = u + tc + tc2.
  *   T2  f'' = 12·A4·u² + 2·P2 has constant sign on at most three pieces of the window
  *       (split at ±w, w = sqrt(-P2/(6·A4)), when P2 < 0; 1/(6·A4) is formed as (1/dd)²·(1/6)).  On a piece [A,B] with
  *       sign(f'') = σ, Fourier's condition says Newton's iteration started where
@@ -44,7 +46,7 @@ typedef struct SUF(torus_k) {
   REAL cx, cy, cz;
   REAL R;
   REAL r2;      /* r²        */
-  REAL rpol;    /* r / 32: largest step the geometric polish may take */
+  REAL rpol2;   /* (r / 32)²: square of the largest distance the geometric polish may move the point */
   REAL k0;      /* R² - r²   */
   REAL Rb2;     /* (R + r)²·(1 + 2⁻⁹): squared radius of the (slightly inflated) bounding sphere */
   REAL rs;      /* r·(1 + 2⁻⁸): half height of the (slightly inflated) bounding slab |y| <= rs */
@@ -60,7 +62,7 @@ static void SUF(torus_prepare)(const trt_torus* t, SUF(torus_k)* k)
   k->cz = (REAL)t->center[2];
   k->R      = R;
   k->r2     = r2;
-  k->rpol   = r * (REAL)0.03125;
+  k->rpol2  = (r * (REAL)0.03125) * (r * (REAL)0.03125);
   k->k0     = R2 - r2;
   const REAL s2 = s * s;
   k->Rb2    = FMA(s2, (REAL)0.001953125, s2);
@@ -238,10 +240,28 @@ static int SUF(torus_first_hit)(const REAL o[3], const REAL d[3], REAL dd, REAL 
   const REAL ex = o[0] - T->cx, ey = o[1] - T->cy, ez = o[2] - T->cz;
   const REAL n  = FMA(ez, d[2], FMA(ey, d[1], ex * d[0]));
   const REAL tc = -n * inv_dd;
-  const REAL qx = FMA(tc, d[0], ex), qy = FMA(tc, d[1], ey), qz = FMA(tc, d[2], ez);
+  REAL qx = FMA(tc, d[0], ex), qy = FMA(tc, d[1], ey), qz = FMA(tc, d[2], ez);
   const REAL m  = FMA(qz, qz, FMA(qy, qy, qx * qx));
   if(!(m <= T->Rb2))
     return 0;
+  /* T1a: second shift.  tc carries a rounding error of ~|tc|·eps, so q·d is not 0 — but the quartic below is formed as if
+   * it were (no u³ term): far from the torus (|tc|·|d| >> R) the dropped terms move the roots by ~|tc|·|d|·eps.  One
+   * more step of the same shift, by tc2 = -(q·d)/dd, leaves q ⟂ d to the rounding of q itself; tc2 stays a separate
+   * (small) term of t = u + tc + tc2, summed with one rounding at the size of t (below).  After the cull, which most
+   * tests do not pass: m, the cull and the window feel q·d only through (q·d)²/dd and a shift of the window's ends by
+   * tc2, far inside the margins by which sphere and slab are inflated. */
+  /* Taken wherever the dropped terms can reach a sixteenth of what f is worth where the walk starts.  They are worth
+   * ≈16·R³·δ, δ = |tc|·|d|·2⁻²⁴ the error of the first shift as a length; f on the inflated slab is ≈R²r²/32
+   * (DESIGN.md §4): 16·R³·δ > R²r²/512 is |tc|·|d| > 2¹¹·r²/R, written (n²/dd)·4R² > 2²⁴·(r²)² — 0.8 R for r/R = 0.02,
+   * 5 R for 0.05, 128 R for 0.25.  Below that the step changes nothing that survives rounding and is not taken: tc2 = 0
+   * leaves q and t = u + tc as they are.  (The FP64 solve takes it at the same distance, sooner than it needs to.) */
+  REAL tc2 = (REAL)0;
+  if(((n * n) * inv_dd) * T->fourR2 > (REAL)16777216 * (T->r2 * T->r2))
+  {
+    const REAL n2 = FMA(qz, d[2], FMA(qy, d[1], qx * d[0]));
+    tc2 = -n2 * inv_dd;
+    qx = FMA(tc2, d[0], qx); qy = FMA(tc2, d[1], qy); qz = FMA(tc2, d[2], qz);
+  }
   const REAL U  = SQRT((T->Rb2 - m) * inv_dd);
   REAL lo = FMAX(tmin - tc, -U);
   REAL hi = FMIN(tmax - tc, U);
@@ -372,7 +392,8 @@ static int SUF(torus_first_hit)(const REAL o[3], const REAL d[3], REAL dd, REAL 
     return 0;
   /* T2b: one Newton step on the geometric form g(u) = (ρ-R)² + py² - r² (ρ = distance from
    * the axis).  g has the same roots as f but its rounding error scales with r², not R⁴,
-   * which matters for thin tubes.  A step larger than r/32 (grazing: g' ≈ 0) is discarded. */
+   * which matters for thin tubes.  A step that would move the point by more than r/32 (grazing: g' ≈ 0) is
+   * discarded: |du|·|d| <= r/32, compared as squares — du is a step in the ray PARAMETER, r/32 a length. */
   {
     const REAL px  = FMA(root, d[0], qx), py = FMA(root, d[1], qy), pz = FMA(root, d[2], qz);
     const REAL rho = SQRT(FMA(pz, pz, px * px));
@@ -381,10 +402,16 @@ static int SUF(torus_first_hit)(const REAL o[3], const REAL d[3], REAL dd, REAL 
     const REAL s   = FMA(pz, d[2], px * d[0]);
     const REAL gh  = FMA(e, s, (py * d[1]) * rho); /* ρ·g'/2 */
     const REAL du  = (REAL)0.5 * ((g * rho) / gh);
-    if(FABS(du) <= T->rpol)
+    if((du * du) * dd <= T->rpol2)
       root = root - du;
   }
-  const REAL t = root + tc;
+  /* t = u + tc + tc2 with ONE rounding at the size of t, as u + tc had before the second shift: the rounding error of
+   * s = big + small is exact in e (Fast2Sum, |big| >= |small|) and joins the small second shift before the last add */
+  const int  far = FABS(root) < FABS(tc);
+  const REAL big = far ? tc : root, small = far ? root : tc;
+  const REAL s   = big + small;
+  const REAL e   = small - (s - big);
+  const REAL t   = s + (e + tc2);
   if(!(t > tmin && t < tmax))
     return 0;
   *t_out = t;

@@ -372,7 +372,7 @@ void torus_prepare(const trt_torus& t, TorusK<Real>& k)
   k.cz = (Real)t.center[2];
   k.R      = R;
   k.r2     = r2;
-  k.rpol   = r * (Real)0.03125;
+  k.rpol2  = (r * (Real)0.03125) * (r * (Real)0.03125);
   k.k0     = R2 - r2;
   k.Rb2    = std::fma(s2, (Real)0.001953125, s2);
   k.rs     = std::fma(r, (Real)0.00390625, r);

@@ -73,7 +73,7 @@ struct TorusK {   // per-torus constants of the solver
   Real cx, cy, cz;
   Real R;
   Real r2;      // r²
-  Real rpol;    // r/32: largest step the geometric polish may take
+  Real rpol2;   // (r/32)²: square of the largest distance the geometric polish may move the point
   Real k0;      // R² - r²
   Real Rb2;     // (R+r)²·(1+2⁻⁹): squared radius of the slightly inflated bounding sphere
   Real rs;      // r·(1+2⁻⁸): half height of the slightly inflated bounding slab |y| <= rs
@@ -193,8 +193,9 @@ template <> struct StepStop<double> { static constexpr double v = 5.960464477539
 template <class Real>
 struct TorusTest {
   // quartic and window
-  Real A4, P2, Q1, S0, w, hi, tc;
+  Real A4, P2, Q1, S0, w, hi, tc, tc2;   // t = u + tc + tc2: the shift and its second, small step (setup)
   Real qx, qy, qz;     // point of closest approach to the torus centre (local frame)
+  Real dsq;            // |d|² as setup() was given it (finish_root: the polish guard)
   // walk: piece [A,B] with sign(f'') = sigma; xe = point to evaluate next (END/PROBE: xe == B)
   Real A, B, xe, root;
   int  sigma, sref, it, mode;
@@ -207,6 +208,7 @@ struct TorusTest {
   {
     const Real ex = ox - T.cx, ey = oy - T.cy, ez = oz - T.cz;
     const Real n  = fma_(ez, dz_, fma_(ey, dy_, ex * dx_));
+    dsq = dd;
     tc = -n * inv_dd;
     qx = fma_(tc, dx_, ex); qy = fma_(tc, dy_, ey); qz = fma_(tc, dz_, ez);
     const Real m = fma_(qz, qz, fma_(qy, qy, qx * qx));
@@ -214,6 +216,23 @@ struct TorusTest {
     found = false;
     if(!(m <= T.Rb2))
       return false;
+    // T1a: second shift.  tc carries a rounding error of ~|tc|·eps, so q·d is not 0 — but the quartic is formed as if it
+    // were (no u³ term): far from the torus the dropped terms move the roots by ~|tc|·|d|·eps.  One more step of the same
+    // shift, by tc2 = -(q·d)/dd, leaves q ⟂ d to the rounding of q itself; tc2 stays a separate (small) term of
+    // t = u + tc + tc2 (finish_root).  After the cull, which most tests do not pass: m, the cull and the window feel q·d
+    // only through (q·d)²/dd and a shift of the window's ends by tc2, far inside the margins of sphere and slab.
+    // Taken wherever the dropped terms can reach a sixteenth of what f is worth where the walk starts.  They are worth
+    // ≈16·R³·δ, δ = |tc|·|d|·2⁻²⁴ the error of the first shift as a length; f on the inflated slab is ≈R²r²/32:
+    // 16·R³·δ > R²r²/512 is |tc|·|d| > 2¹¹·r²/R, written (n²/dd)·4R² > 2²⁴·(r²)² — 0.8 R for r/R = 0.02, 5 R for 0.05, 128 R
+    // for 0.25.  Below that the step changes nothing that survives rounding and is not taken: tc2 = 0 leaves q and
+    // t = u + tc as they are.  (The FP64 solve takes it at the same distance, sooner than it needs to.)
+    tc2 = Real(0);
+    if(((n * n) * inv_dd) * T.fourR2 > Real(16777216) * (T.r2 * T.r2))
+    {
+      const Real n2 = fma_(qz, dz_, fma_(qy, dy_, qx * dx_));
+      tc2 = -n2 * inv_dd;
+      qx = fma_(tc2, dx_, qx); qy = fma_(tc2, dy_, qy); qz = fma_(tc2, dz_, qz);
+    }
     const Real U  = sqrt_((T.Rb2 - m) * inv_dd);
     Real lo = max_(tmin - tc, -U);
     hi = min_(tmax - tc, U);
@@ -658,7 +677,7 @@ struct TorusTest {
   }
 
   // T2b: one Newton step on g(u) = (ρ-R)² + py² - r², whose rounding error scales with r²
-  // instead of R⁴ (a step above r/32 — grazing, g' ≈ 0 — is discarded); then t = u + tc and
+  // instead of R⁴ (a step that would move the point by more than r/32 — grazing, g' ≈ 0 — is discarded); then t = u + tc + tc2 and
   // the open-interval test of the closest-hit query.
   __device__ __forceinline__ bool finish(Real dx_, Real dy_, Real dz_, Real tmin, Real tmax,
                                          const TorusK<Real>& T, Real& t_out) const
@@ -678,9 +697,16 @@ struct TorusTest {
     const Real s   = fma_(pz, dz_, px * dx_);
     gh             = fma_(e, s, (py * dy_) * rho);  // ρ·g'/2
     const Real du  = Real(0.5) * ((g * rho) / gh);
-    if(abs_(du) <= T.rpol)
+    // du is a step in the ray PARAMETER, r/32 a length: |du|·|d| <= r/32, compared as squares
+    if((du * du) * dsq <= T.rpol2)
       r = r - du;
-    const Real t = r + tc;
+    // t = u + tc + tc2 with ONE rounding at the size of t, as u + tc had before the second shift: the rounding error of
+    // s = big + small is exact in er (Fast2Sum, |big| >= |small|) and joins the small second shift before the last add
+    const bool far = abs_(r) < abs_(tc);
+    const Real big = far ? tc : r, small = far ? r : tc;
+    const Real s2  = big + small;
+    const Real er  = small - (s2 - big);
+    const Real t   = s2 + (er + tc2);
     if(!(t > tmin && t < tmax))
       return false;
     t_out = t;
