@@ -39,6 +39,8 @@
  *   media that fill the tubes      of a synthetic diagnostic)            trt_glow*
  *   the same with media that vary  (none: build-defined, emission and
  *   across a tube                  absorption over the flux-surface label)   trt_glow_profile*
+ *   the response of every ray to   (none: build-defined, the geometry
+ *   every knot of such a medium    matrix of emission tomography)            trt_glow_weights*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -865,6 +867,64 @@ int trt_glow_profile(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray
 int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
                          const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_dev, void* stream);
 
+/* ---- the response of every ray to every knot: glow_weights(rays_in -> 17 weights per ray and torus) ----------------- */
+/* Without absorption (every sigma knot 0) trt_glow_profile is linear in the knots:
+ *   L_c(i) = sum over tori j and knots k of W[j][k][i] * knot_j[k][c],
+ * W[j][k][i] being the world length of ray i inside torus j weighted by the hat function of knot k over x = rho^2 / r^2.
+ * trt_glow_weights returns W — the geometry matrix of emission tomography: it depends on the rays and the tori only, and a
+ * fit of the 17 knots to measured lines of sight (least squares, SART, a prior over the knots) starts from it.
+ *
+ * Layout.  weight[(j * TRT_PROFILE_KNOTS + k) * n + i] is the weight of knot k of torus j on ray i: torus-major, then
+ * knot-major, each (torus, knot) pair a stream of n floats like a row of trt_chords; the buffer holds n_tori * 17 * n floats.
+ * Window, per-ray bound, solvers (TRT_SOLVE_F32 / _F64 only), oriented tori and materials not being read: trt_chords'.
+ * Intervals.  For torus j and ray i the intervals (a, b) are exactly trt_chords' for that torus: the same crossings, the
+ * same pairing rule with in0 and in1, every torus over the full window with no enclosure cull, and no dependence on the
+ * other tori — the pieces are NOT cut at other tori's walls, as trt_glow_profile's are.
+ * The rule.  inv_steps = 1.0f / (float)steps formed on the host, len as in trt_chords, inv_r2_j as in trt_glow_profile.
+ * W[0] .. W[16] = 0; then for every interval (a, b) of torus j in order:
+ *   h = (b - a) * inv_steps;  l = h * len;  g = l * 0.5f;
+ *   for s = 0 .. steps - 1:
+ *     m = fma((float)s + 0.5f, h, a);
+ *     for t in ( fma(-0.288675135f, h, m), fma(0.288675135f, h, m) ), t- first, then t+:
+ *       P, q and rho2 exactly as trt_glow_profile forms them: P = fma(t, d, o) - c per component with t converted to the
+ *       solver's precision, in the frame the solver works in (oriented tori included);  q = sqrt(fma(Pz, Pz, Px * Px)) - R;
+ *       rho2 = fma(q, q, Py * Py);
+ *       x = (float)rho2 * inv_r2_j;  y = (x < 1 ? x : 1) * 16;  kn = min((int)y, 15);  f = y - (float)kn;
+ *       W[kn]     = fma(g, 1.0f - f, W[kn]);
+ *       W[kn + 1] = fma(g, f, W[kn + 1]);
+ * The order of the additions into each accumulator is part of the contract; how the kernel is organised is not.
+ * !(tmax_i > tmin) gives 17 * n_tori zeros for that ray and executes no test.
+ *
+ * What follows from the rule.
+ * Partition.  The two hats at a point sum to 1, so sum over k of W[j][k][i] is trt_chords' length[j * n + i] up to FP32
+ * rounding: within (4 * steps + 16) * 2^-24 relative; a length of 0 gives 17 zeros in bits.
+ * Forward.  In a scene of ONE torus with every sigma knot 0, sum over k of W[k] * knot[k][c] is trt_glow_profile's L_c at
+ * the same steps: the same Gauss points and the same f, differing by rounding only.  With several tori it differs by the
+ * quadrature, because the pieces there are cut at every torus' walls and each piece has its own sub-steps.
+ * A torus alone.  A scene that holds torus j alone gives j's 17 rows bit for bit.
+ * Moments.  For a ray parallel to the torus' axis x is quadratic along the ray and two Gauss points integrate a cubic, so
+ * the moments sum W_k, sum W_k x_k and sum W_k (1 - x_k) are exact (up to rounding) at any step count.
+ * Choosing steps.  The single weights are NOT exact: a hat has kinks at the knots, and a sub-step that straddles one
+ * integrates it at second order.  In an FP64 restatement of the rule (one torus R = 1, r = 0.35, axis-parallel rays, a
+ * chord of 0.7) the worst of the 17 weights was off by 1e-1, 2e-2 and 8e-4 at 4, 16 and 64 steps; over the 64 such rays
+ * of tests/test_weights_cpu.py the error of a ray's worst weight fell by 4.99, 4.02 and 4.75 per doubling from 16 to 128
+ * steps in the median (theory: 4; which sub-steps straddle a knot changes with the count).  A fit of the knots therefore wants more sub-steps than the radiance of a smooth
+ * profile does: 64 where a render is content with 4.  In FP32 a long walk adds about steps * 6e-8 relative.
+ *
+ * TRT_E_INVALID, with "trt_glow_weights" in the message: everything trt_chords refuses; steps outside
+ * 1..TRT_MAX_GLOW_STEPS; a solver other than TRT_SOLVE_F32 / _F64; n_tori * 17 * n overflowing 64 bits.  n == 0 is valid
+ * and launches nothing.  A refused call leaves the ctx usable and the output unwritten.
+ * Stats: as trt_chords' (primary_tests = the tori started, pixels = n).
+ * Not here: absorption (the weights given sigma tables need trt_glow_profile's merged pieces and T); a matrix-free
+ * W^T y; a torus mask (a scene that holds torus j alone gives j's rows bit for bit); a fused camera form.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                     uint32_t steps, float tmin, float tmax, float* weight_out);
+/* Device-resident buffers, asynchronous on `stream`.  The call uses no scratch of the ctx, allocates nothing,
+ * synchronises nothing, puts only kernel nodes on the stream and may be captured. */
+int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                         uint32_t steps, float tmin, float tmax, float* weight_dev, void* stream);
+
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal
  * BEF/shaders/raytrace.rgen:21-57), handed out: as SoA streams that feed trt_trace / trt_occluded / trt_crossings /
@@ -1121,7 +1181,8 @@ int trt_cloud_dev(trt_ctx* ctx, const trt_rendered_data* rendered_dev, uint64_t 
 
 /* Counters of the last render, trace, occluded, crossings, shade, shade_camera, fan_occluded, transmittance or shade_through
  * call made with counting enabled.  trt_chords and trt_glow count as well.
- * So does trt_glow_profile, as trt_glow does. */
+ * So does trt_glow_profile, as trt_glow does.
+ * And trt_glow_weights, as trt_chords does. */
 int trt_enable_stats(trt_ctx* ctx, int on);
 int trt_get_stats(trt_ctx* ctx, trt_stats* out); /* waits for the last counted launch (a graph replay: synchronise it yourself) */
 

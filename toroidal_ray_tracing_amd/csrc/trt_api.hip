@@ -1400,6 +1400,56 @@ extern "C" int trt_glow_profile(trt_ctx* ctx, const trt_rays* in, const float* t
   });
 }
 
+// trt_glow_weights*: trt_chords' checks, the step count, and the 17 * n_tori * n floats of the output.
+static int check_glow_weights(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, uint32_t steps, const float* weight)
+{
+  if(int rc = check_media(ctx, in, weight, "trt_glow_weights")) return rc;
+  if(steps < 1 || steps > TRT_MAX_GLOW_STEPS)
+    return fail(ctx, TRT_E_INVALID, "trt_glow_weights: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", steps, TRT_MAX_GLOW_STEPS);
+  if(scene && scene->n_tori && in->n > UINT64_MAX / TRT_PROFILE_KNOTS / scene->n_tori)
+    return fail(ctx, TRT_E_INVALID, "trt_glow_weights: n_tori * %d * n overflows 64 bits", TRT_PROFILE_KNOTS);
+  return TRT_OK;
+}
+extern "C" int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                    uint32_t steps, float tmin, float tmax, float* weight, void* stream)
+{
+  if(int rc = check_glow_weights(ctx, in, scene, steps, weight)) return rc;
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori and the radii are trusted below)
+  GlowWeightsArgs a;
+  std::memset(a.inv_r2, 0, sizeof a.inv_r2);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    const float r2 = scene->tori[j].r * scene->tori[j].r;   // glow_profiles()' inv_r2
+    a.inv_r2[j]    = 1.0f / r2;
+  }
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.steps        = steps;
+  a.inv_steps    = 1.0f / (float)steps;
+  a.weight       = weight;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_weights);
+}
+
+// Host buffers: trt_chords' staging, with 17 streams per torus through buf[kBufOut].
+extern "C" int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                uint32_t steps, float tmin, float tmax, float* weight_out)
+{
+  if(int rc = check_glow_weights(ctx, in, scene, steps, weight_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0 || !scene) return trt_glow_weights_dev(ctx, in, nullptr, scene, steps, tmin, tmax, weight_out, nullptr);   // validates, launches and writes nothing
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
+  if(in->n > SIZE_MAX / sizeof(float) / TRT_PROFILE_KNOTS / scene->n_tori)
+    return fail(ctx, TRT_E_NOMEM, "trt_glow_weights: n_tori * %d * n floats do not fit the address space", TRT_PROFILE_KNOTS);
+  StagedOut out = {weight_out, (size_t)in->n * sizeof(float) * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr};
+  return bounded_query_host(ctx, in, tmax_per_ray, &out, 1, [&](const trt_rays* rays, const float* bounds) {
+    return trt_glow_weights_dev(ctx, rays, bounds, scene, steps, tmin, tmax, (float*)out.dev, nullptr);
+  });
+}
+
 // ------------------------------------------------------------------------------------------
 // camera rays: the two cameras as ray streams, and the supersampled frame
 // ------------------------------------------------------------------------------------------

@@ -285,6 +285,18 @@ struct GlowProfileArgs {
   float*              rgba;
   unsigned long long* stats;
 };
+// trt_glow_weights*: ChordsArgs with the sub-steps per interval (inv_steps = 1.0f / steps) and Profiles' inv_r2; the weight
+// of knot k of torus j on ray i at weight[(j * TRT_PROFILE_KNOTS + k) * rays.n + i] (17 * n_tori streams).
+struct GlowWeightsArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  uint32_t            steps;
+  float               inv_steps;
+  float               inv_r2[TRT_MAX_TORI];
+  float*              weight;
+  unsigned long long* stats;
+};
 
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
@@ -428,6 +440,7 @@ hipError_t launch_shade_through(const SceneK& scene, const ShadeThroughArgs& a, 
 hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream);       // default solver only
 hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_glow_weights(const SceneK& scene, const GlowWeightsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);

@@ -1,4 +1,4 @@
-// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*), gfx950.
+// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*, trt_glow_weights*), gfx950.
 //
 //   tube_inside      whether the point of a ray at parameter t lies inside torus j's tube
 //   tube_intervals   the pairing rule: torus j's crossings and the two inside tests → at most two intervals
@@ -7,7 +7,9 @@
 //                    pieces between the merged interval ends, one float4 per ray out.
 //   glow_profile_kernel   glow with a radial profile per torus: every piece cut into sub-steps, two Gauss–Legendre points
 //                    in each, the profile tables in LDS.
-//   launch_chords, launch_glow, launch_glow_profile   their grid and launch wrappers.
+//   glow_weights_kernel   the response of every ray to every knot of every torus' profile (sigma = 0): chords_kernel with the
+//                    sub-step walk inside each interval, 17 accumulators per lane in LDS, 17 · n_tori streams out.
+//   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights   their grid and launch wrappers.
 //
 // The crossings of torus j are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
 // window, no enclosure cull); include/trt.h states the arithmetic of everything on top of them, expression by expression.
@@ -410,6 +412,94 @@ __global__ __launch_bounds__(256) void glow_profile_kernel(const SceneNoMat scen
 }
 
 // ------------------------------------------------------------------------------------------
+// glow_weights(rays_in → 17 · n_tori streams: the hat-weighted length of every ray per knot and torus)
+// ------------------------------------------------------------------------------------------
+// chords_kernel with glow_profile_kernel's sub-step walk inside every interval: no column, no merge — torus j's intervals
+// are trt_chords', whatever the other tori do.  At each of the two Gauss–Legendre points of a sub-step the label
+// x = rho² / r² (tube_inside's expression, in the solver's frame and precision) picks the knot kn and the fraction f as
+// profile_add does, and half the sub-step's world length goes to the accumulators kn and kn + 1 as g · (1 − f) and g · f.
+// kn differs from lane to lane, so the 17 accumulators are not registers (a private array indexed by kn would go to
+// scratch) but a column of LDS: acc[k][256], the lane's slot k at acc[k * 256 + threadIdx.x].  Within a wave the 64 lanes
+// of one access sit on 64 different banks whatever their k is (k * 256 words is a multiple of 64): no conflict.  A lane
+// touches its own column only, so nothing but the scene staging needs a barrier.  Per torus: zero the column, walk, store
+// the 17 values to their 17 streams (one instruction of 64 consecutive floats each).  The ray in an oriented torus' frame
+// is formed once per torus.  The sub-step loop and the torus loop are uniform for the wave.
+constexpr uint32_t kWeightLanes = 256;
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256) void glow_weights_kernel(const SceneK scene, const GlowWeightsArgs a)
+{
+  __shared__ SceneK S;
+  __shared__ float  acc[TRT_PROFILE_KNOTS * kWeightLanes];
+  stage_scene<ORIENT>(&S, scene);
+  float* const W = acc + threadIdx.x;
+
+  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
+  {
+    const float tmax   = window_end(a.tmax_per_ray, i, a.tmax);
+    const bool  window = tmax > a.tmin;
+    RayK<Real>  r;
+    float       len = 0.0f;
+    if(window)
+    {
+      const v3 o = {ox[i], oy[i], oz[i]};
+      const v3 d = {dx[i], dy[i], dz[i]};
+      r.set(o, d, a.tmin, tmax);
+      len = ray_length(d);
+    }
+    for(int k = 0; k < scene.n_tori; ++k)
+    {
+      const int j = S.order[k];
+      for(uint32_t c = 0; c < TRT_PROFILE_KNOTS; ++c)
+        W[c * kWeightLanes] = 0.0f;
+      if(window)
+      {
+        ++tests;
+        LocalRay<Real> lr = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+        TorusK<Real>   Tk = torus_k<Real>(S, j);
+        if constexpr(ORIENT)
+          if(is_oriented(S, j))
+          {
+            lr.set(S, j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+            Tk = centred(Tk);
+          }
+        const float ir = a.inv_r2[j];
+        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool, bool) {
+          const float h = (v - u) * a.inv_steps;
+          const float l = h * len;
+          const float g = l * 0.5f;
+          for(uint32_t s = 0; s < a.steps; ++s)
+          {
+            const float m = fma_((float)s + 0.5f, h, u);
+            for(int side = 0; side < 2; ++side)
+            {
+              const Real  t  = (Real)fma_(side ? 0.288675135f : -0.288675135f, h, m);
+              const Real  px = fma_(t, lr.dx, lr.ox) - Tk.cx, py = fma_(t, lr.dy, lr.oy) - Tk.cy, pz = fma_(t, lr.dz, lr.oz) - Tk.cz;
+              const Real  q  = sqrt_(fma_(pz, pz, px * px)) - Tk.R;
+              const float x  = (float)fma_(q, q, py * py) * ir;
+              const float y  = (x < 1.0f ? x : 1.0f) * 16.0f;
+              const int   kn = min((int)y, 15);
+              const float f  = y - (float)kn;
+              float* const w = W + (uint32_t)kn * kWeightLanes;
+              w[0]            = fma_(g, 1.0f - f, w[0]);
+              w[kWeightLanes] = fma_(g, f, w[kWeightLanes]);
+            }
+          }
+        });
+      }
+      for(uint32_t c = 0; c < TRT_PROFILE_KNOTS; ++c)
+        st1(a.weight, ((uint64_t)j * TRT_PROFILE_KNOTS + c) * a.rays.n + i, W[c * kWeightLanes]);
+    }
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 // Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here).
@@ -463,6 +553,24 @@ hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, co
     else
     {
       hipLaunchKernelGGL((glow_profile_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, sc, a);
+      return hipGetLastError();
+    }
+  });
+}
+
+// 17 KiB of static LDS for the accumulators beside the scene; no dynamic LDS.
+static_assert(sizeof(SceneK) + sizeof(GlowWeightsArgs) <= 4096, "the kernel-argument segment of glow_weights_kernel");
+hipError_t launch_glow_weights(const SceneK& scene, const GlowWeightsArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.rays.n, tn);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;
+    else
+    {
+      hipLaunchKernelGGL((glow_weights_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
       return hipGetLastError();
     }
   });

@@ -288,6 +288,13 @@ void HelloHip::glowProfile(void* stream, const trt_rays& raysDev, const float* t
   check(trt_glow_profile_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, profiles, steps, tmin, tmax, rgbaDev, stream), "HelloHip::glowProfile");
 }
 
+void HelloHip::glowWeights(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, uint32_t steps, float tmin, float tmax,
+                           float* weightDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_weights_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, steps, tmin, tmax, weightDev, stream), "HelloHip::glowWeights");
+}
+
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {

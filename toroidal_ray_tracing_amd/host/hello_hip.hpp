@@ -123,6 +123,11 @@ public:
   // integrated in `steps` sub-steps (1..TRT_MAX_GLOW_STEPS).  rgbaDev as glow's.
   void glowProfile(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
                    float tmin, float tmax, float* rgbaDev);
+  // The response of every ray to every knot of such a table (trt_glow_weights_dev): weightDev holds n_tori * 17 * n floats,
+  // the weight of knot k of torus j on ray i at [(j * TRT_PROFILE_KNOTS + k) * n + i]; without absorption glowProfile's
+  // L_c is the sum of weight * knot[k][c].  Every interval of chords() is integrated in `steps` sub-steps.
+  void glowWeights(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, uint32_t steps, float tmin, float tmax,
+                   float* weightDev);
 
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the

@@ -320,6 +320,25 @@ class Tracer:
         self._check(self._L.trt_glow_profile_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
                                                  self._profiles(scene, profiles), int(steps), tmin, tmax, _vp(rgba_ptr), _vp(stream)))
 
+    def glow_weights(self, scene, o, d, steps=4, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """The response of every ray to every knot of every torus' profile (trt_glow_weights) on host arrays: the world
+        length of ray i inside torus j weighted by the hat function of knot k over x = rho^2 / r^2, each interval of
+        ``chords`` integrated in ``steps`` sub-steps (1..64).  With every sigma 0 and one torus,
+        ``glow_profile``'s L_c is ``sum_k W[0, k] * knot[k][c]``.  Returns float32 (n_tori, 17, n)."""
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
+        weight = np.empty((scene.n_tori, abi.TRT_PROFILE_KNOTS, n), np.float32)
+        self._check(self._L.trt_glow_weights(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene), int(steps), tmin, tmax,
+                                             weight.ctypes.data))
+        return weight
+
+    def glow_weights_dev(self, scene, ray_ptrs, n, weight_ptr, steps=4, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints): ray_ptrs = 6 addresses; weight_ptr: n_tori * 17 * n floats, torus-major, then
+        knot-major; tmax_ptr: n per-ray bounds or 0.  Asynchronous on ``stream``."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_glow_weights_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), int(steps), tmin, tmax,
+                                                 _vp(weight_ptr), _vp(stream)))
+
     @staticmethod
     def _profiles(scene, profiles):
         if profiles is None:
