@@ -759,6 +759,9 @@ int trt_shade_scene_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_pus
  * is dropped otherwise.  In exact arithmetic that is at most two intervals per torus.  A grazing contact or an unpaired
  * root never produces a chord that runs to tmax = 10000; a window wholly inside a tube, with no crossing, is one interval.
  * Length.  len = sqrtf((dx * dx + dy * dy) + dz * dz): lengths and coefficients are per unit of WORLD length, not of t.
+ * Scale.  With centres, R, r and origins times 2^k, directions times 2^j, the window times 2^(k - j) and every emission,
+ * sigma and knot times 2^-k, the four calls (trt_chords, trt_glow, trt_glow_profile, trt_glow_weights) return lengths and
+ * weights times 2^k and the same rgba, bit for bit, short of overflow and the subnormals (tests/test_gpu_media_domain.py).
  *
  * trt_chords.  length[j * n + i] is the length of ray i inside torus j (torus-major: each torus' lengths are a stream;
  * the buffer holds n_tori * n floats): acc = 0, then acc = acc + (b - a) * len per interval (a, b) in order, plain FP32

@@ -139,11 +139,12 @@ def glow(A, B, d, media, tmin, tmax_i):
     return L, T
 
 
-def ends_clear(o, d, geo, axes, tmin, info):
-    """True where both end points of the window lie more than 1e-3 from every tube surface (a non-finite end point is
-    outside and clear; so is every ray with an empty window)."""
+def ends_clear(o, d, geo, axes, tmin, info, margin=1e-3):
+    """True where both end points of the window lie more than `margin` (one number, or one per torus) from every tube
+    surface (a non-finite end point is outside and clear; so is every ray with an empty window)."""
     o64, d64 = np.asarray(o, np.float64), np.asarray(d, np.float64)
     ok = np.ones(len(o64), bool)
+    margins = np.broadcast_to(np.asarray(margin, np.float64), (len(geo),))
     with np.errstate(invalid="ignore", over="ignore"):
         P1 = o64 + np.where(info["nonempty"], info["tmax_i"], 0.0)[:, None] * d64
     for j, (C, R, r) in enumerate(geo):
@@ -151,19 +152,22 @@ def ends_clear(o, d, geo, axes, tmin, info):
         for P in (o64 + tmin * d64, P1):
             dist = surface_distance(P, C, axis, R, r)
             with np.errstate(invalid="ignore"):
-                ok &= ~(np.abs(dist) <= 1e-3)
+                ok &= ~(np.abs(dist) <= margins[j])
     return ok | ~info["nonempty"]
 
 
-def robust_rays(o, d, geo, axes, tmin, tmax, bound, info):
+def robust_rays(o, d, geo, axes, tmin, tmax, bound, info, delta=1e-4, t_tol=1e-3, end_margin=1e-3):
+    """The module's `robust`.  The margins are absolute, sized for scenes of size 1 and directions of length about 1; a
+    caller off that scale passes its own: delta and t_tol go to ``crossings_truth.classify_margin_all`` (t_tol also
+    keeps the crossings off a per-ray bound; an (n, 1) array gives every ray its own), end_margin to ``ends_clear``."""
     tend = info["tmax_i"]
     o64, d64 = np.asarray(o, np.float64), np.asarray(d, np.float64)
-    ok = ct.classify_margin_all(o64, d64, geo, axes, tmin, np.where(info["nonempty"], tend, tmin)[:, None])
-    ok &= ends_clear(o, d, geo, axes, tmin, info)
+    ok = ct.classify_margin_all(o64, d64, geo, axes, tmin, np.where(info["nonempty"], tend, tmin)[:, None], delta=delta, t_tol=t_tol)
+    ok &= ends_clear(o, d, geo, axes, tmin, info, end_margin)
     if bound is not None:
         t, _, _, _ = ct.all_crossings(o64, d64, geo, axes, tmin, np.inf)
         with np.errstate(invalid="ignore"):
-            ok &= ~np.any(np.abs(t - tend[:, None]) < 1e-3, axis=1)
+            ok &= ~np.any(np.abs(t - tend[:, None]) < t_tol, axis=1)
     return ok | ~info["nonempty"]   # an empty window is decided by the bound alone
 
 
@@ -207,15 +211,17 @@ def cut_bounds(t, cnt, tmin=TMIN):
     return bound, empty
 
 
-def truth_of(o, d, geo, axes, media, tmin=TMIN, tmax=TMAX, bound=None):
+def truth_of(o, d, geo, axes, media, tmin=TMIN, tmax=TMAX, bound=None, delta=1e-4, t_tol=1e-3, end_margin=1e-3):
     """dict(chords (n_tori, n), L (n, 3), T (n,), robust, ends (n,): the number of interval ends of the ray, t_last (n,):
     its largest finite interval end (0 without one), len (n,), inside_whole (n,): some tube holds the whole window
-    without a crossing, to_end (n,): some interval is closed by the window's end, ends_clear (n,), A, B, info)."""
+    without a crossing, to_end (n,): some interval is closed by the window's end, ends_clear (n,), A, B, info).
+    delta, t_tol and end_margin are robust_rays' margins."""
     A, B, info = intervals(o, d, geo, axes, tmin, tmax, bound)
     L, T = glow(A, B, d, media, tmin, info["tmax_i"])
     fin = np.where(np.isnan(B), 0.0, B)
-    return dict(chords=chords(A, B, d), L=L, T=T, robust=robust_rays(o, d, geo, axes, tmin, tmax, bound, info),
-                ends_clear=ends_clear(o, d, geo, axes, tmin, info),
+    return dict(chords=chords(A, B, d), L=L, T=T,
+                robust=robust_rays(o, d, geo, axes, tmin, tmax, bound, info, delta, t_tol, end_margin),
+                ends_clear=ends_clear(o, d, geo, axes, tmin, info, end_margin),
                 ends=(~np.isnan(A)).sum(axis=(0, 2)) + (~np.isnan(B)).sum(axis=(0, 2)), t_last=fin.max(axis=(0, 2)),
                 len=np.linalg.norm(np.asarray(d, np.float64), axis=1),
                 inside_whole=(info["in0"] & info["in1"] & (info["ncross"] == 0)).any(0), to_end=info["to_end"].any(0),

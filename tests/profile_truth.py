@@ -134,10 +134,12 @@ def converged(c, tables, start=64, limit=512, tol=1e-11):
         L0, T0, N = L1, T1, 2 * N
 
 
-def slope_term(c, tables, root_bar):
+def slope_term(c, tables, root_bar, far=None):
     """(n, 4): the bar on what samples that move with the interval ends change, per channel: the largest
     16 · |knot[k+1] - knot[k]| of the tori the ray runs through, times the bound 2 · len / r on |dx / dt| (the smallest r of
-    those tori), times the bar on a root root_bar · max(1, t_last), times the world length of the ray inside the tubes."""
+    those tori), times the bar on a root root_bar · max(1, t_last), times the world length of the ray inside the tubes.
+    `far` (n,) replaces max(1, t_last) where the root bar is stated otherwise (tests/media_domain.py: scale free)."""
+    far = np.maximum(1.0, c["t_last"]) if far is None else far
     slopes = np.array([16.0 * np.abs(np.diff(np.asarray(t, np.float64), axis=0)).max(0) for t in tables])   # (nt, 4)
     r = np.array([g[2] for g in c["geo"]])
     through = c["chords"] > 0.0                                                                                # (nt, n)
@@ -145,7 +147,7 @@ def slope_term(c, tables, root_bar):
     with np.errstate(invalid="ignore"):
         rmin = np.where(through, r[:, None], np.inf).min(0)
     dxdt = np.where(np.isfinite(rmin), 2.0 * c["len"] / np.where(np.isfinite(rmin), rmin, 1.0), 0.0)
-    return slope * (dxdt * root_bar * np.maximum(1.0, c["t_last"]) * c["chords"].sum(0))[:, None]
+    return slope * (dxdt * root_bar * far * c["chords"].sum(0))[:, None]
 
 
 def axis_rays(C, axis, R, r, offsets, start=-5.0):

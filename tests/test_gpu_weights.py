@@ -150,11 +150,12 @@ def test_forward_is_glow_profile(tr, name, j, kind, solver):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. and 5. the rule in FP64; the known answer
 # ---------------------------------------------------------------------------------------------------------------------
-def knot_bar(c, solver, want):
+def knot_bar(c, solver, want, far=None):
     """(n_tori, 1, n) + the terms that depend on the value: the bar on one weight (or on a sum of weights with
-    coefficients in [-1, 1] whose integrand has a slope of at most 16 in x) — see test_against_the_same_rule_in_fp64."""
+    coefficients in [-1, 1] whose integrand has a slope of at most 16 in x) — see test_against_the_same_rule_in_fp64.
+    `far` (n,) replaces max(1, t_last) where the root bar is stated otherwise (tests/test_gpu_media_domain.py)."""
     ends = (~np.isnan(c["A"])).sum(2) + (~np.isnan(c["B"])).sum(2)                       # E_j (n_tori, n)
-    far = np.maximum(1.0, c["t_last"])[None, :]
+    far = (np.maximum(1.0, c["t_last"]) if far is None else far)[None, :]
     r = np.array([g[2] for g in c["geo"]])[:, None]
     moved_ends = ends * ROOT_BAR[solver] * far * c["len"][None, :]
     moved_samples = 16.0 * (2.0 * c["len"][None, :] / r) * (ROOT_BAR[solver] + 2.0 ** -23) * far * c["chords"]
