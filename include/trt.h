@@ -41,6 +41,8 @@
  *   across a tube                  absorption over the flux-surface label)   trt_glow_profile*
  *   the response of every ray to   (none: build-defined, the geometry
  *   every knot of such a medium    matrix of emission tomography)            trt_glow_weights*
+ *   the same response behind       (none: build-defined, the geometry matrix
+ *   media that absorb              weighted by the transmittance in front)   trt_glow_weights_absorbed*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -760,8 +762,9 @@ int trt_shade_scene_camera_dev(trt_ctx* ctx, const trt_globals* g, const trt_pus
  * root never produces a chord that runs to tmax = 10000; a window wholly inside a tube, with no crossing, is one interval.
  * Length.  len = sqrtf((dx * dx + dy * dy) + dz * dz): lengths and coefficients are per unit of WORLD length, not of t.
  * Scale.  With centres, R, r and origins times 2^k, directions times 2^j, the window times 2^(k - j) and every emission,
- * sigma and knot times 2^-k, the four calls (trt_chords, trt_glow, trt_glow_profile, trt_glow_weights) return lengths and
- * weights times 2^k and the same rgba, bit for bit, short of overflow and the subnormals (tests/test_gpu_media_domain.py).
+ * sigma and knot times 2^-k, the five calls (trt_chords, trt_glow, trt_glow_profile, trt_glow_weights, trt_glow_weights_absorbed)
+ * return lengths and weights times 2^k and the same rgba and trans, bit for bit, short of overflow and the subnormals
+ * (tests/test_gpu_media_domain.py, tests/test_gpu_weights_absorbed_domain.py).
  *
  * trt_chords.  length[j * n + i] is the length of ray i inside torus j (torus-major: each torus' lengths are a stream;
  * the buffer holds n_tori * n floats): acc = 0, then acc = acc + (b - a) * len per interval (a, b) in order, plain FP32
@@ -918,7 +921,7 @@ int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax
  * 1..TRT_MAX_GLOW_STEPS; a solver other than TRT_SOLVE_F32 / _F64; n_tori * 17 * n overflowing 64 bits.  n == 0 is valid
  * and launches nothing.  A refused call leaves the ctx usable and the output unwritten.
  * Stats: as trt_chords' (primary_tests = the tori started, pixels = n).
- * Not here: absorption (the weights given sigma tables need trt_glow_profile's merged pieces and T); a matrix-free
+ * Not here: absorption (the weights given sigma tables are trt_glow_weights_absorbed, below); a matrix-free
  * W^T y; a torus mask (a scene that holds torus j alone gives j's rows bit for bit); a fused camera form.
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
@@ -927,6 +930,80 @@ int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray
  * synchronises nothing, puts only kernel nodes on the stream and may be captured. */
 int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
                          uint32_t steps, float tmin, float tmax, float* weight_dev, void* stream);
+
+/* ---- the same response through absorbing media: glow_weights_absorbed(rays_in -> weights, transmittance) ------------- */
+/* With the absorption tables held fixed, trt_glow_profile's radiance is still linear in the emission knots:
+ *   L_c(i) = sum over tori j and knots k of W[j][k][i] * knot_j[k][c],
+ * W[j][k][i] being the length of ray i inside torus j weighted by the hat of knot k and by the transmittance in front of
+ * each sub-step.  One sigma serves all channels, so W does not depend on the channel.  trt_glow_weights_absorbed returns
+ * that W — the geometry matrix of emission tomography for a plasma with optical depth — and the transmittance left.
+ *
+ * Layout.  weight[(j * TRT_PROFILE_KNOTS + k) * n + i], trt_glow_weights' layout: n_tori * 17 * n floats.  trans[i] is the
+ * transmittance left along ray i, n floats; trans may be NULL and is then not written.
+ * profiles[j] belongs to torus j: scene->n_tori host structs, copied before the call returns.  Only knot[k][3] (sigma) is
+ * read and validated; the emission entries are neither read nor validated — the caller passes the very tables it gives
+ * trt_glow_profile.  Window, per-ray bound, solvers (TRT_SOLVE_F32 / _F64 only), oriented tori and materials not being
+ * read: trt_glow_profile's.
+ * The rule.  Every torus is walked: the emission is the unknown, so no torus is "absent", whatever its sigma.  Intervals,
+ * break points, pieces and active masks are trt_glow_profile's with every torus present: the same crossings, pairing rule
+ * and merge.  inv_steps = 1.0f / (float)steps formed on the host, len as in trt_chords, inv_r2_j as in trt_glow_profile.
+ * All W = 0 and T = 1; then, front to back, for every piece (u, v) with v > u and at least one active torus:
+ *   h = (v - u) * inv_steps;  l = h * len;
+ *   for s = 0 .. steps - 1:
+ *     m = fma((float)s + 0.5f, h, u);  t- = fma(-0.288675135f, h, m);  t+ = fma(0.288675135f, h, m), as in trt_glow_profile;
+ *     at each of the two points, a = 0, then for every active torus j in ascending id:
+ *       P, q, rho2, x, y, kn and f exactly as trt_glow_profile forms them (x = (float)rho2 * inv_r2_j;
+ *       y = (x < 1 ? x : 1) * 16;  kn = min((int)y, 15);  f = y - (float)kn);
+ *       a = a + fma(f, sigma_j[kn + 1] - sigma_j[kn], sigma_j[kn]) — channel 3 of trt_glow_profile's sum, the same
+ *       expression in the same order;
+ *     sg = (a- + a+) * 0.5f;
+ *     E and w from (sg, l) exactly as in trt_glow's step: E = 1 and w = l if sg == 0, else tau = sg * l,
+ *     E = exp2p(-tau * 1.44269504f), w = l * P(tau) if tau < 0.25 and (1 - E) / sg otherwise;
+ *     g = (w * 0.5f) * T, with T taken before this sub-step's update;
+ *     at t-, then at t+, and at each point for every active torus j in ascending id:
+ *       W[j][kn]     = fma(g, 1.0f - f, W[j][kn]);
+ *       W[j][kn + 1] = fma(g, f, W[j][kn + 1]);
+ *     T = T * E.
+ * The order of the additions into each accumulator is part of the contract; how the kernel is organised is not (the
+ * width of its blocks is chosen from n_tori, and the result does not depend on it).
+ * !(tmax_i > tmin) gives 17 * n_tori zeros for that ray, trans = 1, and executes no test.
+ *
+ * What follows from the rule.
+ * Transmittance.  trans is trt_glow_profile's T bit for bit at the same steps, when every torus there has a non-zero
+ * table (an all-zero table makes a torus absent there, and its walls cut no piece): the sigma sum and the step are the
+ * same operations.
+ * Forward.  Under the same condition, sum over j and k of W[j][k] * knot_j[k][c] is trt_glow_profile's L_c at the same
+ * steps, with any number of tori and any sigma.  The two differ by rounding only: w, E and T are the same bits in both
+ * calls, and only the association of the products differs.
+ * No absorption.  With every sigma knot 0, g = l * 0.5f exactly.  In a scene where no two tori's intervals overlap on any
+ * ray (one torus, disjoint tubes), W is trt_glow_weights' bit for bit and trans == 1.0f in bits.  With overlapping tubes
+ * it differs by the quadrature — the pieces are cut at every torus' walls — and sum over k of W[j][k] is still trt_chords'
+ * length, up to the rounding of the partition.
+ * A torus alone.  This does NOT hold here: T in front of torus j depends on the others, and so do the pieces.
+ * Partition.  sum over k of W[j][k][i] is the transmittance-weighted length of ray i inside torus j.  With one torus and a
+ * flat sigma table it is trt_glow's L for emission 1.
+ * Scale.  As stated above for the media calls: sigma times 2^-k (with the geometry times 2^k) gives weights times 2^k and
+ * the same trans, bit for bit.
+ * Choosing steps.  As for trt_glow_weights: a hat has kinks at the knots, the single weights are of second order (the error
+ * of a ray's worst weight fell by about 4 per halving of the sub-steps in an FP64 restatement: tests/test_absorbed_cpu.py),
+ * and a fit wants 64 sub-steps.
+ *
+ * TRT_E_INVALID, with "trt_glow_weights_absorbed" in the message: everything trt_glow_weights refuses; NULL profiles; a
+ * sigma knot that is negative, NaN or infinite (the message names the torus and the knot).  n == 0 is valid and launches
+ * nothing.  A refused call leaves the ctx usable and both outputs unwritten.
+ * Stats: primary_tests = the tori started, that is n_tori times the non-empty windows; pixels = n.
+ * Not here: the response to a sigma knot (it is not linear); a matrix-free W^T y; a torus mask; a fused camera form;
+ * a solver for the fit.
+ * Host buffers: copy in, launch, copy out, synchronise. */
+int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                              const trt_profile* profiles, uint32_t steps, float tmin, float tmax,
+                              float* weight_out, float* trans_out);
+/* Device-resident buffers, asynchronous on `stream`.  `profiles` stays a host pointer: the sigma tables travel in the
+ * kernel arguments.  The call uses no scratch of the ctx, allocates nothing, synchronises nothing, puts only kernel nodes
+ * on the stream and may be captured. */
+int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                                  const trt_profile* profiles, uint32_t steps, float tmin, float tmax,
+                                  float* weight_dev, float* trans_dev, void* stream);
 
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal

@@ -1450,6 +1450,73 @@ extern "C" int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* t
   });
 }
 
+// trt_glow_weights_absorbed*: trt_glow_weights' checks under its own name, and the profiles.
+static int check_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, const trt_profile* profiles, uint32_t steps,
+                                       const float* weight)
+{
+  if(int rc = check_media(ctx, in, weight, "trt_glow_weights_absorbed")) return rc;
+  if(!profiles) return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: NULL profiles");
+  if(steps < 1 || steps > TRT_MAX_GLOW_STEPS)
+    return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", steps, TRT_MAX_GLOW_STEPS);
+  if(scene && scene->n_tori && in->n > UINT64_MAX / TRT_PROFILE_KNOTS / scene->n_tori)
+    return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: n_tori * %d * n overflows 64 bits", TRT_PROFILE_KNOTS);
+  return TRT_OK;
+}
+extern "C" int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                             const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* weight,
+                                             float* trans, void* stream)
+{
+  if(int rc = check_glow_weights_absorbed(ctx, in, scene, profiles, steps, weight)) return rc;
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori and the radii are trusted below)
+  GlowWeightsAbsorbedArgs a;
+  std::memset(a.sigma, 0, sizeof a.sigma);
+  std::memset(a.inv_r2, 0, sizeof a.inv_r2);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)   // sigma only: the emission entries are the unknowns, and are not read
+    {
+      const float v = profiles[j].knot[k][3];
+      if(!(v >= 0.0f) || std::isinf(v))
+        return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: the profile of torus %u has sigma = %g at knot %u; sigma must be "
+                                        "finite and not negative", j, (double)v, k);
+      a.sigma[j][k] = v;
+    }
+    const float r2 = scene->tori[j].r * scene->tori[j].r;   // glow_profiles()' inv_r2
+    a.inv_r2[j]    = 1.0f / r2;
+  }
+  a.rays         = *in;
+  a.tmax_per_ray = tmax_per_ray;
+  a.tmin         = tmin;
+  a.tmax         = tmax;
+  a.steps        = steps;
+  a.inv_steps    = 1.0f / (float)steps;
+  a.weight       = weight;
+  a.trans        = trans;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_weights_absorbed);
+}
+
+// Host buffers: trt_glow_weights' staging, and the transmittance (if asked for) through buf[kBufOut + 1].
+extern "C" int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                         const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* weight_out,
+                                         float* trans_out)
+{
+  if(int rc = check_glow_weights_absorbed(ctx, in, scene, profiles, steps, weight_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0 || !scene)   // validates, launches and writes nothing
+    return trt_glow_weights_absorbed_dev(ctx, in, nullptr, scene, profiles, steps, tmin, tmax, weight_out, trans_out, nullptr);
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
+  if(in->n > SIZE_MAX / sizeof(float) / TRT_PROFILE_KNOTS / scene->n_tori)
+    return fail(ctx, TRT_E_NOMEM, "trt_glow_weights_absorbed: n_tori * %d * n floats do not fit the address space", TRT_PROFILE_KNOTS);
+  StagedOut outs[2] = {{weight_out, (size_t)in->n * sizeof(float) * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr},
+                       {trans_out, (size_t)in->n * sizeof(float), kBufOut + 1, nullptr}};
+  return bounded_query_host(ctx, in, tmax_per_ray, outs, trans_out ? 2 : 1, [&](const trt_rays* rays, const float* bounds) {
+    return trt_glow_weights_absorbed_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, (float*)outs[0].dev,
+                                         trans_out ? (float*)outs[1].dev : nullptr, nullptr);
+  });
+}
+
 // ------------------------------------------------------------------------------------------
 // camera rays: the two cameras as ray streams, and the supersampled frame
 // ------------------------------------------------------------------------------------------

@@ -370,6 +370,7 @@ Tuning tuning_from_env()
   u64("TRT_POST_BLOCKS_PER_CU", t.post_blocks_per_cu);
   u64("TRT_SPLAT_BLOCKS_PER_CU", t.splat_blocks_per_cu);
   i32("TRT_SPLAT_VARIANT", t.splat_variant);
+  u32("TRT_ABSORBED_LANES", t.absorbed_lanes);
 #endif
   return t;
 }

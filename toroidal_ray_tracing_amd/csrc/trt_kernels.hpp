@@ -136,6 +136,7 @@ struct Tuning {
   uint64_t post_blocks_per_cu = 0;    // TRT_POST_BLOCKS_PER_CU
   uint64_t splat_blocks_per_cu = 0;   // TRT_SPLAT_BLOCKS_PER_CU
   int      splat_variant      = -1;   // TRT_SPLAT_VARIANT
+  uint32_t absorbed_lanes     = 0;    // TRT_ABSORBED_LANES: 64 | 128 | 256, glow_weights_absorbed_kernel's block width where it fits 64 KiB of LDS; 0 = chosen from n_tori
 };
 Tuning tuning_from_env();   // defaults in the release build
 
@@ -297,6 +298,21 @@ struct GlowWeightsArgs {
   float*              weight;
   unsigned long long* stats;
 };
+// trt_glow_weights_absorbed*: GlowWeightsArgs with the sigma column of every torus' profile (validated and copied on the
+// host, indexed by TORUS id: 544 B for eight tori; the kernel stages them into LDS) and the transmittance left along ray i
+// at trans[i] (nullptr: not written).
+struct GlowWeightsAbsorbedArgs {
+  trt_rays            rays;
+  const float*        tmax_per_ray;
+  float               tmin, tmax;
+  uint32_t            steps;
+  float               inv_steps;
+  float               sigma[TRT_MAX_TORI][TRT_PROFILE_KNOTS];
+  float               inv_r2[TRT_MAX_TORI];
+  float*              weight;
+  float*              trans;
+  unsigned long long* stats;
+};
 
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
@@ -417,6 +433,13 @@ inline uint32_t stream_grid(uint64_t n, const Tuning& tn)
   const uint64_t want = (n + 255) / 256, cap = tn.trace_blocks ? tn.trace_blocks : 256u * 16u;
   return (uint32_t)(want < cap ? want : cap);
 }
+// The same for blocks of `lanes` threads (64, 128 or 256): one block per `lanes` items, the cap scaled so that the grid
+// holds as many lanes as stream_grid's.
+inline uint32_t stream_grid_lanes(uint64_t n, uint32_t lanes, const Tuning& tn)
+{
+  const uint64_t want = (n + lanes - 1) / lanes, cap = (uint64_t)(tn.trace_blocks ? tn.trace_blocks : 256u * 16u) * (256u / lanes);
+  return (uint32_t)(want < cap ? want : cap);
+}
 // The grid of a kernel that runs shade_camera_walk (trt_render.hpp): one wave per 8×8 tile of the band, four to a block.
 inline uint32_t camera_grid(const CameraArgs& c, const Tuning& tn)
 {
@@ -441,6 +464,7 @@ hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning&
 hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream);       // default solver only
 hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_glow_weights(const SceneK& scene, const GlowWeightsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_glow_weights_absorbed(const SceneK& scene, const GlowWeightsAbsorbedArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);

@@ -1,4 +1,5 @@
-// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*, trt_glow_weights*), gfx950.
+// trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*, trt_glow_weights*,
+// trt_glow_weights_absorbed*), gfx950.
 //
 //   tube_inside      whether the point of a ray at parameter t lies inside torus j's tube
 //   tube_intervals   the pairing rule: torus j's crossings and the two inside tests → at most two intervals
@@ -9,7 +10,10 @@
 //                    in each, the profile tables in LDS.
 //   glow_weights_kernel   the response of every ray to every knot of every torus' profile (sigma = 0): chords_kernel with the
 //                    sub-step walk inside each interval, 17 accumulators per lane in LDS, 17 · n_tori streams out.
-//   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights   their grid and launch wrappers.
+//   glow_weights_absorbed_kernel   the same response behind absorbing media: glow_profile_kernel's merged pieces and running T,
+//                    glow_weights_kernel's deposit into the accumulators of ALL tori, the block width chosen from n_tori.
+//   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights, launch_glow_weights_absorbed   their grid and
+//                    launch wrappers.
 //
 // The crossings of torus j are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
 // window, no enclosure cull); include/trt.h states the arithmetic of everything on top of them, expression by expression.
@@ -163,17 +167,26 @@ __device__ __forceinline__ float one_minus_exp_over(float tau)
   return fma_(tau, p, 1.0f);
 }
 
-// The homogeneous step of trt_glow over the world length l, with the summed emission (e0, e1, e2) and absorption sg:
-// glow_kernel's piece and glow_profile_kernel's sub-step.
-__device__ __forceinline__ void glow_step(float e0, float e1, float e2, float sg, float l, float& Lr, float& Lg, float& Lb, float& T)
+// What a homogeneous step over the world length l with the absorption sg lets through, E = exp(−sg · l), and the weight
+// wgt = (1 − E) / sg of what it emits (l where sg is 0; the series below kGlowSeries).
+__device__ __forceinline__ void glow_step_weight(float sg, float l, float& E, float& wgt)
 {
   const float tau = sg * l;
-  float E = 1.0f, wgt = l;
+  E   = 1.0f;
+  wgt = l;
   if(sg != 0.0f)
   {
     E   = exp2_poly(-tau * 1.44269504f);
     wgt = tau < kGlowSeries ? l * one_minus_exp_over(tau) : (1.0f - E) / sg;
   }
+}
+
+// The homogeneous step of trt_glow over the world length l, with the summed emission (e0, e1, e2) and absorption sg:
+// glow_kernel's piece and glow_profile_kernel's sub-step.
+__device__ __forceinline__ void glow_step(float e0, float e1, float e2, float sg, float l, float& Lr, float& Lg, float& Lb, float& T)
+{
+  float E, wgt;
+  glow_step_weight(sg, l, E, wgt);
   Lr = fma_(e0 * wgt, T, Lr);
   Lg = fma_(e1 * wgt, T, Lg);
   Lb = fma_(e2 * wgt, T, Lb);
@@ -500,6 +513,155 @@ __global__ __launch_bounds__(256) void glow_weights_kernel(const SceneK scene, c
 }
 
 // ------------------------------------------------------------------------------------------
+// glow_weights_absorbed(rays_in → 17 · n_tori streams and the transmittance: the weights behind absorbing media)
+// ------------------------------------------------------------------------------------------
+// glow_profile_kernel's column, merge and piece walk with EVERY torus present, and glow_weights_kernel's deposit: in every
+// sub-step the sigma of the active tori is summed at the two Gauss–Legendre points as profile_add sums channel 3, the step
+// gives E and the weight w (glow_step_weight), and g = (w · 0.5) · T — T in front of the sub-step — goes to the knots kn
+// and kn + 1 of every active torus at both points.  A sub-step deposits into every active torus, so the accumulators of
+// ALL tori are live at once: 17 · n_tori floats per lane, lane-minor in dynamic LDS (acc[(j · 17 + k) · LANES + lane]: the
+// 64 lanes of an access sit on 64 different banks whatever their k is).  Behind them, per lane: y = min(x, 1) · 16 of the
+// two points for every torus (2 · n_tori floats) — kn and f come from y alone, so the deposit reads them back instead of
+// forming the point in the torus' frame a second time, and no private array indexed by j goes to scratch — and the 4 · n_tori
+// slots of the crossing column.  96 · n_tori bytes per lane in all: the host picks LANES (256, 128 or 64) from n_tori so
+// that a block stays below 64 KiB.  A lane touches its own columns only and the order of the additions into an
+// accumulator is the walk's, so the result does not depend on LANES and nothing but the staging needs a barrier.
+constexpr uint32_t kAbsorbedLaneBytes = 4u * (TRT_PROFILE_KNOTS + 2u) + 4u * (uint32_t)(sizeof(float) + sizeof(uint8_t));   // per torus: 96
+static_assert(sizeof(SceneNoMat) + sizeof(GlowWeightsAbsorbedArgs) <= 4096, "the kernel-argument segment of glow_weights_absorbed_kernel");
+template <class Real, bool ORIENT, uint32_t LANES>
+__global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const SceneNoMat scene, const GlowWeightsAbsorbedArgs a)
+{
+  __shared__ SceneK S;
+  __shared__ float  sigma[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float lane_lds[];   // [17 n_tori][LANES] acc, [2 n_tori][LANES] y, [K][LANES] t, [K][LANES] bytes
+  const uint32_t n_tori = scene.head[0];
+  {
+    const float* src = &a.sigma[0][0];
+    for(uint32_t i = threadIdx.x; i < TRT_PROFILE_KNOTS * n_tori; i += LANES)
+      sigma[i] = src[i];
+  }
+  stage_scene_no_mat<ORIENT>(&S, scene);
+  __syncthreads();   // publishes the tables and the scene
+
+  const uint32_t K   = 4u * n_tori, n_acc = TRT_PROFILE_KNOTS * n_tori;
+  float* const   W   = lane_lds + threadIdx.x;
+  float* const   Y   = lane_lds + n_acc * LANES + threadIdx.x;
+  float*         ct  = lane_lds + (n_acc + 2u * n_tori) * LANES + threadIdx.x;
+  uint8_t*       cw  = reinterpret_cast<uint8_t*>(lane_lds + (n_acc + 2u * n_tori + K) * LANES) + threadIdx.x;
+
+  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * LANES;
+  for(uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x; i < a.rays.n; i += stride)
+  {
+    const float tmax = window_end(a.tmax_per_ray, i, a.tmax);
+    float       T    = 1.0f;
+    for(uint32_t c = 0; c < n_acc; ++c)
+      W[c * LANES] = 0.0f;
+    if(tmax > a.tmin)
+    {
+      const v3 o = {ox[i], oy[i], oz[i]};
+      const v3 d = {dx[i], dy[i], dz[i]};
+      RayK<Real> r;
+      r.set(o, d, a.tmin, tmax);
+      const float len = ray_length(d);
+      uint32_t active = 0u, count = 0u;
+      for(int k = 0; k < S.n_tori; ++k)
+      {
+        const int j = S.order[k];
+        ++tests;
+        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
+          if(from_start) active |= 1u << j;
+          else column_insert<LANES>(ct, cw, K, count, u, j, true);
+          if(!to_end) column_insert<LANES>(ct, cw, K, count, v, j, false);
+        });
+      }
+      float u = a.tmin;
+      for(uint32_t k = 0; k <= count; ++k)
+      {
+        const bool     last = k == count;
+        const float    v    = last ? tmax : ct[k * LANES];
+        const uint32_t w    = last ? 0u : cw[k * LANES];
+        if(active != 0u && v > u)
+        {
+          const float h = (v - u) * a.inv_steps;
+          const float l = h * len;
+          for(uint32_t s = 0; s < a.steps; ++s)
+          {
+            const float m  = fma_((float)s + 0.5f, h, u);
+            const Real  ta = (Real)fma_(-0.288675135f, h, m), tb = (Real)fma_(0.288675135f, h, m);
+            float A = 0.0f, B = 0.0f;
+            for(uint32_t j = 0; j < n_tori; ++j)
+              if((active >> j) & 1u)
+              {
+                LocalRay<Real> lr = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+                TorusK<Real>   Tk = torus_k<Real>(S, (int)j);
+                if constexpr(ORIENT)
+                  if(is_oriented(S, (int)j))
+                  {
+                    lr.set(S, (int)j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+                    Tk = centred(Tk);
+                  }
+                const Real  ax = fma_(ta, lr.dx, lr.ox) - Tk.cx, ay = fma_(ta, lr.dy, lr.oy) - Tk.cy, az = fma_(ta, lr.dz, lr.oz) - Tk.cz;
+                const Real  bx = fma_(tb, lr.dx, lr.ox) - Tk.cx, by = fma_(tb, lr.dy, lr.oy) - Tk.cy, bz = fma_(tb, lr.dz, lr.oz) - Tk.cz;
+                const Real  qa = sqrt_(fma_(az, az, ax * ax)) - Tk.R, qb = sqrt_(fma_(bz, bz, bx * bx)) - Tk.R;
+                const float ir = a.inv_r2[j];
+                const float xa = (float)fma_(qa, qa, ay * ay) * ir, xb = (float)fma_(qb, qb, by * by) * ir;
+                const float ya = (xa < 1.0f ? xa : 1.0f) * 16.0f, yb = (xb < 1.0f ? xb : 1.0f) * 16.0f;
+                const int   ka = min((int)ya, 15), kb = min((int)yb, 15);
+                const float* const sg = sigma + j * TRT_PROFILE_KNOTS;
+                A = A + fma_(ya - (float)ka, sg[ka + 1] - sg[ka], sg[ka]);
+                B = B + fma_(yb - (float)kb, sg[kb + 1] - sg[kb], sg[kb]);
+                Y[(2u * j) * LANES]      = ya;
+                Y[(2u * j + 1u) * LANES] = yb;
+              }
+            float E, wgt;
+            glow_step_weight((A + B) * 0.5f, l, E, wgt);
+            const float g = (wgt * 0.5f) * T;
+            // The deposits at t-, then at t+.  The four accumulators are read at once — one LDS latency per torus, not four
+            // in a row — and where t+ falls on a slot of t- it adds to what t- left there: the same operations in the same
+            // order per accumulator.  The stores go out t- first, so that a shared slot keeps the value with both deposits.
+            for(uint32_t j = 0; j < n_tori; ++j)
+              if((active >> j) & 1u)
+              {
+                const float  ya = Y[(2u * j) * LANES], yb = Y[(2u * j + 1u) * LANES];
+                const int    ka = min((int)ya, 15), kb = min((int)yb, 15);
+                const float  fa = ya - (float)ka, fb = yb - (float)kb;
+                float* const wa = W + (j * TRT_PROFILE_KNOTS + (uint32_t)ka) * LANES;
+                float* const wb = W + (j * TRT_PROFILE_KNOTS + (uint32_t)kb) * LANES;
+                float a0 = wa[0], a1 = wa[LANES], b0 = wb[0], b1 = wb[LANES];
+                a0 = fma_(g, 1.0f - fa, a0);
+                a1 = fma_(g, fa, a1);
+                b0 = kb == ka ? a0 : (kb == ka + 1 ? a1 : b0);
+                b1 = kb == ka ? a1 : (kb + 1 == ka ? a0 : b1);
+                b0 = fma_(g, 1.0f - fb, b0);
+                b1 = fma_(g, fb, b1);
+                wa[0]     = a0;
+                wa[LANES] = a1;
+                wb[0]     = b0;
+                wb[LANES] = b1;
+              }
+            T = T * E;
+          }
+        }
+        const uint32_t bit = 1u << (w >> 1);
+        if(!last)
+          active = (w & 1u) ? (active | bit) : (active & ~bit);
+        u = v;
+      }
+    }
+    for(uint32_t c = 0; c < n_acc; ++c)
+      st1(a.weight, (uint64_t)c * a.rays.n + i, W[c * LANES]);
+    if(a.trans)
+      st1(a.trans, i, T);
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 // Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here).
@@ -572,6 +734,49 @@ hipError_t launch_glow_weights(const SceneK& scene, const GlowWeightsArgs& a, co
     {
       hipLaunchKernelGGL((glow_weights_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
       return hipGetLastError();
+    }
+  });
+}
+
+// The block width from n_tori: 96 · n_tori bytes of dynamic LDS per lane beside 2.4 KiB of static LDS (the scene, the
+// sigma tables), every block at or below 64 KiB — no function attribute is needed and at least two blocks share a CU.
+// 256 lanes up to two tori (48 KiB), 128 up to five (60 KiB), 64 beyond (48 KiB for eight).  TRT_ABSORBED_LANES (64, 128
+// or 256, for measurements: tools/bench_weights_absorbed.py) overrides the choice where the block still fits 64 KiB.
+uint32_t glow_weights_absorbed_lanes(int n_tori, const Tuning& tn)
+{
+  const uint32_t pick = n_tori <= 2 ? 256u : n_tori <= 5 ? 128u : 64u, want = tn.absorbed_lanes;
+  if((want == 64u || want == 128u || want == 256u) && want * kAbsorbedLaneBytes * (uint32_t)n_tori + 4096u <= 65536u)
+    return want;
+  return pick;
+}
+template <class Real, bool ORIENT, uint32_t LANES>
+static hipError_t launch_absorbed_width(const SceneNoMat& sc, const GlowWeightsAbsorbedArgs& a, uint32_t n_tori, const Tuning& tn, hipStream_t stream)
+{
+  static_assert(LANES * kAbsorbedLaneBytes * (LANES == 256u ? 2u : LANES == 128u ? 5u : TRT_MAX_TORI) + sizeof(SceneK) + 1024u <= 65536u,
+                "a block of glow_weights_absorbed_kernel stays at or below 64 KiB of LDS");
+  hipLaunchKernelGGL((glow_weights_absorbed_kernel<Real, ORIENT, LANES>), dim3(stream_grid_lanes(a.rays.n, LANES, tn)), dim3(LANES),
+                     LANES * kAbsorbedLaneBytes * n_tori, stream, sc, a);
+  return hipGetLastError();
+}
+hipError_t launch_glow_weights_absorbed(const SceneK& scene, const GlowWeightsAbsorbedArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.rays.n == 0)
+    return hipSuccess;
+  const uint32_t lanes = glow_weights_absorbed_lanes(scene.n_tori, tn);
+  SceneNoMat     sc;
+  std::memcpy(sc.head, &scene, sizeof sc.head);
+  std::memcpy(sc.rot, scene.rot, sizeof sc.rot);
+  return with_solver(scene, [&](auto real, auto alt, auto ori) {
+    if constexpr(decltype(alt)::value)
+      return hipErrorInvalidValue;
+    else
+    {
+      using Real          = decltype(real);
+      constexpr bool kOri = decltype(ori)::value;
+      const uint32_t nt   = (uint32_t)scene.n_tori;
+      return lanes == 256u ? launch_absorbed_width<Real, kOri, 256u>(sc, a, nt, tn, stream)
+           : lanes == 128u ? launch_absorbed_width<Real, kOri, 128u>(sc, a, nt, tn, stream)
+                           : launch_absorbed_width<Real, kOri, 64u>(sc, a, nt, tn, stream);
     }
   });
 }

@@ -560,25 +560,27 @@ __device__ __forceinline__ void shade_camera_walk(const CameraArgs& cam, float* 
 // its reasons: crossings_kernel, trt_rays.hip).  ct / cw point at the lane's slot 0; `count` is the number of crossings
 // met so far (it may exceed K).  Insertion is stable — a crossing goes behind every kept one with t <= its own — and
 // once the column is full only a crossing strictly below the last kept one gets in.  (Parameters by reference, as the
-// lambda this was captured them: passed by value, crossings_kernel comes out two VGPRs larger.)
+// lambda this was captured them: passed by value, crossings_kernel comes out two VGPRs larger.)  LANES is the block's width,
+// the stride between a lane's slots: 256 everywhere but in glow_weights_absorbed_kernel.
 constexpr uint32_t kCrossingSlotBytes = 256u * (sizeof(float) + sizeof(uint8_t));   // dynamic LDS per slot
 static_assert(TRT_MAX_TORI <= 128, "the column packs id << 1 | entering into a byte");
+template <uint32_t LANES = 256u>
 __device__ __forceinline__ void column_insert(float* const& ct, uint8_t* const& cw, const uint32_t& K, uint32_t& count, float t, const int& j, bool entering)
 {
   uint32_t p = umin(count, K);   // slots kept so far
   ++count;
   if(p == K)
   {
-    if(!(t < ct[(K - 1u) * 256u])) return;
+    if(!(t < ct[(K - 1u) * LANES])) return;
     p = K - 1u;
   }
-  for(; p > 0u && ct[(p - 1u) * 256u] > t; --p)
+  for(; p > 0u && ct[(p - 1u) * LANES] > t; --p)
   {
-    ct[p * 256u] = ct[(p - 1u) * 256u];
-    cw[p * 256u] = cw[(p - 1u) * 256u];
+    ct[p * LANES] = ct[(p - 1u) * LANES];
+    cw[p * LANES] = cw[(p - 1u) * LANES];
   }
-  ct[p * 256u] = t;
-  cw[p * 256u] = (uint8_t)(((uint32_t)j << 1) | (entering ? 1u : 0u));
+  ct[p * LANES] = t;
+  cw[p * LANES] = (uint8_t)(((uint32_t)j << 1) | (entering ? 1u : 0u));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -295,6 +295,14 @@ void HelloHip::glowWeights(void* stream, const trt_rays& raysDev, const float* t
   check(trt_glow_weights_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, steps, tmin, tmax, weightDev, stream), "HelloHip::glowWeights");
 }
 
+void HelloHip::glowWeightsAbsorbed(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles,
+                                   uint32_t steps, float tmin, float tmax, float* weightDev, float* transDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_weights_absorbed_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, profiles, steps, tmin, tmax, weightDev, transDev, stream),
+        "HelloHip::glowWeightsAbsorbed");
+}
+
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {

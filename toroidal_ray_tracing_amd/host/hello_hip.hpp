@@ -128,6 +128,11 @@ public:
   // L_c is the sum of weight * knot[k][c].  Every interval of chords() is integrated in `steps` sub-steps.
   void glowWeights(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, uint32_t steps, float tmin, float tmax,
                    float* weightDev);
+  // The same response behind media that absorb (trt_glow_weights_absorbed_dev): glowProfile's tables, of which only sigma is
+  // read; every deposit is weighted by the transmittance in front of it, so that glowProfile's L_c is the sum of
+  // weight * knot[k][c] over tori and knots with any sigma.  transDev: the transmittance left per ray, or nullptr.
+  void glowWeightsAbsorbed(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles,
+                           uint32_t steps, float tmin, float tmax, float* weightDev, float* transDev);
 
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the

@@ -339,6 +339,29 @@ class Tracer:
         self._check(self._L.trt_glow_weights_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene), int(steps), tmin, tmax,
                                                  _vp(weight_ptr), _vp(stream)))
 
+    def glow_weights_absorbed(self, scene, o, d, profiles, steps=4, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """``glow_weights`` behind media that absorb (trt_glow_weights_absorbed) on host arrays: profiles as
+        ``glow_profile`` takes them, of which only sigma is read; the pieces are ``glow_profile``'s with every torus
+        present, and every sub-step's deposit is weighted by the transmittance in front of it, so that ``glow_profile``'s
+        L_c is ``sum_jk W[j, k] * knot_j[k][c]`` up to rounding.  Returns (W float32 (n_tori, 17, n), T float32 (n,))."""
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
+        weight = np.empty((scene.n_tori, abi.TRT_PROFILE_KNOTS, n), np.float32)
+        trans = np.empty(n, np.float32)
+        self._check(self._L.trt_glow_weights_absorbed(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene),
+                                                      self._profiles(scene, profiles), int(steps), tmin, tmax,
+                                                      weight.ctypes.data, trans.ctypes.data))
+        return weight, trans
+
+    def glow_weights_absorbed_dev(self, scene, ray_ptrs, n, profiles, weight_ptr, trans_ptr=0, steps=4, tmax_ptr=0, tmin=0.001,
+                                  tmax=10000.0, stream=0):
+        """Device pointers (ints) as in ``glow_weights_dev``; trans_ptr: n floats or 0 (not written); ``profiles`` stays on
+        the host (the sigma tables travel in the launch's arguments).  Asynchronous on ``stream``."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_glow_weights_absorbed_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
+                                                          self._profiles(scene, profiles), int(steps), tmin, tmax,
+                                                          _vp(weight_ptr), _vp(trans_ptr), _vp(stream)))
+
     @staticmethod
     def _profiles(scene, profiles):
         if profiles is None:
