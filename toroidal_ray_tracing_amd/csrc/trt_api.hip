@@ -1246,41 +1246,100 @@ static int check_media(trt_ctx* ctx, const trt_rays* in, const void* out, const 
   if(!out) return fail(ctx, TRT_E_INVALID, "%s: NULL output", who);
   return check_walk_solver(ctx, who);
 }
+// The refusals several of them share; a call makes them behind check_media(), each in the place it has among that call's others.
+static int check_steps(trt_ctx* ctx, const char* who, uint32_t steps)
+{
+  if(steps >= 1 && steps <= TRT_MAX_GLOW_STEPS) return TRT_OK;
+  return fail(ctx, TRT_E_INVALID, "%s: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", who, steps, TRT_MAX_GLOW_STEPS);
+}
+static int check_rgba(trt_ctx* ctx, const char* who, const float* rgba)
+{
+  if(!((uintptr_t)rgba & 15)) return TRT_OK;
+  return fail(ctx, TRT_E_INVALID, "%s: the rgba output must be 16-byte aligned (it is written as float4)", who);
+}
+// The output of the calls that write `per_ray` (1 or TRT_PROFILE_KNOTS) streams per torus: its float count in 64 bits, and
+// — for a host buffer, behind build_scene(), so that n_tori can be trusted — its bytes in the address space.
+static int check_streams_count(trt_ctx* ctx, const char* who, const trt_rays* in, const trt_scene* scene, uint32_t per_ray)
+{
+  if(!(scene && scene->n_tori && in->n > UINT64_MAX / per_ray / scene->n_tori)) return TRT_OK;
+  if(per_ray == 1) return fail(ctx, TRT_E_INVALID, "%s: n_tori * n overflows 64 bits", who);
+  return fail(ctx, TRT_E_INVALID, "%s: n_tori * %u * n overflows 64 bits", who, per_ray);
+}
+static int check_streams_bytes(trt_ctx* ctx, const char* who, const trt_rays* in, const trt_scene* scene, uint32_t per_ray)
+{
+  if(!(in->n > SIZE_MAX / sizeof(float) / per_ray / scene->n_tori)) return TRT_OK;
+  if(per_ray == 1) return fail(ctx, TRT_E_NOMEM, "%s: n_tori * n floats do not fit the address space", who);
+  return fail(ctx, TRT_E_NOMEM, "%s: n_tori * %u * n floats do not fit the address space", who, per_ray);
+}
+// Emission and sigma must be finite and not negative.
+static bool medium_value_ok(float v) { return v >= 0.0f && !std::isinf(v); }
+// 1 / r² of every torus of a built scene: r * r rounded to FP32, then the quotient; zero behind n_tori.
+static void fill_inv_r2(const trt_scene* scene, float (&inv_r2)[TRT_MAX_TORI])
+{
+  std::memset(inv_r2, 0, sizeof inv_r2);
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+  {
+    const float r2 = scene->tori[j].r * scene->tori[j].r;
+    inv_r2[j]      = 1.0f / r2;
+  }
+}
+// What every *Args of the family begins with, and the sub-steps of those that have them.
+static MediaRays media_rays(const trt_rays* in, const float* tmax_per_ray, float tmin, float tmax) { return {*in, tmax_per_ray, tmin, tmax}; }
+static MediaSteps media_steps(uint32_t steps) { return {steps, 1.0f / (float)steps}; }
+
+// The host-buffer form of a call that writes streams (`who`), behind its own checks: with no ray or no scene dev() on the
+// host pointers validates, launches and writes nothing; else the rays staged like trt_trace's, the bounds through
+// buf[kBufTmax], the per_ray * n_tori streams through buf[kBufOut] and `second` (a float per ray, if asked for) through
+// buf[kBufOut + 1].  dev(rays, bounds, out, second) is the *_dev form.
+template <class Dev>
+static int media_streams_host(trt_ctx* ctx, const char* who, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                              uint32_t per_ray, float* out, float* second, Dev&& dev)
+{
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0 || !scene) return dev(in, nullptr, out, second);
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  if(int rc = check_streams_bytes(ctx, who, in, scene, per_ray)) return rc;
+  StagedOut outs[2] = {{out, (size_t)in->n * sizeof(float) * per_ray * scene->n_tori, kBufOut, nullptr},
+                       {second, (size_t)in->n * sizeof(float), kBufOut + 1, nullptr}};
+  return bounded_query_host(ctx, in, tmax_per_ray, outs, second ? 2 : 1, [&](const trt_rays* rays, const float* bounds) {
+    return dev(rays, bounds, (float*)outs[0].dev, second ? (float*)outs[1].dev : nullptr);
+  });
+}
+// The host-buffer form of a call that writes a float4 per ray, behind its own checks: with no ray dev() on the host
+// pointer validates, launches and writes nothing; else the image goes through buf[kBufRgba].  dev(rays, bounds, rgba).
+template <class Dev>
+static int media_rgba_host(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, float* rgba_out, Dev&& dev)
+{
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(in->n == 0) return dev(in, nullptr, rgba_out);
+  StagedOut image = {rgba_out, (size_t)in->n * 4 * sizeof(float), kBufRgba, nullptr};
+  return bounded_query_host(ctx, in, tmax_per_ray, &image, 1,
+                            [&](const trt_rays* rays, const float* bounds) { return dev(rays, bounds, (float*)image.dev); });
+}
 
 static int check_chords(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, const float* length)
 {
   if(int rc = check_media(ctx, in, length, "trt_chords")) return rc;
-  if(scene && scene->n_tori && in->n > UINT64_MAX / scene->n_tori)
-    return fail(ctx, TRT_E_INVALID, "trt_chords: n_tori * n overflows 64 bits");
-  return TRT_OK;
+  return check_streams_count(ctx, "trt_chords", in, scene, 1);
 }
 extern "C" int trt_chords_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
                               float tmax, float* length, void* stream)
 {
   if(int rc = check_chords(ctx, in, scene, length)) return rc;
   ChordsArgs a;
-  a.rays         = *in;
-  a.tmax_per_ray = tmax_per_ray;
-  a.tmin         = tmin;
-  a.tmax         = tmax;
-  a.length       = length;
+  a.in     = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.length = length;
   return ray_query(ctx, scene, stream, in->n, a, launch_chords);
 }
-
-// Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], the n_tori streams through buf[kBufOut].
 extern "C" int trt_chords(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, float tmin,
                           float tmax, float* length_out)
 {
   if(int rc = check_chords(ctx, in, scene, length_out)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0 || !scene) return trt_chords_dev(ctx, in, nullptr, scene, tmin, tmax, length_out, nullptr);   // validates, launches and writes nothing
-  const SceneK* S = nullptr;
-  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
-  if(in->n > SIZE_MAX / sizeof(float) / scene->n_tori) return fail(ctx, TRT_E_NOMEM, "trt_chords: n_tori * n floats do not fit the address space");
-  StagedOut out = {length_out, (size_t)in->n * sizeof(float) * scene->n_tori, kBufOut, nullptr};
-  return bounded_query_host(ctx, in, tmax_per_ray, &out, 1, [&](const trt_rays* rays, const float* bounds) {
-    return trt_chords_dev(ctx, rays, bounds, scene, tmin, tmax, (float*)out.dev, nullptr);
-  });
+  return media_streams_host(ctx, "trt_chords", in, tmax_per_ray, scene, 1, length_out, nullptr,
+                            [&](const trt_rays* rays, const float* bounds, float* length, float*) {
+                              return trt_chords_dev(ctx, rays, bounds, scene, tmin, tmax, length, nullptr);
+                            });
 }
 
 // The media of trt_glow*, validated (the scene first, so that n_tori can be trusted) and copied into the kernel arguments.
@@ -1293,7 +1352,7 @@ static int glow_media(trt_ctx* ctx, const trt_scene* scene, const trt_medium* me
   {
     const float v[4] = {media[j].emission[0], media[j].emission[1], media[j].emission[2], media[j].sigma};
     for(int c = 0; c < 4; ++c)
-      if(!(v[c] >= 0.0f) || std::isinf(v[c]))
+      if(!medium_value_ok(v[c]))
         return fail(ctx, TRT_E_INVALID, "trt_glow: the medium of torus %u has %s = %g; emission and sigma must be finite and not negative",
                     j, c < 3 ? "an emission" : "sigma", (double)v[c]);
     out.m[j] = media[j];
@@ -1306,8 +1365,7 @@ static int check_glow(trt_ctx* ctx, const trt_rays* in, const trt_medium* media,
 {
   if(int rc = check_media(ctx, in, rgba, "trt_glow")) return rc;
   if(!media) return fail(ctx, TRT_E_INVALID, "trt_glow: NULL media");
-  if((uintptr_t)rgba & 15) return fail(ctx, TRT_E_INVALID, "trt_glow: the rgba output must be 16-byte aligned (it is written as float4)");
-  return TRT_OK;
+  return check_rgba(ctx, "trt_glow", rgba);
 }
 extern "C" int trt_glow_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, const trt_medium* media,
                             float tmin, float tmax, float* rgba, void* stream)
@@ -1315,29 +1373,21 @@ extern "C" int trt_glow_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_
   if(int rc = check_glow(ctx, in, media, rgba)) return rc;
   GlowArgs a;
   if(int rc = glow_media(ctx, scene, media, a.media)) return rc;
-  a.rays         = *in;
-  a.tmax_per_ray = tmax_per_ray;
-  a.tmin         = tmin;
-  a.tmax         = tmax;
-  a.rgba         = rgba;
+  a.in   = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.rgba = rgba;
   return ray_query(ctx, scene, stream, in->n, a, launch_glow);
 }
-
-// Host buffers: the rays staged like trt_trace's, the bounds through buf[kBufTmax], the float4 per ray through buf[kBufRgba].
 extern "C" int trt_glow(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene, const trt_medium* media,
                         float tmin, float tmax, float* rgba_out)
 {
   if(int rc = check_glow(ctx, in, media, rgba_out)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0) return trt_glow_dev(ctx, in, nullptr, scene, media, tmin, tmax, rgba_out, nullptr);   // validates, launches and writes nothing
-  StagedOut image = {rgba_out, (size_t)in->n * 4 * sizeof(float), kBufRgba, nullptr};
-  return bounded_query_host(ctx, in, tmax_per_ray, &image, 1, [&](const trt_rays* rays, const float* bounds) {
-    return trt_glow_dev(ctx, rays, bounds, scene, media, tmin, tmax, (float*)image.dev, nullptr);
+  return media_rgba_host(ctx, in, tmax_per_ray, rgba_out, [&](const trt_rays* rays, const float* bounds, float* rgba) {
+    return trt_glow_dev(ctx, rays, bounds, scene, media, tmin, tmax, rgba, nullptr);
   });
 }
 
 // The profiles of trt_glow_profile*, validated (the scene first, so that n_tori can be trusted) and copied into the kernel
-// arguments with the 1 / r² of every torus: r * r rounded to FP32, then the quotient.
+// arguments with the 1 / r² of every torus.
 static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile* profiles, Profiles& out)
 {
   const SceneK* S = nullptr;
@@ -1349,27 +1399,23 @@ static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile
       for(int c = 0; c < 4; ++c)
       {
         const float v = profiles[j].knot[k][c];
-        if(!(v >= 0.0f) || std::isinf(v))
+        if(!medium_value_ok(v))
           return fail(ctx, TRT_E_INVALID, "trt_glow_profile: the profile of torus %u has %s = %g at knot %u; emission and sigma must be "
                                           "finite and not negative", j, c < 3 ? "an emission" : "sigma", (double)v, k);
         if(v != 0.0f)
           out.present |= 1u << j;
       }
     out.p[j] = profiles[j];
-    const float r2 = scene->tori[j].r * scene->tori[j].r;
-    out.inv_r2[j]  = 1.0f / r2;
   }
+  fill_inv_r2(scene, out.inv_r2);
   return TRT_OK;
 }
 static int check_glow_profile(trt_ctx* ctx, const trt_rays* in, const trt_profile* profiles, uint32_t steps, const float* rgba)
 {
   if(int rc = check_media(ctx, in, rgba, "trt_glow_profile")) return rc;
   if(!profiles) return fail(ctx, TRT_E_INVALID, "trt_glow_profile: NULL profiles");
-  if(steps < 1 || steps > TRT_MAX_GLOW_STEPS)
-    return fail(ctx, TRT_E_INVALID, "trt_glow_profile: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", steps, TRT_MAX_GLOW_STEPS);
-  if((uintptr_t)rgba & 15)
-    return fail(ctx, TRT_E_INVALID, "trt_glow_profile: the rgba output must be 16-byte aligned (it is written as float4)");
-  return TRT_OK;
+  if(int rc = check_steps(ctx, "trt_glow_profile", steps)) return rc;
+  return check_rgba(ctx, "trt_glow_profile", rgba);
 }
 extern "C" int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                     const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba, void* stream)
@@ -1377,26 +1423,17 @@ extern "C" int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in, const floa
   if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba)) return rc;
   GlowProfileArgs a;
   if(int rc = glow_profiles(ctx, scene, profiles, a.prof)) return rc;
-  a.rays         = *in;
-  a.tmax_per_ray = tmax_per_ray;
-  a.tmin         = tmin;
-  a.tmax         = tmax;
-  a.steps        = steps;
-  a.inv_steps    = 1.0f / (float)steps;
-  a.rgba         = rgba;
+  a.in   = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub  = media_steps(steps);
+  a.rgba = rgba;
   return ray_query(ctx, scene, stream, in->n, a, launch_glow_profile);
 }
-
-// Host buffers: trt_glow's staging.
 extern "C" int trt_glow_profile(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                 const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_out)
 {
   if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba_out)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0) return trt_glow_profile_dev(ctx, in, nullptr, scene, profiles, steps, tmin, tmax, rgba_out, nullptr);   // validates, launches and writes nothing
-  StagedOut image = {rgba_out, (size_t)in->n * 4 * sizeof(float), kBufRgba, nullptr};
-  return bounded_query_host(ctx, in, tmax_per_ray, &image, 1, [&](const trt_rays* rays, const float* bounds) {
-    return trt_glow_profile_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, (float*)image.dev, nullptr);
+  return media_rgba_host(ctx, in, tmax_per_ray, rgba_out, [&](const trt_rays* rays, const float* bounds, float* rgba) {
+    return trt_glow_profile_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, rgba, nullptr);
   });
 }
 
@@ -1404,11 +1441,8 @@ extern "C" int trt_glow_profile(trt_ctx* ctx, const trt_rays* in, const float* t
 static int check_glow_weights(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, uint32_t steps, const float* weight)
 {
   if(int rc = check_media(ctx, in, weight, "trt_glow_weights")) return rc;
-  if(steps < 1 || steps > TRT_MAX_GLOW_STEPS)
-    return fail(ctx, TRT_E_INVALID, "trt_glow_weights: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", steps, TRT_MAX_GLOW_STEPS);
-  if(scene && scene->n_tori && in->n > UINT64_MAX / TRT_PROFILE_KNOTS / scene->n_tori)
-    return fail(ctx, TRT_E_INVALID, "trt_glow_weights: n_tori * %d * n overflows 64 bits", TRT_PROFILE_KNOTS);
-  return TRT_OK;
+  if(int rc = check_steps(ctx, "trt_glow_weights", steps)) return rc;
+  return check_streams_count(ctx, "trt_glow_weights", in, scene, TRT_PROFILE_KNOTS);
 }
 extern "C" int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                     uint32_t steps, float tmin, float tmax, float* weight, void* stream)
@@ -1417,37 +1451,20 @@ extern "C" int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in, const floa
   const SceneK* S = nullptr;
   if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori and the radii are trusted below)
   GlowWeightsArgs a;
-  std::memset(a.inv_r2, 0, sizeof a.inv_r2);
-  for(uint32_t j = 0; j < scene->n_tori; ++j)
-  {
-    const float r2 = scene->tori[j].r * scene->tori[j].r;   // glow_profiles()' inv_r2
-    a.inv_r2[j]    = 1.0f / r2;
-  }
-  a.rays         = *in;
-  a.tmax_per_ray = tmax_per_ray;
-  a.tmin         = tmin;
-  a.tmax         = tmax;
-  a.steps        = steps;
-  a.inv_steps    = 1.0f / (float)steps;
-  a.weight       = weight;
+  fill_inv_r2(scene, a.inv_r2);
+  a.in     = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub    = media_steps(steps);
+  a.weight = weight;
   return ray_query(ctx, scene, stream, in->n, a, launch_glow_weights);
 }
-
-// Host buffers: trt_chords' staging, with 17 streams per torus through buf[kBufOut].
 extern "C" int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                 uint32_t steps, float tmin, float tmax, float* weight_out)
 {
   if(int rc = check_glow_weights(ctx, in, scene, steps, weight_out)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0 || !scene) return trt_glow_weights_dev(ctx, in, nullptr, scene, steps, tmin, tmax, weight_out, nullptr);   // validates, launches and writes nothing
-  const SceneK* S = nullptr;
-  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
-  if(in->n > SIZE_MAX / sizeof(float) / TRT_PROFILE_KNOTS / scene->n_tori)
-    return fail(ctx, TRT_E_NOMEM, "trt_glow_weights: n_tori * %d * n floats do not fit the address space", TRT_PROFILE_KNOTS);
-  StagedOut out = {weight_out, (size_t)in->n * sizeof(float) * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr};
-  return bounded_query_host(ctx, in, tmax_per_ray, &out, 1, [&](const trt_rays* rays, const float* bounds) {
-    return trt_glow_weights_dev(ctx, rays, bounds, scene, steps, tmin, tmax, (float*)out.dev, nullptr);
-  });
+  return media_streams_host(ctx, "trt_glow_weights", in, tmax_per_ray, scene, TRT_PROFILE_KNOTS, weight_out, nullptr,
+                            [&](const trt_rays* rays, const float* bounds, float* weight, float*) {
+                              return trt_glow_weights_dev(ctx, rays, bounds, scene, steps, tmin, tmax, weight, nullptr);
+                            });
 }
 
 // trt_glow_weights_absorbed*: trt_glow_weights' checks under its own name, and the profiles.
@@ -1456,11 +1473,8 @@ static int check_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const t
 {
   if(int rc = check_media(ctx, in, weight, "trt_glow_weights_absorbed")) return rc;
   if(!profiles) return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: NULL profiles");
-  if(steps < 1 || steps > TRT_MAX_GLOW_STEPS)
-    return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: steps = %u, must be 1..%d (TRT_MAX_GLOW_STEPS)", steps, TRT_MAX_GLOW_STEPS);
-  if(scene && scene->n_tori && in->n > UINT64_MAX / TRT_PROFILE_KNOTS / scene->n_tori)
-    return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: n_tori * %d * n overflows 64 bits", TRT_PROFILE_KNOTS);
-  return TRT_OK;
+  if(int rc = check_steps(ctx, "trt_glow_weights_absorbed", steps)) return rc;
+  return check_streams_count(ctx, "trt_glow_weights_absorbed", in, scene, TRT_PROFILE_KNOTS);
 }
 extern "C" int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                              const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* weight,
@@ -1471,50 +1485,31 @@ extern "C" int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in, c
   if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori and the radii are trusted below)
   GlowWeightsAbsorbedArgs a;
   std::memset(a.sigma, 0, sizeof a.sigma);
-  std::memset(a.inv_r2, 0, sizeof a.inv_r2);
   for(uint32_t j = 0; j < scene->n_tori; ++j)
-  {
     for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)   // sigma only: the emission entries are the unknowns, and are not read
     {
       const float v = profiles[j].knot[k][3];
-      if(!(v >= 0.0f) || std::isinf(v))
+      if(!medium_value_ok(v))
         return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: the profile of torus %u has sigma = %g at knot %u; sigma must be "
                                         "finite and not negative", j, (double)v, k);
       a.sigma[j][k] = v;
     }
-    const float r2 = scene->tori[j].r * scene->tori[j].r;   // glow_profiles()' inv_r2
-    a.inv_r2[j]    = 1.0f / r2;
-  }
-  a.rays         = *in;
-  a.tmax_per_ray = tmax_per_ray;
-  a.tmin         = tmin;
-  a.tmax         = tmax;
-  a.steps        = steps;
-  a.inv_steps    = 1.0f / (float)steps;
-  a.weight       = weight;
-  a.trans        = trans;
+  fill_inv_r2(scene, a.inv_r2);
+  a.in     = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub    = media_steps(steps);
+  a.weight = weight;
+  a.trans  = trans;
   return ray_query(ctx, scene, stream, in->n, a, launch_glow_weights_absorbed);
 }
-
-// Host buffers: trt_glow_weights' staging, and the transmittance (if asked for) through buf[kBufOut + 1].
 extern "C" int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                          const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* weight_out,
                                          float* trans_out)
 {
   if(int rc = check_glow_weights_absorbed(ctx, in, scene, profiles, steps, weight_out)) return rc;
-  TRT_HIP(ctx, hipSetDevice(ctx->device));
-  if(in->n == 0 || !scene)   // validates, launches and writes nothing
-    return trt_glow_weights_absorbed_dev(ctx, in, nullptr, scene, profiles, steps, tmin, tmax, weight_out, trans_out, nullptr);
-  const SceneK* S = nullptr;
-  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori is trusted below)
-  if(in->n > SIZE_MAX / sizeof(float) / TRT_PROFILE_KNOTS / scene->n_tori)
-    return fail(ctx, TRT_E_NOMEM, "trt_glow_weights_absorbed: n_tori * %d * n floats do not fit the address space", TRT_PROFILE_KNOTS);
-  StagedOut outs[2] = {{weight_out, (size_t)in->n * sizeof(float) * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr},
-                       {trans_out, (size_t)in->n * sizeof(float), kBufOut + 1, nullptr}};
-  return bounded_query_host(ctx, in, tmax_per_ray, outs, trans_out ? 2 : 1, [&](const trt_rays* rays, const float* bounds) {
-    return trt_glow_weights_absorbed_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, (float*)outs[0].dev,
-                                         trans_out ? (float*)outs[1].dev : nullptr, nullptr);
-  });
+  return media_streams_host(ctx, "trt_glow_weights_absorbed", in, tmax_per_ray, scene, TRT_PROFILE_KNOTS, weight_out, trans_out,
+                            [&](const trt_rays* rays, const float* bounds, float* weight, float* trans) {
+                              return trt_glow_weights_absorbed_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, weight, trans, nullptr);
+                            });
 }
 
 // ------------------------------------------------------------------------------------------

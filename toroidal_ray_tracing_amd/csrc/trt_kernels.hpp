@@ -242,12 +242,21 @@ struct TransmittanceArgs {
 // trt_shade_through*: ShadeArgs with the opacities; the kernel's dynamic LDS holds 4 * n_tori crossing slots per lane.
 using ShadeThroughArgs = StreamShade<Opacity>;
 
-// trt_chords*, trt_glow*: ray i has the window (tmin, min(tmax_per_ray[i], tmax)); tmax_per_ray == nullptr: every ray ends at tmax.
+// What the *Args of the media family (trt_chords*, trt_glow*) begin with — `in`, their first member: ray i has the window
+// (tmin, min(tmax_per_ray[i], tmax)); tmax_per_ray == nullptr: every ray ends at tmax.
+struct MediaRays {
+  trt_rays     rays;
+  const float* tmax_per_ray;
+  float        tmin, tmax;
+};
+// The sub-steps per piece or interval of the calls that integrate a profile; inv_steps = 1.0f / steps.
+struct MediaSteps {
+  uint32_t steps;   // 1 .. TRT_MAX_GLOW_STEPS
+  float    inv_steps;
+};
 // trt_chords*: the length of ray i inside torus j's tube at length[j * rays.n + i] (torus-major: n_tori streams).
 struct ChordsArgs {
-  trt_rays            rays;
-  const float*        tmax_per_ray;
-  float               tmin, tmax;
+  MediaRays           in;
   float*              length;
   unsigned long long* stats;
 };
@@ -260,9 +269,7 @@ struct Media {
 };
 // trt_glow*: (L_r, L_g, L_b, T) of ray i at rgba[4 i], 16-byte aligned; the kernel's dynamic LDS holds 4 * n_tori slots per lane.
 struct GlowArgs {
-  trt_rays            rays;
-  const float*        tmax_per_ray;
-  float               tmin, tmax;
+  MediaRays           in;
   Media               media;
   float*              rgba;
   unsigned long long* stats;
@@ -275,25 +282,19 @@ struct Profiles {
   float       inv_r2[TRT_MAX_TORI];
   uint32_t    present;
 };
-// trt_glow_profile*: GlowArgs with the profiles in place of the media and the sub-steps per piece (inv_steps = 1.0f / steps).
+// trt_glow_profile*: GlowArgs with the profiles in place of the media, cut into sub-steps.
 struct GlowProfileArgs {
-  trt_rays            rays;
-  const float*        tmax_per_ray;
-  float               tmin, tmax;
-  uint32_t            steps;
-  float               inv_steps;
+  MediaRays           in;
+  MediaSteps          sub;
   Profiles            prof;
   float*              rgba;
   unsigned long long* stats;
 };
-// trt_glow_weights*: ChordsArgs with the sub-steps per interval (inv_steps = 1.0f / steps) and Profiles' inv_r2; the weight
-// of knot k of torus j on ray i at weight[(j * TRT_PROFILE_KNOTS + k) * rays.n + i] (17 * n_tori streams).
+// trt_glow_weights*: ChordsArgs with sub-steps and Profiles' inv_r2; the weight of knot k of torus j on ray i at
+// weight[(j * TRT_PROFILE_KNOTS + k) * rays.n + i] (17 * n_tori streams).
 struct GlowWeightsArgs {
-  trt_rays            rays;
-  const float*        tmax_per_ray;
-  float               tmin, tmax;
-  uint32_t            steps;
-  float               inv_steps;
+  MediaRays           in;
+  MediaSteps          sub;
   float               inv_r2[TRT_MAX_TORI];
   float*              weight;
   unsigned long long* stats;
@@ -302,11 +303,8 @@ struct GlowWeightsArgs {
 // host, indexed by TORUS id: 544 B for eight tori; the kernel stages them into LDS) and the transmittance left along ray i
 // at trans[i] (nullptr: not written).
 struct GlowWeightsAbsorbedArgs {
-  trt_rays            rays;
-  const float*        tmax_per_ray;
-  float               tmin, tmax;
-  uint32_t            steps;
-  float               inv_steps;
+  MediaRays           in;
+  MediaSteps          sub;
   float               sigma[TRT_MAX_TORI][TRT_PROFILE_KNOTS];
   float               inv_r2[TRT_MAX_TORI];
   float*              weight;

@@ -1,17 +1,24 @@
 // trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*, trt_glow_weights*,
 // trt_glow_weights_absorbed*), gfx950.
 //
-//   tube_inside      whether the point of a ray at parameter t lies inside torus j's tube
+// What the kernels share, each said once:
+//   tube_frame, tube_rho2   the ray in torus j's frame, and the tube label of its point at t: the inside test and every
+//                    profile lookup are this one expression
 //   tube_intervals   the pairing rule: torus j's crossings and the two inside tests → at most two intervals
-//   chords_kernel    chords(rays_in → the length of every ray inside every tube): n_tori coalesced streams out.
-//   glow_kernel      glow(rays_in → radiance and the transmittance left): the emission–absorption integral over the
-//                    pieces between the merged interval ends, one float4 per ray out.
-//   glow_profile_kernel   glow with a radial profile per torus: every piece cut into sub-steps, two Gauss–Legendre points
-//                    in each, the profile tables in LDS.
-//   glow_weights_kernel   the response of every ray to every knot of every torus' profile (sigma = 0): chords_kernel with the
-//                    sub-step walk inside each interval, 17 accumulators per lane in LDS, 17 · n_tori streams out.
-//   glow_weights_absorbed_kernel   the same response behind absorbing media: glow_profile_kernel's merged pieces and running T,
-//                    glow_weights_kernel's deposit into the accumulators of ALL tori, the block width chosen from n_tori.
+//   media_ray        ray i's window, and behind a window that is not empty its RayK and world length
+//   for_each_ray     the grid-stride loop over the rays and the counted-tests epilogue
+//   merged_pieces    the intervals of several tori merged in the lane's crossing column, walked piece by piece
+//   knot_of, gauss_pair, glow_step_weight   a label's knot and fraction; the two points of a sub-step; E and the weight of a step
+// The kernels, one lane per ray:
+//   chords_kernel    the length of every ray inside every tube: the intervals summed, n_tori coalesced streams out.
+//   glow_kernel      radiance and the transmittance left: the emission–absorption integral over the merged pieces of the
+//                    tori with a medium, one float4 per ray out.
+//   glow_profile_kernel   glow with a radial profile per torus: every piece cut into sub-steps, the tables (in LDS) read at
+//                    the two Gauss–Legendre points of each.
+//   glow_weights_kernel   the response of every ray to every knot of every torus' profile (sigma = 0): the sub-steps inside
+//                    each interval of a torus, 17 accumulators per lane in LDS, 17 · n_tori streams out.
+//   glow_weights_absorbed_kernel   the same response behind absorbing media: the merged pieces of ALL tori with a running T,
+//                    the accumulators of all tori live at once, the block width chosen from n_tori.
 //   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights, launch_glow_weights_absorbed   their grid and
 //                    launch wrappers.
 //
@@ -26,25 +33,40 @@
 namespace trt {
 
 // ------------------------------------------------------------------------------------------
-// the pairing rule
+// the tube label and the pairing rule
 // ------------------------------------------------------------------------------------------
-// P = fma(t, d, o) per component in the solver precision, (o, d) being the ray torus_crossings() hands the solver: the
-// world ray and torus_k()'s centre, or — wave-uniform — the ray in the frame of an oriented torus and a centre of zero.
-// q = sqrt(fma(pz, pz, px·px)) − R; inside iff fma(q, q, py·py) < r².  A non-finite point compares false: outside.
+// The ray torus_crossings() hands the solver for torus j, and the torus it is tested against: the world ray and torus_k()'s
+// centre, or — wave-uniform — the ray in the frame of an oriented torus and a centre of zero.
+template <class Real, bool ORIENT>
+__device__ __forceinline__ void tube_frame(const SceneK& S, int j, const RayK<Real>& r, LocalRay<Real>& l, TorusK<Real>& T)
+{
+  l = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
+  T = torus_k<Real>(S, j);
+  if constexpr(ORIENT)
+    if(is_oriented(S, j))
+    {
+      l.set(S, j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+      T = centred(T);
+    }
+}
+// The label of the ray's point at t, rho² — the squared distance from the tube's centre circle — in the solver precision:
+// P = fma(t, d, o) − c per component, q = sqrt(fma(pz, pz, px·px)) − R, rho² = fma(q, q, py·py).  rho² < r² is inside,
+// (float)rho² · inv_r2 is the x of a profile: the two agree on this expression to the bit (include/trt.h).
+template <class Real>
+__device__ __forceinline__ Real tube_rho2(const LocalRay<Real>& l, const TorusK<Real>& T, Real t)
+{
+  const Real px = fma_(t, l.dx, l.ox) - T.cx, py = fma_(t, l.dy, l.oy) - T.cy, pz = fma_(t, l.dz, l.oz) - T.cz;
+  const Real q  = sqrt_(fma_(pz, pz, px * px)) - T.R;
+  return fma_(q, q, py * py);
+}
+// Whether the point of ray r at t lies inside torus i's tube.  A non-finite point compares false: outside.
 template <class Real, bool ORIENT>
 __device__ __forceinline__ bool tube_inside(const SceneK& S, int i, const RayK<Real>& r, float t)
 {
-  LocalRay<Real> l = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
-  TorusK<Real>   T = torus_k<Real>(S, i);
-  if constexpr(ORIENT)
-    if(is_oriented(S, i))
-    {
-      l.set(S, i, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-      T = centred(T);
-    }
-  const Real px = fma_((Real)t, l.dx, l.ox) - T.cx, py = fma_((Real)t, l.dy, l.oy) - T.cy, pz = fma_((Real)t, l.dz, l.oz) - T.cz;
-  const Real q  = sqrt_(fma_(pz, pz, px * px)) - T.R;
-  return fma_(q, q, py * py) < T.r2;
+  LocalRay<Real> l;
+  TorusK<Real>   T;
+  tube_frame<Real, ORIENT>(S, i, r, l, T);
+  return tube_rho2(l, T, (Real)t) < T.r2;
 }
 
 // emit(a, b, from_start, to_end) per interval of torus j inside the window (r.tmin, r.tmax) of ray r, left to right:
@@ -97,44 +119,56 @@ __device__ __forceinline__ void tube_intervals(const SceneK& S, int j, const Ray
     emit(open, r.tmax, first, true);
 }
 
-// The window of ray i: the per-ray bound clipped by the scalar (a NaN bound stays NaN and empties the window).
-__device__ __forceinline__ float window_end(const float* tmax_per_ray, uint64_t i, float tmax)
+// ------------------------------------------------------------------------------------------
+// the rays of a query
+// ------------------------------------------------------------------------------------------
+// Ray i of a query: whether its window (in.tmin, min(tmax_per_ray[i], in.tmax)) — the per-ray bound clipped by the scalar; a
+// NaN bound stays NaN and empties it — is not empty.  Only then are the ray's streams read: r holds the ray and its window,
+// len the world length per unit of t.
+template <class Real>
+__device__ __forceinline__ bool media_ray(const MediaRays& in, uint64_t i, RayK<Real>& r, float& len)
 {
-  const float b = tmax_per_ray ? ((gptr<const float>)tmax_per_ray)[i] : tmax;
-  return b > tmax ? tmax : b;
+  const float b    = in.tmax_per_ray ? ((gptr<const float>)in.tmax_per_ray)[i] : in.tmax;
+  const float tmax = b > in.tmax ? in.tmax : b;
+  if(!(tmax > in.tmin))
+    return false;
+  const gptr<const float> ox = (gptr<const float>)in.rays.ox, oy = (gptr<const float>)in.rays.oy, oz = (gptr<const float>)in.rays.oz;
+  const gptr<const float> dx = (gptr<const float>)in.rays.dx, dy = (gptr<const float>)in.rays.dy, dz = (gptr<const float>)in.rays.dz;
+  const v3 o = {ox[i], oy[i], oz[i]};
+  const v3 d = {dx[i], dy[i], dz[i]};
+  r.set(o, d, in.tmin, tmax);
+  len = sqrt_((d.x * d.x + d.y * d.y) + d.z * d.z);
+  return true;
 }
-// World length per unit of t.
-__device__ __forceinline__ float ray_length(v3 d) { return sqrt_((d.x * d.x + d.y * d.y) + d.z * d.z); }
+// body(i, tests, wc) for every ray i of the block's lanes (grid-stride), then the block's counts into `stats`.  A body counts
+// the tori it tests in `tests`.
+template <class Body>
+__device__ __forceinline__ void for_each_ray(const MediaRays& in, unsigned long long* stats, Body&& body)
+{
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < in.rays.n; i += stride)
+    body(i, tests, wc);
+  if(stats)
+    block_add_stats(stats, tests, 0u, 0u, wc);
+}
 
 // ------------------------------------------------------------------------------------------
 // chords(rays_in → n_tori streams of lengths)
 // ------------------------------------------------------------------------------------------
-// One lane per ray, no LDS beyond the scene.  The torus loop is wave-uniform, so the store of torus j is one
-// instruction of 64 consecutive floats of stream j.  A ray whose window is empty executes no test and stores zeros.
+// No LDS beyond the scene.  The torus loop is wave-uniform, so the store of torus j is one instruction of 64 consecutive
+// floats of stream j.  A ray whose window is empty executes no test and stores zeros.
 template <class Real, bool ORIENT = false>
 __global__ __launch_bounds__(256) void chords_kernel(const SceneK scene, const ChordsArgs a)
 {
   __shared__ SceneK S;
   stage_scene<ORIENT>(&S, scene);
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  uint32_t       tests  = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
-  {
-    const float tmax   = window_end(a.tmax_per_ray, i, a.tmax);
-    const bool  window = tmax > a.tmin;
-    RayK<Real>  r;
-    float       len = 0.0f;
-    if(window)
-    {
-      const v3 o = {ox[i], oy[i], oz[i]};
-      const v3 d = {dx[i], dy[i], dz[i]};
-      r.set(o, d, a.tmin, tmax);
-      len = ray_length(d);
-    }
+  for_each_ray(a.in, a.stats, [&](uint64_t i, uint32_t& tests, WorkCount& wc) {
+    RayK<Real> r;
+    float      len = 0.0f;
+    const bool window = media_ray(a.in, i, r, len);
     for(int k = 0; k < S.n_tori; ++k)
     {
       const int j   = S.order[k];
@@ -144,11 +178,9 @@ __global__ __launch_bounds__(256) void chords_kernel(const SceneK scene, const C
         ++tests;
         tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool, bool) { acc = acc + (v - u) * len; });
       }
-      st1(a.length, (uint64_t)j * a.rays.n + i, acc);
+      st1(a.length, (uint64_t)j * a.in.rays.n + i, acc);
     }
-  }
-  if(a.stats)
-    block_add_stats(a.stats, tests, 0u, 0u, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -181,8 +213,8 @@ __device__ __forceinline__ void glow_step_weight(float sg, float l, float& E, fl
   }
 }
 
-// The homogeneous step of trt_glow over the world length l, with the summed emission (e0, e1, e2) and absorption sg:
-// glow_kernel's piece and glow_profile_kernel's sub-step.
+// The homogeneous step of trt_glow over the world length l, with the summed emission (e0, e1, e2) and absorption sg: a
+// piece of glow_kernel, a sub-step of glow_profile_kernel.
 __device__ __forceinline__ void glow_step(float e0, float e1, float e2, float sg, float l, float& Lr, float& Lg, float& Lb, float& T)
 {
   float E, wgt;
@@ -193,14 +225,52 @@ __device__ __forceinline__ void glow_step(float e0, float e1, float e2, float sg
   T  = T * E;
 }
 
-// One lane owns one ray.  A torus with a medium (bit j of media.present) goes through the pairing rule; the ends of its
-// intervals go into the lane's sorted column in dynamic LDS (column_insert: crossings_kernel's layout, K = 4 · n_tori
-// slots — two intervals per torus at most, so nothing is ever truncated) with the byte id << 1 | 1 for a start and
-// id << 1 for an end.  An interval that starts with the window is a bit of the initial active mask instead of a slot,
-// and one that ends with the window has no end slot: the last piece closes it.  Then the pieces between consecutive
-// break points are walked front to back.  The sums over the active tori are a loop over the torus id that is uniform
-// for the wave (its bound and the media come from the kernel arguments: scalar loads), predicated by the lane's mask.
-// Equal break points give an empty piece, which is skipped: their order in the column does not matter.
+// ------------------------------------------------------------------------------------------
+// the merged pieces of a ray
+// ------------------------------------------------------------------------------------------
+// piece(u, v, active) for every non-empty piece (u, v) of ray r's window inside some tube, front to back; bit j of `active`:
+// the piece lies inside torus j.  A torus with bit j of `present` goes through the pairing rule (and counts in `tests`);
+// the ends of its intervals go into the lane's sorted column in dynamic LDS (column_insert: crossings_kernel's layout, K =
+// 4 · n_tori slots — two intervals per torus at most, so nothing is ever truncated — at the stride LANES) with the byte
+// id << 1 | 1 for a start and id << 1 for an end.  An interval that starts with the window is a bit of the initial
+// active mask instead of a slot, and one that ends with the window has no end slot: the last piece closes it.  Then the
+// pieces between consecutive break points are walked.  Equal break points give an empty piece, which is skipped: their
+// order in the column does not matter.  (Parameters by reference, for column_insert's reason.)
+template <class Real, bool ORIENT, uint32_t LANES, class Piece>
+__device__ __forceinline__ void merged_pieces(const SceneK& S, const RayK<Real>& r, const uint32_t& present, float* const& ct, uint8_t* const& cw,
+                                              const uint32_t& K, uint32_t& tests, WorkCount& wc, Piece&& piece)
+{
+  uint32_t active = 0u, count = 0u;
+  for(int k = 0; k < S.n_tori; ++k)
+  {
+    const int j = S.order[k];
+    if(!((present >> j) & 1u))
+      continue;
+    ++tests;
+    tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
+      if(from_start) active |= 1u << j;
+      else column_insert<LANES>(ct, cw, K, count, u, j, true);
+      if(!to_end) column_insert<LANES>(ct, cw, K, count, v, j, false);
+    });
+  }
+  float u = r.tmin;
+  for(uint32_t k = 0; k <= count; ++k)
+  {
+    const bool     last = k == count;
+    const float    v    = last ? r.tmax : ct[k * LANES];
+    const uint32_t w    = last ? 0u : cw[k * LANES];
+    if(active != 0u && v > u)
+      piece(u, v, active);
+    const uint32_t bit = 1u << (w >> 1);
+    if(!last)
+      active = (w & 1u) ? (active | bit) : (active & ~bit);
+    u = v;
+  }
+}
+
+// The pieces of the tori with a medium (bit j of media.present).  The sums over the active tori of a piece are a loop over
+// the torus id that is uniform for the wave (its bound and the media come from the kernel arguments: scalar loads),
+// predicated by the lane's mask.
 template <class Real, bool ORIENT = false>
 __global__ __launch_bounds__(256) void glow_kernel(const SceneK scene, const GlowArgs a)
 {
@@ -212,64 +282,24 @@ __global__ __launch_bounds__(256) void glow_kernel(const SceneK scene, const Glo
   float*         ct = crossing_lds + threadIdx.x;
   uint8_t*       cw = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  uint32_t       tests  = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
-  {
-    const float tmax = window_end(a.tmax_per_ray, i, a.tmax);
-    float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f;
-    if(tmax > a.tmin)
-    {
-      const v3 o = {ox[i], oy[i], oz[i]};
-      const v3 d = {dx[i], dy[i], dz[i]};
-      RayK<Real> r;
-      r.set(o, d, a.tmin, tmax);
-      const float len = ray_length(d);
-      uint32_t active = 0u, count = 0u;
-      for(int k = 0; k < S.n_tori; ++k)
-      {
-        const int j = S.order[k];
-        if(!((a.media.present >> j) & 1u))
-          continue;
-        ++tests;
-        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
-          if(from_start) active |= 1u << j;
-          else column_insert(ct, cw, K, count, u, j, true);
-          if(!to_end) column_insert(ct, cw, K, count, v, j, false);
-        });
-      }
-      float u = a.tmin;
-      for(uint32_t k = 0; k <= count; ++k)
-      {
-        const bool     last = k == count;
-        const float    v    = last ? tmax : ct[k * 256u];
-        const uint32_t w    = last ? 0u : cw[k * 256u];
-        if(active != 0u && v > u)
-        {
-          float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f, sg = 0.0f;
-          for(int j = 0; j < scene.n_tori; ++j)
-            if((active >> j) & 1u)
-            {
-              e0 = e0 + a.media.m[j].emission[0];
-              e1 = e1 + a.media.m[j].emission[1];
-              e2 = e2 + a.media.m[j].emission[2];
-              sg = sg + a.media.m[j].sigma;
-            }
-          glow_step(e0, e1, e2, sg, (v - u) * len, Lr, Lg, Lb, T);
-        }
-        const uint32_t bit = 1u << (w >> 1);
-        if(!last)
-          active = (w & 1u) ? (active | bit) : (active & ~bit);
-        u = v;
-      }
-    }
+  for_each_ray(a.in, a.stats, [&](uint64_t i, uint32_t& tests, WorkCount& wc) {
+    float      Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f, len;
+    RayK<Real> r;
+    if(media_ray(a.in, i, r, len))
+      merged_pieces<Real, ORIENT, 256u>(S, r, a.media.present, ct, cw, K, tests, wc, [&](float u, float v, uint32_t active) {
+        float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f, sg = 0.0f;
+        for(int j = 0; j < scene.n_tori; ++j)
+          if((active >> j) & 1u)
+          {
+            e0 = e0 + a.media.m[j].emission[0];
+            e1 = e1 + a.media.m[j].emission[1];
+            e2 = e2 + a.media.m[j].emission[2];
+            sg = sg + a.media.m[j].sigma;
+          }
+        glow_step(e0, e1, e2, sg, (v - u) * len, Lr, Lg, Lb, T);
+      });
     st4(a.rgba + 4 * i, make_float4(Lr, Lg, Lb, T));
-  }
-  if(a.stats)
-    block_add_stats(a.stats, tests, 0u, 0u, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -303,25 +333,52 @@ __device__ __forceinline__ void stage_scene_no_mat(SceneK* lds, const SceneNoMat
     }
   }
 }
+// What the launches of those kernels pass for the scene.
+inline SceneNoMat scene_no_mat(const SceneK& scene)
+{
+  SceneNoMat sc;
+  std::memcpy(sc.head, &scene, sizeof sc.head);
+  std::memcpy(sc.rot, scene.rot, sizeof sc.rot);
+  return sc;
+}
 
-// The knots k and k + 1 of one profile, interpolated at x = rho² / r²: y = min(x, 1) · 16 (a NaN x goes to the wall),
-// k = min((int)y, 15), f = y − k, channel c = fma(f, knot[k+1][c] − knot[k][c], knot[k][c]); added to acc.
+// The knot k and the fraction f of a label x = rho² / r²: y = min(x, 1) · 16 (a NaN x goes to the wall), k = min((int)y, 15),
+// f = y − k.  knot_of returns y, from which knot_split gives k and f again.
+__device__ __forceinline__ void knot_split(float y, int& k, float& f)
+{
+  k = min((int)y, 15);
+  f = y - (float)k;
+}
+__device__ __forceinline__ float knot_of(float x, int& k, float& f)
+{
+  const float y = (x < 1.0f ? x : 1.0f) * 16.0f;
+  knot_split(y, k, f);
+  return y;
+}
+// The knots k and k + 1 of one profile, interpolated at x: channel c = fma(f, knot[k+1][c] − knot[k][c], knot[k][c]); added to acc.
 __device__ __forceinline__ void profile_add(const float4* knots, float x, float4& acc)
 {
-  const float  y  = (x < 1.0f ? x : 1.0f) * 16.0f;
-  const int    k  = min((int)y, 15);
-  const float  f  = y - (float)k;
+  int   k;
+  float f;
+  knot_of(x, k, f);
   const float4 lo = knots[k], hi = knots[k + 1];
   acc.x = acc.x + fma_(f, hi.x - lo.x, lo.x);
   acc.y = acc.y + fma_(f, hi.y - lo.y, lo.y);
   acc.z = acc.z + fma_(f, hi.z - lo.z, lo.z);
   acc.w = acc.w + fma_(f, hi.w - lo.w, lo.w);
 }
+// The two Gauss–Legendre parameters of sub-step s of a piece that starts at u, h being the sub-step's length in t:
+// its middle m = fma(s + 0.5, h, u), and m ∓ h / (2 √3).
+__device__ __forceinline__ void gauss_pair(uint32_t s, float h, float u, float& ta, float& tb)
+{
+  const float m = fma_((float)s + 0.5f, h, u);
+  ta = fma_(-0.288675135f, h, m);
+  tb = fma_(0.288675135f, h, m);
+}
 
-// glow_kernel with a radial profile per torus in place of its medium: intervals, column and pieces are glow_kernel's,
-// line for line.  Every piece with an active torus is cut into a.steps equal sub-steps; at the two Gauss–Legendre
-// points of a sub-step every active torus is asked for x = rho² / r² at the point — tube_inside's expression, in the
-// solver's frame and precision — and its table for the four channels there; the two sums are averaged and go through
+// The pieces of the tori with a profile (bit j of prof.present), each cut into a.sub.steps equal sub-steps; at the two
+// Gauss–Legendre points of a sub-step every active torus is asked for x = rho² / r² at the point — in the solver's frame
+// and precision — and its table for the four channels there; the two sums are averaged and go through
 // glow_step.  The sub-step loop and the torus loop are uniform for the wave (their bounds come from the arguments) and
 // predicated by the lane's mask.  The knot index differs from lane to lane, so the tables are staged into LDS once per
 // block: a knot is one 16-byte read.  The ray in an oriented torus' frame depends on the ray and the torus alone, but
@@ -346,91 +403,42 @@ __global__ __launch_bounds__(256) void glow_profile_kernel(const SceneNoMat scen
   float*         ct = crossing_lds + threadIdx.x;
   uint8_t*       cw = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  const int      n_tori = (int)scene.head[0];
-  uint32_t       tests  = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
-  {
-    const float tmax = window_end(a.tmax_per_ray, i, a.tmax);
-    float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f;
-    if(tmax > a.tmin)
-    {
-      const v3 o = {ox[i], oy[i], oz[i]};
-      const v3 d = {dx[i], dy[i], dz[i]};
-      RayK<Real> r;
-      r.set(o, d, a.tmin, tmax);
-      const float len = ray_length(d);
-      uint32_t active = 0u, count = 0u;
-      for(int k = 0; k < S.n_tori; ++k)
-      {
-        const int j = S.order[k];
-        if(!((a.prof.present >> j) & 1u))
-          continue;
-        ++tests;
-        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
-          if(from_start) active |= 1u << j;
-          else column_insert(ct, cw, K, count, u, j, true);
-          if(!to_end) column_insert(ct, cw, K, count, v, j, false);
-        });
-      }
-      float u = a.tmin;
-      for(uint32_t k = 0; k <= count; ++k)
-      {
-        const bool     last = k == count;
-        const float    v    = last ? tmax : ct[k * 256u];
-        const uint32_t w    = last ? 0u : cw[k * 256u];
-        if(active != 0u && v > u)
+  const int n_tori = (int)scene.head[0];
+  for_each_ray(a.in, a.stats, [&](uint64_t i, uint32_t& tests, WorkCount& wc) {
+    float      Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f, len;
+    RayK<Real> r;
+    if(media_ray(a.in, i, r, len))
+      merged_pieces<Real, ORIENT, 256u>(S, r, a.prof.present, ct, cw, K, tests, wc, [&](float u, float v, uint32_t active) {
+        const float h = (v - u) * a.sub.inv_steps;
+        const float l = h * len;
+        for(uint32_t s = 0; s < a.sub.steps; ++s)
         {
-          const float h = (v - u) * a.inv_steps;
-          const float l = h * len;
-          for(uint32_t s = 0; s < a.steps; ++s)
-          {
-            const float m  = fma_((float)s + 0.5f, h, u);
-            const Real  ta = (Real)fma_(-0.288675135f, h, m), tb = (Real)fma_(0.288675135f, h, m);
-            float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
-            for(int j = 0; j < n_tori; ++j)
-              if((active >> j) & 1u)
-              {
-                LocalRay<Real> lr = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
-                TorusK<Real>   Tk = torus_k<Real>(S, j);
-                if constexpr(ORIENT)
-                  if(is_oriented(S, j))
-                  {
-                    lr.set(S, j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-                    Tk = centred(Tk);
-                  }
-                const Real  ax = fma_(ta, lr.dx, lr.ox) - Tk.cx, ay = fma_(ta, lr.dy, lr.oy) - Tk.cy, az = fma_(ta, lr.dz, lr.oz) - Tk.cz;
-                const Real  bx = fma_(tb, lr.dx, lr.ox) - Tk.cx, by = fma_(tb, lr.dy, lr.oy) - Tk.cy, bz = fma_(tb, lr.dz, lr.oz) - Tk.cz;
-                const Real  qa = sqrt_(fma_(az, az, ax * ax)) - Tk.R, qb = sqrt_(fma_(bz, bz, bx * bx)) - Tk.R;
-                const float ir = a.prof.inv_r2[j];
-                profile_add(knots + j * TRT_PROFILE_KNOTS, (float)fma_(qa, qa, ay * ay) * ir, A);
-                profile_add(knots + j * TRT_PROFILE_KNOTS, (float)fma_(qb, qb, by * by) * ir, B);
-              }
-            glow_step((A.x + B.x) * 0.5f, (A.y + B.y) * 0.5f, (A.z + B.z) * 0.5f, (A.w + B.w) * 0.5f, l, Lr, Lg, Lb, T);
-          }
+          float ta, tb;
+          gauss_pair(s, h, u, ta, tb);
+          float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
+          for(int j = 0; j < n_tori; ++j)
+            if((active >> j) & 1u)
+            {
+              LocalRay<Real> lr;
+              TorusK<Real>   Tk;
+              tube_frame<Real, ORIENT>(S, j, r, lr, Tk);
+              const float ir = a.prof.inv_r2[j];
+              profile_add(knots + j * TRT_PROFILE_KNOTS, (float)tube_rho2(lr, Tk, (Real)ta) * ir, A);
+              profile_add(knots + j * TRT_PROFILE_KNOTS, (float)tube_rho2(lr, Tk, (Real)tb) * ir, B);
+            }
+          glow_step((A.x + B.x) * 0.5f, (A.y + B.y) * 0.5f, (A.z + B.z) * 0.5f, (A.w + B.w) * 0.5f, l, Lr, Lg, Lb, T);
         }
-        const uint32_t bit = 1u << (w >> 1);
-        if(!last)
-          active = (w & 1u) ? (active | bit) : (active & ~bit);
-        u = v;
-      }
-    }
+      });
     st4(a.rgba + 4 * i, make_float4(Lr, Lg, Lb, T));
-  }
-  if(a.stats)
-    block_add_stats(a.stats, tests, 0u, 0u, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
 // glow_weights(rays_in → 17 · n_tori streams: the hat-weighted length of every ray per knot and torus)
 // ------------------------------------------------------------------------------------------
-// chords_kernel with glow_profile_kernel's sub-step walk inside every interval: no column, no merge — torus j's intervals
-// are trt_chords', whatever the other tori do.  At each of the two Gauss–Legendre points of a sub-step the label
-// x = rho² / r² (tube_inside's expression, in the solver's frame and precision) picks the knot kn and the fraction f as
-// profile_add does, and half the sub-step's world length goes to the accumulators kn and kn + 1 as g · (1 − f) and g · f.
+// The sub-steps inside every interval of a torus: no column, no merge — torus j's intervals are trt_chords', whatever the
+// other tori do.  At each of the two Gauss–Legendre points of a sub-step the label x = rho² / r² picks the knot kn and the
+// fraction f, and half the sub-step's world length goes to the accumulators kn and kn + 1 as g · (1 − f) and g · f.
 // kn differs from lane to lane, so the 17 accumulators are not registers (a private array indexed by kn would go to
 // scratch) but a column of LDS: acc[k][256], the lane's slot k at acc[k * 256 + threadIdx.x].  Within a wave the 64 lanes
 // of one access sit on 64 different banks whatever their k is (k * 256 words is a multiple of 64): no conflict.  A lane
@@ -446,24 +454,10 @@ __global__ __launch_bounds__(256) void glow_weights_kernel(const SceneK scene, c
   stage_scene<ORIENT>(&S, scene);
   float* const W = acc + threadIdx.x;
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
-  uint32_t       tests  = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.rays.n; i += stride)
-  {
-    const float tmax   = window_end(a.tmax_per_ray, i, a.tmax);
-    const bool  window = tmax > a.tmin;
-    RayK<Real>  r;
-    float       len = 0.0f;
-    if(window)
-    {
-      const v3 o = {ox[i], oy[i], oz[i]};
-      const v3 d = {dx[i], dy[i], dz[i]};
-      r.set(o, d, a.tmin, tmax);
-      len = ray_length(d);
-    }
+  for_each_ray(a.in, a.stats, [&](uint64_t i, uint32_t& tests, WorkCount& wc) {
+    RayK<Real> r;
+    float      len = 0.0f;
+    const bool window = media_ray(a.in, i, r, len);
     for(int k = 0; k < scene.n_tori; ++k)
     {
       const int j = S.order[k];
@@ -472,31 +466,23 @@ __global__ __launch_bounds__(256) void glow_weights_kernel(const SceneK scene, c
       if(window)
       {
         ++tests;
-        LocalRay<Real> lr = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
-        TorusK<Real>   Tk = torus_k<Real>(S, j);
-        if constexpr(ORIENT)
-          if(is_oriented(S, j))
-          {
-            lr.set(S, j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-            Tk = centred(Tk);
-          }
+        LocalRay<Real> lr;
+        TorusK<Real>   Tk;
+        tube_frame<Real, ORIENT>(S, j, r, lr, Tk);
         const float ir = a.inv_r2[j];
         tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool, bool) {
-          const float h = (v - u) * a.inv_steps;
+          const float h = (v - u) * a.sub.inv_steps;
           const float l = h * len;
           const float g = l * 0.5f;
-          for(uint32_t s = 0; s < a.steps; ++s)
+          for(uint32_t s = 0; s < a.sub.steps; ++s)
           {
-            const float m = fma_((float)s + 0.5f, h, u);
+            float t[2];
+            gauss_pair(s, h, u, t[0], t[1]);
             for(int side = 0; side < 2; ++side)
             {
-              const Real  t  = (Real)fma_(side ? 0.288675135f : -0.288675135f, h, m);
-              const Real  px = fma_(t, lr.dx, lr.ox) - Tk.cx, py = fma_(t, lr.dy, lr.oy) - Tk.cy, pz = fma_(t, lr.dz, lr.oz) - Tk.cz;
-              const Real  q  = sqrt_(fma_(pz, pz, px * px)) - Tk.R;
-              const float x  = (float)fma_(q, q, py * py) * ir;
-              const float y  = (x < 1.0f ? x : 1.0f) * 16.0f;
-              const int   kn = min((int)y, 15);
-              const float f  = y - (float)kn;
+              int   kn;
+              float f;
+              knot_of((float)tube_rho2(lr, Tk, (Real)t[side]) * ir, kn, f);
               float* const w = W + (uint32_t)kn * kWeightLanes;
               w[0]            = fma_(g, 1.0f - f, w[0]);
               w[kWeightLanes] = fma_(g, f, w[kWeightLanes]);
@@ -505,17 +491,15 @@ __global__ __launch_bounds__(256) void glow_weights_kernel(const SceneK scene, c
         });
       }
       for(uint32_t c = 0; c < TRT_PROFILE_KNOTS; ++c)
-        st1(a.weight, ((uint64_t)j * TRT_PROFILE_KNOTS + c) * a.rays.n + i, W[c * kWeightLanes]);
+        st1(a.weight, ((uint64_t)j * TRT_PROFILE_KNOTS + c) * a.in.rays.n + i, W[c * kWeightLanes]);
     }
-  }
-  if(a.stats)
-    block_add_stats(a.stats, tests, 0u, 0u, wc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------
 // glow_weights_absorbed(rays_in → 17 · n_tori streams and the transmittance: the weights behind absorbing media)
 // ------------------------------------------------------------------------------------------
-// glow_profile_kernel's column, merge and piece walk with EVERY torus present, and glow_weights_kernel's deposit: in every
+// The merged pieces with EVERY torus present, cut into sub-steps, and the deposit of glow_weights_kernel: in every
 // sub-step the sigma of the active tori is summed at the two Gauss–Legendre points as profile_add sums channel 3, the step
 // gives E and the weight w (glow_step_weight), and g = (w · 0.5) · T — T in front of the sub-step — goes to the knots kn
 // and kn + 1 of every active torus at both points.  A sub-step deposits into every active torus, so the accumulators of
@@ -549,111 +533,76 @@ __global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const Scen
   float*         ct  = lane_lds + (n_acc + 2u * n_tori) * LANES + threadIdx.x;
   uint8_t*       cw  = reinterpret_cast<uint8_t*>(lane_lds + (n_acc + 2u * n_tori + K) * LANES) + threadIdx.x;
 
-  const gptr<const float> ox = (gptr<const float>)a.rays.ox, oy = (gptr<const float>)a.rays.oy, oz = (gptr<const float>)a.rays.oz;
-  const gptr<const float> dx = (gptr<const float>)a.rays.dx, dy = (gptr<const float>)a.rays.dy, dz = (gptr<const float>)a.rays.dz;
+  // (for_each_ray's loop, written out: as a callback, this kernel's body has its scalar registers spilt to lanes — 18 more
+  // v_writelane, 16 more v_readlane — and its 64-step rows measure 1.2 to 1.7 % slower; profiles/r29_media_one_walk.txt)
   uint32_t       tests  = 0;
   WorkCount      wc;
   const uint64_t stride = (uint64_t)gridDim.x * LANES;
-  for(uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x; i < a.rays.n; i += stride)
+  for(uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x; i < a.in.rays.n; i += stride)
   {
-    const float tmax = window_end(a.tmax_per_ray, i, a.tmax);
-    float       T    = 1.0f;
+    float      T = 1.0f, len;
+    RayK<Real> r;
+    const bool window = media_ray(a.in, i, r, len);
     for(uint32_t c = 0; c < n_acc; ++c)
       W[c * LANES] = 0.0f;
-    if(tmax > a.tmin)
-    {
-      const v3 o = {ox[i], oy[i], oz[i]};
-      const v3 d = {dx[i], dy[i], dz[i]};
-      RayK<Real> r;
-      r.set(o, d, a.tmin, tmax);
-      const float len = ray_length(d);
-      uint32_t active = 0u, count = 0u;
-      for(int k = 0; k < S.n_tori; ++k)
-      {
-        const int j = S.order[k];
-        ++tests;
-        tube_intervals<Real, ORIENT>(S, j, r, wc, [&](float u, float v, bool from_start, bool to_end) {
-          if(from_start) active |= 1u << j;
-          else column_insert<LANES>(ct, cw, K, count, u, j, true);
-          if(!to_end) column_insert<LANES>(ct, cw, K, count, v, j, false);
-        });
-      }
-      float u = a.tmin;
-      for(uint32_t k = 0; k <= count; ++k)
-      {
-        const bool     last = k == count;
-        const float    v    = last ? tmax : ct[k * LANES];
-        const uint32_t w    = last ? 0u : cw[k * LANES];
-        if(active != 0u && v > u)
+    if(window)
+      merged_pieces<Real, ORIENT, LANES>(S, r, ~0u, ct, cw, K, tests, wc, [&](float u, float v, uint32_t active) {
+        const float h = (v - u) * a.sub.inv_steps;
+        const float l = h * len;
+        for(uint32_t s = 0; s < a.sub.steps; ++s)
         {
-          const float h = (v - u) * a.inv_steps;
-          const float l = h * len;
-          for(uint32_t s = 0; s < a.steps; ++s)
-          {
-            const float m  = fma_((float)s + 0.5f, h, u);
-            const Real  ta = (Real)fma_(-0.288675135f, h, m), tb = (Real)fma_(0.288675135f, h, m);
-            float A = 0.0f, B = 0.0f;
-            for(uint32_t j = 0; j < n_tori; ++j)
-              if((active >> j) & 1u)
-              {
-                LocalRay<Real> lr = {(Real)r.ox, (Real)r.oy, (Real)r.oz, (Real)r.dx, (Real)r.dy, (Real)r.dz, r.dd, r.inv_dd};
-                TorusK<Real>   Tk = torus_k<Real>(S, (int)j);
-                if constexpr(ORIENT)
-                  if(is_oriented(S, (int)j))
-                  {
-                    lr.set(S, (int)j, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-                    Tk = centred(Tk);
-                  }
-                const Real  ax = fma_(ta, lr.dx, lr.ox) - Tk.cx, ay = fma_(ta, lr.dy, lr.oy) - Tk.cy, az = fma_(ta, lr.dz, lr.oz) - Tk.cz;
-                const Real  bx = fma_(tb, lr.dx, lr.ox) - Tk.cx, by = fma_(tb, lr.dy, lr.oy) - Tk.cy, bz = fma_(tb, lr.dz, lr.oz) - Tk.cz;
-                const Real  qa = sqrt_(fma_(az, az, ax * ax)) - Tk.R, qb = sqrt_(fma_(bz, bz, bx * bx)) - Tk.R;
-                const float ir = a.inv_r2[j];
-                const float xa = (float)fma_(qa, qa, ay * ay) * ir, xb = (float)fma_(qb, qb, by * by) * ir;
-                const float ya = (xa < 1.0f ? xa : 1.0f) * 16.0f, yb = (xb < 1.0f ? xb : 1.0f) * 16.0f;
-                const int   ka = min((int)ya, 15), kb = min((int)yb, 15);
-                const float* const sg = sigma + j * TRT_PROFILE_KNOTS;
-                A = A + fma_(ya - (float)ka, sg[ka + 1] - sg[ka], sg[ka]);
-                B = B + fma_(yb - (float)kb, sg[kb + 1] - sg[kb], sg[kb]);
-                Y[(2u * j) * LANES]      = ya;
-                Y[(2u * j + 1u) * LANES] = yb;
-              }
-            float E, wgt;
-            glow_step_weight((A + B) * 0.5f, l, E, wgt);
-            const float g = (wgt * 0.5f) * T;
-            // The deposits at t-, then at t+.  The four accumulators are read at once — one LDS latency per torus, not four
-            // in a row — and where t+ falls on a slot of t- it adds to what t- left there: the same operations in the same
-            // order per accumulator.  The stores go out t- first, so that a shared slot keeps the value with both deposits.
-            for(uint32_t j = 0; j < n_tori; ++j)
-              if((active >> j) & 1u)
-              {
-                const float  ya = Y[(2u * j) * LANES], yb = Y[(2u * j + 1u) * LANES];
-                const int    ka = min((int)ya, 15), kb = min((int)yb, 15);
-                const float  fa = ya - (float)ka, fb = yb - (float)kb;
-                float* const wa = W + (j * TRT_PROFILE_KNOTS + (uint32_t)ka) * LANES;
-                float* const wb = W + (j * TRT_PROFILE_KNOTS + (uint32_t)kb) * LANES;
-                float a0 = wa[0], a1 = wa[LANES], b0 = wb[0], b1 = wb[LANES];
-                a0 = fma_(g, 1.0f - fa, a0);
-                a1 = fma_(g, fa, a1);
-                b0 = kb == ka ? a0 : (kb == ka + 1 ? a1 : b0);
-                b1 = kb == ka ? a1 : (kb + 1 == ka ? a0 : b1);
-                b0 = fma_(g, 1.0f - fb, b0);
-                b1 = fma_(g, fb, b1);
-                wa[0]     = a0;
-                wa[LANES] = a1;
-                wb[0]     = b0;
-                wb[LANES] = b1;
-              }
-            T = T * E;
-          }
+          float ta, tb;
+          gauss_pair(s, h, u, ta, tb);
+          float A = 0.0f, B = 0.0f;
+          for(uint32_t j = 0; j < n_tori; ++j)
+            if((active >> j) & 1u)
+            {
+              LocalRay<Real> lr;
+              TorusK<Real>   Tk;
+              tube_frame<Real, ORIENT>(S, (int)j, r, lr, Tk);
+              const float ir = a.inv_r2[j];
+              int         ka, kb;
+              float       fa, fb;
+              const float ya = knot_of((float)tube_rho2(lr, Tk, (Real)ta) * ir, ka, fa);
+              const float yb = knot_of((float)tube_rho2(lr, Tk, (Real)tb) * ir, kb, fb);
+              const float* const sg = sigma + j * TRT_PROFILE_KNOTS;
+              A = A + fma_(fa, sg[ka + 1] - sg[ka], sg[ka]);
+              B = B + fma_(fb, sg[kb + 1] - sg[kb], sg[kb]);
+              Y[(2u * j) * LANES]      = ya;
+              Y[(2u * j + 1u) * LANES] = yb;
+            }
+          float E, wgt;
+          glow_step_weight((A + B) * 0.5f, l, E, wgt);
+          const float g = (wgt * 0.5f) * T;
+          // The deposits at t-, then at t+.  The four accumulators are read at once — one LDS latency per torus, not four
+          // in a row — and where t+ falls on a slot of t- it adds to what t- left there: the same operations in the same
+          // order per accumulator.  The stores go out t- first, so that a shared slot keeps the value with both deposits.
+          for(uint32_t j = 0; j < n_tori; ++j)
+            if((active >> j) & 1u)
+            {
+              int   ka, kb;
+              float fa, fb;
+              knot_split(Y[(2u * j) * LANES], ka, fa);
+              knot_split(Y[(2u * j + 1u) * LANES], kb, fb);
+              float* const wa = W + (j * TRT_PROFILE_KNOTS + (uint32_t)ka) * LANES;
+              float* const wb = W + (j * TRT_PROFILE_KNOTS + (uint32_t)kb) * LANES;
+              float a0 = wa[0], a1 = wa[LANES], b0 = wb[0], b1 = wb[LANES];
+              a0 = fma_(g, 1.0f - fa, a0);
+              a1 = fma_(g, fa, a1);
+              b0 = kb == ka ? a0 : (kb == ka + 1 ? a1 : b0);
+              b1 = kb == ka ? a1 : (kb + 1 == ka ? a0 : b1);
+              b0 = fma_(g, 1.0f - fb, b0);
+              b1 = fma_(g, fb, b1);
+              wa[0]     = a0;
+              wa[LANES] = a1;
+              wb[0]     = b0;
+              wb[LANES] = b1;
+            }
+          T = T * E;
         }
-        const uint32_t bit = 1u << (w >> 1);
-        if(!last)
-          active = (w & 1u) ? (active | bit) : (active & ~bit);
-        u = v;
-      }
-    }
+      });
     for(uint32_t c = 0; c < n_acc; ++c)
-      st1(a.weight, (uint64_t)c * a.rays.n + i, W[c * LANES]);
+      st1(a.weight, (uint64_t)c * a.in.rays.n + i, W[c * LANES]);
     if(a.trans)
       st1(a.trans, i, T);
   }
@@ -664,59 +613,54 @@ __global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const Scen
 // ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
-// Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here).
-hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning& tn, hipStream_t stream)
+// Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here): launch(real, ori)
+// with the scene's Real as a value and its ORIENT flag as a type, then the launch's error.
+template <class Launch>
+static hipError_t launch_default_solver(const SceneK& scene, Launch&& launch)
 {
-  if(a.rays.n == 0)
-    return hipSuccess;
-  const uint32_t grid = stream_grid(a.rays.n, tn);
   return with_solver(scene, [&](auto real, auto alt, auto ori) {
     if constexpr(decltype(alt)::value)
       return hipErrorInvalidValue;
     else
     {
-      hipLaunchKernelGGL((chords_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
+      launch(real, ori);
       return hipGetLastError();
     }
+  });
+}
+
+hipError_t launch_chords(const SceneK& scene, const ChordsArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.in.rays.n == 0)
+    return hipSuccess;
+  const uint32_t grid = stream_grid(a.in.rays.n, tn);
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    hipLaunchKernelGGL((chords_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
   });
 }
 
 // 4 · n_tori slots per lane: 5 KiB of columns for one torus, 40 KiB for eight (shade_through_kernel's).
 hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn, hipStream_t stream)
 {
-  if(a.rays.n == 0)
+  if(a.in.rays.n == 0)
     return hipSuccess;
-  const uint32_t grid = stream_grid(a.rays.n, tn);
+  const uint32_t grid = stream_grid(a.in.rays.n, tn);
   const uint32_t lds  = 4u * (uint32_t)scene.n_tori * kCrossingSlotBytes;
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    if constexpr(decltype(alt)::value)
-      return hipErrorInvalidValue;
-    else
-    {
-      hipLaunchKernelGGL((glow_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, scene, a);
-      return hipGetLastError();
-    }
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    hipLaunchKernelGGL((glow_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, scene, a);
   });
 }
 
 // glow_kernel's columns; the tables are static LDS (2176 B).  The scene travels without its materials (SceneNoMat).
 hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream)
 {
-  if(a.rays.n == 0)
+  if(a.in.rays.n == 0)
     return hipSuccess;
-  const uint32_t grid = stream_grid(a.rays.n, tn);
-  const uint32_t lds  = 4u * (uint32_t)scene.n_tori * kCrossingSlotBytes;
-  SceneNoMat     sc;
-  std::memcpy(sc.head, &scene, sizeof sc.head);
-  std::memcpy(sc.rot, scene.rot, sizeof sc.rot);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    if constexpr(decltype(alt)::value)
-      return hipErrorInvalidValue;
-    else
-    {
-      hipLaunchKernelGGL((glow_profile_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, sc, a);
-      return hipGetLastError();
-    }
+  const uint32_t   grid = stream_grid(a.in.rays.n, tn);
+  const uint32_t   lds  = 4u * (uint32_t)scene.n_tori * kCrossingSlotBytes;
+  const SceneNoMat sc   = scene_no_mat(scene);
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    hipLaunchKernelGGL((glow_profile_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, sc, a);
   });
 }
 
@@ -724,17 +668,11 @@ hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, co
 static_assert(sizeof(SceneK) + sizeof(GlowWeightsArgs) <= 4096, "the kernel-argument segment of glow_weights_kernel");
 hipError_t launch_glow_weights(const SceneK& scene, const GlowWeightsArgs& a, const Tuning& tn, hipStream_t stream)
 {
-  if(a.rays.n == 0)
+  if(a.in.rays.n == 0)
     return hipSuccess;
-  const uint32_t grid = stream_grid(a.rays.n, tn);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    if constexpr(decltype(alt)::value)
-      return hipErrorInvalidValue;
-    else
-    {
-      hipLaunchKernelGGL((glow_weights_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
-      return hipGetLastError();
-    }
+  const uint32_t grid = stream_grid(a.in.rays.n, tn);
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    hipLaunchKernelGGL((glow_weights_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), 0, stream, scene, a);
   });
 }
 
@@ -750,34 +688,26 @@ uint32_t glow_weights_absorbed_lanes(int n_tori, const Tuning& tn)
   return pick;
 }
 template <class Real, bool ORIENT, uint32_t LANES>
-static hipError_t launch_absorbed_width(const SceneNoMat& sc, const GlowWeightsAbsorbedArgs& a, uint32_t n_tori, const Tuning& tn, hipStream_t stream)
+static void launch_absorbed_width(const SceneNoMat& sc, const GlowWeightsAbsorbedArgs& a, uint32_t n_tori, const Tuning& tn, hipStream_t stream)
 {
   static_assert(LANES * kAbsorbedLaneBytes * (LANES == 256u ? 2u : LANES == 128u ? 5u : TRT_MAX_TORI) + sizeof(SceneK) + 1024u <= 65536u,
                 "a block of glow_weights_absorbed_kernel stays at or below 64 KiB of LDS");
-  hipLaunchKernelGGL((glow_weights_absorbed_kernel<Real, ORIENT, LANES>), dim3(stream_grid_lanes(a.rays.n, LANES, tn)), dim3(LANES),
+  hipLaunchKernelGGL((glow_weights_absorbed_kernel<Real, ORIENT, LANES>), dim3(stream_grid_lanes(a.in.rays.n, LANES, tn)), dim3(LANES),
                      LANES * kAbsorbedLaneBytes * n_tori, stream, sc, a);
-  return hipGetLastError();
 }
 hipError_t launch_glow_weights_absorbed(const SceneK& scene, const GlowWeightsAbsorbedArgs& a, const Tuning& tn, hipStream_t stream)
 {
-  if(a.rays.n == 0)
+  if(a.in.rays.n == 0)
     return hipSuccess;
-  const uint32_t lanes = glow_weights_absorbed_lanes(scene.n_tori, tn);
-  SceneNoMat     sc;
-  std::memcpy(sc.head, &scene, sizeof sc.head);
-  std::memcpy(sc.rot, scene.rot, sizeof sc.rot);
-  return with_solver(scene, [&](auto real, auto alt, auto ori) {
-    if constexpr(decltype(alt)::value)
-      return hipErrorInvalidValue;
-    else
-    {
-      using Real          = decltype(real);
-      constexpr bool kOri = decltype(ori)::value;
-      const uint32_t nt   = (uint32_t)scene.n_tori;
-      return lanes == 256u ? launch_absorbed_width<Real, kOri, 256u>(sc, a, nt, tn, stream)
-           : lanes == 128u ? launch_absorbed_width<Real, kOri, 128u>(sc, a, nt, tn, stream)
-                           : launch_absorbed_width<Real, kOri, 64u>(sc, a, nt, tn, stream);
-    }
+  const uint32_t   lanes = glow_weights_absorbed_lanes(scene.n_tori, tn);
+  const SceneNoMat sc    = scene_no_mat(scene);
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    using Real          = decltype(real);
+    constexpr bool kOri = decltype(ori)::value;
+    const uint32_t nt   = (uint32_t)scene.n_tori;
+    if(lanes == 256u) launch_absorbed_width<Real, kOri, 256u>(sc, a, nt, tn, stream);
+    else if(lanes == 128u) launch_absorbed_width<Real, kOri, 128u>(sc, a, nt, tn, stream);
+    else launch_absorbed_width<Real, kOri, 64u>(sc, a, nt, tn, stream);
   });
 }
 
