@@ -43,6 +43,8 @@
  *   every knot of such a medium    matrix of emission tomography)            trt_glow_weights*
  *   the same response behind       (none: build-defined, the geometry matrix
  *   media that absorb              weighted by the transmittance in front)   trt_glow_weights_absorbed*
+ *   that matrix applied without    (none: build-defined, the forward and the
+ *   leaving the GPU: W x, W^T y    adjoint product of iterative tomography)  trt_glow_project* / trt_glow_backproject*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -921,8 +923,9 @@ int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax
  * 1..TRT_MAX_GLOW_STEPS; a solver other than TRT_SOLVE_F32 / _F64; n_tori * 17 * n overflowing 64 bits.  n == 0 is valid
  * and launches nothing.  A refused call leaves the ctx usable and the output unwritten.
  * Stats: as trt_chords' (primary_tests = the tori started, pixels = n).
- * Not here: absorption (the weights given sigma tables are trt_glow_weights_absorbed, below); a matrix-free
- * W^T y; a torus mask (a scene that holds torus j alone gives j's rows bit for bit); a fused camera form.
+ * Not here: absorption (the weights given sigma tables are trt_glow_weights_absorbed, below; the matrix-free products
+ * W x and W^T y, trt_glow_project and trt_glow_backproject, are built on those); W^T W; a torus mask (a scene that holds
+ * torus j alone gives j's rows bit for bit); a fused camera form.
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                      uint32_t steps, float tmin, float tmax, float* weight_out);
@@ -992,8 +995,8 @@ int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax
  * sigma knot that is negative, NaN or infinite (the message names the torus and the knot).  n == 0 is valid and launches
  * nothing.  A refused call leaves the ctx usable and both outputs unwritten.
  * Stats: primary_tests = the tori started, that is n_tori times the non-empty windows; pixels = n.
- * Not here: the response to a sigma knot (it is not linear); a matrix-free W^T y; a torus mask; a fused camera form;
- * a solver for the fit.
+ * Not here: the response to a sigma knot (it is not linear); W^T W (the matrix-free W x and W^T y are trt_glow_project
+ * and trt_glow_backproject, below); a torus mask; a fused camera form; a solver for the fit.
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                               const trt_profile* profiles, uint32_t steps, float tmin, float tmax,
@@ -1004,6 +1007,72 @@ int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const float* tma
 int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
                                   const trt_profile* profiles, uint32_t steps, float tmin, float tmax,
                                   float* weight_dev, float* trans_dev, void* stream);
+
+/* ---- that matrix applied on the GPU: glow_project(rays_in, x -> W x), glow_backproject(rays_in, y -> W^T y) ---------- */
+/* Every iterative reconstruction on trt_glow_weights_absorbed's W (Landweber, SART, CGLS, MLEM) needs a matrix-free
+ * W^T y beside the forward product W x, and never W itself: 68 bytes per ray and torus that these two calls do not
+ * write.  Throughout, W[j][k][i]
+ * is trt_glow_weights_absorbed's weight for the same rays, per-ray bound, scene, axes, solver, profiles, steps, tmin and
+ * tmax BIT FOR BIT — the same rule and the same order of additions into every accumulator, every torus present, the pieces
+ * cut at every torus' walls — and T[i] is its trans, bit for bit.  Only knot[k][3] (sigma) of `profiles` enters W.
+ * Window, per-ray bound, solvers (TRT_SOLVE_F32 / _F64 only), oriented tori and materials not being read:
+ * trt_glow_weights_absorbed's.
+ *
+ * trt_glow_project: the forward product.  The signature is trt_glow_profile's.  profiles must not be NULL: the emission
+ * channels 0..2 of profiles[j] are x, channel 3 is sigma, and all four are validated as trt_glow_profile validates them
+ * (finite and not negative; the message names the torus and the knot).  Per ray i and channel c = 0..2, in FP64:
+ *   p = 0.0;
+ *   for j = 0 .. n_tori - 1 ascending, then k = 0 .. 16 ascending:
+ *     p = p + (double)W[j][k][i] * (double)knot_j[k][c];     the product of two floats is exact in FP64; then ONE rounded
+ *                                                            FP64 addition (no contraction changes that)
+ *   L_c = (float)p;
+ * rgba[4 i ..] = (L_r, L_g, L_b, T[i]), 16-byte aligned, n * 4 floats.  !(tmax_i > tmin) gives (0, 0, 0, 1) and executes no
+ * test.  The result is reproducible in bits from W and the tables, and trt_glow_backproject is the adjoint of exactly this
+ * map.  Against trt_glow_profile: when every torus has a non-zero table there, the two differ by rounding only (w, E and
+ * T are the same bits; the association of the products differs); a torus with an all-zero table is absent THERE and cuts
+ * no piece, while here every torus is walked and its walls cut the pieces, so the quadrature differs as well — which is
+ * why trt_glow_profile is the adjoint of no back-projection built on W.
+ * TRT_E_INVALID, with "trt_glow_project" in the message: everything trt_glow_profile refuses.  n == 0 is valid, launches
+ * nothing and writes nothing.  Stats: trt_glow_weights_absorbed's.
+ *
+ * trt_glow_backproject: the adjoint.  y holds 4 * n floats in the rgba layout the glow calls write, 16-byte aligned:
+ * channels 0..2 are read, channel 3 is IGNORED (a residual image formed from a glow output passes as it stands, whatever
+ * its fourth channel holds).  profiles may be NULL: all-zero sigma tables — the same absorbed rule with zero tables (every
+ * torus walked, the pieces cut at every wall), NOT trt_glow_weights' uncut intervals; the emission entries are neither
+ * read nor validated.  back holds n_tori * 17 * 4 DOUBLES, 16-byte aligned:
+ *   back[(j * 17 + k) * 4 + c] = sum over i of W[j][k][i] * y[4 i + c]      for c = 0..2,
+ *   back[(j * 17 + k) * 4 + 3] = sum over i of W[j][k][i]                   the column sum SART and MLEM normalise by.
+ * Arithmetic.  Every term is the exact FP64 product of two floats and the sums are FP64.  The ORDER of the additions is
+ * not part of the contract; what is: for finite y, |back - exact| <= n * 2^-53 * sum over i of |W * y| (the bound of any
+ * summation order: gamma_(n-1) <= n u for every n in reach); a sum whose terms are all zero is 0.0; and the same call on the
+ * same ctx with the same tuning gives the same bits every time, a graph replay against the captured launch's own result
+ * included — there are no floating-point atomics.  y is device (or host) data and is not validated: a non-finite
+ * y[4 i + c] leaves channel c of the output unspecified.  A ray with an empty window contributes nothing.  n == 0 is
+ * valid and writes n_tori * 17 * 4 zeros.
+ * TRT_E_INVALID, with "trt_glow_backproject" in the message: everything trt_glow_weights_absorbed refuses but NULL
+ * profiles; NULL y with n > 0; y or back not 16-byte aligned.  A refused call leaves the ctx usable and back unwritten.
+ * Stats: trt_glow_weights_absorbed's.
+ * Not here: W^T W; a torus mask; a fused camera form; a solver for the fit (examples/matrix_free_fit_main.cpp runs CGLS on
+ * the two calls).
+ * Host buffers: copy in, launch, copy out, synchronise. */
+int trt_glow_project(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                     const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`.  `profiles` stays a host pointer: the tables travel in the kernel
+ * arguments.  The call uses no scratch of the ctx, allocates nothing, synchronises nothing, puts only kernel nodes on the
+ * stream and may be captured. */
+int trt_glow_project_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                         const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_dev, void* stream);
+int trt_glow_backproject(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                         const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y,
+                         double* back_out);
+/* Device-resident buffers, asynchronous on `stream`; two kernel nodes, nothing else.  The blocks' partial sums (at most
+ * 2048 rows of n_tori * 17 * 4 doubles) live in scratch of the ctx, under the scratch table's rule: the area grows in an
+ * un-captured call only, so before the call is captured into a hipGraph make one eager call with at least the same n and
+ * n_tori (a capture that would have to grow it is refused with TRT_E_INVALID); a graph keeps the block it was captured with.
+ * Calls that share the ctx share that area: order them on one stream, or give concurrent streams a ctx each. */
+int trt_glow_backproject_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                             const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y_dev,
+                             double* back_dev, void* stream);
 
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal

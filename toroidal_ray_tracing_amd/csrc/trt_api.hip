@@ -53,6 +53,7 @@ enum Buf {
   kBufBins,                     // … binned form: per-bin count / offset / cursor words (count zero between calls)
   kBufRecs,                     // … binned form: point records sorted by bin
   kBufCloud,                    // trt_cloud_dev: the header words and the chunk table (CloudWord, trt_cloud.hpp)
+  kBufBackproject,              // trt_glow_backproject_dev: the blocks' rows of FP64 partials (GlowBackprojectArgs::partials)
   kBufCount
 };
 
@@ -1388,7 +1389,7 @@ extern "C" int trt_glow(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_
 
 // The profiles of trt_glow_profile*, validated (the scene first, so that n_tori can be trusted) and copied into the kernel
 // arguments with the 1 / r² of every torus.
-static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile* profiles, Profiles& out)
+static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile* profiles, Profiles& out, const char* who = "trt_glow_profile")
 {
   const SceneK* S = nullptr;
   if(int rc = build_scene(ctx, scene, S)) return rc;
@@ -1400,8 +1401,8 @@ static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile
       {
         const float v = profiles[j].knot[k][c];
         if(!medium_value_ok(v))
-          return fail(ctx, TRT_E_INVALID, "trt_glow_profile: the profile of torus %u has %s = %g at knot %u; emission and sigma must be "
-                                          "finite and not negative", j, c < 3 ? "an emission" : "sigma", (double)v, k);
+          return fail(ctx, TRT_E_INVALID, "%s: the profile of torus %u has %s = %g at knot %u; emission and sigma must be "
+                                          "finite and not negative", who, j, c < 3 ? "an emission" : "sigma", (double)v, k);
         if(v != 0.0f)
           out.present |= 1u << j;
       }
@@ -1410,12 +1411,13 @@ static int glow_profiles(trt_ctx* ctx, const trt_scene* scene, const trt_profile
   fill_inv_r2(scene, out.inv_r2);
   return TRT_OK;
 }
-static int check_glow_profile(trt_ctx* ctx, const trt_rays* in, const trt_profile* profiles, uint32_t steps, const float* rgba)
+static int check_glow_profile(trt_ctx* ctx, const trt_rays* in, const trt_profile* profiles, uint32_t steps, const float* rgba,
+                              const char* who = "trt_glow_profile")
 {
-  if(int rc = check_media(ctx, in, rgba, "trt_glow_profile")) return rc;
-  if(!profiles) return fail(ctx, TRT_E_INVALID, "trt_glow_profile: NULL profiles");
-  if(int rc = check_steps(ctx, "trt_glow_profile", steps)) return rc;
-  return check_rgba(ctx, "trt_glow_profile", rgba);
+  if(int rc = check_media(ctx, in, rgba, who)) return rc;
+  if(!profiles) return fail(ctx, TRT_E_INVALID, "%s: NULL profiles", who);
+  if(int rc = check_steps(ctx, who, steps)) return rc;
+  return check_rgba(ctx, who, rgba);
 }
 extern "C" int trt_glow_profile_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                                     const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba, void* stream)
@@ -1467,6 +1469,24 @@ extern "C" int trt_glow_weights(trt_ctx* ctx, const trt_rays* in, const float* t
                             });
 }
 
+// The sigma column of every torus' profile of a built scene, validated and packed for the kernel arguments (`who`:
+// trt_glow_weights_absorbed*, trt_glow_backproject*); profiles == NULL, where a call allows it: all zero.
+static int sigma_tables(trt_ctx* ctx, const char* who, const trt_scene* scene, const trt_profile* profiles,
+                        float (&sigma)[TRT_MAX_TORI][TRT_PROFILE_KNOTS])
+{
+  std::memset(sigma, 0, sizeof sigma);
+  for(uint32_t j = 0; profiles && j < scene->n_tori; ++j)
+    for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)   // sigma only: the emission entries are the unknowns, and are not read
+    {
+      const float v = profiles[j].knot[k][3];
+      if(!medium_value_ok(v))
+        return fail(ctx, TRT_E_INVALID, "%s: the profile of torus %u has sigma = %g at knot %u; sigma must be "
+                                        "finite and not negative", who, j, (double)v, k);
+      sigma[j][k] = v;
+    }
+  return TRT_OK;
+}
+
 // trt_glow_weights_absorbed*: trt_glow_weights' checks under its own name, and the profiles.
 static int check_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const trt_scene* scene, const trt_profile* profiles, uint32_t steps,
                                        const float* weight)
@@ -1484,16 +1504,7 @@ extern "C" int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in, c
   const SceneK* S = nullptr;
   if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori and the radii are trusted below)
   GlowWeightsAbsorbedArgs a;
-  std::memset(a.sigma, 0, sizeof a.sigma);
-  for(uint32_t j = 0; j < scene->n_tori; ++j)
-    for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)   // sigma only: the emission entries are the unknowns, and are not read
-    {
-      const float v = profiles[j].knot[k][3];
-      if(!medium_value_ok(v))
-        return fail(ctx, TRT_E_INVALID, "trt_glow_weights_absorbed: the profile of torus %u has sigma = %g at knot %u; sigma must be "
-                                        "finite and not negative", j, (double)v, k);
-      a.sigma[j][k] = v;
-    }
+  if(int rc = sigma_tables(ctx, "trt_glow_weights_absorbed", scene, profiles, a.sigma)) return rc;
   fill_inv_r2(scene, a.inv_r2);
   a.in     = media_rays(in, tmax_per_ray, tmin, tmax);
   a.sub    = media_steps(steps);
@@ -1510,6 +1521,84 @@ extern "C" int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const
                             [&](const trt_rays* rays, const float* bounds, float* weight, float* trans) {
                               return trt_glow_weights_absorbed_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, weight, trans, nullptr);
                             });
+}
+
+// trt_glow_project*: trt_glow_profile's signature, checks and tables under its own name; every torus is walked.
+extern "C" int trt_glow_project_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                    const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba, void* stream)
+{
+  if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba, "trt_glow_project")) return rc;
+  GlowProfileArgs a;
+  if(int rc = glow_profiles(ctx, scene, profiles, a.prof, "trt_glow_project")) return rc;
+  a.in   = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub  = media_steps(steps);
+  a.rgba = rgba;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_project);
+}
+extern "C" int trt_glow_project(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_out)
+{
+  if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba_out, "trt_glow_project")) return rc;
+  return media_rgba_host(ctx, in, tmax_per_ray, rgba_out, [&](const trt_rays* rays, const float* bounds, float* rgba) {
+    return trt_glow_project_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, rgba, nullptr);
+  });
+}
+
+// trt_glow_backproject*: trt_glow_weights_absorbed's checks under its own name, with the image in and 4 * 17 * n_tori doubles out.
+static int check_glow_backproject(trt_ctx* ctx, const trt_rays* in, uint32_t steps, const float* y, const double* back)
+{
+  const char* const who = "trt_glow_backproject";
+  if(int rc = check_media(ctx, in, back, who)) return rc;
+  if(in->n && !y) return fail(ctx, TRT_E_INVALID, "%s: NULL y", who);
+  if(int rc = check_steps(ctx, who, steps)) return rc;
+  if((uintptr_t)y & 15) return fail(ctx, TRT_E_INVALID, "%s: y must be 16-byte aligned (it is read as float4)", who);
+  if((uintptr_t)back & 15) return fail(ctx, TRT_E_INVALID, "%s: back must be 16-byte aligned", who);
+  if(in->n > UINT64_MAX / 4 / sizeof(float)) return fail(ctx, TRT_E_INVALID, "%s: 4 * n floats overflow 64 bits", who);
+  return TRT_OK;
+}
+extern "C" int trt_glow_backproject_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                        const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y,
+                                        double* back, void* stream)
+{
+  if(int rc = check_glow_backproject(ctx, in, steps, y, back)) return rc;
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;   // (n_tori and the radii are trusted below)
+  GlowBackprojectArgs a;
+  if(int rc = sigma_tables(ctx, "trt_glow_backproject", scene, profiles, a.sigma)) return rc;
+  fill_inv_r2(scene, a.inv_r2);
+  a.in   = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub  = media_steps(steps);
+  a.y    = y;
+  a.back = back;
+  // the blocks' rows: scratch of the ctx, grown here — outside a capture only (grow() refuses inside one: an eager call of
+  // at least this n and n_tori sizes it first); a captured launch keeps the block it was captured with (retired, not freed)
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  a.rows = glow_backproject_rows((int)scene->n_tori, in->n, ctx->tn);
+  if(int rc = grow(ctx, ctx->buf[kBufBackproject], (size_t)a.rows * 4 * TRT_PROFILE_KNOTS * scene->n_tori * sizeof(double), (hipStream_t)stream))
+    return rc;
+  a.partials = (double*)ctx->buf[kBufBackproject].p;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_backproject);
+}
+extern "C" int trt_glow_backproject(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                    const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y,
+                                    double* back_out)
+{
+  if(int rc = check_glow_backproject(ctx, in, steps, y, back_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  const auto dev = [&](const trt_rays* rays, const float* bounds, const float* image, double* back) {
+    return trt_glow_backproject_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, image, back, nullptr);
+  };
+  if(!scene) return dev(in, nullptr, y, back_out);   // (refused there)
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  if(in->n > SIZE_MAX / 4 / sizeof(float)) return fail(ctx, TRT_E_NOMEM, "trt_glow_backproject: 4 * n floats do not fit the address space");
+  StagedOut out = {back_out, sizeof(double) * 4 * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr};
+  return bounded_query_host(ctx, in, in->n ? tmax_per_ray : nullptr, &out, 1, [&](const trt_rays* rays, const float* bounds) {
+    const float* d_y = nullptr;
+    if(in->n)
+      if(int rc = stage_in(ctx, kBufRgba, y, (size_t)in->n * 4 * sizeof(float), (void**)&d_y)) return rc;
+    return dev(rays, bounds, d_y, (double*)out.dev);
+  });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -311,6 +311,22 @@ struct GlowWeightsAbsorbedArgs {
   float*              trans;
   unsigned long long* stats;
 };
+// trt_glow_project*: GlowProfileArgs as it stands — the emission channels of prof.p are x, channel 3 sigma; prof.present is
+// not read (every torus is walked).
+// trt_glow_backproject*: GlowWeightsAbsorbedArgs' walk with the image y (4 * rays.n floats, 16-byte aligned, channel 3 not
+// read) in place of the outputs.  The blocks leave `rows` rows of 4 * 17 * n_tori doubles in `partials` (scratch of the
+// ctx; rows = glow_backproject_rows(), the grid), which the second kernel adds in row order into back[(j * 17 + k) * 4 + c].
+struct GlowBackprojectArgs {
+  MediaRays           in;
+  MediaSteps          sub;
+  float               sigma[TRT_MAX_TORI][TRT_PROFILE_KNOTS];
+  float               inv_r2[TRT_MAX_TORI];
+  const float*        y;
+  double*             partials;
+  uint32_t            rows;
+  double*             back;
+  unsigned long long* stats;
+};
 
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
@@ -463,6 +479,9 @@ hipError_t launch_glow(const SceneK& scene, const GlowArgs& a, const Tuning& tn,
 hipError_t launch_glow_profile(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_glow_weights(const SceneK& scene, const GlowWeightsArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_glow_weights_absorbed(const SceneK& scene, const GlowWeightsAbsorbedArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_glow_project(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_glow_backproject(const SceneK& scene, const GlowBackprojectArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+uint32_t   glow_backproject_rows(int n_tori, uint64_t n, const Tuning& tn);   // the grid of glow_backproject_kernel = the rows of its partials
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);

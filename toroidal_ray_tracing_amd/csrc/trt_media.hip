@@ -1,5 +1,5 @@
 // trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*, trt_glow_weights*,
-// trt_glow_weights_absorbed*), gfx950.
+// trt_glow_weights_absorbed*, trt_glow_project*, trt_glow_backproject*), gfx950.
 //
 // What the kernels share, each said once:
 //   tube_frame, tube_rho2   the ray in torus j's frame, and the tube label of its point at t: the inside test and every
@@ -19,8 +19,10 @@
 //                    each interval of a torus, 17 accumulators per lane in LDS, 17 · n_tori streams out.
 //   glow_weights_absorbed_kernel   the same response behind absorbing media: the merged pieces of ALL tori with a running T,
 //                    the accumulators of all tori live at once, the block width chosen from n_tori.
-//   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights, launch_glow_weights_absorbed   their grid and
-//                    launch wrappers.
+//   glow_project_kernel, glow_backproject_kernel   that walk again, with the weights used on the chip: W · x per ray, and
+//                    Wᵀ y in FP64 reduced over the rays (backproject_sum_kernel adds the blocks' rows).
+//   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights, launch_glow_weights_absorbed, launch_glow_project,
+//                    launch_glow_backproject   their grid and launch wrappers.
 //
 // The crossings of torus j are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
 // window, no enclosure cull); include/trt.h states the arithmetic of everything on top of them, expression by expression.
@@ -510,46 +512,60 @@ __global__ __launch_bounds__(256) void glow_weights_kernel(const SceneK scene, c
 // slots of the crossing column.  96 · n_tori bytes per lane in all: the host picks LANES (256, 128 or 64) from n_tori so
 // that a block stays below 64 KiB.  A lane touches its own columns only and the order of the additions into an
 // accumulator is the walk's, so the result does not depend on LANES and nothing but the staging needs a barrier.
+//
+// Three kernels run this walk and differ in what leaves the chip behind it: glow_weights_absorbed_kernel stores the
+// columns, glow_project_kernel their FP64 dot products with the emission tables, glow_backproject_kernel their products
+// with an image, reduced over the rays.  What they share is said once: absorbed_stage (the sigma tables and the scene into
+// LDS), AbsorbedLane (where a lane's columns are) and absorbed_ray (the walk of one ray into the lane's accumulators).
 constexpr uint32_t kAbsorbedLaneBytes = 4u * (TRT_PROFILE_KNOTS + 2u) + 4u * (uint32_t)(sizeof(float) + sizeof(uint8_t));   // per torus: 96
 static_assert(sizeof(SceneNoMat) + sizeof(GlowWeightsAbsorbedArgs) <= 4096, "the kernel-argument segment of glow_weights_absorbed_kernel");
-template <class Real, bool ORIENT, uint32_t LANES>
-__global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const SceneNoMat scene, const GlowWeightsAbsorbedArgs a)
+static_assert(sizeof(SceneNoMat) + sizeof(GlowProfileArgs) <= 4096, "the kernel-argument segment of glow_project_kernel");
+static_assert(sizeof(SceneNoMat) + sizeof(GlowBackprojectArgs) <= 4096, "the kernel-argument segment of glow_backproject_kernel");
+// sigma[j * 17 + k] = src[(j * 17 + k) * step]: GlowWeightsAbsorbedArgs' packed tables (step 1), or channel 3 of
+// trt_profile's knots (step 4, src at knot[0][3]).  Ends with the barrier that publishes the tables and the scene.
+template <bool ORIENT, uint32_t LANES>
+__device__ __forceinline__ void absorbed_stage(SceneK* S, float* sigma, const SceneNoMat& scene, const float* src, uint32_t step)
 {
-  __shared__ SceneK S;
-  __shared__ float  sigma[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
-  extern __shared__ float lane_lds[];   // [17 n_tori][LANES] acc, [2 n_tori][LANES] y, [K][LANES] t, [K][LANES] bytes
-  const uint32_t n_tori = scene.head[0];
+  for(uint32_t i = threadIdx.x; i < TRT_PROFILE_KNOTS * scene.head[0]; i += LANES)
+    sigma[i] = src[i * step];
+  stage_scene_no_mat<ORIENT>(S, scene);
+  __syncthreads();
+}
+// The lane's columns in the block's dynamic LDS: [17 n_tori][LANES] acc, [2 n_tori][LANES] y, [K][LANES] t, [K][LANES] bytes.
+template <uint32_t LANES>
+struct AbsorbedLane {
+  uint32_t K, n_acc;
+  float*   W;
+  float*   Y;
+  float*   ct;
+  uint8_t* cw;
+  __device__ __forceinline__ AbsorbedLane(float* lane_lds, uint32_t n_tori)
+    : K(4u * n_tori), n_acc(TRT_PROFILE_KNOTS * n_tori), W(lane_lds + threadIdx.x), Y(lane_lds + n_acc * LANES + threadIdx.x),
+      ct(lane_lds + (n_acc + 2u * n_tori) * LANES + threadIdx.x),
+      cw(reinterpret_cast<uint8_t*>(lane_lds + (n_acc + 2u * n_tori + K) * LANES) + threadIdx.x)
   {
-    const float* src = &a.sigma[0][0];
-    for(uint32_t i = threadIdx.x; i < TRT_PROFILE_KNOTS * n_tori; i += LANES)
-      sigma[i] = src[i];
   }
-  stage_scene_no_mat<ORIENT>(&S, scene);
-  __syncthreads();   // publishes the tables and the scene
-
-  const uint32_t K   = 4u * n_tori, n_acc = TRT_PROFILE_KNOTS * n_tori;
-  float* const   W   = lane_lds + threadIdx.x;
-  float* const   Y   = lane_lds + n_acc * LANES + threadIdx.x;
-  float*         ct  = lane_lds + (n_acc + 2u * n_tori) * LANES + threadIdx.x;
-  uint8_t*       cw  = reinterpret_cast<uint8_t*>(lane_lds + (n_acc + 2u * n_tori + K) * LANES) + threadIdx.x;
-
-  // (for_each_ray's loop, written out: as a callback, this kernel's body has its scalar registers spilt to lanes — 18 more
-  // v_writelane, 16 more v_readlane — and its 64-step rows measure 1.2 to 1.7 % slower; profiles/r29_media_one_walk.txt)
-  uint32_t       tests  = 0;
-  WorkCount      wc;
-  const uint64_t stride = (uint64_t)gridDim.x * LANES;
-  for(uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x; i < a.in.rays.n; i += stride)
+};
+// Ray i of `in` walked into the lane's accumulators (zeroed first; an empty window leaves them zero and executes no
+// test); returns the transmittance left.  (Parameters by reference, for column_insert's reason.)
+template <class Real, bool ORIENT, uint32_t LANES>
+__device__ __forceinline__ float absorbed_ray(const SceneK& S, const float* const& sigma, const MediaRays& in, const MediaSteps& sub,
+                                              const float (&inv_r2)[TRT_MAX_TORI], const uint32_t& n_tori, const uint64_t& i,
+                                              const AbsorbedLane<LANES>& lane, uint32_t& tests, WorkCount& wc)
+{
+  float* const W = lane.W;
+  float* const Y = lane.Y;
   {
     float      T = 1.0f, len;
     RayK<Real> r;
-    const bool window = media_ray(a.in, i, r, len);
-    for(uint32_t c = 0; c < n_acc; ++c)
+    const bool window = media_ray(in, i, r, len);
+    for(uint32_t c = 0; c < lane.n_acc; ++c)
       W[c * LANES] = 0.0f;
     if(window)
-      merged_pieces<Real, ORIENT, LANES>(S, r, ~0u, ct, cw, K, tests, wc, [&](float u, float v, uint32_t active) {
-        const float h = (v - u) * a.sub.inv_steps;
+      merged_pieces<Real, ORIENT, LANES>(S, r, ~0u, lane.ct, lane.cw, lane.K, tests, wc, [&](float u, float v, uint32_t active) {
+        const float h = (v - u) * sub.inv_steps;
         const float l = h * len;
-        for(uint32_t s = 0; s < a.sub.steps; ++s)
+        for(uint32_t s = 0; s < sub.steps; ++s)
         {
           float ta, tb;
           gauss_pair(s, h, u, ta, tb);
@@ -560,7 +576,7 @@ __global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const Scen
               LocalRay<Real> lr;
               TorusK<Real>   Tk;
               tube_frame<Real, ORIENT>(S, (int)j, r, lr, Tk);
-              const float ir = a.inv_r2[j];
+              const float ir = inv_r2[j];
               int         ka, kb;
               float       fa, fb;
               const float ya = knot_of((float)tube_rho2(lr, Tk, (Real)ta) * ir, ka, fa);
@@ -601,13 +617,187 @@ __global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const Scen
           T = T * E;
         }
       });
-    for(uint32_t c = 0; c < n_acc; ++c)
-      st1(a.weight, (uint64_t)c * a.in.rays.n + i, W[c * LANES]);
+    return T;
+  }
+}
+
+template <class Real, bool ORIENT, uint32_t LANES>
+__global__ __launch_bounds__(LANES) void glow_weights_absorbed_kernel(const SceneNoMat scene, const GlowWeightsAbsorbedArgs a)
+{
+  __shared__ SceneK S;
+  __shared__ float  sigma[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float lane_lds[];
+  const uint32_t n_tori = scene.head[0];
+  absorbed_stage<ORIENT, LANES>(&S, sigma, scene, &a.sigma[0][0], 1u);
+  const AbsorbedLane<LANES> lane(lane_lds, n_tori);
+
+  // (for_each_ray's loop, written out: as a callback, this kernel's body has its scalar registers spilt to lanes — 18 more
+  // v_writelane, 16 more v_readlane — and its 64-step rows measure 1.2 to 1.7 % slower; profiles/r29_media_one_walk.txt)
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * LANES;
+  for(uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x; i < a.in.rays.n; i += stride)
+  {
+    const float T = absorbed_ray<Real, ORIENT, LANES>(S, sigma, a.in, a.sub, a.inv_r2, n_tori, i, lane, tests, wc);
+    for(uint32_t c = 0; c < lane.n_acc; ++c)
+      st1(a.weight, (uint64_t)c * a.in.rays.n + i, lane.W[c * LANES]);
     if(a.trans)
       st1(a.trans, i, T);
   }
   if(a.stats)
     block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
+// glow_project(rays_in → W · x and the transmittance): the forward product with exactly those weights
+// ------------------------------------------------------------------------------------------
+// Behind a ray's walk the lane reads its own column back, torus by torus and knot by knot, and forms the three dot products
+// with the emission tables as include/trt.h states them: p = p + (double)W · (double)knot, the product exact, one rounded
+// FP64 addition (the unit is compiled with -ffp-contract=off; a contracted fma would round the same sum once as well, the
+// product being exact).  The tables stay in the kernel arguments: j and k are uniform for the wave, so a knot is a scalar
+// load and costs no LDS.  One 16-byte store per ray; no weight leaves the chip.
+template <class Real, bool ORIENT, uint32_t LANES>
+__global__ __launch_bounds__(LANES) void glow_project_kernel(const SceneNoMat scene, const GlowProfileArgs a)
+{
+  __shared__ SceneK S;
+  __shared__ float  sigma[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float lane_lds[];
+  const uint32_t n_tori = scene.head[0];
+  absorbed_stage<ORIENT, LANES>(&S, sigma, scene, &a.prof.p[0].knot[0][3], 4u);
+  const AbsorbedLane<LANES> lane(lane_lds, n_tori);
+
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * LANES;
+  for(uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x; i < a.in.rays.n; i += stride)
+  {
+    const float T = absorbed_ray<Real, ORIENT, LANES>(S, sigma, a.in, a.sub, a.prof.inv_r2, n_tori, i, lane, tests, wc);
+    double      pr = 0.0, pg = 0.0, pb = 0.0;
+    for(uint32_t j = 0; j < n_tori; ++j)
+      for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)
+      {
+        const double w = (double)lane.W[(j * TRT_PROFILE_KNOTS + k) * LANES];
+        pr = pr + w * (double)a.prof.p[j].knot[k][0];
+        pg = pg + w * (double)a.prof.p[j].knot[k][1];
+        pb = pb + w * (double)a.prof.p[j].knot[k][2];
+      }
+    st4(a.rgba + 4 * i, make_float4((float)pr, (float)pg, (float)pb, T));
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+
+// ------------------------------------------------------------------------------------------
+// glow_backproject(rays_in, y → Wᵀ y and the column sums, in FP64): the adjoint with exactly those weights
+// ------------------------------------------------------------------------------------------
+// A block takes the rays in rounds of LANES (grid-stride; the loop is uniform for the block, a lane behind the last ray
+// holds a zero column and a zero y).  Behind a round's walks the block holds W[c][lane] for its LANES rays in LDS, and
+// reduces them against y over the lanes by a TRANSPOSED read: thread e of a pass owns the output (row c = e >> 2, channel
+// ch = e & 3) and adds the LANES terms (double)W[c][l] · (double)y[l][ch] — each product exact in FP64 — one after the
+// other into an FP64 accumulator.  Channel 3 of y is replaced by 1.0f on the way in: its output is the column sum.
+//   Why not cross-lane operations: a wave-wide tree over DPP takes six FP64 additions and twelve register moves per lane
+//   and output — 4 · 17 · n_tori outputs, so 3264 additions per lane and round for eight tori — where the transposed read
+//   takes ONE addition per lane and output, and two LDS reads.
+//   Banks: the four threads of a row read the same word of W (a broadcast), and the 16 rows of a wave start their walk over
+//   the lanes rotated by c — l = (step + c) mod LANES — so that they sit on 16 different banks (c · LANES is a multiple of
+//   64).  y lies lane-major, four floats per lane: the wave's 16 lanes times four channels are 64 consecutive words.  The
+//   order of a row's additions is therefore rotated by its c, and fixed: the same bits from every launch.
+//   Where y lies: in the lane's y and crossing columns, which are dead behind the walk (24 · n_tori bytes per lane; 16 are
+//   needed) — a barrier in front (every walk of the round has ended) and one behind the reduction (the next round's walks
+//   overwrite them).
+//   The partials over the rounds: 4 · 17 · n_tori FP64 values per block.  They are the threads' REGISTERS, not LDS: a
+//   block of 128 lanes for five tori has 1704 bytes of its 64 KiB left, and the 2720 that its partials take do not fit.
+//   The pass loop is unrolled (PASSES = the outputs of the widest scene of this block width over LANES: 1, 3 or 9), so
+//   acc[] is never indexed at run time and stays in 2 · PASSES registers.  An output belongs to one thread for the whole
+//   kernel, so its additions are ordered without any atomic.
+// At its end the block writes its row of 4 · 17 · n_tori doubles to partials[blockIdx.x]; backproject_sum_kernel adds the rows
+// in index order.  No floating-point atomics anywhere: the bits depend on (n, the grid, LANES) alone.
+static_assert(4u * sizeof(float) <= (2u + 4u) * sizeof(float), "a lane's y fits its dead y and t columns for one torus already: the reduction adds no LDS");
+template <class Real, bool ORIENT, uint32_t LANES>
+__global__ __launch_bounds__(LANES) void glow_backproject_kernel(const SceneNoMat scene, const GlowBackprojectArgs a)
+{
+  constexpr uint32_t kMaxTori = LANES == 256u ? 2u : LANES == 128u ? 5u : TRT_MAX_TORI;
+  constexpr uint32_t PASSES   = (4u * TRT_PROFILE_KNOTS * kMaxTori + LANES - 1u) / LANES;
+  __shared__ SceneK S;
+  __shared__ float  sigma[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float lane_lds[];
+  const uint32_t n_tori = scene.head[0];
+  absorbed_stage<ORIENT, LANES>(&S, sigma, scene, &a.sigma[0][0], 1u);
+  const AbsorbedLane<LANES> lane(lane_lds, n_tori);
+  const uint32_t n_out = 4u * lane.n_acc;
+  float* const   ys    = lane_lds + lane.n_acc * LANES;   // [LANES][4]
+
+  double acc[PASSES];
+#pragma unroll
+  for(uint32_t p = 0; p < PASSES; ++p)
+    acc[p] = 0.0;
+
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * LANES;
+  for(uint64_t base = (uint64_t)blockIdx.x * LANES; base < a.in.rays.n; base += stride)
+  {
+    const uint64_t i = base + threadIdx.x;
+    float          y0 = 0.0f, y1 = 0.0f, y2 = 0.0f;
+    if(i < a.in.rays.n)
+    {
+      absorbed_ray<Real, ORIENT, LANES>(S, sigma, a.in, a.sub, a.inv_r2, n_tori, i, lane, tests, wc);
+      const f4v y = *((gptr<const f4v>)(a.y + 4 * i));
+      y0 = y.x;
+      y1 = y.y;
+      y2 = y.z;
+    }
+    else
+      for(uint32_t c = 0; c < lane.n_acc; ++c)
+        lane.W[c * LANES] = 0.0f;
+    __syncthreads();   // every walk of the round has ended: the columns are whole, the y and crossing columns dead
+    ys[4u * threadIdx.x]      = y0;
+    ys[4u * threadIdx.x + 1u] = y1;
+    ys[4u * threadIdx.x + 2u] = y2;
+    ys[4u * threadIdx.x + 3u] = 1.0f;
+    __syncthreads();
+#pragma unroll
+    for(uint32_t p = 0; p < PASSES; ++p)
+    {
+      const uint32_t e = p * LANES + threadIdx.x;
+      if(e < n_out)
+      {
+        const uint32_t     c = e >> 2, ch = e & 3u;
+        const float* const w = lane_lds + c * LANES;
+        double             s = acc[p];
+#pragma unroll 4
+        for(uint32_t step = 0; step < LANES; ++step)   // (unrolled by four: whole, the nine passes of 64 lanes spill)
+        {
+          const uint32_t l = (step + c) & (LANES - 1u);
+          s = s + (double)w[l] * (double)ys[4u * l + ch];
+        }
+        acc[p] = s;
+      }
+    }
+    __syncthreads();   // the next round's walks write where y lies
+  }
+#pragma unroll
+  for(uint32_t p = 0; p < PASSES; ++p)
+  {
+    const uint32_t e = p * LANES + threadIdx.x;
+    if(e < n_out)
+      ((gptr<double>)a.partials)[(uint64_t)blockIdx.x * n_out + e] = acc[p];
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+// back[e] = 0.0 + partials[0][e] + partials[1][e] + … in row order, one thread per output: `rows` dependent FP64 additions
+// (2048 at the most), the loads in front of them.  rows == 0 (no ray) writes zeros.
+__global__ __launch_bounds__(256) void backproject_sum_kernel(const double* partials, uint32_t rows, uint32_t n_out, double* back)
+{
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if(e >= n_out)
+    return;
+  double s = 0.0;
+#pragma unroll 8
+  for(uint32_t r = 0; r < rows; ++r)
+    s = s + ((gptr<const double>)partials)[(uint64_t)r * n_out + e];
+  ((gptr<double>)back)[e] = s;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -709,6 +899,67 @@ hipError_t launch_glow_weights_absorbed(const SceneK& scene, const GlowWeightsAb
     else if(lanes == 128u) launch_absorbed_width<Real, kOri, 128u>(sc, a, nt, tn, stream);
     else launch_absorbed_width<Real, kOri, 64u>(sc, a, nt, tn, stream);
   });
+}
+
+// trt_glow_project*: the same blocks and the same grid; the emission tables ride in the arguments beside the scene.
+template <class Real, bool ORIENT, uint32_t LANES>
+static void launch_project_width(const SceneNoMat& sc, const GlowProfileArgs& a, uint32_t n_tori, const Tuning& tn, hipStream_t stream)
+{
+  hipLaunchKernelGGL((glow_project_kernel<Real, ORIENT, LANES>), dim3(stream_grid_lanes(a.in.rays.n, LANES, tn)), dim3(LANES),
+                     LANES * kAbsorbedLaneBytes * n_tori, stream, sc, a);
+}
+hipError_t launch_glow_project(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.in.rays.n == 0)
+    return hipSuccess;
+  const uint32_t   lanes = glow_weights_absorbed_lanes(scene.n_tori, tn);
+  const SceneNoMat sc    = scene_no_mat(scene);
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    using Real          = decltype(real);
+    constexpr bool kOri = decltype(ori)::value;
+    const uint32_t nt   = (uint32_t)scene.n_tori;
+    if(lanes == 256u) launch_project_width<Real, kOri, 256u>(sc, a, nt, tn, stream);
+    else if(lanes == 128u) launch_project_width<Real, kOri, 128u>(sc, a, nt, tn, stream);
+    else launch_project_width<Real, kOri, 64u>(sc, a, nt, tn, stream);
+  });
+}
+
+// trt_glow_backproject*: the same blocks on an eighth of the grid — every block leaves a row of partials, so the grid is
+// what fills the device (131072 lanes: two blocks of 256 or eight of 64 per CU) and the rows stay at 2048 at the most;
+// the blocks go round their rays instead.  glow_backproject_rows is that grid: the host sizes the partials by it.
+uint32_t glow_backproject_rows(int n_tori, uint64_t n, const Tuning& tn)
+{
+  const uint32_t lanes = glow_weights_absorbed_lanes(n_tori, tn);
+  const uint64_t want = (n + lanes - 1) / lanes, cap = (uint64_t)(tn.trace_blocks ? tn.trace_blocks : 512u) * (256u / lanes);
+  return (uint32_t)(want < cap ? want : cap);
+}
+template <class Real, bool ORIENT, uint32_t LANES>
+static void launch_backproject_width(const SceneNoMat& sc, const GlowBackprojectArgs& a, uint32_t n_tori, hipStream_t stream)
+{
+  hipLaunchKernelGGL((glow_backproject_kernel<Real, ORIENT, LANES>), dim3(a.rows), dim3(LANES), LANES * kAbsorbedLaneBytes * n_tori, stream, sc, a);
+}
+hipError_t launch_glow_backproject(const SceneK& scene, const GlowBackprojectArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  const uint32_t nt = (uint32_t)scene.n_tori, n_out = 4u * TRT_PROFILE_KNOTS * nt;
+  if(a.rows != glow_backproject_rows(scene.n_tori, a.in.rays.n, tn))
+    return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  if(a.rows)
+  {
+    const uint32_t   lanes = glow_weights_absorbed_lanes(scene.n_tori, tn);
+    const SceneNoMat sc    = scene_no_mat(scene);
+    e = launch_default_solver(scene, [&](auto real, auto ori) {
+      using Real          = decltype(real);
+      constexpr bool kOri = decltype(ori)::value;
+      if(lanes == 256u) launch_backproject_width<Real, kOri, 256u>(sc, a, nt, stream);
+      else if(lanes == 128u) launch_backproject_width<Real, kOri, 128u>(sc, a, nt, stream);
+      else launch_backproject_width<Real, kOri, 64u>(sc, a, nt, stream);
+    });
+  }
+  if(e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(backproject_sum_kernel, dim3((n_out + 255u) / 256u), dim3(256), 0, stream, a.partials, a.rows, n_out, a.back);
+  return hipGetLastError();
 }
 
 }  // namespace trt

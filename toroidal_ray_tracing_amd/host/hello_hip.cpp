@@ -303,6 +303,21 @@ void HelloHip::glowWeightsAbsorbed(void* stream, const trt_rays& raysDev, const 
         "HelloHip::glowWeightsAbsorbed");
 }
 
+void HelloHip::glowProject(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
+                           float tmin, float tmax, float* rgbaDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_project_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, profiles, steps, tmin, tmax, rgbaDev, stream), "HelloHip::glowProject");
+}
+
+void HelloHip::glowBackproject(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles,
+                               uint32_t steps, float tmin, float tmax, const float* yDev, double* backDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_backproject_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, profiles, steps, tmin, tmax, yDev, backDev, stream),
+        "HelloHip::glowBackproject");
+}
+
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {

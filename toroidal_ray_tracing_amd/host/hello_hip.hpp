@@ -133,6 +133,15 @@ public:
   // weight * knot[k][c] over tori and knots with any sigma.  transDev: the transmittance left per ray, or nullptr.
   void glowWeightsAbsorbed(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles,
                            uint32_t steps, float tmin, float tmax, float* weightDev, float* transDev);
+  // That matrix applied on the device, never stored (trt_glow_project_dev, trt_glow_backproject_dev).  glowProject: W x
+  // with the emission channels of `profiles` as x, summed in FP64 and rounded once; rgbaDev as glow's, its T the
+  // transmittance left.  glowBackproject: yDev (n * 4 floats, the layout of rgbaDev; channel 3 is not read) to backDev,
+  // n_tori * 17 * 4 doubles: W^T y in channels 0..2 and the column sums in channel 3; profiles may be nullptr (no absorption).
+  // The adjoint keeps partial sums in scratch of the context: make one eager call before capturing it.
+  void glowProject(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
+                   float tmin, float tmax, float* rgbaDev);
+  void glowBackproject(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
+                       float tmin, float tmax, const float* yDev, double* backDev);
 
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the

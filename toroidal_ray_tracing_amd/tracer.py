@@ -362,6 +362,50 @@ class Tracer:
                                                           self._profiles(scene, profiles), int(steps), tmin, tmax,
                                                           _vp(weight_ptr), _vp(trans_ptr), _vp(stream)))
 
+    def glow_project(self, scene, o, d, profiles, steps=4, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """The forward product ``W x`` with exactly ``glow_weights_absorbed``'s weights (trt_glow_project) on host arrays,
+        without the weights leaving the GPU: ``profiles`` as ``glow_profile`` takes them — the emission channels are x,
+        channel 3 sigma — and every torus walked, whatever its table.  Per ray and channel the products
+        ``W[j, k] * knot_j[k][c]`` are summed in FP64, j then k ascending, and rounded once.  Returns float32 (n, 4):
+        (L_r, L_g, L_b, T), T being ``glow_weights_absorbed``'s trans in bits."""
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
+        rgba = np.empty((n, 4), np.float32)
+        self._check(self._L.trt_glow_project(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene),
+                                             self._profiles(scene, profiles), int(steps), tmin, tmax, rgba.ctypes.data))
+        return rgba
+
+    def glow_project_dev(self, scene, ray_ptrs, n, profiles, rgba_ptr, steps=4, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints) as in ``glow_profile_dev``.  Asynchronous on ``stream``; no scratch of the context."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_glow_project_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
+                                                 self._profiles(scene, profiles), int(steps), tmin, tmax, _vp(rgba_ptr), _vp(stream)))
+
+    def glow_backproject(self, scene, o, d, y, profiles=None, steps=4, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """The adjoint ``W^T y`` of ``glow_project`` (trt_glow_backproject) on host arrays: ``y`` float32 (n, 4) in the
+        layout the glow calls return — channels 0..2 are read, channel 3 is ignored; ``profiles`` gives sigma (None:
+        no absorption).  Returns float64 (n_tori, 17, 4): ``sum_i W[j, k, i] * y[i, c]`` in channels 0..2 and the
+        column sum ``sum_i W[j, k, i]`` in channel 3, each product exact and the sums FP64, the same bits from every
+        call."""
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
+        y = np.ascontiguousarray(y, np.float32).reshape(n, 4)
+        back = np.empty((scene.n_tori, abi.TRT_PROFILE_KNOTS, 4), np.float64)
+        self._check(self._L.trt_glow_backproject(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene),
+                                                 self._profiles(scene, profiles), int(steps), tmin, tmax, abi.ptr(y) if n else None,
+                                                 back.ctypes.data))
+        return back
+
+    def glow_backproject_dev(self, scene, ray_ptrs, n, y_ptr, back_ptr, profiles=None, steps=4, tmax_ptr=0, tmin=0.001, tmax=10000.0,
+                             stream=0):
+        """Device pointers (ints): y_ptr n * 4 floats and back_ptr n_tori * 17 * 4 doubles, both 16-byte aligned.
+        Asynchronous on ``stream``.  The call keeps its blocks' partial sums in scratch of the context: it may be captured
+        once an eager call with at least this n and n_tori has sized that scratch."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_glow_backproject_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
+                                                     self._profiles(scene, profiles), int(steps), tmin, tmax, _vp(y_ptr), _vp(back_ptr),
+                                                     _vp(stream)))
+
     @staticmethod
     def _profiles(scene, profiles):
         if profiles is None:
