@@ -45,6 +45,8 @@
  *   media that absorb              weighted by the transmittance in front)   trt_glow_weights_absorbed*
  *   that matrix applied without    (none: build-defined, the forward and the
  *   leaving the GPU: W x, W^T y    adjoint product of iterative tomography)  trt_glow_project* / trt_glow_backproject*
+ *   the derivative of that forward (none: build-defined, J v and J^T y with
+ *   map in ALL four channels       the sigma knots: the step of a sigma fit) trt_glow_tangent* / trt_glow_adjoint*
  *   TLAS + ObjDesc + materials     REFL/hello_vulkan.cpp:645-683,264-273 trt_scene
  *   RenderedData SSBO              BEF/shaders/host_device.h:101-107     trt_rendered_data
  *
@@ -995,8 +997,9 @@ int trt_glow_weights_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax
  * sigma knot that is negative, NaN or infinite (the message names the torus and the knot).  n == 0 is valid and launches
  * nothing.  A refused call leaves the ctx usable and both outputs unwritten.
  * Stats: primary_tests = the tori started, that is n_tori times the non-empty windows; pixels = n.
- * Not here: the response to a sigma knot (it is not linear); W^T W (the matrix-free W x and W^T y are trt_glow_project
- * and trt_glow_backproject, below); a torus mask; a fused camera form; a solver for the fit.
+ * Not here: the response to a sigma knot as a matrix (it is not linear: its derivative at given tables, applied matrix-free,
+ * is trt_glow_tangent / trt_glow_adjoint, below); W^T W (the matrix-free W x and W^T y are trt_glow_project and
+ * trt_glow_backproject, below); a torus mask; a fused camera form; a solver for the fit.
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_glow_weights_absorbed(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                               const trt_profile* profiles, uint32_t steps, float tmin, float tmax,
@@ -1052,8 +1055,8 @@ int trt_glow_weights_absorbed_dev(trt_ctx* ctx, const trt_rays* in_dev, const fl
  * TRT_E_INVALID, with "trt_glow_backproject" in the message: everything trt_glow_weights_absorbed refuses but NULL
  * profiles; NULL y with n > 0; y or back not 16-byte aligned.  A refused call leaves the ctx usable and back unwritten.
  * Stats: trt_glow_weights_absorbed's.
- * Not here: W^T W; a torus mask; a fused camera form; a solver for the fit (examples/matrix_free_fit_main.cpp runs CGLS on
- * the two calls).
+ * Not here: the derivative with respect to sigma (trt_glow_tangent / trt_glow_adjoint, below); W^T W; a torus mask; a
+ * fused camera form; a solver for the fit (examples/matrix_free_fit_main.cpp runs CGLS on the two calls).
  * Host buffers: copy in, launch, copy out, synchronise. */
 int trt_glow_project(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
                      const trt_profile* profiles, uint32_t steps, float tmin, float tmax, float* rgba_out);
@@ -1073,6 +1076,86 @@ int trt_glow_backproject(trt_ctx* ctx, const trt_rays* in, const float* tmax_per
 int trt_glow_backproject_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
                              const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y_dev,
                              double* back_dev, void* stream);
+
+/* ---- the derivative of that forward map: glow_tangent(rays_in, delta -> J delta), glow_adjoint(rays_in, y -> J^T y) ---- */
+/* A fit of the absorption (Gauss-Newton, Levenberg-Marquardt, L-BFGS) needs the Jacobian of the forward map with respect
+ * to ALL FOUR channels of the tables, in the two matrix-free forms trt_glow_project / trt_glow_backproject have for W.
+ * The function that is differentiated, F, is trt_glow_project's rule in EXACT arithmetic: every torus walked, the pieces
+ * cut at every torus' walls, `steps` sub-steps of two Gauss points per piece; for ray i it maps the tables p[j][k][c]
+ * (c = 0..2 emission, c = 3 sigma) to (L_r, L_g, L_b, T).  Number the sub-steps of a ray s = 0, 1, ... front to back over
+ * all its pieces.  In sub-step s:
+ *   l_s        the world length h * len;
+ *   hat_s[j][k]  half the sum over the two Gauss points of the hat weight of knot k of torus j (1 - f at kn, f at kn + 1,
+ *              active j only): what trt_glow_weights_absorbed deposits by;
+ *   e_{s,c} = sum_jk hat_s[j][k] * p[j][k][c],   sg_s = sum_jk hat_s[j][k] * p[j][k][3];
+ *   tau = sg_s * l_s,  E_s = exp(-tau),  w_s = (1 - E_s) / sg_s  (l_s at sg_s = 0);
+ *   w'_s = dw_s / dsg_s = (l_s * E_s - w_s) / sg_s  (-l_s^2 / 2 at sg_s = 0, the continuous limit: the sg == 0 branch of
+ *              the rule is no kink);
+ *   T_s = prod_{s' < s} E_s',   L_c = sum_s e_{s,c} * w_s * T_s,   T = prod_s E_s;
+ *   B_{s,c} = sum_{s'' > s} e_{s'',c} * w_s'' * T_s''      what arrives from behind sub-step s.
+ * The pieces, the Gauss points, kn and f depend on the rays and the tori alone, so F is smooth in the tables and J, its
+ * derivative at `profiles`, is exact.  Window, per-ray bound, solvers (TRT_SOLVE_F32 / _F64 only), oriented tori and
+ * materials not being read: trt_glow_weights_absorbed's.
+ *
+ * trt_glow_tangent: J * delta.  With de_{s,c} and dsg_s formed from `delta` by the same hat_s:
+ *   dL_c = sum_s [ de_{s,c} * w_s * T_s + dsg_s * ( e_{s,c} * w'_s * T_s - l_s * B_{s,c} ) ]
+ *   dT   = -T * sum_s l_s * dsg_s
+ * rgba[4 i ..] = (dL_r, dL_g, dL_b, dT), 16-byte aligned, n * 4 floats.  profiles is validated as trt_glow_project validates
+ * it (finite, not negative, NULL refused).  delta must be finite and may have ANY SIGN; NULL is refused.  !(tmax_i > tmin)
+ * gives (0, 0, 0, 0) — the fourth entry is a derivative, 0 there and not 1 — and executes no test.  Where delta has no
+ * sigma entry other than zero, dT is +0.0f in bits.  n == 0 is valid, launches nothing and writes nothing.
+ * TRT_E_INVALID, with "trt_glow_tangent" in the message: everything trt_glow_project refuses; NULL delta; a delta entry
+ * that is NaN or infinite (the message names the torus and the knot).  A refused call leaves the ctx usable and rgba
+ * unwritten.  Stats: trt_glow_weights_absorbed's.
+ *
+ * trt_glow_adjoint: J^T * y.  y holds 4 * n floats in the rgba layout, 16-byte aligned, and ALL FOUR CHANNELS ARE READ:
+ * channel 3 is dPhi/dT, the derivative of the caller's objective with respect to the transmittance — UNLIKE
+ * trt_glow_backproject, WHICH IGNORES CHANNEL 3: a residual image whose fourth channel holds anything but the residual of
+ * T (or zero) must have it cleared first.  grad holds n_tori * 17 * 4 DOUBLES in the layout of the table itself, 16-byte
+ * aligned:
+ *   grad[(j * 17 + k) * 4 + c] = sum over i of W[j][k][i] * y[4 i + c]                       c = 0..2: trt_glow_backproject's
+ *   grad[(j * 17 + k) * 4 + 3] = sum over i of G_i[j][k],    G_i[j][k] = sum_s lambda_s * hat_s[j][k],
+ *   lambda_s = sum_{c<3} y_c * ( e_{s,c} * w'_s * T_s - l_s * B_{s,c} ) - y_3 * T * l_s
+ * G_i is formed per ray in FP32 by the walk; the sum over the rays is FP64 without floating-point atomics, and the same
+ * call on the same ctx with the same tuning gives the same bits every time, a graph replay against the captured launch's
+ * own result included.  Channels 0..2 are under trt_glow_backproject's arithmetic contract: every term is the exact FP64
+ * product of two floats and the sums are FP64; the order of the additions is not part of the contract; for finite y,
+ * |grad - exact| <= n * 2^-53 * sum over i of |W * y|; a sum whose terms are all zero is 0.0.  y is device (or host) data
+ * and is not validated: a non-finite y[4 i + c] leaves the outputs it enters unspecified.  A ray with an empty window
+ * contributes nothing.  With y >= 0 every sigma entry is <= 0.  n == 0 is valid and writes n_tori * 17 * 4 zeros.
+ * TRT_E_INVALID, with "trt_glow_adjoint" in the message: everything trt_glow_backproject refuses, and NULL profiles (the
+ * emission enters lambda: all four channels are validated as trt_glow_project validates them).  A refused call leaves the
+ * ctx usable and grad unwritten.  Stats: trt_glow_weights_absorbed's (one walk is counted).
+ *
+ * Arithmetic of both.  THE ORDER OF THE FP32 OPERATIONS IS NOT PART OF EITHER CONTRACT: only the definitions above, the
+ * error bars tests/test_gpu_jacobian.py derives from them, and the determinism are.  w' does not cancel at small tau: below
+ * tau = 1 it is the series l^2 * Q(tau), Q = -1/2 + tau/3 - tau^2/8 + tau^3/30 - ..., above it the quotient.  The adjoint
+ * forms B as L_c minus the prefix through s, so its rounding is relative to L_c, not to B.
+ * Not here: second derivatives; J^T J; a torus mask; a fused camera form; a solver for the fit
+ * (examples/sigma_fit_main.cpp runs Gauss-Newton with CGLS on the two calls).
+ * Host buffers: copy in, launch, copy out, synchronise. */
+int trt_glow_tangent(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                     const trt_profile* profiles, const trt_profile* delta, uint32_t steps, float tmin, float tmax,
+                     float* rgba_out);
+/* Device-resident buffers, asynchronous on `stream`; two kernel nodes, nothing else.  `profiles` and `delta` stay host
+ * pointers.  Two table sets do not fit the kernel arguments beside the scene: a store kernel, whose own arguments carry
+ * delta, writes it to 2176 bytes of scratch of the ctx in front of the walk.  That area follows the scratch table's rule:
+ * it is allocated by the first un-captured call, so make one eager call before capturing (a capture that would have to
+ * allocate it is refused with TRT_E_INVALID).  Calls that share the ctx share the area: order them on one stream. */
+int trt_glow_tangent_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                         const trt_profile* profiles, const trt_profile* delta, uint32_t steps, float tmin, float tmax,
+                         float* rgba_dev, void* stream);
+int trt_glow_adjoint(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                     const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y,
+                     double* grad_out);
+/* Device-resident buffers, asynchronous on `stream`; four kernel nodes, nothing else.  The blocks' partial sums (at most
+ * 2048 rows of n_tori * 17 * 5 doubles) live in scratch of the ctx, under trt_glow_backproject_dev's rule: the area grows in
+ * an un-captured call only, so before the call is captured into a hipGraph make one eager call with at least the same n and
+ * n_tori (a capture that would have to grow it is refused with TRT_E_INVALID); a graph keeps the block it was captured with.
+ * Calls that share the ctx share that area: order them on one stream, or give concurrent streams a ctx each. */
+int trt_glow_adjoint_dev(trt_ctx* ctx, const trt_rays* in_dev, const float* tmax_per_ray_dev, const trt_scene* scene,
+                         const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y_dev,
+                         double* grad_dev, void* stream);
 
 /* ---- camera rays: the two cameras of trt_render* as ray streams, with sub-pixel offsets ------------------------------ */
 /* The primary rays trt_render* generates inside its kernels (pinhole REFL/shaders/raytrace.rgen:42-48, toroidal

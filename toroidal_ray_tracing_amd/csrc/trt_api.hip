@@ -54,6 +54,8 @@ enum Buf {
   kBufRecs,                     // … binned form: point records sorted by bin
   kBufCloud,                    // trt_cloud_dev: the header words and the chunk table (CloudWord, trt_cloud.hpp)
   kBufBackproject,              // trt_glow_backproject_dev: the blocks' rows of FP64 partials (GlowBackprojectArgs::partials)
+  kBufTangent,                  // trt_glow_tangent_dev: the direction's tables (GlowTangentArgs::delta_dev, 2176 B)
+  kBufAdjoint,                  // trt_glow_adjoint_dev: the rows of both kernels' partials (GlowAdjointArgs::partials_w, then ::partials_g)
   kBufCount
 };
 
@@ -1593,6 +1595,109 @@ extern "C" int trt_glow_backproject(trt_ctx* ctx, const trt_rays* in, const floa
   if(int rc = build_scene(ctx, scene, S)) return rc;
   if(in->n > SIZE_MAX / 4 / sizeof(float)) return fail(ctx, TRT_E_NOMEM, "trt_glow_backproject: 4 * n floats do not fit the address space");
   StagedOut out = {back_out, sizeof(double) * 4 * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr};
+  return bounded_query_host(ctx, in, in->n ? tmax_per_ray : nullptr, &out, 1, [&](const trt_rays* rays, const float* bounds) {
+    const float* d_y = nullptr;
+    if(in->n)
+      if(int rc = stage_in(ctx, kBufRgba, y, (size_t)in->n * 4 * sizeof(float), (void**)&d_y)) return rc;
+    return dev(rays, bounds, d_y, (double*)out.dev);
+  });
+}
+
+// trt_glow_tangent*: trt_glow_project's checks and tables under its own name, and the direction — finite, of any sign.
+static int check_glow_delta(trt_ctx* ctx, const trt_scene* scene, const trt_profile* delta)
+{
+  for(uint32_t j = 0; j < scene->n_tori; ++j)
+    for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)
+      for(int c = 0; c < 4; ++c)
+        if(!std::isfinite(delta[j].knot[k][c]))
+          return fail(ctx, TRT_E_INVALID, "trt_glow_tangent: delta of torus %u has %s = %g at knot %u; it must be finite", j,
+                      c < 3 ? "an emission" : "sigma", (double)delta[j].knot[k][c], k);
+  return TRT_OK;
+}
+static int check_glow_tangent(trt_ctx* ctx, const trt_rays* in, const trt_profile* profiles, const trt_profile* delta, uint32_t steps,
+                              const float* rgba)
+{
+  if(int rc = check_glow_profile(ctx, in, profiles, steps, rgba, "trt_glow_tangent")) return rc;
+  if(!delta) return fail(ctx, TRT_E_INVALID, "trt_glow_tangent: NULL delta");
+  return TRT_OK;
+}
+extern "C" int trt_glow_tangent_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                    const trt_profile* profiles, const trt_profile* delta, uint32_t steps, float tmin, float tmax,
+                                    float* rgba, void* stream)
+{
+  if(int rc = check_glow_tangent(ctx, in, profiles, delta, steps, rgba)) return rc;
+  GlowTangentArgs a;
+  if(int rc = glow_profiles(ctx, scene, profiles, a.prof, "trt_glow_tangent")) return rc;   // (n_tori is trusted below)
+  if(int rc = check_glow_delta(ctx, scene, delta)) return rc;
+  std::memset(a.delta, 0, sizeof a.delta);
+  std::memcpy(a.delta, delta, sizeof(trt_profile) * scene->n_tori);
+  a.in   = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub  = media_steps(steps);
+  a.rgba = rgba;
+  // the direction's tables: scratch of the ctx, under backproject's rule (a first call inside a capture is refused)
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  if(int rc = grow(ctx, ctx->buf[kBufTangent], sizeof a.delta, (hipStream_t)stream)) return rc;
+  a.delta_dev = (float*)ctx->buf[kBufTangent].p;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_tangent);
+}
+extern "C" int trt_glow_tangent(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                const trt_profile* profiles, const trt_profile* delta, uint32_t steps, float tmin, float tmax,
+                                float* rgba_out)
+{
+  if(int rc = check_glow_tangent(ctx, in, profiles, delta, steps, rgba_out)) return rc;
+  return media_rgba_host(ctx, in, tmax_per_ray, rgba_out, [&](const trt_rays* rays, const float* bounds, float* rgba) {
+    return trt_glow_tangent_dev(ctx, rays, bounds, scene, profiles, delta, steps, tmin, tmax, rgba, nullptr);
+  });
+}
+
+// trt_glow_adjoint*: trt_glow_backproject's checks under its own name, and the profiles — all four channels enter.
+static int check_glow_adjoint(trt_ctx* ctx, const trt_rays* in, const trt_profile* profiles, uint32_t steps, const float* y,
+                              const double* grad)
+{
+  const char* const who = "trt_glow_adjoint";
+  if(int rc = check_media(ctx, in, grad, who)) return rc;
+  if(!profiles) return fail(ctx, TRT_E_INVALID, "%s: NULL profiles", who);
+  if(in->n && !y) return fail(ctx, TRT_E_INVALID, "%s: NULL y", who);
+  if(int rc = check_steps(ctx, who, steps)) return rc;
+  if((uintptr_t)y & 15) return fail(ctx, TRT_E_INVALID, "%s: y must be 16-byte aligned (it is read as float4)", who);
+  if((uintptr_t)grad & 15) return fail(ctx, TRT_E_INVALID, "%s: grad must be 16-byte aligned", who);
+  if(in->n > UINT64_MAX / 4 / sizeof(float)) return fail(ctx, TRT_E_INVALID, "%s: 4 * n floats overflow 64 bits", who);
+  return TRT_OK;
+}
+extern "C" int trt_glow_adjoint_dev(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                    const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y,
+                                    double* grad, void* stream)
+{
+  if(int rc = check_glow_adjoint(ctx, in, profiles, steps, y, grad)) return rc;
+  GlowAdjointArgs a;
+  if(int rc = glow_profiles(ctx, scene, profiles, a.prof, "trt_glow_adjoint")) return rc;   // (n_tori is trusted below)
+  a.in   = media_rays(in, tmax_per_ray, tmin, tmax);
+  a.sub  = media_steps(steps);
+  a.y    = y;
+  a.grad = grad;
+  // the rows of both kernels: scratch of the ctx under backproject's rule, 4 * 17 * n_tori doubles per row, then 17 * n_tori
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  a.rows = glow_backproject_rows((int)scene->n_tori, in->n, ctx->tn);
+  const size_t row = (size_t)TRT_PROFILE_KNOTS * scene->n_tori;
+  if(int rc = grow(ctx, ctx->buf[kBufAdjoint], (size_t)a.rows * 5 * row * sizeof(double), (hipStream_t)stream)) return rc;
+  a.partials_w = (double*)ctx->buf[kBufAdjoint].p;
+  a.partials_g = a.partials_w + (size_t)a.rows * 4 * row;
+  return ray_query(ctx, scene, stream, in->n, a, launch_glow_adjoint);
+}
+extern "C" int trt_glow_adjoint(trt_ctx* ctx, const trt_rays* in, const float* tmax_per_ray, const trt_scene* scene,
+                                const trt_profile* profiles, uint32_t steps, float tmin, float tmax, const float* y,
+                                double* grad_out)
+{
+  if(int rc = check_glow_adjoint(ctx, in, profiles, steps, y, grad_out)) return rc;
+  TRT_HIP(ctx, hipSetDevice(ctx->device));
+  const auto dev = [&](const trt_rays* rays, const float* bounds, const float* image, double* grad) {
+    return trt_glow_adjoint_dev(ctx, rays, bounds, scene, profiles, steps, tmin, tmax, image, grad, nullptr);
+  };
+  if(!scene) return dev(in, nullptr, y, grad_out);   // (refused there)
+  const SceneK* S = nullptr;
+  if(int rc = build_scene(ctx, scene, S)) return rc;
+  if(in->n > SIZE_MAX / 4 / sizeof(float)) return fail(ctx, TRT_E_NOMEM, "trt_glow_adjoint: 4 * n floats do not fit the address space");
+  StagedOut out = {grad_out, sizeof(double) * 4 * TRT_PROFILE_KNOTS * scene->n_tori, kBufOut, nullptr};
   return bounded_query_host(ctx, in, in->n ? tmax_per_ray : nullptr, &out, 1, [&](const trt_rays* rays, const float* bounds) {
     const float* d_y = nullptr;
     if(in->n)

@@ -327,6 +327,33 @@ struct GlowBackprojectArgs {
   double*             back;
   unsigned long long* stats;
 };
+// trt_glow_tangent*: GlowProfileArgs' walk at `prof` with every torus present (prof.present is not read) and the direction
+// `delta` (any sign) beside it.  Two table sets do not fit the kernel-argument segment beside the scene: a store kernel,
+// whose own arguments carry `delta`, writes it to `delta_dev` (2176 B of scratch of the ctx) in front of the walk, which
+// stages it from there into LDS.  rgba[4 i ..] = (dL_r, dL_g, dL_b, dT).
+struct GlowTangentArgs {
+  MediaRays           in;
+  MediaSteps          sub;
+  Profiles            prof;
+  trt_profile         delta[TRT_MAX_TORI];
+  float*              delta_dev;
+  float*              rgba;
+  unsigned long long* stats;
+};
+// trt_glow_adjoint*: the image y (4 * rays.n floats, 16-byte aligned, ALL four channels read) to grad[(j * 17 + k) * 4 + c].
+// Channels 0..2 and their partials `partials_w` are GlowBackprojectArgs' (sigma = channel 3 of prof), channel 3 is the
+// sigma kernel's: `rows` rows of 17 * n_tori doubles in `partials_g`, added in row order.  rows = glow_backproject_rows().
+struct GlowAdjointArgs {
+  MediaRays           in;
+  MediaSteps          sub;
+  Profiles            prof;
+  const float*        y;
+  double*             partials_w;
+  double*             partials_g;
+  uint32_t            rows;
+  double*             grad;
+  unsigned long long* stats;
+};
 
 // trt_camera_rays*, trt_shade_camera*: the rays of a camera for the rows [row_begin, row_end) of a W x H frame, `samples`
 // per pixel.  Pixel i of the band (i = (y - row_begin) * W + x, n_px of them) and sample s: ray s * n_px + i, the
@@ -482,6 +509,8 @@ hipError_t launch_glow_weights_absorbed(const SceneK& scene, const GlowWeightsAb
 hipError_t launch_glow_project(const SceneK& scene, const GlowProfileArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_glow_backproject(const SceneK& scene, const GlowBackprojectArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 uint32_t   glow_backproject_rows(int n_tori, uint64_t n, const Tuning& tn);   // the grid of glow_backproject_kernel = the rows of its partials
+hipError_t launch_glow_tangent(const SceneK& scene, const GlowTangentArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
+hipError_t launch_glow_adjoint(const SceneK& scene, const GlowAdjointArgs& a, const Tuning& tn, hipStream_t stream);   // default solver only
 hipError_t launch_camera_rays(const CameraRaysArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_camera(const SceneK& scene, const ShadeCameraArgs& a, const Tuning& tn, hipStream_t stream);
 hipError_t launch_shade_refract(const SceneK& scene, const ShadeRefractArgs& a, const Tuning& tn, hipStream_t stream);

@@ -1,5 +1,5 @@
 // trt_media.hip — media that fill the tubes, integrated along caller-supplied rays (trt_chords*, trt_glow*, trt_glow_profile*, trt_glow_weights*,
-// trt_glow_weights_absorbed*, trt_glow_project*, trt_glow_backproject*), gfx950.
+// trt_glow_weights_absorbed*, trt_glow_project*, trt_glow_backproject*, trt_glow_tangent*, trt_glow_adjoint*), gfx950.
 //
 // What the kernels share, each said once:
 //   tube_frame, tube_rho2   the ray in torus j's frame, and the tube label of its point at t: the inside test and every
@@ -7,7 +7,8 @@
 //   tube_intervals   the pairing rule: torus j's crossings and the two inside tests → at most two intervals
 //   media_ray        ray i's window, and behind a window that is not empty its RayK and world length
 //   for_each_ray     the grid-stride loop over the rays and the counted-tests epilogue
-//   merged_pieces    the intervals of several tori merged in the lane's crossing column, walked piece by piece
+//   merged_pieces    the intervals of several tori merged in the lane's crossing column, walked piece by piece (merged_fill,
+//                    then merged_walk: a kernel that walks a ray twice fills once)
 //   knot_of, gauss_pair, glow_step_weight   a label's knot and fraction; the two points of a sub-step; E and the weight of a step
 // The kernels, one lane per ray:
 //   chords_kernel    the length of every ray inside every tube: the intervals summed, n_tori coalesced streams out.
@@ -21,8 +22,12 @@
 //                    the accumulators of all tori live at once, the block width chosen from n_tori.
 //   glow_project_kernel, glow_backproject_kernel   that walk again, with the weights used on the chip: W · x per ray, and
 //                    Wᵀ y in FP64 reduced over the rays (backproject_sum_kernel adds the blocks' rows).
+//   glow_tangent_kernel, glow_sigma_adjoint_kernel   the derivative of glow_project_kernel's map with respect to all four
+//                    channels of the tables: J · delta per ray in one sweep (store_tables_kernel puts the direction's tables
+//                    where the walk finds them), and the sigma entries of Jᵀ y — two sweeps over the lane's stored column,
+//                    reduced as the back-projection reduces (adjoint_sum_kernel adds the blocks' rows).
 //   launch_chords, launch_glow, launch_glow_profile, launch_glow_weights, launch_glow_weights_absorbed, launch_glow_project,
-//                    launch_glow_backproject   their grid and launch wrappers.
+//                    launch_glow_backproject, launch_glow_tangent, launch_glow_adjoint   their grid and launch wrappers.
 //
 // The crossings of torus j are trt_crossings' (torus_crossings, trt_device.hpp: every torus in S.order over the full
 // window, no enclosure cull); include/trt.h states the arithmetic of everything on top of them, expression by expression.
@@ -238,11 +243,15 @@ __device__ __forceinline__ void glow_step(float e0, float e1, float e2, float sg
 // active mask instead of a slot, and one that ends with the window has no end slot: the last piece closes it.  Then the
 // pieces between consecutive break points are walked.  Equal break points give an empty piece, which is skipped: their
 // order in the column does not matter.  (Parameters by reference, for column_insert's reason.)
-template <class Real, bool ORIENT, uint32_t LANES, class Piece>
-__device__ __forceinline__ void merged_pieces(const SceneK& S, const RayK<Real>& r, const uint32_t& present, float* const& ct, uint8_t* const& cw,
-                                              const uint32_t& K, uint32_t& tests, WorkCount& wc, Piece&& piece)
+// The two halves, for a kernel that walks the pieces of a ray more than once (the roots are solved once): merged_fill
+// leaves the column, its length `count` and the initial mask `active`; merged_walk walks the pieces from them and leaves
+// all three as they are.
+template <class Real, bool ORIENT, uint32_t LANES>
+__device__ __forceinline__ void merged_fill(const SceneK& S, const RayK<Real>& r, const uint32_t& present, float* const& ct, uint8_t* const& cw,
+                                            const uint32_t& K, uint32_t& tests, WorkCount& wc, uint32_t& active, uint32_t& count)
 {
-  uint32_t active = 0u, count = 0u;
+  active = 0u;
+  count  = 0u;
   for(int k = 0; k < S.n_tori; ++k)
   {
     const int j = S.order[k];
@@ -255,6 +264,11 @@ __device__ __forceinline__ void merged_pieces(const SceneK& S, const RayK<Real>&
       if(!to_end) column_insert<LANES>(ct, cw, K, count, v, j, false);
     });
   }
+}
+template <class Real, uint32_t LANES, class Piece>
+__device__ __forceinline__ void merged_walk(const RayK<Real>& r, float* const& ct, uint8_t* const& cw, uint32_t active,
+                                            const uint32_t& count, Piece&& piece)
+{
   float u = r.tmin;
   for(uint32_t k = 0; k <= count; ++k)
   {
@@ -268,6 +282,14 @@ __device__ __forceinline__ void merged_pieces(const SceneK& S, const RayK<Real>&
       active = (w & 1u) ? (active | bit) : (active & ~bit);
     u = v;
   }
+}
+template <class Real, bool ORIENT, uint32_t LANES, class Piece>
+__device__ __forceinline__ void merged_pieces(const SceneK& S, const RayK<Real>& r, const uint32_t& present, float* const& ct, uint8_t* const& cw,
+                                              const uint32_t& K, uint32_t& tests, WorkCount& wc, Piece&& piece)
+{
+  uint32_t active, count;
+  merged_fill<Real, ORIENT, LANES>(S, r, present, ct, cw, K, tests, wc, active, count);
+  merged_walk<Real, LANES>(r, ct, cw, active, count, piece);
 }
 
 // The pieces of the tori with a medium (bit j of media.present).  The sums over the active tori of a piece are a loop over
@@ -546,6 +568,35 @@ struct AbsorbedLane {
   {
   }
 };
+// g to the hats of a sub-step, for every active torus j from the y of its two points in Y: g · (1 − f) to the accumulator
+// kn and g · f to kn + 1, at t-, then at t+.  The four accumulators are read at once — one LDS latency per torus, not four
+// in a row — and where t+ falls on a slot of t- it adds to what t- left there: the same operations in the same order per
+// accumulator.  The stores go out t- first, so that a shared slot keeps the value with both deposits.
+template <uint32_t LANES>
+__device__ __forceinline__ void hat_deposit(float* const& W, const float* const& Y, const uint32_t& n_tori, const uint32_t& active, const float g)
+{
+  for(uint32_t j = 0; j < n_tori; ++j)
+    if((active >> j) & 1u)
+    {
+      int   ka, kb;
+      float fa, fb;
+      knot_split(Y[(2u * j) * LANES], ka, fa);
+      knot_split(Y[(2u * j + 1u) * LANES], kb, fb);
+      float* const wa = W + (j * TRT_PROFILE_KNOTS + (uint32_t)ka) * LANES;
+      float* const wb = W + (j * TRT_PROFILE_KNOTS + (uint32_t)kb) * LANES;
+      float a0 = wa[0], a1 = wa[LANES], b0 = wb[0], b1 = wb[LANES];
+      a0 = fma_(g, 1.0f - fa, a0);
+      a1 = fma_(g, fa, a1);
+      b0 = kb == ka ? a0 : (kb == ka + 1 ? a1 : b0);
+      b1 = kb == ka ? a1 : (kb + 1 == ka ? a0 : b1);
+      b0 = fma_(g, 1.0f - fb, b0);
+      b1 = fma_(g, fb, b1);
+      wa[0]     = a0;
+      wa[LANES] = a1;
+      wb[0]     = b0;
+      wb[LANES] = b1;
+    }
+}
 // Ray i of `in` walked into the lane's accumulators (zeroed first; an empty window leaves them zero and executes no
 // test); returns the transmittance left.  (Parameters by reference, for column_insert's reason.)
 template <class Real, bool ORIENT, uint32_t LANES>
@@ -589,31 +640,7 @@ __device__ __forceinline__ float absorbed_ray(const SceneK& S, const float* cons
             }
           float E, wgt;
           glow_step_weight((A + B) * 0.5f, l, E, wgt);
-          const float g = (wgt * 0.5f) * T;
-          // The deposits at t-, then at t+.  The four accumulators are read at once — one LDS latency per torus, not four
-          // in a row — and where t+ falls on a slot of t- it adds to what t- left there: the same operations in the same
-          // order per accumulator.  The stores go out t- first, so that a shared slot keeps the value with both deposits.
-          for(uint32_t j = 0; j < n_tori; ++j)
-            if((active >> j) & 1u)
-            {
-              int   ka, kb;
-              float fa, fb;
-              knot_split(Y[(2u * j) * LANES], ka, fa);
-              knot_split(Y[(2u * j + 1u) * LANES], kb, fb);
-              float* const wa = W + (j * TRT_PROFILE_KNOTS + (uint32_t)ka) * LANES;
-              float* const wb = W + (j * TRT_PROFILE_KNOTS + (uint32_t)kb) * LANES;
-              float a0 = wa[0], a1 = wa[LANES], b0 = wb[0], b1 = wb[LANES];
-              a0 = fma_(g, 1.0f - fa, a0);
-              a1 = fma_(g, fa, a1);
-              b0 = kb == ka ? a0 : (kb == ka + 1 ? a1 : b0);
-              b1 = kb == ka ? a1 : (kb + 1 == ka ? a0 : b1);
-              b0 = fma_(g, 1.0f - fb, b0);
-              b1 = fma_(g, fb, b1);
-              wa[0]     = a0;
-              wa[LANES] = a1;
-              wb[0]     = b0;
-              wb[LANES] = b1;
-            }
+          hat_deposit<LANES>(W, Y, n_tori, active, (wgt * 0.5f) * T);
           T = T * E;
         }
       });
@@ -801,6 +828,294 @@ __global__ __launch_bounds__(256) void backproject_sum_kernel(const double* part
 }
 
 // ------------------------------------------------------------------------------------------
+// glow_tangent, glow_adjoint: J v and Jᵀ y of the forward rule with respect to all four channels of the tables
+// ------------------------------------------------------------------------------------------
+// F maps the tables to (L_r, L_g, L_b, T) of a ray by glow_project_kernel's rule in exact arithmetic; include/trt.h states
+// its derivative.  Per sub-step s, with e and sg the tables at the hats of the sub-step, l its world length, E and w as
+// glow_step_weight gives them, T_s the transmittance in front of it:
+//   dL_c = Σ_s [ de_c · w · T_s + dsg · (e_c · w' · T_s − l · B_c) ]     B_c: what arrives from behind s;   dT = −T Σ_s l · dsg
+// w' = ∂w/∂sg = (l · E − w) / sg.  The quotient cancels at small τ = sg · l (l · E and w both go to l), so below
+// kGlowSlopeSeries it is the series l² · Q(τ), Q(τ) = Σ_m (−1)^(m+1) (m + 1) / (m + 2)! · τ^m = −1/2 + τ/3 − τ²/8 + τ³/30 − …
+// to τ¹⁰, Horner with fma: the series alternates with falling terms, so what is left out is below the first term left
+// out, 12/13! = 1.93e-9 at τ = 1 against |Q| >= 0.264 there — 7.3e-9 relative.  At τ >= 1 the quotient loses a factor
+// 2 (1 + 1/τ) E / |E − (1 − E)/τ| <= 2.8 on E's rounding.  sg = 0 takes the series: −l²/2, the continuous limit.  The
+// threshold is on τ alone and l enters by products only: a scene scaled by a power of two with the tables scaled the
+// other way gives the same bits times that power.
+constexpr float kGlowSlopeSeries = 1.0f;
+__device__ __forceinline__ float glow_step_slope(float sg, float l, float E, float wgt)
+{
+  const float tau = sg * l;
+  if(!(tau < kGlowSlopeSeries))
+    return (l * E - wgt) / sg;
+  float q = fma_(tau, -2.29644327e-8f, 2.50521084e-7f);   // -11/12!, 10/11!
+  q = fma_(tau, q, -2.48015873e-6f);                      // -9/10!
+  q = fma_(tau, q, 2.20458554e-5f);                       // 8/9!
+  q = fma_(tau, q, -1.73611111e-4f);                      // -7/8!
+  q = fma_(tau, q, 1.19047619e-3f);                       // 6/7!
+  q = fma_(tau, q, -6.94444444e-3f);                      // -5/6!
+  q = fma_(tau, q, 3.33333333e-2f);                       // 4/5!
+  q = fma_(tau, q, -0.125f);                              // -3/4!
+  q = fma_(tau, q, 3.33333333e-1f);                       // 2/3!
+  q = fma_(tau, q, -0.5f);                                // -1/2!
+  return l * (l * q);
+}
+
+// each(j, xa, xb) for every active torus j: the labels x = rho² / r² of the two Gauss points ta, tb of a sub-step, formed
+// as glow_profile_kernel and absorbed_ray form them.
+template <class Real, bool ORIENT, class Each>
+__device__ __forceinline__ void substep_labels(const SceneK& S, const RayK<Real>& r, const float (&inv_r2)[TRT_MAX_TORI], const uint32_t& n_tori,
+                                               const uint32_t& active, float ta, float tb, Each&& each)
+{
+  for(uint32_t j = 0; j < n_tori; ++j)
+    if((active >> j) & 1u)
+    {
+      LocalRay<Real> lr;
+      TorusK<Real>   Tk;
+      tube_frame<Real, ORIENT>(S, (int)j, r, lr, Tk);
+      const float ir = inv_r2[j];
+      each(j, (float)tube_rho2(lr, Tk, (Real)ta) * ir, (float)tube_rho2(lr, Tk, (Real)tb) * ir);
+    }
+}
+// `words` 32-bit words of tables into LDS, from the kernel arguments or from device memory.
+__device__ __forceinline__ void stage_tables(float4* lds, const void* src, uint32_t words)
+{
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
+  uint32_t*       d = reinterpret_cast<uint32_t*>(lds);
+  for(uint32_t i = threadIdx.x; i < words; i += blockDim.x)
+    d[i] = s[i];
+}
+
+// The store kernel in front of glow_tangent_kernel: the direction's tables from its own arguments to the ctx's scratch.
+struct ProfileTables {
+  trt_profile p[TRT_MAX_TORI];
+};
+__global__ __launch_bounds__(256) void store_tables_kernel(const ProfileTables t, float* dst)
+{
+  const uint32_t  i   = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&t);
+  if(i < sizeof(ProfileTables) / 4u)
+    ((gptr<uint32_t>)reinterpret_cast<uint32_t*>(dst))[i] = src[i];
+}
+
+// glow_profile_kernel's layout — one lane per ray, 256 lanes, the crossing column in dynamic LDS — with every torus present
+// and two tables in static LDS: the point of linearisation from the arguments, the direction from `delta` (device memory:
+// both do not fit the argument segment).  Forward mode needs one sweep: with D = −Σ_{s'<s} l · dsg carried along, the term
+// −dsg_{s'} · l_{s'} · B summed over s' is Σ_s e_c · w · T_s · D_s, and dT = T · D.  D is carried with its sign — fma(−l, dsg, D)
+// stays +0 where no sigma moves — so that dT is +0 there, not −0.  No per-torus accumulator: 256 lanes at every n_tori.
+static_assert(sizeof(SceneNoMat) + sizeof(GlowProfileArgs) + sizeof(float*) <= 4096, "the kernel-argument segment of glow_tangent_kernel");
+static_assert(sizeof(ProfileTables) + sizeof(float*) <= 4096, "the kernel-argument segment of store_tables_kernel");
+template <class Real, bool ORIENT = false>
+__global__ __launch_bounds__(256) void glow_tangent_kernel(const SceneNoMat scene, const GlowProfileArgs a, const float* delta)
+{
+  __shared__ SceneK S;
+  __shared__ float4 knots[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  __shared__ float4 dknots[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float crossing_lds[];   // [K][256] t, then [K][256] bytes
+  const uint32_t n_tori = scene.head[0];
+  stage_tables(knots, &a.prof.p[0], 4u * TRT_PROFILE_KNOTS * n_tori);
+  {
+    const gptr<const uint32_t> src = (gptr<const uint32_t>)reinterpret_cast<const uint32_t*>(delta);
+    uint32_t*                  dst = reinterpret_cast<uint32_t*>(dknots);
+    for(uint32_t i = threadIdx.x; i < 4u * TRT_PROFILE_KNOTS * n_tori; i += blockDim.x)
+      dst[i] = src[i];
+  }
+  stage_scene_no_mat<ORIENT>(&S, scene);
+  __syncthreads();   // publishes the tables and the scene
+
+  const uint32_t K  = 4u * n_tori;
+  float*         ct = crossing_lds + threadIdx.x;
+  uint8_t*       cw = reinterpret_cast<uint8_t*>(crossing_lds + K * 256u) + threadIdx.x;
+
+  for_each_ray(a.in, a.stats, [&](uint64_t i, uint32_t& tests, WorkCount& wc) {
+    float      Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f, D = 0.0f, len;
+    RayK<Real> r;
+    if(media_ray(a.in, i, r, len))
+      merged_pieces<Real, ORIENT, 256u>(S, r, ~0u, ct, cw, K, tests, wc, [&](float u, float v, uint32_t active) {
+        const float h = (v - u) * a.sub.inv_steps;
+        const float l = h * len;
+        for(uint32_t s = 0; s < a.sub.steps; ++s)
+        {
+          float ta, tb;
+          gauss_pair(s, h, u, ta, tb);
+          float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A, dA = A, dB = A;
+          substep_labels<Real, ORIENT>(S, r, a.prof.inv_r2, n_tori, active, ta, tb, [&](uint32_t j, float xa, float xb) {
+            profile_add(knots + j * TRT_PROFILE_KNOTS, xa, A);
+            profile_add(knots + j * TRT_PROFILE_KNOTS, xb, B);
+            profile_add(dknots + j * TRT_PROFILE_KNOTS, xa, dA);
+            profile_add(dknots + j * TRT_PROFILE_KNOTS, xb, dB);
+          });
+          const float e0 = (A.x + B.x) * 0.5f, e1 = (A.y + B.y) * 0.5f, e2 = (A.z + B.z) * 0.5f, sg = (A.w + B.w) * 0.5f;
+          const float d0 = (dA.x + dB.x) * 0.5f, d1 = (dA.y + dB.y) * 0.5f, d2 = (dA.z + dB.z) * 0.5f, dsg = (dA.w + dB.w) * 0.5f;
+          float E, wgt;
+          glow_step_weight(sg, l, E, wgt);
+          const float k = dsg * glow_step_slope(sg, l, E, wgt);
+          // (de · w + dsg · w' · e + e · w · D) · T: with dsg == 0 and D == 0 this is glow_step's e · w · T of de, to the bit
+          Lr = fma_(fma_(e0 * wgt, D, fma_(d0, wgt, k * e0)), T, Lr);
+          Lg = fma_(fma_(e1 * wgt, D, fma_(d1, wgt, k * e1)), T, Lg);
+          Lb = fma_(fma_(e2 * wgt, D, fma_(d2, wgt, k * e2)), T, Lb);
+          D  = fma_(-l, dsg, D);
+          T  = T * E;
+        }
+      });
+    st4(a.rgba + 4 * i, make_float4(Lr, Lg, Lb, T * D));
+  });
+}
+
+// The sigma half of the adjoint: G[j][k] = Σ_s λ_s · hat_s[j][k] per ray in AbsorbedLane's layout (G where W is: 96 bytes
+// per lane and torus, the same block widths), then Σ over the rays in FP64 as glow_backproject_kernel sums W.
+//   λ_s = Σ_{c<3} y_c (e_c · w' · T_s − l · B_c) − y_3 · T · l          B_c = L_c − Σ_{s'<=s} e_c · w · T_{s'}
+// B needs the ray's whole L_c and λ its final T, so the ray's stored crossing column is walked TWICE (merged_fill once,
+// merged_walk twice: the roots are solved once): the first sweep is glow_profile_kernel's sub-step and leaves L_c and T;
+// the second repeats it — the same operations, so its prefix ends on L_c to the bit and B >= 0 throughout, ending at 0 —
+// and deposits λ_s / 2 at the hats of both points (hat_deposit).  All four channels of the tables are read: float4 knots
+// in static LDS, 1632 B more than absorbed_stage's sigma[].
+//   The reduction is glow_backproject_kernel's transposed read with the multiplier 1: thread e owns row c = e and adds the
+//   LANES values (double)G[c][l], l = (step + c) mod LANES (64 rows of a wave on 64 banks), into an FP64 register; 17 ·
+//   n_tori outputs, so one pass at 256 and 128 lanes and three at 64.  One row of partials per block, summed in row order
+//   by adjoint_sum_kernel into slot 3 of every knot.  No floating-point atomics.
+struct GlowSigmaAdjointArgs {
+  MediaRays           in;
+  MediaSteps          sub;
+  Profiles            prof;
+  const float*        y;
+  double*             partials;
+  unsigned long long* stats;
+};
+static_assert(sizeof(SceneNoMat) + sizeof(GlowSigmaAdjointArgs) <= 4096, "the kernel-argument segment of glow_sigma_adjoint_kernel");
+template <class Real, bool ORIENT, uint32_t LANES>
+__global__ __launch_bounds__(LANES) void glow_sigma_adjoint_kernel(const SceneNoMat scene, const GlowSigmaAdjointArgs a)
+{
+  constexpr uint32_t kMaxTori = LANES == 256u ? 2u : LANES == 128u ? 5u : TRT_MAX_TORI;
+  constexpr uint32_t PASSES   = (TRT_PROFILE_KNOTS * kMaxTori + LANES - 1u) / LANES;
+  __shared__ SceneK S;
+  __shared__ float4 knots[TRT_MAX_TORI * TRT_PROFILE_KNOTS];
+  extern __shared__ float lane_lds[];
+  const uint32_t n_tori = scene.head[0];
+  stage_tables(knots, &a.prof.p[0], 4u * TRT_PROFILE_KNOTS * n_tori);
+  stage_scene_no_mat<ORIENT>(&S, scene);
+  __syncthreads();   // publishes the tables and the scene
+  const AbsorbedLane<LANES> lane(lane_lds, n_tori);
+  float* const G = lane.W;
+  float* const Y = lane.Y;
+
+  double acc[PASSES];
+#pragma unroll
+  for(uint32_t p = 0; p < PASSES; ++p)
+    acc[p] = 0.0;
+
+  uint32_t       tests  = 0;
+  WorkCount      wc;
+  const uint64_t stride = (uint64_t)gridDim.x * LANES;
+  for(uint64_t base = (uint64_t)blockIdx.x * LANES; base < a.in.rays.n; base += stride)
+  {
+    const uint64_t i = base + threadIdx.x;
+    for(uint32_t c = 0; c < lane.n_acc; ++c)
+      G[c * LANES] = 0.0f;
+    float      len;
+    RayK<Real> r;
+    if(i < a.in.rays.n && media_ray(a.in, i, r, len))
+    {
+      uint32_t active0, count;
+      merged_fill<Real, ORIENT, LANES>(S, r, ~0u, lane.ct, lane.cw, lane.K, tests, wc, active0, count);
+      const f4v y = *((gptr<const f4v>)(a.y + 4 * i));
+      // e and sg of sub-step s of the piece (u, u + steps · h) at its two points, whose y go to Y for the deposit if `keep`
+      const auto tables_at = [&](auto keep, uint32_t s, float h, float u, uint32_t active, float& e0, float& e1, float& e2, float& sg) {
+        float ta, tb;
+        gauss_pair(s, h, u, ta, tb);
+        float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
+        substep_labels<Real, ORIENT>(S, r, a.prof.inv_r2, n_tori, active, ta, tb, [&](uint32_t j, float xa, float xb) {
+          if constexpr(decltype(keep)::value)
+          {
+            int   k;
+            float f;
+            Y[(2u * j) * LANES]      = knot_of(xa, k, f);
+            Y[(2u * j + 1u) * LANES] = knot_of(xb, k, f);
+          }
+          profile_add(knots + j * TRT_PROFILE_KNOTS, xa, A);
+          profile_add(knots + j * TRT_PROFILE_KNOTS, xb, B);
+        });
+        e0 = (A.x + B.x) * 0.5f;
+        e1 = (A.y + B.y) * 0.5f;
+        e2 = (A.z + B.z) * 0.5f;
+        sg = (A.w + B.w) * 0.5f;
+      };
+      float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f, T = 1.0f;
+      merged_walk<Real, LANES>(r, lane.ct, lane.cw, active0, count, [&](float u, float v, uint32_t active) {
+        const float h = (v - u) * a.sub.inv_steps;
+        const float l = h * len;
+        for(uint32_t s = 0; s < a.sub.steps; ++s)
+        {
+          float e0, e1, e2, sg;
+          tables_at(std::false_type{}, s, h, u, active, e0, e1, e2, sg);
+          glow_step(e0, e1, e2, sg, l, Lr, Lg, Lb, T);
+        }
+      });
+      const float yT = y.w * T;
+      float       Pr = 0.0f, Pg = 0.0f, Pb = 0.0f;
+      T = 1.0f;
+      merged_walk<Real, LANES>(r, lane.ct, lane.cw, active0, count, [&](float u, float v, uint32_t active) {
+        const float h = (v - u) * a.sub.inv_steps;
+        const float l = h * len;
+        for(uint32_t s = 0; s < a.sub.steps; ++s)
+        {
+          float e0, e1, e2, sg, E, wgt;
+          tables_at(std::true_type{}, s, h, u, active, e0, e1, e2, sg);
+          glow_step_weight(sg, l, E, wgt);
+          const float k = glow_step_slope(sg, l, E, wgt) * T;
+          Pr = fma_(e0 * wgt, T, Pr);   // glow_step's operations: the prefix through s
+          Pg = fma_(e1 * wgt, T, Pg);
+          Pb = fma_(e2 * wgt, T, Pb);
+          float lam = y.x * fma_(-l, Lr - Pr, e0 * k);
+          lam = fma_(y.y, fma_(-l, Lg - Pg, e1 * k), lam);
+          lam = fma_(y.z, fma_(-l, Lb - Pb, e2 * k), lam);
+          lam = fma_(-yT, l, lam);
+          hat_deposit<LANES>(G, Y, n_tori, active, lam * 0.5f);
+          T = T * E;
+        }
+      });
+    }
+    __syncthreads();   // every walk of the round has ended: the columns are whole
+#pragma unroll
+    for(uint32_t p = 0; p < PASSES; ++p)
+    {
+      const uint32_t c = p * LANES + threadIdx.x;
+      if(c < lane.n_acc)
+      {
+        const float* const g = lane_lds + c * LANES;
+        double             s = acc[p];
+#pragma unroll 4
+        for(uint32_t step = 0; step < LANES; ++step)
+          s = s + (double)g[(step + c) & (LANES - 1u)];
+        acc[p] = s;
+      }
+    }
+    __syncthreads();   // the next round's walks zero the columns
+  }
+#pragma unroll
+  for(uint32_t p = 0; p < PASSES; ++p)
+  {
+    const uint32_t c = p * LANES + threadIdx.x;
+    if(c < lane.n_acc)
+      ((gptr<double>)a.partials)[(uint64_t)blockIdx.x * lane.n_acc + c] = acc[p];
+  }
+  if(a.stats)
+    block_add_stats(a.stats, tests, 0u, 0u, wc);
+}
+// grad[4 c + 3] = 0.0 + partials[0][c] + partials[1][c] + … in row order, one thread per knot: backproject_sum_kernel for
+// the sigma slot.  rows == 0 (no ray) writes zeros.
+__global__ __launch_bounds__(256) void adjoint_sum_kernel(const double* partials, uint32_t rows, uint32_t n_acc, double* grad)
+{
+  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+  if(c >= n_acc)
+    return;
+  double s = 0.0;
+#pragma unroll 8
+  for(uint32_t r = 0; r < rows; ++r)
+    s = s + ((gptr<const double>)partials)[(uint64_t)r * n_acc + c];
+  ((gptr<double>)grad)[4u * c + 3u] = s;
+}
+
+// ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 // Default solver only (the enumeration is the walk's: trt_api.hip refuses the others before it gets here): launch(real, ori)
@@ -959,6 +1274,85 @@ hipError_t launch_glow_backproject(const SceneK& scene, const GlowBackprojectArg
   if(e != hipSuccess)
     return e;
   hipLaunchKernelGGL(backproject_sum_kernel, dim3((n_out + 255u) / 256u), dim3(256), 0, stream, a.partials, a.rows, n_out, a.back);
+  return hipGetLastError();
+}
+
+// trt_glow_tangent*: the store kernel (the direction's tables to a.delta_dev), then glow_profile_kernel's grid and columns.
+hipError_t launch_glow_tangent(const SceneK& scene, const GlowTangentArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  if(a.in.rays.n == 0)
+    return hipSuccess;
+  ProfileTables t;
+  std::memcpy(t.p, a.delta, sizeof t.p);
+  hipLaunchKernelGGL(store_tables_kernel, dim3((uint32_t)(sizeof t / 4u + 255u) / 256u), dim3(256), 0, stream, t, a.delta_dev);
+  if(const hipError_t e = hipGetLastError(); e != hipSuccess)
+    return e;
+  GlowProfileArgs p;
+  p.in    = a.in;
+  p.sub   = a.sub;
+  p.prof  = a.prof;
+  p.rgba  = a.rgba;
+  p.stats = a.stats;
+  const uint32_t     grid  = stream_grid(a.in.rays.n, tn);
+  const uint32_t     lds   = 4u * (uint32_t)scene.n_tori * kCrossingSlotBytes;
+  const SceneNoMat   sc    = scene_no_mat(scene);
+  const float* const delta = a.delta_dev;
+  return launch_default_solver(scene, [&](auto real, auto ori) {
+    hipLaunchKernelGGL((glow_tangent_kernel<decltype(real), decltype(ori)::value>), dim3(grid), dim3(256), lds, stream, sc, p, delta);
+  });
+}
+
+// trt_glow_adjoint*: launch_glow_backproject as it stands for channels 0..2 (its column sums land in slot 3 and its walk
+// is not counted: the statistics are one walk's), then the sigma kernel on the same grid and its sum, which overwrites slot 3.
+template <class Real, bool ORIENT, uint32_t LANES>
+static void launch_sigma_adjoint_width(const SceneNoMat& sc, const GlowSigmaAdjointArgs& a, uint32_t rows, uint32_t n_tori, hipStream_t stream)
+{
+  static_assert(LANES * kAbsorbedLaneBytes * (LANES == 256u ? 2u : LANES == 128u ? 5u : TRT_MAX_TORI) + sizeof(SceneK) +
+                        sizeof(float4) * TRT_MAX_TORI * TRT_PROFILE_KNOTS + 64u <= 65536u,
+                "a block of glow_sigma_adjoint_kernel stays at or below 64 KiB of LDS");
+  hipLaunchKernelGGL((glow_sigma_adjoint_kernel<Real, ORIENT, LANES>), dim3(rows), dim3(LANES), LANES * kAbsorbedLaneBytes * n_tori, stream, sc, a);
+}
+hipError_t launch_glow_adjoint(const SceneK& scene, const GlowAdjointArgs& a, const Tuning& tn, hipStream_t stream)
+{
+  const uint32_t      nt = (uint32_t)scene.n_tori;
+  GlowBackprojectArgs w;
+  w.in  = a.in;
+  w.sub = a.sub;
+  std::memset(w.sigma, 0, sizeof w.sigma);
+  for(uint32_t j = 0; j < nt; ++j)
+    for(uint32_t k = 0; k < TRT_PROFILE_KNOTS; ++k)
+      w.sigma[j][k] = a.prof.p[j].knot[k][3];
+  std::memcpy(w.inv_r2, a.prof.inv_r2, sizeof w.inv_r2);
+  w.y        = a.y;
+  w.partials = a.partials_w;
+  w.rows     = a.rows;
+  w.back     = a.grad;
+  w.stats    = nullptr;
+  if(const hipError_t e = launch_glow_backproject(scene, w, tn, stream); e != hipSuccess)
+    return e;
+  if(a.rows)
+  {
+    GlowSigmaAdjointArgs g;
+    g.in       = a.in;
+    g.sub      = a.sub;
+    g.prof     = a.prof;
+    g.y        = a.y;
+    g.partials = a.partials_g;
+    g.stats    = a.stats;
+    const uint32_t   lanes = glow_weights_absorbed_lanes(scene.n_tori, tn);
+    const SceneNoMat sc    = scene_no_mat(scene);
+    const hipError_t e     = launch_default_solver(scene, [&](auto real, auto ori) {
+      using Real          = decltype(real);
+      constexpr bool kOri = decltype(ori)::value;
+      if(lanes == 256u) launch_sigma_adjoint_width<Real, kOri, 256u>(sc, g, a.rows, nt, stream);
+      else if(lanes == 128u) launch_sigma_adjoint_width<Real, kOri, 128u>(sc, g, a.rows, nt, stream);
+      else launch_sigma_adjoint_width<Real, kOri, 64u>(sc, g, a.rows, nt, stream);
+    });
+    if(e != hipSuccess)
+      return e;
+  }
+  const uint32_t n_acc = TRT_PROFILE_KNOTS * nt;
+  hipLaunchKernelGGL(adjoint_sum_kernel, dim3((n_acc + 255u) / 256u), dim3(256), 0, stream, a.partials_g, a.rows, n_acc, a.grad);
   return hipGetLastError();
 }
 

@@ -318,6 +318,22 @@ void HelloHip::glowBackproject(void* stream, const trt_rays& raysDev, const floa
         "HelloHip::glowBackproject");
 }
 
+void HelloHip::glowTangent(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles,
+                           const trt_profile* delta, uint32_t steps, float tmin, float tmax, float* rgbaDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_tangent_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, profiles, delta, steps, tmin, tmax, rgbaDev, stream),
+        "HelloHip::glowTangent");
+}
+
+void HelloHip::glowAdjoint(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
+                           float tmin, float tmax, const float* yDev, double* gradDev)
+{
+  const trt_scene scene{m_tori.data(), (uint32_t)m_tori.size(), m_materials.data(), (uint32_t)m_materials.size()};
+  check(trt_glow_adjoint_dev(m_ctx, &raysDev, tmaxPerRayDev, &scene, profiles, steps, tmin, tmax, yDev, gradDev, stream),
+        "HelloHip::glowAdjoint");
+}
+
 void HelloHip::fanOccluded(void* stream, const trt_hits& atDev, uint64_t n, int frame, uint32_t samples, const float* dirs, float tmin,
                            float tmax, uint64_t* bitsDev, float* openDev)
 {

@@ -142,6 +142,14 @@ public:
                    float tmin, float tmax, float* rgbaDev);
   void glowBackproject(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
                        float tmin, float tmax, const float* yDev, double* backDev);
+  // The derivative of glowProject's map with respect to all four channels of the tables, at `profiles`
+  // (trt_glow_tangent_dev, trt_glow_adjoint_dev).  glowTangent: J delta per ray, (dL_r, dL_g, dL_b, dT) in rgbaDev; delta of
+  // any sign.  glowAdjoint: J^T y in gradDev, n_tori * 17 * 4 doubles in the layout of the tables; ALL four channels of yDev
+  // are read (glowBackproject ignores the fourth).  Both use scratch of the context: make one eager call before capturing.
+  void glowTangent(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, const trt_profile* delta,
+                   uint32_t steps, float tmin, float tmax, float* rgbaDev);
+  void glowAdjoint(void* stream, const trt_rays& raysDev, const float* tmaxPerRayDev, const trt_profile* profiles, uint32_t steps,
+                   float tmin, float tmax, const float* yDev, double* gradDev);
 
   // Ambient occlusion on the record raytrace-style calls leave on the device (trt_fan_occluded_dev): from each of the n points
   // of atDev, `samples` any-hit rays with the directions dirs (samples x 3 host floats; frame TRT_FAN_LOCAL: about the

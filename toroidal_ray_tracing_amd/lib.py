@@ -74,6 +74,17 @@ SYMBOLS = {
     "trt_glow_backproject_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_void_p, C.POINTER(abi.trt_scene),
                                            C.POINTER(abi.trt_profile), C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "trt_glow_tangent": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_void_p, C.POINTER(abi.trt_scene),
+                                   C.POINTER(abi.trt_profile), C.POINTER(abi.trt_profile), C.c_uint32, C.c_float, C.c_float,
+                                   C.c_void_p]),
+    "trt_glow_tangent_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_void_p, C.POINTER(abi.trt_scene),
+                                       C.POINTER(abi.trt_profile), C.POINTER(abi.trt_profile), C.c_uint32, C.c_float, C.c_float,
+                                       C.c_void_p, C.c_void_p]),
+    "trt_glow_adjoint": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_void_p, C.POINTER(abi.trt_scene),
+                                   C.POINTER(abi.trt_profile), C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "trt_glow_adjoint_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_rays), C.c_void_p, C.POINTER(abi.trt_scene),
+                                       C.POINTER(abi.trt_profile), C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "trt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.c_uint32, C.c_uint32,
                                   C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, abi.f32p, C.POINTER(abi.trt_rays_out)]),
     "trt_camera_rays_dev": (C.c_int, [C.c_void_p, C.POINTER(abi.trt_globals), C.POINTER(abi.trt_push), C.c_uint32, C.c_uint32,

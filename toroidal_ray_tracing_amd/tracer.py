@@ -406,6 +406,50 @@ class Tracer:
                                                      self._profiles(scene, profiles), int(steps), tmin, tmax, _vp(y_ptr), _vp(back_ptr),
                                                      _vp(stream)))
 
+    def glow_tangent(self, scene, o, d, profiles, delta, steps=4, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """``J delta`` (trt_glow_tangent) on host arrays: the derivative of ``glow_project``'s map, in exact arithmetic, at
+        ``profiles`` in the direction ``delta`` — both as ``glow_profile`` takes its tables, all four channels; ``delta``
+        finite, of any sign.  Returns float32 (n, 4): (dL_r, dL_g, dL_b, dT); (0, 0, 0, 0) for an empty window."""
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
+        rgba = np.empty((n, 4), np.float32)
+        self._check(self._L.trt_glow_tangent(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene),
+                                             self._profiles(scene, profiles), self._profiles(scene, delta), int(steps), tmin, tmax,
+                                             rgba.ctypes.data))
+        return rgba
+
+    def glow_tangent_dev(self, scene, ray_ptrs, n, profiles, delta, rgba_ptr, steps=4, tmax_ptr=0, tmin=0.001, tmax=10000.0, stream=0):
+        """Device pointers (ints) as in ``glow_project_dev``.  Asynchronous on ``stream``.  The direction's tables go through
+        scratch of the context: it may be captured once one eager call has been made."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_glow_tangent_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
+                                                 self._profiles(scene, profiles), self._profiles(scene, delta), int(steps), tmin, tmax,
+                                                 _vp(rgba_ptr), _vp(stream)))
+
+    def glow_adjoint(self, scene, o, d, y, profiles, steps=4, tmin=0.001, tmax=10000.0, tmax_per_ray=None):
+        """``J^T y`` (trt_glow_adjoint) on host arrays: ``y`` float32 (n, 4), ALL four channels read — channel 3 is the
+        derivative of the objective with respect to T, unlike ``glow_backproject``, which ignores it.  Returns float64
+        (n_tori, 17, 4) in the layout of the tables: channels 0..2 are ``glow_backproject``'s, channel 3 the gradient with
+        respect to the sigma knots.  The same bits from every call."""
+        keep, rays, n = self._host_rays(o, d)
+        bound = self._bounds(tmax_per_ray, n)
+        y = np.ascontiguousarray(y, np.float32).reshape(n, 4)
+        grad = np.empty((scene.n_tori, abi.TRT_PROFILE_KNOTS, 4), np.float64)
+        self._check(self._L.trt_glow_adjoint(self._h, C.byref(rays), abi.ptr(bound), self._scene(scene),
+                                             self._profiles(scene, profiles), int(steps), tmin, tmax, abi.ptr(y) if n else None,
+                                             grad.ctypes.data))
+        return grad
+
+    def glow_adjoint_dev(self, scene, ray_ptrs, n, y_ptr, grad_ptr, profiles, steps=4, tmax_ptr=0, tmin=0.001, tmax=10000.0,
+                         stream=0):
+        """Device pointers (ints): y_ptr n * 4 floats and grad_ptr n_tori * 17 * 4 doubles, both 16-byte aligned.
+        Asynchronous on ``stream``.  Scratch as ``glow_backproject_dev``: it may be captured once an eager call with at
+        least this n and n_tori has sized it."""
+        rays = self._dev_rays(ray_ptrs, n)
+        self._check(self._L.trt_glow_adjoint_dev(self._h, C.byref(rays), _vp(tmax_ptr), self._scene(scene),
+                                                 self._profiles(scene, profiles), int(steps), tmin, tmax, _vp(y_ptr), _vp(grad_ptr),
+                                                 _vp(stream)))
+
     @staticmethod
     def _profiles(scene, profiles):
         if profiles is None:
